@@ -2,7 +2,14 @@
 """bench.py -- headline benchmark of the matching -> BA hot path on MI355X (BASELINE.json metric:
 "BA iterations/sec + matched-pairs/sec, 200-img/300k-pt scene").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: it builds the BA scene, runs W warm-up and K timed LM iterations (region A), and prints
+ONE JSON line (metric / value / unit / higher_is_better / dtype / ms_per_step + the scene and the cost).  --full adds everything
+else listed below (regions B-E, the per-phase / per-kernel device times and rooflines, the distance matrix, the CPU baseline) to
+the same line; the --no-* switches only narrow a --full run.  --dump-outputs DIR writes what the timed steps computed
+(DIR/intrinsics.npy, extrinsics.npy, points.npy, ba_cost.npy; float64) right after them: the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 N>1: either launched by torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the env), or
 run bare -- then this process only spawns the N ranks (before anything touches the GPU), waits, relays rank 0's JSON
@@ -113,6 +120,11 @@ def main():
     ap.add_argument("--staged-match-copy", action="store_true", help="match lists into device buffers, then one D2H copy per pass (default: written to pinned host memory by the kernel)")
     ap.add_argument("--match-steps", type=int, default=0, help="matching passes timed (default: min(steps, 20))")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (default: the box's cores, at most 16)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline: matching, triangulation, drop-in calls, device phase / kernel times, "
+                         "rooflines, distance matrix, CPU baseline (a plain run times the BA steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the BA parameters and cost after the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -151,7 +163,7 @@ def main():
 
     # ------------------------------------------------------------------ materialised 10k x 10k distance matrix
     gemm = None
-    if not args.no_gemm and rank == 0:
+    if args.full and not args.no_gemm and rank == 0:
         nq = nt = 10000
         dd = gen_sift(2, nq, seed=synth.SEED + 100000)
         q = torch.from_numpy(dd[0]).cuda(); t = torch.from_numpy(dd[1]).cuda()
@@ -231,6 +243,38 @@ def main():
     s1 = pb.iterate(args.steps)
     barrier()
     t_ba = max_over_ranks(time.perf_counter() - t0)
+    ba_its = args.steps / t_ba
+    n_red = 6 * (n_img - 1) + 4
+    n_obs = sc["n_obs"]
+    if args.dump_outputs:
+        # what a caller of the timed path receives after its last step: the refined parameters (points in the caller's order) and
+        # the cost before / after the timed steps; float64, 48 MB at C5.  At N > 1 each rank writes its own point shard.
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        K4, ext, pts = pb.params()
+        np.save(os.path.join(args.dump_outputs, "points.npy" if world == 1 else f"points_rank{rank}.npy"), pts)
+        if rank == 0:
+            np.save(os.path.join(args.dump_outputs, "intrinsics.npy"), K4)
+            np.save(os.path.join(args.dump_outputs, "extrinsics.npy"), ext)
+            np.save(os.path.join(args.dump_outputs, "ba_cost.npy"), np.array([s1["initial_cost"], s1["final_cost"]], np.float64))
+
+    def finish():
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({
+                "metric": "ba_iterations_per_sec", "value": ba_its, "unit": "it/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * t_ba / args.steps,
+                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+                "data": "synthetic (SURVEY 8d constructions; " + ("std::mt19937_64, seed 20240607 + i" if mt else "numpy PCG64, seed 20240607 + i") + ")",
+                "config": {"workload": f"{args.config}: {n_img} cameras / {n_pt} points / {n_obs} observations BA", "reduced_system_order": n_red},
+                "ba_cost": {"initial": (s0 or s1)["initial_cost"], "after_timed_steps": s1["final_cost"],
+                            "successful_steps": s1["successful_steps"], "iterations": s1["iterations"]},
+                "note": "headline only: --full adds matching, triangulation, the drop-in calls, device phase / kernel times, rooflines and the CPU baseline"}))
+        finish()
+        return
     # per-phase / per-kernel device times: the same number of steps again with the library's HIP-event instrumentation on
     # (thirteen event records per iteration cost ~27 us, so the headline steps above run without them)
     ctx.set_kernel_timing(True)
@@ -250,9 +294,6 @@ def main():
         torch.cuda.synchronize()
         br.append(e0.elapsed_time(e1))
     ev_overhead_ms = max(0.0, float(np.median(br[10:])) - 0.002)
-    ba_its = args.steps / t_ba
-    n_red = 6 * (n_img - 1) + 4
-    n_obs = sc["n_obs"]
     # algorithmic bytes per LM iteration: observation records read by the linearisation and by the
     # candidate-cost pass, points read + written, cameras, S written + read by the factorisation + factor written
     b_it = 2 * 24 * n_obs + 2 * 24 * n_pt + 2 * 48 * n_img + 3 * 8 * n_red * n_red
@@ -618,9 +659,7 @@ def main():
             "cpu_baseline_4thr": cpu4,
         }
         print(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

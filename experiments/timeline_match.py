@@ -1,4 +1,4 @@
-"""Kernel timeline of one matching pass from a rocprofv3 --kernel-trace CSV of `bench.py --no-gemm --no-cpu-baseline`."""
+"""Kernel timeline of one matching pass from a rocprofv3 --kernel-trace CSV of `bench.py --full --no-gemm --no-cpu-baseline`."""
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))

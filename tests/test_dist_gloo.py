@@ -196,7 +196,7 @@ def test_bench_starts_its_own_ranks_and_reports_one_line(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "small", "--steps", "6", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-gemm"], capture_output=True, text=True, env=env, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-gemm"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -221,7 +221,7 @@ def test_bench_under_the_drivers_launcher(tmp_path):
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--config", "small", "--steps", "6",
-                          "--warmup", "2", "--no-cpu-baseline", "--no-gemm"], capture_output=True, text=True, env=env, timeout=600)
+                          "--warmup", "2", "--full", "--no-cpu-baseline", "--no-gemm"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
