@@ -113,6 +113,21 @@ int sfmhip_descset_info(sfmhip_descset*, int* kind, int* rows, int* dim, int* ex
 int sfmhip_knn2_dev(sfmhip_ctx*, const sfmhip_descset* query, const sfmhip_descset* train,
                     int32_t* d_idx2, float* d_dist2, int force_path);
 
+/* Cross check (mutual matching; no reference counterpart -- the reference matches consecutive frames with the ratio test only,
+ * NView:873-913).  For a pair (query set Q, train set T) the reverse best of train row j is rev_idx[j] = the query row nearest to j
+ * (ties -> lower query index) and rev_dist[j] its distance, with the bits the forward path reports (L2: sqrtf of the squared
+ * distance; Hamming2: the integer as float); idx -1 / dist FLT_MAX (L2) or 2^31 (Hamming2) when Q has no rows.  That is kNN-2 of T
+ * against Q, column 0.  With SFMHIP_MATCH_MUTUAL the ratio tail runs unchanged (min_dist, gate) and a kept row i -> j then also needs
+ * rev_idx[j] == i: a subset of the plain list in query order, every surviving element identical to its plain counterpart.  This is
+ * a cross check in the sense of BFMatcher(norm, crossCheck = true) but makes no claim of matching OpenCV's own implementation, whose
+ * behaviour this project cannot pin.
+ * The int8 and FP4 Hamming2 paths find the reverse best inside their kNN kernels; the exact fp32 and VALU Hamming2 paths run a
+ * second kNN-2 with the operands swapped. */
+#define SFMHIP_MATCH_MUTUAL 1
+/* sfmhip_knn2_dev + d_rev_idx / d_rev_dist (train rows of `train`, device); force_path as sfmhip_knn2_dev.  Enqueues only. */
+int sfmhip_knn2_mutual_dev(sfmhip_ctx*, const sfmhip_descset* query, const sfmhip_descset* train,
+                           int32_t* d_idx2, float* d_dist2, int32_t* d_rev_idx, float* d_rev_dist, int force_path);
+
 /* host-buffer one-shots (what a reference-side binding of BFMatcher::knnMatch(k=2) calls) */
 int sfmhip_knn2_l2_f32(sfmhip_ctx*, const float* q, int nq, const float* t, int nt, int dim,
                        size_t ldq, size_t ldt, int32_t* idx2, float* dist2);
@@ -147,6 +162,15 @@ int sfmhip_match_pairs(sfmhip_ctx*, sfmhip_descset* const* sets, int n_sets,
                        const int32_t* pairs, int n_pairs,
                        double ratio, float floor_, float mult,
                        sfm_dmatch* matches_out, int max_per_pair, int32_t* counts_out);
+/* the same with flags: 0 = sfmhip_match_pairs(_dev) exactly; SFMHIP_MATCH_MUTUAL = cross check (above); other bits: SFMHIP_E_ARG */
+int sfmhip_match_pairs_ex_dev(sfmhip_ctx*, sfmhip_descset* const* sets, int n_sets,
+                              const int32_t* pairs, int n_pairs,
+                              double ratio, float floor_, float mult, int flags,
+                              sfm_dmatch* d_matches, int max_per_pair, int32_t* d_counts);
+int sfmhip_match_pairs_ex(sfmhip_ctx*, sfmhip_descset* const* sets, int n_sets,
+                          const int32_t* pairs, int n_pairs,
+                          double ratio, float floor_, float mult, int flags,
+                          sfm_dmatch* matches_out, int max_per_pair, int32_t* counts_out);
 
 /* Materialised L2 distance matrix dist[i*ld + j] = sqrtf(sum_k (q[i,k]-t[j,k])^2), rows_q x rows_t
  * float32 in HBM (the "10k x 10k SIFT distance GEMM" roofline case; what cv::batchDistance(K=0)
@@ -290,6 +314,10 @@ int  sfmhip_ba_solve_multi(sfmhip_ctx* const* ctxs, int n_ctx, double* intrinsic
 int  sfmhip_match_pairs_multi(sfmhip_ctx* const* ctxs, int n_ctx, int kind, const void* const* desc, const int32_t* rows, int dim,
                               const size_t* ld, int n_images, const int32_t* pairs, int n_pairs,
                               double ratio, float floor_, float mult, sfm_dmatch* matches, int max_per_pair, int32_t* counts);
+/* the same with flags (0 or SFMHIP_MATCH_MUTUAL, as sfmhip_match_pairs_ex) */
+int  sfmhip_match_pairs_multi_ex(sfmhip_ctx* const* ctxs, int n_ctx, int kind, const void* const* desc, const int32_t* rows, int dim,
+                                 const size_t* ld, int n_images, const int32_t* pairs, int n_pairs,
+                                 double ratio, float floor_, float mult, int flags, sfm_dmatch* matches, int max_per_pair, int32_t* counts);
 /* test hook: the next n device allocations of the context fail (SFMHIP_E_HIP) -- what an out-of-memory device looks like to its callers */
 int  sfmhip_debug_fail_allocations(sfmhip_ctx*, int n);
 /* run the LM loop to termination */

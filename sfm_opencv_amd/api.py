@@ -180,6 +180,34 @@ class Context:
         """idx2 (nq,2) int32 / dist2 (nq,2) float32 torch CUDA tensors; enqueues only."""
         self._check(self.lib.sfmhip_knn2_dev(self.h, qset.handle, tset.handle, idx2.data_ptr(), dist2.data_ptr(), force_path))
 
+    def knn2_mutual_dev(self, qset, tset, idx2, dist2, rev_idx, rev_dist, force_path=0):
+        """sfmhip_knn2_mutual_dev: knn2_dev + the nearest query of every train row (rev_idx (nt,) int32 / rev_dist (nt,) float32
+        torch CUDA tensors); enqueues only."""
+        self._check(self.lib.sfmhip_knn2_mutual_dev(self.h, qset.handle, tset.handle, idx2.data_ptr(), dist2.data_ptr(),
+                                                    rev_idx.data_ptr(), rev_dist.data_ptr(), force_path))
+
+    def _knn2_mutual_host(self, sets, nq, nt, force_path):
+        import torch
+        dev = torch.device("cuda", self.device)
+        idx = torch.empty((max(nq, 1), 2), dtype=torch.int32, device=dev); dist = torch.empty((max(nq, 1), 2), dtype=torch.float32, device=dev)
+        ridx = torch.empty(max(nt, 1), dtype=torch.int32, device=dev); rdist = torch.empty(max(nt, 1), dtype=torch.float32, device=dev)
+        self.knn2_mutual_dev(sets[0], sets[1], idx, dist, ridx, rdist, force_path)
+        self.synchronize()
+        out = (idx[:nq].cpu().numpy(), dist[:nq].cpu().numpy(), ridx[:nt].cpu().numpy(), rdist[:nt].cpu().numpy())
+        for s in sets:
+            s.close()
+        return out
+
+    def knn2_mutual_l2(self, q, t, force_path=0):
+        """(idx2, dist2, rev_idx, rev_dist) of float32 host rows: kNN-2 of q against t and the nearest q row of every t row."""
+        q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
+        return self._knn2_mutual_host([self.descset_l2(q), self.descset_l2(t)], q.shape[0], t.shape[0], force_path)
+
+    def knn2_mutual_hamming2(self, q, t, force_path=0):
+        """the Hamming2 form of knn2_mutual_l2 (uint8 host rows)"""
+        q = np.ascontiguousarray(q, np.uint8); t = np.ascontiguousarray(t, np.uint8)
+        return self._knn2_mutual_host([self.descset_hamming2(q), self.descset_hamming2(t)], q.shape[0], t.shape[0], force_path)
+
     def knn2_l2(self, q, t):
         q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
         nq, dim = q.shape; nt = t.shape[0]
@@ -196,8 +224,9 @@ class Context:
                                                      idx.ctypes.data, dist.ctypes.data))
         return idx, dist
 
-    def match_pairs(self, sets, pairs, ratio=0.6, floor_=10.0, mult=5.0):
-        """sets: list of DescSet; pairs: (n_pairs, 2) int.  Returns list of DMATCH arrays (host)."""
+    def match_pairs(self, sets, pairs, ratio=0.6, floor_=10.0, mult=5.0, cross_check=False):
+        """sets: list of DescSet; pairs: (n_pairs, 2) int.  Returns list of DMATCH arrays (host).
+        cross_check: keep a match i -> j only if i is also the nearest query of j (SFMHIP_MATCH_MUTUAL)."""
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         n_pairs = pairs.shape[0]
         if n_pairs == 0:
@@ -206,17 +235,17 @@ class Context:
         out = np.empty((n_pairs, mpp), DMATCH)        # (only out[p, :counts[p]] is ever handed out: zero-filling 16 MB cost ~1 ms of a 4 ms chain)
         counts = np.zeros(n_pairs, np.int32)
         arr = (C.c_void_p * len(sets))(*[s.handle for s in sets])
-        self._check(self.lib.sfmhip_match_pairs(self.h, arr, len(sets), pairs.ctypes.data, n_pairs,
-                                                ratio, floor_, mult, out.ctypes.data, mpp, counts.ctypes.data))
+        self._check(self.lib.sfmhip_match_pairs_ex(self.h, arr, len(sets), pairs.ctypes.data, n_pairs, ratio, floor_, mult,
+                                                   _lib.MATCH_MUTUAL if cross_check else 0, out.ctypes.data, mpp, counts.ctypes.data))
         # views into the one result buffer (a copy per pair cost 3.8 ms of a 13 ms C4 chain from host rows)
         return [out[p, :c] for p, c in enumerate(counts.tolist())]
 
-    def match_pairs_dev(self, sets, pairs, d_matches, max_per_pair, d_counts, ratio=0.6, floor_=10.0, mult=5.0):
+    def match_pairs_dev(self, sets, pairs, d_matches, max_per_pair, d_counts, ratio=0.6, floor_=10.0, mult=5.0, cross_check=False):
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         arr = (C.c_void_p * len(sets))(*[s.handle for s in sets])
-        self._check(self.lib.sfmhip_match_pairs_dev(self.h, arr, len(sets), pairs.ctypes.data, pairs.shape[0],
-                                                    ratio, floor_, mult, d_matches.data_ptr(), max_per_pair,
-                                                    d_counts.data_ptr()))
+        self._check(self.lib.sfmhip_match_pairs_ex_dev(self.h, arr, len(sets), pairs.ctypes.data, pairs.shape[0],
+                                                       ratio, floor_, mult, _lib.MATCH_MUTUAL if cross_check else 0,
+                                                       d_matches.data_ptr(), max_per_pair, d_counts.data_ptr()))
 
     def l2_distance_matrix_dev(self, qset, tset, dist, force_path=0):
         """dist: torch float32 CUDA tensor (nq, >= nt), row-contiguous; enqueues only."""
@@ -396,7 +425,7 @@ def ba_solve_multi(ctxs, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None):
     return K4, ext, pts, s.asdict()
 
 
-def match_pairs_multi(ctxs, mats, pairs, ratio=0.6, floor_=10.0, mult=5.0):
+def match_pairs_multi(ctxs, mats, pairs, ratio=0.6, floor_=10.0, mult=5.0, cross_check=False):
     """sfmhip_match_pairs_multi: host matrices (float32: L2, uint8: Hamming2) matched over several contexts of this process, the pairs in
     contiguous blocks; list of DMATCH arrays in pair order."""
     pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
@@ -411,8 +440,9 @@ def match_pairs_multi(ctxs, mats, pairs, ratio=0.6, floor_=10.0, mult=5.0):
     mpp = max(1, int(rows[pairs[:, 0]].max()))
     out = np.empty((n_pairs, mpp), DMATCH); counts = np.zeros(n_pairs, np.int32)
     carr = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
-    ctxs[0]._check(ctxs[0].lib.sfmhip_match_pairs_multi(carr, len(ctxs), 2 if ham else 1, ptrs, rows.ctypes.data, dim, None, n, pairs.ctypes.data, n_pairs,
-                                                         ratio, floor_, mult, out.ctypes.data, mpp, counts.ctypes.data))
+    ctxs[0]._check(ctxs[0].lib.sfmhip_match_pairs_multi_ex(carr, len(ctxs), 2 if ham else 1, ptrs, rows.ctypes.data, dim, None, n, pairs.ctypes.data,
+                                                            n_pairs, ratio, floor_, mult, _lib.MATCH_MUTUAL if cross_check else 0,
+                                                            out.ctypes.data, mpp, counts.ctypes.data))
     return [out[p, :c] for p, c in enumerate(counts.tolist())]
 
 
@@ -441,9 +471,9 @@ def default_context():
     return _default_ctx
 
 
-def match_features(query, train, ctx=None):
+def match_features(query, train, ctx=None, cross_check=False):
     """NViewReconstuct.cpp:873 (uint8 rows -> NORM_HAMMING2) / TwoViewReconstruct.cpp:156 (float32 rows -> NORM_L2).
-    Returns the DMatch array in query order."""
+    Returns the DMatch array in query order.  cross_check=True: only mutual nearest neighbours survive (no reference counterpart)."""
     ctx = ctx or default_context()
     query = np.asarray(query); train = np.asarray(train)
     if query.dtype == np.uint8:
@@ -452,10 +482,10 @@ def match_features(query, train, ctx=None):
         sets = [ctx.descset_l2(query), ctx.descset_l2(train)]
     if query.shape[0] == 0:
         return np.zeros(0, DMATCH)
-    return ctx.match_pairs(sets, [[0, 1]])[0]
+    return ctx.match_pairs(sets, [[0, 1]], cross_check=cross_check)[0]
 
 
-def match_features_for_all(descriptor_for_all, ctx=None):
+def match_features_for_all(descriptor_for_all, ctx=None, cross_check=False):
     """NViewReconstuct.cpp:850-871: consecutive pairs (i, i+1); one batched launch sequence for the whole chain."""
     ctx = ctx or default_context()
     n = len(descriptor_for_all)
@@ -466,10 +496,10 @@ def match_features_for_all(descriptor_for_all, ctx=None):
     if len({(m.dtype, m.shape[1]) for m in mats}) == 1 and mats[0].dtype in (np.float32, np.uint8):
         # ONE C call for the whole chain (sfmhip_match_pairs_multi on this context: sets created from the host matrices in one pass of
         # the staging threads, one preparation launch, one batched kNN-2 + ratio tail, sets released)
-        out = match_pairs_multi([ctx], mats, pairs)
+        out = match_pairs_multi([ctx], mats, pairs, cross_check=cross_check)
     else:
         sets = ctx.descsets_host(mats)
-        out = ctx.match_pairs(sets, pairs)
+        out = ctx.match_pairs(sets, pairs, cross_check=cross_check)
     for i, m in enumerate(out):
         if len(m) == 0:
             print("[Warning]: zero matches between %d and %d." % (i, i + 1))

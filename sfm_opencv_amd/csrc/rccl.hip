@@ -282,9 +282,17 @@ extern "C" int sfmhip_match_pairs_multi(sfmhip_ctx* const* ctxs, int n_ctx, int 
                                         const size_t* ld, int n_images, const int32_t* pairs, int n_pairs,
                                         double ratio, float floor_, float mult, sfm_dmatch* matches, int max_per_pair, int32_t* counts)
 {
+    return sfmhip_match_pairs_multi_ex(ctxs, n_ctx, kind, desc, rows, dim, ld, n_images, pairs, n_pairs, ratio, floor_, mult, 0, matches, max_per_pair, counts);
+}
+
+extern "C" int sfmhip_match_pairs_multi_ex(sfmhip_ctx* const* ctxs, int n_ctx, int kind, const void* const* desc, const int32_t* rows, int dim,
+                                           const size_t* ld, int n_images, const int32_t* pairs, int n_pairs,
+                                           double ratio, float floor_, float mult, int flags, sfm_dmatch* matches, int max_per_pair, int32_t* counts)
+{
     if (!ctxs || n_ctx < 1 || n_ctx > 64 || !ctxs[0]) return SFMHIP_E_ARG;
     sfmhip_ctx* c0 = ctxs[0];
     SFM_RANGE("sfmhip_match_pairs_multi");
+    SFM_ARG_CHECK(c0, (flags & ~SFMHIP_MATCH_MUTUAL) == 0);
     SFM_ARG_CHECK(c0, (kind == SFMHIP_DESC_L2_F32 || kind == SFMHIP_DESC_HAMMING2_U8) && n_images >= 0 && n_pairs >= 0 && dim > 0 && max_per_pair >= 0);
     SFM_ARG_CHECK(c0, (n_images == 0 || (desc && rows)) && (n_pairs == 0 || (pairs && counts && (matches || max_per_pair == 0))));
     for (int r = 0; r < n_ctx; ++r) SFM_ARG_CHECK(c0, ctxs[r] != nullptr);
@@ -308,7 +316,7 @@ extern "C" int sfmhip_match_pairs_multi(sfmhip_ctx* const* ctxs, int n_ctx, int 
         int rc = kind == SFMHIP_DESC_L2_F32 ? sfmhip_descsets_create_l2_host(ctx, (const float* const*)dp.data(), rw.data(), dim, lds.data(), ni, sets.data())
                                             : sfmhip_descsets_create_hamming2_host(ctx, (const uint8_t* const*)dp.data(), rw.data(), dim, lds.data(), ni, sets.data());
         if (rc == SFMHIP_OK)
-            rc = sfmhip_match_pairs(ctx, sets.data(), ni, lp.data(), p1 - p0, ratio, floor_, mult, matches + (size_t)p0 * max_per_pair, max_per_pair, counts + p0);
+            rc = sfmhip_match_pairs_ex(ctx, sets.data(), ni, lp.data(), p1 - p0, ratio, floor_, mult, flags, matches + (size_t)p0 * max_per_pair, max_per_pair, counts + p0);
         for (sfmhip_descset* s : sets) if (s) sfmhip_descset_destroy(s);
         rcs[r] = rc;
     };

@@ -84,8 +84,29 @@ inline bool set_ba_devices(const std::vector<int>& devices)
 
 // ---- matching (NView:873-913, 850-871) ---------------------------------------------------------------------------
 // CV_8U rows -> NORM_HAMMING2 (the live configuration, NView:876); CV_32F rows -> NORM_L2 (TwoViewReconstruct.cpp:159)
-inline void match_features(const Mat& query, const Mat& train, std::vector<DMatch>& matches)
+inline void match_features(const Mat& query, const Mat& train, std::vector<DMatch>& matches, bool cross_check = false)
 {
+    if (cross_check) {          // the one pair through sfmhip_match_pairs_ex, which carries the flag (this context only, as below)
+        matches.clear();
+        sfmhip_ctx* c = context();
+        if (!c || query.rows == 0) return;
+        sfmhip_descset* sets[2] = { nullptr, nullptr };
+        const Mat* m[2] = { &query, &train };
+        int rc = SFMHIP_OK;
+        for (int i = 0; i < 2 && rc == SFMHIP_OK; ++i)
+            rc = m[i]->type == CV_8U ? sfmhip_descset_create_hamming2_host(c, m[i]->ptr<uint8_t>(), m[i]->rows, m[i]->cols, (size_t)m[i]->cols, &sets[i])
+                                     : sfmhip_descset_create_l2_host(c, m[i]->ptr<float>(), m[i]->rows, m[i]->cols, (size_t)m[i]->cols, &sets[i]);
+        std::vector<DMatch> out((size_t)query.rows);
+        const int32_t pr[2] = { 0, 1 };
+        int32_t cnt = 0;
+        if (rc == SFMHIP_OK)
+            rc = sfmhip_match_pairs_ex(c, sets, 2, pr, 1, 0.6, 10.0f, 5.0f, SFMHIP_MATCH_MUTUAL, reinterpret_cast<sfm_dmatch*>(out.data()), query.rows, &cnt);
+        for (auto* s : sets) sfmhip_descset_destroy(s);
+        if (rc != SFMHIP_OK) { printf("[Err]: match_features: %s\n", sfmhip_last_error(c)); return; }
+        out.resize((size_t)cnt);
+        matches.swap(out);
+        return;
+    }
     matches.clear();
     sfmhip_ctx* ctx = context();
     if (!ctx || query.rows == 0) return;
@@ -102,9 +123,11 @@ inline void match_features(const Mat& query, const Mat& train, std::vector<DMatc
     matches.swap(out);
 }
 
-// one batched launch sequence for the whole chain instead of N-1 serial calls
-inline void match_features_for_all(const std::vector<Mat>& descriptor_for_all, std::vector<std::vector<DMatch>>& matches_for_all)
+// one batched launch sequence for the whole chain instead of N-1 serial calls.  cross_check: keep a match i -> j only if i is also
+// the nearest query of j (SFMHIP_MATCH_MUTUAL; not in the reference, which runs the ratio test only)
+inline void match_features_for_all(const std::vector<Mat>& descriptor_for_all, std::vector<std::vector<DMatch>>& matches_for_all, bool cross_check = false)
 {
+    const int flags = cross_check ? SFMHIP_MATCH_MUTUAL : 0;
     matches_for_all.clear();
     sfmhip_ctx* ctx = context();
     const int n = (int)descriptor_for_all.size();
@@ -127,9 +150,9 @@ inline void match_features_for_all(const std::vector<Mat>& descriptor_for_all, s
         for (int i = 0; i + 1 < n; ++i) { printf("Matching images %d - %d\n", i, i + 1); pairs.push_back(i); pairs.push_back(i + 1); }
         std::vector<DMatch> out((size_t)(n - 1) * max_rows);
         const bool ham = descriptor_for_all[0].type == CV_8U;
-        rc = sfmhip_match_pairs_multi(ba_contexts().data(), (int)ba_contexts().size(), ham ? SFMHIP_DESC_HAMMING2_U8 : SFMHIP_DESC_L2_F32, ptrs.data(), rows.data(),
-                                      descriptor_for_all[0].cols, nullptr, n, pairs.data(), n - 1, 0.6, 10.0f, 5.0f,
-                                      reinterpret_cast<sfm_dmatch*>(out.data()), max_rows, counts.data());
+        rc = sfmhip_match_pairs_multi_ex(ba_contexts().data(), (int)ba_contexts().size(), ham ? SFMHIP_DESC_HAMMING2_U8 : SFMHIP_DESC_L2_F32, ptrs.data(), rows.data(),
+                                         descriptor_for_all[0].cols, nullptr, n, pairs.data(), n - 1, 0.6, 10.0f, 5.0f, flags,
+                                         reinterpret_cast<sfm_dmatch*>(out.data()), max_rows, counts.data());
         if (rc != SFMHIP_OK) { printf("[Err]: match_features_for_all: %s\n", sfmhip_last_error(ctx)); return; }
         for (int i = 0; i + 1 < n; ++i) {
             matches_for_all.emplace_back(out.begin() + (size_t)i * max_rows, out.begin() + (size_t)i * max_rows + counts[i]);
@@ -160,8 +183,8 @@ inline void match_features_for_all(const std::vector<Mat>& descriptor_for_all, s
     for (int i = 0; i + 1 < n; ++i) { printf("Matching images %d - %d\n", i, i + 1); pairs.push_back(i); pairs.push_back(i + 1); }
     std::vector<DMatch> out((size_t)(n - 1) * max_rows);
     if (rc == SFMHIP_OK)
-        rc = sfmhip_match_pairs(ctx, sets.data(), n, pairs.data(), n - 1, 0.6, 10.0f, 5.0f,
-                                reinterpret_cast<sfm_dmatch*>(out.data()), max_rows, counts.data());
+        rc = sfmhip_match_pairs_ex(ctx, sets.data(), n, pairs.data(), n - 1, 0.6, 10.0f, 5.0f, flags,
+                                   reinterpret_cast<sfm_dmatch*>(out.data()), max_rows, counts.data());
     for (auto* s : sets) sfmhip_descset_destroy(s);
     if (rc != SFMHIP_OK) { printf("[Err]: match_features_for_all: %s\n", sfmhip_last_error(ctx)); return; }
     for (int i = 0; i + 1 < n; ++i) {

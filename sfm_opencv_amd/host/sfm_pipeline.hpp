@@ -229,6 +229,7 @@ struct PipelineOptions {
     bool akaze = false;                    // directory input: AKAZE + M-LDB rows (the reference's live extractor, NView:797) or SIFT (its commented twin,
                                            // TwoView:112).  driver_main sets the default per program: NViewReconstruct AKAZE, TwoViewReconstruct SIFT
     double refine_px = 0.0;                // > 0: after BA, refine_structure(max_px) + a second BA (extension, not reference behaviour)
+    bool cross_check = false;              // mutual nearest neighbours only, after the ratio test (extension, not reference behaviour)
 };
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
@@ -237,7 +238,7 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
     const Mat& K = f.K;
     auto& kpts_for_all = f.key_points_for_all; auto& colors_for_all = f.colors_for_all;
     std::vector<std::vector<DMatch>> matches_for_all;
-    match_features_for_all(f.descriptor_for_all, matches_for_all);
+    match_features_for_all(f.descriptor_for_all, matches_for_all, opt.cross_check);
     if (matches_for_all.empty()) { printf("[Err]: fewer than two usable images.\n"); return -1; }
 
     std::vector<Point3d> pts3d;
@@ -336,7 +337,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 {
     if (f.descriptor_for_all.size() < 2) { printf("[Err]: two images needed.\n"); return -1; }
     std::vector<DMatch> matches;
-    match_features(f.descriptor_for_all[0], f.descriptor_for_all[1], matches);
+    match_features(f.descriptor_for_all[0], f.descriptor_for_all[1], matches, opt.cross_check);
     std::vector<Point2f> p1, p2;
     std::vector<Vec3b> c1, c2;
     Mat R, T, mask;
@@ -363,7 +364,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -385,6 +386,7 @@ inline int driver_main(int argc, char** argv, bool nview)
         else if (a == "--akaze") opt.akaze = true;
         else if (a == "--sift") opt.akaze = false;
         else if (a.rfind("--max-features=", 0) == 0) opt.max_features = std::atoi(a.c_str() + 15);
+        else if (a == "--cross-check") opt.cross_check = true;
         else if (a == "--refine") opt.refine_px = 4.0;
         else if (a.rfind("--refine=", 0) == 0) opt.refine_px = std::atof(a.c_str() + 9);
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
