@@ -268,7 +268,13 @@ int sfmhip_ba_solve(sfmhip_ctx*, double* intrinsic4, double* ext6, int n_cam, do
                     const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
                     const sfm_ba_options* opts, sfm_ba_summary* summary);
 
-/* Resident form (bench, multi-GPU): create uploads + builds the per-point / per-camera orderings. */
+/* Resident form (bench, multi-GPU): create uploads + builds the per-point / per-camera orderings.
+ * Environment, read by every sfmhip_ba_create (per problem, not per process): SFMHIP_BA_SEAM = bit mask of the pieces of an LM
+ * iteration that ride inside its big kernels; unset = all of them.  Bit 2 (value 4): the back-substitution also runs the point
+ * pass of the next linearisation at the candidate (ba_back_kernel_lin), so an accepted step whose radius grows as guessed starts
+ * without ba_point_kernel; single rank, linearizer 0 and up to 699,050 points only (both sets of per-point arrays, 2 x 192 B per point, within the
+ * 256 MB last-level cache: beyond that the separate launch measured faster).  0: every
+ * piece is a launch of its own.  The results are the same bits either way. */
 int  sfmhip_ba_create(sfmhip_ctx*, const double* intrinsic4, const double* ext6, int n_cam,
                       const double* pts, int n_pt,
                       const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
@@ -341,7 +347,9 @@ int  sfmhip_ba_reduced_system(sfmhip_ba*, double radius, double* S, double* rhs,
 int  sfmhip_ba_debug_table(sfmhip_ba*, const char* name, void* out, size_t cap_bytes, size_t* n_bytes);
 /* average device time (ms) per LM iteration of the last sfmhip_ba_iterate call, measured with HIP events on the
  * context's stream WHILE sfmhip_set_kernel_timing(ctx, 1) is in effect (all zero otherwise: the thirteen event records
- * cost ~27 us per iteration, so they are off by default): [0]=linearise+Schur build, [1]=reduced solve, [2]=back-substitution+cost, [3]=total,
+ * cost ~27 us per iteration, so they are off by default): [0]=linearise+Schur build, [1]=reduced solve, [2]=back-substitution+cost, [3]=total
+ * (with SFMHIP_BA_SEAM bit 2 the point pass of an iteration's linearisation ran inside the PREVIOUS iteration's back-substitution: its
+ * time is part of [2], not of [0], except in the iterations that fall back to ba_point_kernel),
  * single kernels: [4]=ba_camera_kernel, [5]=ba_schur_kernel -- or, where the two share one launch, [4]=ba_camschur_kernel and [5]=0
  * ([4]=ba_tile_kernel with linearizer = 2) --, [6]=chol_node_forward_kernel of the leaf level (0 if unused);
  * [7] = number of non-zero 32x32 blocks of the Cholesky factor (not a time) */

@@ -243,6 +243,15 @@ struct sfmhip_ba {
     // chain solver (ba_chain.hpp): plan, factor records, the sub-trees' exported fronts
     bool use_chain = false; ChainArgs chain; double *d_chain_rec = nullptr, *d_chain_img = nullptr; size_t chain_rec_cap = 0, chain_img_cap = 0;
     size_t chain_lds1 = 0, chain_lds2 = 0;
+    // SFMHIP_BA_SEAM (read per handle in sfmhip_ba_create): bit 2 (value 4) = the back-substitution also runs the point pass of the
+    // next linearisation at the candidate (ba_back_kernel_lin), into the second point-side buffer set below.  An accepted step
+    // whose new radius is the one that pass was damped with swaps the sets, and the next build skips ba_point_kernel.
+    int seam = 4;
+    double *d_Vinv2 = nullptr, *d_bp2 = nullptr, *d_WK2 = nullptr, *d_colsq_p2 = nullptr, *d_part_pt2 = nullptr;
+    int* d_err_pt = nullptr;       // [2]: non-SPD flag of the point pass held by [0] the current set (if it was adopted), [1] the second set
+    int err_cur = 0;               // which of the two flags belongs to the current set
+    bool pt_ready = false;         // the current set holds the point pass at the current parameters and radius (adopted, not yet consumed)
+    bool pt_fold_err = false;      // ... and its flag has yet to reach the host: the next ba_back_reduce_kernel folds it in
     bool built = false; int build_parity = 0;    // d_msg holds the undamped linearisation at the CURRENT parameters (set by a speculative build)
     double phase_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; int phase_cnt = 0;
 };
@@ -322,6 +331,14 @@ static int call_allreduce(sfmhip_ba* h, double* buf, size_t count)
 
 static int enqueue_build_exchange(sfmhip_ba* h, double* carry);
 
+// forget an adopted point pass (the linearisation point or the scaling is about to change under it) and re-arm both flags
+static int drop_point_pass(sfmhip_ba* h)
+{
+    h->pt_ready = false; h->pt_fold_err = false;
+    if (h->d_err_pt) SFM_HIP_TRY(h->ctx, hipMemsetAsync(h->d_err_pt, 0, 2 * sizeof(int), h->ctx->stream));
+    return SFMHIP_OK;
+}
+
 // linearise: message = [S | rhs | diagU | graw | scal] (undamped), summed over ranks.  at_candidate: at the candidate
 // parameters the last back-substitution produced (speculative build of the next iteration, see ba_loop).
 static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool timed, double* carry = nullptr)
@@ -352,7 +369,9 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
         SFM_HIP_TRY(ctx, hipGetLastError());
         return enqueue_build_exchange(h, carry);
     }
-    hipLaunchKernelGGL(ba_point_kernel, dim3(h->n_pt_blocks), dim3(256), 0, st, P, h->d_err);
+    // the point pass: already there if the last back-substitution computed it at what is now the current point (ba_loop)
+    if (h->pt_ready && !at_candidate) { h->pt_ready = false; h->pt_fold_err = true; }
+    else hipLaunchKernelGGL(ba_point_kernel, dim3(h->n_pt_blocks), dim3(256), 0, st, P, h->d_err);
     // camera items and pair chunks in one launch, then their folds in one launch (ba_kernels.hpp: ba_camschur_kernel)
     const int n_cam_blocks = round_up(h->nc * h->cam_split * (h->fixK ? 1 : 2), 8);
     const int n_schur_blocks = h->nblk > 0 ? round_up(ceil_div(h->nchunk, 4), 8) : 0;
@@ -420,7 +439,8 @@ static int enqueue_damp(sfmhip_ba* h, double radius)
 static int enqueue_linearize(sfmhip_ba* h, double radius, bool damp)
 {
     h->built = false;
-    int rc = enqueue_build(h, radius, false, false); if (rc) return rc;
+    int rc = drop_point_pass(h); if (rc) return rc;
+    rc = enqueue_build(h, radius, false, false); if (rc) return rc;
     return damp ? enqueue_damp(h, radius) : SFMHIP_OK;
 }
 
@@ -512,7 +532,8 @@ static int enqueue_solve(sfmhip_ba* h)
     return SFMHIP_OK;
 }
 
-static int enqueue_back(sfmhip_ba* h, double radius)
+// lin_radius > 0: ba_back_kernel_lin, the point pass of the next linearisation damped with lin_radius into the second set
+static int enqueue_back(sfmhip_ba* h, double radius, double lin_radius = 0.0)
 {
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
@@ -530,10 +551,18 @@ static int enqueue_back(sfmhip_ba* h, double radius)
         if (h->use_sparse && h->nseg > 1 && h->d_topbuf) { n1 = h->topbuf_count & ~(size_t)1; h->top_cleared = (n1 == h->topbuf_count); }
         h->cleared = true;
     }
-    hipLaunchKernelGGL(ba_back_kernel, dim3(h->n_pt_blocks + (n0 + n1 ? BACK_ZERO_BLOCKS : 0)), dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1);
+    const dim3 back_grid(h->n_pt_blocks + (n0 + n1 ? BACK_ZERO_BLOCKS : 0));
     const double* d_scal = h->d_msg + (size_t)h->npad * h->npad + 3 * (size_t)h->npad;
+    int* err_fold = fuse_publish && h->pt_fold_err ? h->d_err_pt + h->err_cur : nullptr;
+    if (lin_radius > 0.0) {
+        const PtOut O = { h->d_Vinv2, h->d_bp2, h->d_WK2, h->d_colsq_p2, h->d_part_pt2 };
+        hipLaunchKernelGGL(ba_back_kernel_lin, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1, O, lin_radius,
+                           h->d_err_pt + (h->err_cur ^ 1));
+    } else
+        hipLaunchKernelGGL(ba_back_kernel, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1);
     hipLaunchKernelGGL(ba_back_reduce_kernel, dim3(1), dim3(256), 0, st, h->d_part_back, h->n_pt_blocks, h->d_back4,
-                       d_scal, h->d_cam2, h->d_err, fuse_publish ? h->h_scal : (double*)nullptr, fuse_publish ? ++h->pub_seq : 0ull);
+                       d_scal, h->d_cam2, h->d_err, fuse_publish ? h->h_scal : (double*)nullptr, fuse_publish ? ++h->pub_seq : 0ull, err_fold);
+    if (err_fold) h->pt_fold_err = false;
     h->published = fuse_publish;
     SFM_HIP_TRY(ctx, hipGetLastError());
     // five doubles: the four step scalars and this rank's error flag (a non-SPD V of a local point): every rank must take
@@ -1032,7 +1061,7 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
     const sfm_ba_options& o = h->o;
-    if (!h->started) { const auto ts = std::chrono::steady_clock::now(); int rc = ba_start(h); if (rc) return rc; h->start_ms = ms_since(ts); }
+    if (!h->started) { const auto ts = std::chrono::steady_clock::now(); int rc = drop_point_pass(h); if (rc) return rc; rc = ba_start(h); if (rc) return rc; h->start_ms = ms_since(ts); }
     const int it_end = h->iter + max_it;
     const size_t np2 = (size_t)h->npad * h->npad;
     const double* d_scal = h->d_msg + np2 + 3 * (size_t)h->npad;
@@ -1066,13 +1095,15 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
         if (timing) SFM_HIP_TRY(ctx, hipEventRecord(ti[0], st));
         rc = enqueue_solve(h); if (rc) return rc;
         if (timing) SFM_HIP_TRY(ctx, hipEventRecord(ti[1], st));
-        h->publish_in_back = true; h->fold_step_scalars = folded;
-        rc = enqueue_back(h, h->radius); h->publish_in_back = false; h->fold_step_scalars = false; if (rc) return rc;
-        if (timing) SFM_HIP_TRY(ctx, hipEventRecord(ti[2], st));
-        // the point blocks are damped inside the build, so the speculation must also guess the next radius: a step with
+        // the point blocks are damped inside the build, so a speculation must also guess the next radius: a step with
         // rho >= 0.937 (the normal case while LM is making progress) grows it by exactly 1 / (1/3)
-        bool speculated = false;
         const double spec_radius = std::min(o.max_trust_region_radius, h->radius / (1.0 / 3.0));
+        // single rank, per-observation lineariser: the back-substitution carries the next point pass (SFMHIP_BA_SEAM bit 2)
+        const bool lin_in_back = (h->seam & 4) && !h->ar_fn && !h->use_tiles && !speculate && h->d_Vinv2;
+        h->publish_in_back = true; h->fold_step_scalars = folded;
+        rc = enqueue_back(h, h->radius, lin_in_back ? spec_radius : 0.0); h->publish_in_back = false; h->fold_step_scalars = false; if (rc) return rc;
+        if (timing) SFM_HIP_TRY(ctx, hipEventRecord(ti[2], st));
+        bool speculated = false;
         // folded: ba_back_reduce_kernel has parked this linearisation's cost and gradient maximum in d_back4[5..6] (the build below
         // overwrites the message tail they live in), and the exchange of the build sums d_back4[0..4] over the ranks
         if (folded) {
@@ -1134,17 +1165,26 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
                 h->radius = h->radius / std::max(1.0 / 3.0, 1.0 - t * t * t);
                 h->radius = std::min(o.max_trust_region_radius, h->radius);
                 h->built = speculated && h->radius == spec_radius;      // built at what is now the current point, with the radius it guessed
+                if (lin_in_back && h->radius == spec_radius) {           // so is the point pass in the second set: swap it in
+                    std::swap(h->d_Vinv, h->d_Vinv2); std::swap(h->d_bp, h->d_bp2); std::swap(h->d_WK, h->d_WK2);
+                    std::swap(h->d_colsq_p, h->d_colsq_p2); std::swap(h->d_part_pt, h->d_part_pt2);
+                    h->err_cur ^= 1; h->pt_ready = true;
+                }
                 h->nu = 2.0; ++h->nsucc; accepted = true;
             } else {
                 h->radius = h->radius / h->nu; h->nu *= 2.0;
             }
         }
+        // a point pass that was not adopted may have left its flag up: re-arm it before the next back-substitution writes the set again
+        if (lin_in_back && !h->pt_ready) SFM_HIP_TRY(ctx, hipMemsetAsync(h->d_err_pt + (h->err_cur ^ 1), 0, sizeof(int), st));
 #ifdef SFMHIP_EXPERIMENTS
         if (o.verbose) fprintf(stderr, "[sfmhip_ba dbg] err %d mcc %.6e cand %.12e dn %.3e\n", err, mcc, cand_raw, dn);
 #endif
         if (o.verbose)
             printf("[sfmhip_ba] it %d cost %.12e gmax %.3e radius %.3e %s\n", h->iter, h->x_cost, gmax, h->radius, accepted ? "ok" : "rejected");
     }
+    // left through a break: the flag of a point pass that was not adopted is still to be re-armed
+    if (h->d_err_pt && !h->pt_ready) SFM_HIP_TRY(ctx, hipMemsetAsync(h->d_err_pt + (h->err_cur ^ 1), 0, sizeof(int), st));
     (void)hipStreamSynchronize(st);
     read_pending_timing(h);
     return SFMHIP_OK;
@@ -1457,6 +1497,7 @@ int sfmhip_ba_create(sfmhip_ctx* ctx, const double* K4, const double* ext6, int 
     h->n_pt_blocks = std::max(1, ceil_div(n_pt, 256));
     // one arena for the many small and medium device arrays of a problem (a hipMalloc each cost more than the uploads)
     h->arena_chunk = (size_t)n_pt * 360 + (size_t)n_obs * 72 + (size_t)n_cam * 4096 + (1u << 20);
+    if (const char* e = getenv("SFMHIP_BA_SEAM")) h->seam = atoi(e) & 4;      // per handle: 0 = the launch sequence without any fused piece
 #ifdef SFMHIP_EXPERIMENTS
     h->force_dense = getenv("SFMHIP_DENSE_SOLVER") != nullptr;
     if (const char* e = getenv("SFMHIP_FUSE_MAX_BLOCKS")) h->fuse_max_blocks = atoi(e);      // measurement knob: 0 = always two launches on two streams
@@ -1482,6 +1523,15 @@ int sfmhip_ba_create(sfmhip_ctx* ctx, const double* K4, const double* ext6, int 
     TRY_RC(dalloc(h, &h->d_Vinv, 6 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_bp, 3 * (size_t)n_pt));
     TRY_RC(dalloc(h, &h->d_WK, 12 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_colsq_p, 3 * (size_t)n_pt));
     TRY_RC(dalloc(h, &h->d_part_pt, 32 * (size_t)h->n_pt_blocks)); TRY_RC(dalloc(h, &h->d_part_back, 4 * (size_t)h->n_pt_blocks));
+    // Second point-side set: the point pass the back-substitution computes ahead.  Only while both sets (2 x 192 B per point) fit the
+    // 256 MB last-level cache: measured faster at 80k and 300k points (C3 0.164 -> 0.161, C4 0.299 -> 0.290 ms per iteration), slower
+    // at 2M (C5 1.16 -> 1.29 ms), where neither set stays on chip and the separate, purely streaming ba_point_kernel is ahead.
+    if ((h->seam & 4) && !h->use_tiles && 2 * 192 * (size_t)n_pt <= ((size_t)256 << 20)) {
+        TRY_RC(dalloc(h, &h->d_Vinv2, 6 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_bp2, 3 * (size_t)n_pt));
+        TRY_RC(dalloc(h, &h->d_WK2, 12 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_colsq_p2, 3 * (size_t)n_pt));
+        TRY_RC(dalloc(h, &h->d_part_pt2, 32 * (size_t)h->n_pt_blocks)); TRY_RC(dalloc(h, &h->d_err_pt, 2));
+        TRY_RC(drop_point_pass(h));
+    }
     TRY_RC(dalloc(h, &h->d_part_cam, (size_t)CAMACC * n_cam * 32));
     TRY_RC(dalloc(h, &h->d_Linv, (size_t)(h->npad_max / NB) * NB * NB)); TRY_RC(dalloc(h, &h->d_y, (size_t)h->npad_max));
     TRY_RC(dalloc(h, &h->d_back4, 8)); TRY_RC(dalloc(h, &h->d_cam2, 2)); TRY_RC(dalloc(h, &h->d_xnorm, 64)); TRY_RC(dalloc(h, &h->d_err, 1));
@@ -1501,6 +1551,8 @@ int sfmhip_ba_create(sfmhip_ctx* ctx, const double* K4, const double* ext6, int 
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { sfmhip_ba_destroy(h); ctx->last_error = "upload failed"; return SFMHIP_E_HIP; }
     h->setup_ms[3] = ms_since(t0);
     if (h->o.verbose)
+        printf("[sfmhip_ba] seam %d: the next point pass %s\n", h->seam, h->d_Vinv2 ? "rides in the back-substitution (ba_back_kernel_lin)" : "is a launch of its own (ba_point_kernel)");
+    if (h->o.verbose)
         printf("[sfmhip_ba] create %.2f ms (inputs + observation sort %.2f, orderings %.2f, pair lists %.2f)\n", h->setup_ms[3], h->setup_ms[0],
                h->setup_ms[1] - h->setup_ms[0], h->setup_ms[2] - h->setup_ms[1]);
     *out = h;
@@ -1512,6 +1564,7 @@ int sfmhip_ba_set_allreduce(sfmhip_ba* h, sfmhip_allreduce_fn fn, void* user, in
     SFM_DEVICE_GUARD(h ? h->ctx : nullptr);
     if (!h || world < 1 || world > 64 || rank < 0 || rank >= world) return SFMHIP_E_ARG;
     h->ar_fn = fn; h->ar_user = user; h->rank = rank; h->world = world;
+    { int rc = drop_point_pass(h); if (rc) return rc; }
     h->started = false; h->built = false; h->cleared = false; h->campre_valid = false; h->top_cleared = false;
     return SFMHIP_OK;
 }
@@ -1524,6 +1577,7 @@ int sfmhip_ba_reset(sfmhip_ba* h)
     SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_K, h->d_K0, 4 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_ext, h->d_ext0, 6 * (size_t)h->nc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     if (h->np) SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_pts, h->d_pts0, 3 * (size_t)h->np * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    { int rc = drop_point_pass(h); if (rc) return rc; }
     h->started = false; h->built = false; h->cleared = false; h->campre_valid = false; h->top_cleared = false;
     for (double& v : h->phase_acc) v = 0; h->phase_cnt = 0;
     return SFMHIP_OK;

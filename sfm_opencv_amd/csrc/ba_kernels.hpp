@@ -360,90 +360,99 @@ __device__ __forceinline__ double wave_reduce_scatter(const double (&a)[N], int 
 // part_pt[block][32] = { cost, SKK[10], gK[4], gmax, UKK = sum EK'EK [10], sum EK'r [4], - , - }: the last two sums run over
 // every observation, so they are taken here, where each observation is linearised with its intrinsic columns anyway
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ba_point_kernel(BADev P, int* __restrict__ err)
+// The point pass has two callers: ba_point_kernel (at the current parameters) and ba_back_kernel_lin (at the candidate the
+// back-substitution has just formed, for the NEXT iteration).  Both run the pieces below with the same operands in the
+// same order, so an adopted speculative pass holds the bits ba_point_kernel would have produced.
+struct PtOut { double *Vinv, *bp, *WK, *colsq_p, *part_pt; };     // where a point pass stores (one of the handle's two sets)
+#define PT_STAGE (64 * 13)      // doubles of LDS per wave for the store transposition
+struct PtAcc {
+    double acc[30];             // the part_pt record of this thread's point (slots 16..29 are summed over its observations)
+    double V[6], b[3], WK[12], cost;
+};
+__device__ __forceinline__ void pt_zero(PtAcc& a)
 {
-    __shared__ double red[4][32];
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    double acc[30];
 #pragma unroll
-    for (int i = 0; i < 30; ++i) acc[i] = 0.0;
-    // per-point results, stored after the block below through a per-wave LDS transposition (see there)
-    double Vi[6] = { 0, 0, 0, 0, 0, 0 }, b[3] = { 0, 0, 0 }, WK[12], cs[3] = { 0, 0, 0 };
+    for (int i = 0; i < 30; ++i) a.acc[i] = 0.0;
 #pragma unroll
-    for (int i = 0; i < 12; ++i) WK[i] = 0.0;
-    if (p < P.np) {
-        const double X[3] = { P.pts[3 * p], P.pts[3 * p + 1], P.pts[3 * p + 2] };
-        const double sp[3] = { P.scale_p[3 * p], P.scale_p[3 * p + 1], P.scale_p[3 * p + 2] };
-        double V[6] = { 0, 0, 0, 0, 0, 0 };
-        double cost = 0.0;
-        const int s0 = P.pt_start[p], s1 = P.pt_start[p + 1];
-        for (int k = s0; k < s1; ++k) {
-            const int c = P.ocam[k];
-            ObsLin o;
-            obs_linearize(P.K, P.campre + CAMPRE * (size_t)c, P.ext + 6 * c + 3, X, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a,
-                          P.fixK ? nullptr : P.scale_c + P.koff, nullptr, sp, o);
-            cost += 0.5 * o.rho0;
-            // two chained fma per sum (x*y + z*w + acc would be mul, fma, add)
+    for (int i = 0; i < 6; ++i) a.V[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a.b[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) a.WK[i] = 0.0;
+    a.cost = 0.0;
+}
+// one observation, linearised without camera columns
+__device__ __forceinline__ void pt_accumulate(int fixK, const ObsLin& o, PtAcc& a)
+{
+    a.cost += 0.5 * o.rho0;
+    // two chained fma per sum (x*y + z*w + acc would be mul, fma, add)
 #define ACC2(dst, x0, y0, x1, y1) do { dst = fma(x0, y0, dst); dst = fma(x1, y1, dst); } while (0)
-            if (!P.fixK) {
-                int a = 16;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) { ACC2(acc[a], o.EK[0][i], o.EK[0][j], o.EK[1][i], o.EK[1][j]); ++a; }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ACC2(acc[26 + i], o.EK[0][i], o.r[0], o.EK[1][i], o.r[1]);
-            }
-            ACC2(V[0], o.F[0][0], o.F[0][0], o.F[1][0], o.F[1][0]);
-            ACC2(V[1], o.F[0][1], o.F[0][0], o.F[1][1], o.F[1][0]);
-            ACC2(V[2], o.F[0][1], o.F[0][1], o.F[1][1], o.F[1][1]);
-            ACC2(V[3], o.F[0][2], o.F[0][0], o.F[1][2], o.F[1][0]);
-            ACC2(V[4], o.F[0][2], o.F[0][1], o.F[1][2], o.F[1][1]);
-            ACC2(V[5], o.F[0][2], o.F[0][2], o.F[1][2], o.F[1][2]);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) ACC2(b[j], o.F[0][j], o.r[0], o.F[1][j], o.r[1]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) ACC2(WK[3 * i + j], o.EK[0][i], o.F[0][j], o.EK[1][i], o.F[1][j]);
-#undef ACC2
-        }
-        cs[0] = V[0]; cs[1] = V[2]; cs[2] = V[5];
-        V[0] += fmin(fmax(cs[0], P.min_diag), P.max_diag) / P.radius;
-        V[2] += fmin(fmax(cs[1], P.min_diag), P.max_diag) / P.radius;
-        V[5] += fmin(fmax(cs[2], P.min_diag), P.max_diag) / P.radius;
-        if (!inv3_spd(V, Vi)) *err = 1;
-        // T = WK Vi (4x3); SKK = T WK' ; gK = T b
-        double T[12];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) symv3(Vi, &WK[3 * i], &T[3 * i]);
-        acc[0] = cost;
-        int q = 1;
+    if (!fixK) {
+        int s = 16;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j <= i; ++j)
-                acc[q++] = T[3 * i] * WK[3 * j] + T[3 * i + 1] * WK[3 * j + 1] + T[3 * i + 2] * WK[3 * j + 2];
+            for (int j = 0; j <= i; ++j) { ACC2(a.acc[s], o.EK[0][i], o.EK[0][j], o.EK[1][i], o.EK[1][j]); ++s; }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[11 + i] = T[3 * i] * b[0] + T[3 * i + 1] * b[1] + T[3 * i + 2] * b[2];
-        acc[15] = fmax(fabs(b[0] * rcp_nr(sp[0])), fmax(fabs(b[1] * rcp_nr(sp[1])), fabs(b[2] * rcp_nr(sp[2]))));
+        for (int i = 0; i < 4; ++i) ACC2(a.acc[26 + i], o.EK[0][i], o.r[0], o.EK[1][i], o.r[1]);
     }
+    ACC2(a.V[0], o.F[0][0], o.F[0][0], o.F[1][0], o.F[1][0]);
+    ACC2(a.V[1], o.F[0][1], o.F[0][0], o.F[1][1], o.F[1][0]);
+    ACC2(a.V[2], o.F[0][1], o.F[0][1], o.F[1][1], o.F[1][1]);
+    ACC2(a.V[3], o.F[0][2], o.F[0][0], o.F[1][2], o.F[1][0]);
+    ACC2(a.V[4], o.F[0][2], o.F[0][1], o.F[1][2], o.F[1][1]);
+    ACC2(a.V[5], o.F[0][2], o.F[0][2], o.F[1][2], o.F[1][2]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ACC2(a.b[j], o.F[0][j], o.r[0], o.F[1][j], o.r[1]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) ACC2(a.WK[3 * i + j], o.EK[0][i], o.F[0][j], o.EK[1][i], o.F[1][j]);
+#undef ACC2
+}
+// after the last observation: damping with `radius`, V^-1, and the point's share of the part_pt record
+__device__ __forceinline__ void pt_finish(const BADev& P, double radius, const double sp[3], PtAcc& a, double Vi[6], double cs[3], int* __restrict__ err)
+{
+    double* V = a.V; const double* b = a.b; const double* WK = a.WK;
+    cs[0] = V[0]; cs[1] = V[2]; cs[2] = V[5];
+    V[0] += fmin(fmax(cs[0], P.min_diag), P.max_diag) / radius;
+    V[2] += fmin(fmax(cs[1], P.min_diag), P.max_diag) / radius;
+    V[5] += fmin(fmax(cs[2], P.min_diag), P.max_diag) / radius;
+    if (!inv3_spd(V, Vi)) *err = 1;
+    // T = WK Vi (4x3); SKK = T WK' ; gK = T b
+    double T[12];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) symv3(Vi, &WK[3 * i], &T[3 * i]);
+    a.acc[0] = a.cost;
+    int q = 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j)
+            a.acc[q++] = T[3 * i] * WK[3 * j] + T[3 * i + 1] * WK[3 * j + 1] + T[3 * i + 2] * WK[3 * j + 2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a.acc[11 + i] = T[3 * i] * b[0] + T[3 * i + 1] * b[1] + T[3 * i + 2] * b[2];
+    a.acc[15] = fmax(fabs(b[0] * rcp_nr(sp[0])), fmax(fabs(b[1] * rcp_nr(sp[1])), fabs(b[2] * rcp_nr(sp[2]))));
+}
+// the block's stores; stage: 4 * PT_STAGE doubles of LDS, red: 4 x 32.  Every thread of the block calls it (one barrier).
+__device__ __forceinline__ void pt_store(const BADev& P, const PtOut& O, double* __restrict__ stage, double (*red)[32],
+                                         const PtAcc& a, const double Vi[6], const double cs[3])
+{
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     {
         // Stores through a per-wave LDS transposition: a wave's 64 records of an array are one contiguous span, written as
         // whole 16-byte (8-byte) pieces lane after lane.  Stored straight from the registers, every instruction scattered
         // 16 B per lane at a 48/96-byte stride: 13 partial-line requests per point at the L2, ~4M per launch.
-        __shared__ double stage[4][64 * 13];
-        double* buf = stage[wave];
+        double* buf = stage + wave * PT_STAGE;
         const int first = blockIdx.x * 256 + wave * 64;               // this wave's first point
         const int npts = min(64, P.np - first);                        // records of this wave that exist (<= 0: none)
         // W_K: 12 doubles per point = 384 double2 per wave
 #pragma unroll
-        for (int i = 0; i < 12; ++i) buf[lane * 13 + i] = WK[i];
+        for (int i = 0; i < 12; ++i) buf[lane * 13 + i] = a.WK[i];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const int j = lane + 64 * i, pt = j / 6, pr = j - 6 * pt;
-            if (pt < npts) *(double2*)(P.WK + 12 * (size_t)first + 2 * j) = make_double2(buf[pt * 13 + 2 * pr], buf[pt * 13 + 2 * pr + 1]);
+            if (pt < npts) *(double2*)(O.WK + 12 * (size_t)first + 2 * j) = make_double2(buf[pt * 13 + 2 * pr], buf[pt * 13 + 2 * pr + 1]);
         }
         // V^-1: 6 doubles per point = 192 double2 per wave
 #pragma unroll
@@ -451,23 +460,23 @@ __global__ __launch_bounds__(256) void ba_point_kernel(BADev P, int* __restrict_
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int j = lane + 64 * i, pt = j / 3, pr = j - 3 * pt;
-            if (pt < npts) *(double2*)(P.Vinv + 6 * (size_t)first + 2 * j) = make_double2(buf[pt * 7 + 2 * pr], buf[pt * 7 + 2 * pr + 1]);
+            if (pt < npts) *(double2*)(O.Vinv + 6 * (size_t)first + 2 * j) = make_double2(buf[pt * 7 + 2 * pr], buf[pt * 7 + 2 * pr + 1]);
         }
         // b_p and the raw column norms: 3 doubles per point, already contiguous as [point][3]
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { buf[lane * 3 + i] = b[i]; buf[256 + lane * 3 + i] = cs[i]; }
+        for (int i = 0; i < 3; ++i) { buf[lane * 3 + i] = a.b[i]; buf[256 + lane * 3 + i] = cs[i]; }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int f = lane + 64 * i;
-            if (f < 3 * npts) { P.bp[3 * (size_t)first + f] = buf[f]; P.colsq_p[3 * (size_t)first + f] = buf[256 + f]; }
+            if (f < 3 * npts) { O.bp[3 * (size_t)first + f] = buf[f]; O.colsq_p[3 * (size_t)first + f] = buf[256 + f]; }
         }
     }
     {
         double v29[29];                     // the 29 sums: slots 0..14 and 16..29 (slot 15 is a maximum)
 #pragma unroll
-        for (int i = 0; i < 29; ++i) v29[i] = acc[i < 15 ? i : i + 1];
+        for (int i = 0; i < 29; ++i) v29[i] = a.acc[i < 15 ? i : i + 1];
         const double tot = wave_reduce_scatter(v29, lane);
-        const double gm = wave_max(acc[15]);
+        const double gm = wave_max(a.acc[15]);
         const int j = wave_scatter_index(lane);
         if (j < 29) red[wave][j < 15 ? j : j + 1] = tot;
         if (lane == 0) red[wave][15] = gm;
@@ -477,8 +486,34 @@ __global__ __launch_bounds__(256) void ba_point_kernel(BADev P, int* __restrict_
         const int i = threadIdx.x;
         double v = red[0][i];
         for (int w = 1; w < 4; ++w) v = (i == 15) ? fmax(v, red[w][i]) : v + red[w][i];
-        P.part_pt[32 * (size_t)blockIdx.x + i] = v;
+        O.part_pt[32 * (size_t)blockIdx.x + i] = v;
     }
+}
+
+__global__ __launch_bounds__(256) void ba_point_kernel(BADev P, int* __restrict__ err)
+{
+    __shared__ double red[4][32];
+    __shared__ __attribute__((aligned(16))) double stage[4 * PT_STAGE];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    // per-point results, stored after the block below through a per-wave LDS transposition (pt_store)
+    PtAcc a;
+    pt_zero(a);
+    double Vi[6] = { 0, 0, 0, 0, 0, 0 }, cs[3] = { 0, 0, 0 };
+    if (p < P.np) {
+        const double X[3] = { P.pts[3 * p], P.pts[3 * p + 1], P.pts[3 * p + 2] };
+        const double sp[3] = { P.scale_p[3 * p], P.scale_p[3 * p + 1], P.scale_p[3 * p + 2] };
+        const int s0 = P.pt_start[p], s1 = P.pt_start[p + 1];
+        for (int k = s0; k < s1; ++k) {
+            const int c = P.ocam[k];
+            ObsLin o;
+            obs_linearize(P.K, P.campre + CAMPRE * (size_t)c, P.ext + 6 * c + 3, X, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a,
+                          P.fixK ? nullptr : P.scale_c + P.koff, nullptr, sp, o);
+            pt_accumulate(P.fixK, o, a);
+        }
+        pt_finish(P, P.radius, sp, a, Vi, cs, err);
+    }
+    const PtOut O = { P.Vinv, P.bp, P.WK, P.colsq_p, P.part_pt };
+    pt_store(P, O, stage, red, a, Vi, cs);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -966,8 +1001,14 @@ struct BackCam { const double *pre, *t, *pre_c, *t_c, *sc, *y; };     // one cam
 
 // body of K_back for one point; cam_at(c) -> BackCam
 #define BACK_ESAVE 8      // observations per point whose (E y) pair the first pass parks in LDS for the second (longer tracks re-derive it)
-template <typename CamAt>
-__device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_at, double acc[4], double (*esave)[256][2])
+// LIN: also the point pass of the NEXT linearisation, at the candidate (what ba_point_kernel would do one iteration later if
+// the step is accepted), in a loop of its own behind the candidate pass: its gathers are hits by then.  (Inside the candidate
+// pass, sharing the projection, its 36 accumulators on top of that pass's live values spilled 240 registers at three waves per
+// SIMD; the separate loop: 10, outside the loops.)  next_radius damps it; Vi_n / cs_n return V^-1 and the raw column norms,
+// a the sums (pt_store writes them).
+template <bool LIN, typename CamAt>
+__device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_at, double acc[4], double (*esave)[256][2],
+                                              PtAcc* a, double* Vi_n, double* cs_n, double next_radius, int* __restrict__ err_n)
 {
     const int tid = threadIdx.x;
     const double X[3] = { P.pts[3 * p], P.pts[3 * p + 1], P.pts[3 * p + 2] };
@@ -1027,6 +1068,15 @@ __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_a
         acc[0] -= m0 * (o.r[0] + 0.5 * m0) + m1 * (o.r[1] + 0.5 * m1);
         acc[1] += obs_cost(P.Kc, rec.pre_c, rec.t_c, Xc, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a);
     }
+    if (LIN) {
+        for (int k = s0; k < s1; ++k) {
+            const BackCam rec = cam_at(P.ocam[k]);
+            ObsLin oc;
+            obs_linearize(P.Kc, rec.pre_c, rec.t_c, Xc, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a, sK, nullptr, sp, oc);
+            pt_accumulate(P.fixK, oc, *a);
+        }
+        pt_finish(P, next_radius, sp, *a, Vi_n, cs_n, err_n);
+    }
 }
 
 // fills one camera record (BACK_REC doubles) from the global arrays
@@ -1046,11 +1096,16 @@ __device__ __forceinline__ double back_rec_value(const BADev& P, int c, int f)
 // rank the reduced system S and the solver's private buffers, which the factorisation has consumed by now and the next
 // linearisation expects empty -- as two hipMemsetAsync calls behind the step's last kernel they sat on the critical path.
 #define BACK_ZERO_BLOCKS 512
-__global__ __launch_bounds__(256, 3) void ba_back_kernel(BADev P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1)
+template <bool LIN>
+__device__ __forceinline__ void ba_back_body(const BADev& P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1,
+                                             const PtOut& O, double next_radius, int* __restrict__ err_n)
 {
     __shared__ double red[4][4];
     __shared__ __attribute__((aligned(16))) double cam[BACK_NCL][BACK_REC];
-    __shared__ double esave[BACK_ESAVE][256][2];
+    // the (E y) pairs of the first pass; the point pass's store transposition reuses the space once the block is through with them
+    __shared__ __attribute__((aligned(16))) double esave_raw[BACK_ESAVE * 256 * 2];
+    static_assert(4 * PT_STAGE <= BACK_ESAVE * 256 * 2, "store staging must fit the esave buffer");
+    double (*esave)[256][2] = (double (*)[256][2])esave_raw;
     if ((int)blockIdx.x >= n_pt_blocks) {
         const size_t zb = blockIdx.x - n_pt_blocks, nzb = gridDim.x - n_pt_blocks;
         const size_t total2 = (n0 + n1) / 2, per = (total2 + nzb - 1) / nzb, h0 = n0 / 2;
@@ -1072,17 +1127,25 @@ __global__ __launch_bounds__(256, 3) void ba_back_kernel(BADev P, int n_pt_block
         for (int e = threadIdx.x; e < n; e += 256) cam[e / BACK_REC][e % BACK_REC] = back_rec_value(P, cmin + e / BACK_REC, e % BACK_REC);
     }
     __syncthreads();
+    PtAcc a;
+    double Vi_n[6] = { 0, 0, 0, 0, 0, 0 }, cs_n[3] = { 0, 0, 0 };
+    if (LIN) pt_zero(a);
     if (p < P.np) {
         if (staged) {
-            ba_back_point(P, p, [&](int c) {
+            ba_back_point<LIN>(P, p, [&](int c) {
                 const double* r = &cam[c - cmin][0];
-                return BackCam{ r, r + 20, r + 23, r + 43, r + 46, r + 52 }; }, acc, esave);
+                return BackCam{ r, r + 20, r + 23, r + 43, r + 46, r + 52 }; }, acc, esave, &a, Vi_n, cs_n, next_radius, err_n);
         } else {            // the block's points span too many cameras: straight from the global arrays
-            ba_back_point(P, p, [&](int c) {
+            ba_back_point<LIN>(P, p, [&](int c) {
                 const int co = cam_off(P, c);
                 return BackCam{ P.campre + CAMPRE * (size_t)c, P.ext + 6 * c + 3, P.campre_c + CAMPRE * (size_t)c, P.extc + 6 * c + 3,
-                                P.scale_c + (co < 0 ? 0 : co), P.y + (co < 0 ? 0 : co) }; }, acc, esave);
+                                P.scale_c + (co < 0 ? 0 : co), P.y + (co < 0 ? 0 : co) }; }, acc, esave, &a, Vi_n, cs_n, next_radius, err_n);
         }
+    }
+    if (LIN) {
+        __shared__ double red_pt[4][32];
+        __syncthreads();            // every thread is through with esave
+        pt_store(P, O, esave_raw, red_pt, a, Vi_n, cs_n);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] = wave_sum(acc[i]);
@@ -1095,13 +1158,25 @@ __global__ __launch_bounds__(256, 3) void ba_back_kernel(BADev P, int n_pt_block
         P.part_back[4 * (size_t)blockIdx.x + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
     }
 }
+__global__ __launch_bounds__(256, 3) void ba_back_kernel(BADev P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1)
+{
+    ba_back_body<false>(P, n_pt_blocks, z0, n0, z1, n1, PtOut{}, 0.0, nullptr);
+}
+// The same + the point pass of the next linearisation at the candidate, damped with next_radius (the radius an accepted step
+// with rho >= 0.937 leads to), into the point-side buffer set O; a non-SPD V there raises *err_n, a flag of its own that
+// counts only once the set is adopted (ba_loop).
+__global__ __launch_bounds__(256, 3) void ba_back_kernel_lin(BADev P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1,
+                                                             PtOut O, double next_radius, int* __restrict__ err_n)
+{
+    ba_back_body<true>(P, n_pt_blocks, z0, n0, z1, n1, O, next_radius, err_n);
+}
 
 // out4 = sum over blocks of part_back
 // With host_out != nullptr (single rank: nothing is all-reduced in between) the block also publishes the decision scalars,
 // i.e. does ba_publish_kernel's job in the same launch.
 __global__ __launch_bounds__(256) void ba_back_reduce_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ out4,
                                                              const double* __restrict__ scal2, const double* __restrict__ cam2, int* __restrict__ err,
-                                                             double* __restrict__ host_out, unsigned long long seq)
+                                                             double* __restrict__ host_out, unsigned long long seq, int* __restrict__ err_fold)
 {
     __shared__ double red[4][4];
     double acc[4] = { 0, 0, 0, 0 };
@@ -1128,7 +1203,12 @@ __global__ __launch_bounds__(256) void ba_back_reduce_kernel(const double* __res
         const int l = threadIdx.x;
         if (l >= 64 && l < 66) host_out[l - 64] = scal2[l - 64];
         else if (l >= 66 && l < 68) host_out[6 + l - 66] = cam2[l - 66];
-        else if (l == 68) { host_out[8] = (double)*err; *err = 0; }
+        else if (l == 68) {
+            // err_fold: this iteration's point pass came out of the previous ba_back_kernel_lin, its non-SPD flag with it
+            int e = *err;
+            if (err_fold) { if (*err_fold != 0) e = 1; *err_fold = 0; }
+            host_out[8] = (double)e; *err = 0;
+        }
         __threadfence_system();
         __syncthreads();
         if (l == 0) __hip_atomic_store((unsigned long long*)(host_out + 15), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
