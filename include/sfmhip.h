@@ -279,6 +279,36 @@ int  sfmhip_ba_create(sfmhip_ctx*, const double* intrinsic4, const double* ext6,
                       const double* pts, int n_pt,
                       const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
                       const sfm_ba_options* opts, sfmhip_ba** out);
+/* Constant parameter blocks: ceres::Problem::SetParameterBlockConstant on any camera or point (the reference fixes camera 0 only,
+ * NView:1178) -- local / windowed BA, motion-only (all points constant), structure-only (all cameras constant), anchoring.
+ * cam_const: n_cam flags or NULL; pt_const: n_pt flags or NULL; nonzero = constant.  Camera c is constant iff
+ * (cam_const && cam_const[c]) || (c == 0 && opts->fix_first_camera); the intrinsics iff opts->fix_intrinsics.  NULL or all-zero masks
+ * give exactly what sfmhip_ba_create / _solve give.
+ *   - Constant blocks are never modified: sfmhip_ba_get_params and the _solve outputs return them bit for bit as given.  (Problems the
+ *     legacy options express -- no mask, or the mask {0} -- keep the legacy arithmetic x + 0 for camera 0 and fixed intrinsics, which
+ *     turns an input -0.0 into +0.0, as sfmhip_ba_solve always has.)
+ *   - Layout: the reduced system covers the free cameras in ascending camera index, then the intrinsics if free (today's layout with the
+ *     constant cameras' rows and columns deleted); so do sfmhip_ba_reduced_system and its n.  Its cost is the LM's cost (below).
+ *   - Fully constant observations (constant camera, constant point, fixed intrinsics) take no part in the LM loop (step, gain ratio,
+ *     function_tolerance test); their cost 1/2 sum rho(|r|^2) is computed once at create and added to initial_cost and final_cost, as
+ *     Ceres' reduced program does with its fixed cost.  num_residuals stays 2 * n_obs.
+ *   - The tolerance tests (gradient max-norm, |x|, |dx|) run over the free parameters only.
+ *   - Any block may be constant, all of them included: all cameras constant with fixed intrinsics (n = 0, structure-only), all points
+ *     constant (no Schur pairs, motion-only).  A problem with no free parameter returns SFMHIP_BA_CONVERGENCE after 0 iterations with
+ *     initial_cost == final_cost == the fixed cost.
+ *   - linearizer = 2 with a constant point runs the per-observation kernels (which store V^-1 = 0 for it), not the run tiles.
+ *   - Under an all-reduce hook a problem with constant blocks beyond camera 0 never selects the chain solver (solver 0 then means 1).
+ *     The ranks agree on it among themselves (a rank whose shard holds none of the constant points follows the others), so each
+ *     process of a multi-process run passes its own shard's pt_const.
+ *   - sfmhip_ba_debug_table reports the internal numbering, where the constant cameras come first. */
+int  sfmhip_ba_create_ex(sfmhip_ctx*, const double* intrinsic4, const double* ext6, int n_cam,
+                         const double* pts, int n_pt,
+                         const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                         const uint8_t* cam_const, const uint8_t* pt_const, const sfm_ba_options* opts, sfmhip_ba** out);
+/* sfmhip_ba_solve with constant blocks (semantics: sfmhip_ba_create_ex) */
+int  sfmhip_ba_solve_ex(sfmhip_ctx*, double* intrinsic4, double* ext6, int n_cam, double* pts, int n_pt,
+                        const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                        const uint8_t* cam_const, const uint8_t* pt_const, const sfm_ba_options* opts, sfm_ba_summary* summary);
 void sfmhip_ba_destroy(sfmhip_ba*);
 /* Multi-GPU: this rank holds a shard of the points (all their observations) and a replica of the
  * cameras/intrinsics.  The hook must sum `count` doubles at device pointer `d_buf` in place over all
@@ -312,6 +342,11 @@ int  sfmhip_rccl_allreduce_f64(sfmhip_ctx*, void* comm, void* d_buf, size_t coun
 int  sfmhip_ba_solve_multi(sfmhip_ctx* const* ctxs, int n_ctx, double* intrinsic4, double* ext6, int n_cam, double* pts, int n_pt,
                            const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
                            const sfm_ba_options* opts, sfm_ba_summary* summary);
+/* the same with constant blocks (sfmhip_ba_create_ex): cam_const is replicated on every context, pt_const sharded with its points;
+ * the fixed cost is summed over the shards.  n_ctx = 1 is sfmhip_ba_solve_ex. */
+int  sfmhip_ba_solve_multi_ex(sfmhip_ctx* const* ctxs, int n_ctx, double* intrinsic4, double* ext6, int n_cam, double* pts, int n_pt,
+                              const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                              const uint8_t* cam_const, const uint8_t* pt_const, const sfm_ba_options* opts, sfm_ba_summary* summary);
 /* match_features_for_all (NView:850-871) from HOST matrices on several GPUs of one process: the pairs in n_ctx contiguous blocks, a block's
  * images uploaded to its context only over that device's own PCIe link (a chain: a block of images + one halo image), one host thread per
  * context, no exchange; matches[p * max_per_pair ...] / counts[p] in pair order, exactly what sfmhip_descsets_create_*_host +
@@ -334,7 +369,7 @@ int  sfmhip_ba_iterate(sfmhip_ba*, int n_iter, sfm_ba_summary* summary);
 int  sfmhip_ba_reset(sfmhip_ba*);
 int  sfmhip_ba_get_params(sfmhip_ba*, double* intrinsic4, double* ext6, double* pts);
 /* Test/diagnostic: linearise at the current parameters with trust-region radius `radius` and copy
- * out the reduced camera system (order n = 6*(n_cam - fixed) + 4*(!fix_intrinsics); S row-major n x n,
+ * out the reduced camera system (order n = 6*(n_cam - constant cameras) + 4*(!fix_intrinsics); S row-major n x n,
  * both triangles filled; rhs n) after the all-reduce.  Either pointer may be NULL.  radius < 0: the points are
  * damped with |radius| but the camera-side damping is skipped, so the result is additive over point shards. */
 int  sfmhip_ba_reduced_system(sfmhip_ba*, double radius, double* S, double* rhs, int* n, double* cost);

@@ -61,6 +61,7 @@ SYMBOLS = [
     "sfmhip_rccl_available", "sfmhip_rccl_get_unique_id", "sfmhip_rccl_comm_create", "sfmhip_rccl_comm_destroy",
     "sfmhip_ba_set_rccl", "sfmhip_rccl_allreduce_f64", "sfmhip_ba_solve_multi", "sfmhip_match_pairs_multi", "sfmhip_debug_fail_allocations",
     "sfmhip_knn2_mutual_dev", "sfmhip_match_pairs_ex_dev", "sfmhip_match_pairs_ex", "sfmhip_match_pairs_multi_ex",
+    "sfmhip_ba_create_ex", "sfmhip_ba_solve_ex", "sfmhip_ba_solve_multi_ex",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -145,6 +146,9 @@ def load():
         "sfmhip_match_pairs_ex_dev": (i32, [vp, C.POINTER(vp), i32, vp, i32, f64, f32, f32, i32, vp, i32, vp]),
         "sfmhip_match_pairs_ex": (i32, [vp, C.POINTER(vp), i32, vp, i32, f64, f32, f32, i32, vp, i32, vp]),
         "sfmhip_match_pairs_multi_ex": (i32, [C.POINTER(vp), i32, i32, C.POINTER(vp), vp, i32, C.POINTER(sz), i32, vp, i32, f64, f32, f32, i32, vp, i32, vp]),
+        "sfmhip_ba_create_ex": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(BAOptions), C.POINTER(vp)]),
+        "sfmhip_ba_solve_ex": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(BAOptions), C.POINTER(BASummary)]),
+        "sfmhip_ba_solve_multi_ex": (i32, [C.POINTER(vp), i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(BAOptions), C.POINTER(BASummary)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

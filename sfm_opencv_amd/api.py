@@ -298,20 +298,28 @@ class Context:
             setattr(o, k, v)
         return o
 
-    def ba_create(self, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None):
-        return BAProblem(self, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts)
+    def ba_create(self, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None, cam_const=None, pt_const=None):
+        """cam_const / pt_const: per-camera / per-point flags (bool or uint8), nonzero = constant (sfmhip_ba_create_ex); None: none"""
+        return BAProblem(self, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts, cam_const, pt_const)
 
-    def ba_solve(self, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None):
-        """One-shot sfmhip_ba_solve on copies; returns (K4, ext, pts, summary dict)."""
+    def ba_solve(self, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None, cam_const=None, pt_const=None):
+        """One-shot sfmhip_ba_solve on copies; returns (K4, ext, pts, summary dict).  cam_const / pt_const: as ba_create
+        (sfmhip_ba_solve_ex)."""
         K4 = np.array(K4, np.float64).reshape(4).copy(); ext = np.array(ext, np.float64).reshape(-1, 6).copy()
         pts = np.array(pts, np.float64).reshape(-1, 3).copy()
         oc = np.ascontiguousarray(obs_cam, np.int32); op = np.ascontiguousarray(obs_pt, np.int32)
         uv = np.ascontiguousarray(obs_uv, np.float64).reshape(-1, 2)
         o = opts if opts is not None else self.ba_options()
         s = BASummary()
-        self._check(self.lib.sfmhip_ba_solve(self.h, K4.ctypes.data, ext.ctypes.data, ext.shape[0], pts.ctypes.data,
-                                             pts.shape[0], oc.ctypes.data, op.ctypes.data, uv.ctypes.data, oc.shape[0],
-                                             C.byref(o), C.byref(s)))
+        if cam_const is None and pt_const is None:
+            self._check(self.lib.sfmhip_ba_solve(self.h, K4.ctypes.data, ext.ctypes.data, ext.shape[0], pts.ctypes.data,
+                                                 pts.shape[0], oc.ctypes.data, op.ctypes.data, uv.ctypes.data, oc.shape[0],
+                                                 C.byref(o), C.byref(s)))
+        else:
+            cm, pm = _const_mask(cam_const, ext.shape[0]), _const_mask(pt_const, pts.shape[0])
+            self._check(self.lib.sfmhip_ba_solve_ex(self.h, K4.ctypes.data, ext.ctypes.data, ext.shape[0], pts.ctypes.data,
+                                                    pts.shape[0], oc.ctypes.data, op.ctypes.data, uv.ctypes.data, oc.shape[0],
+                                                    _mask_ptr(cm), _mask_ptr(pm), C.byref(o), C.byref(s)))
         return K4, ext, pts, s.asdict()
 
     # ---------------------------------------------------------------- normals
@@ -322,10 +330,35 @@ class Context:
         return out
 
 
-class BAProblem:
-    """HBM-resident BA problem (sfmhip_ba_create)."""
+def _const_mask(m, n):
+    """None, or a contiguous uint8 array of n flags (bool / integer input)"""
+    if m is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(m).reshape(-1) != 0, np.uint8)
+    if a.shape[0] != n:
+        raise ValueError(f"constant mask of {a.shape[0]} entries for {n} blocks")
+    return a
 
-    def __init__(self, ctx, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None):
+
+def _mask_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _index_mask(idx, n):
+    """index list -> uint8 flags (None stays None)"""
+    if idx is None:
+        return None
+    idx = np.asarray(idx, np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= n):
+        raise ValueError("constant block index out of range")
+    m = np.zeros(n, np.uint8); m[idx] = 1
+    return m
+
+
+class BAProblem:
+    """HBM-resident BA problem (sfmhip_ba_create; with cam_const / pt_const: sfmhip_ba_create_ex)."""
+
+    def __init__(self, ctx, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None, cam_const=None, pt_const=None):
         self.ctx = ctx
         K4 = np.ascontiguousarray(K4, np.float64).reshape(4); ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)
         pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
@@ -335,8 +368,14 @@ class BAProblem:
         o = opts if opts is not None else ctx.ba_options()
         self.opts = o
         h = C.c_void_p()
-        ctx._check(ctx.lib.sfmhip_ba_create(ctx.h, K4.ctypes.data, ext.ctypes.data, self.n_cam, pts.ctypes.data, self.n_pt,
-                                            oc.ctypes.data, op.ctypes.data, uv.ctypes.data, self.n_obs, C.byref(o), C.byref(h)))
+        if cam_const is None and pt_const is None:
+            ctx._check(ctx.lib.sfmhip_ba_create(ctx.h, K4.ctypes.data, ext.ctypes.data, self.n_cam, pts.ctypes.data, self.n_pt,
+                                                oc.ctypes.data, op.ctypes.data, uv.ctypes.data, self.n_obs, C.byref(o), C.byref(h)))
+        else:
+            cm, pm = _const_mask(cam_const, self.n_cam), _const_mask(pt_const, self.n_pt)
+            ctx._check(ctx.lib.sfmhip_ba_create_ex(ctx.h, K4.ctypes.data, ext.ctypes.data, self.n_cam, pts.ctypes.data, self.n_pt,
+                                                   oc.ctypes.data, op.ctypes.data, uv.ctypes.data, self.n_obs, _mask_ptr(cm), _mask_ptr(pm),
+                                                   C.byref(o), C.byref(h)))
         self.h = h
         self._cb = None
 
@@ -410,9 +449,9 @@ class BAProblem:
             pass
 
 
-def ba_solve_multi(ctxs, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None):
+def ba_solve_multi(ctxs, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None, cam_const=None, pt_const=None):
     """sfmhip_ba_solve_multi on copies: one context per GPU of this process (two contexts on one device: host-staged rehearsal).
-    Returns (K4, ext, pts, summary dict)."""
+    cam_const / pt_const: as Context.ba_create (sfmhip_ba_solve_multi_ex).  Returns (K4, ext, pts, summary dict)."""
     K4 = np.array(K4, np.float64).reshape(4).copy(); ext = np.array(ext, np.float64).reshape(-1, 6).copy()
     pts = np.array(pts, np.float64).reshape(-1, 3).copy()
     oc = np.ascontiguousarray(obs_cam, np.int32); op = np.ascontiguousarray(obs_pt, np.int32)
@@ -420,8 +459,14 @@ def ba_solve_multi(ctxs, K4, ext, pts, obs_cam, obs_pt, obs_uv, opts=None):
     o = opts if opts is not None else ctxs[0].ba_options()
     s = BASummary()
     arr = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
-    ctxs[0]._check(ctxs[0].lib.sfmhip_ba_solve_multi(arr, len(ctxs), K4.ctypes.data, ext.ctypes.data, ext.shape[0], pts.ctypes.data, pts.shape[0],
-                                                      oc.ctypes.data, op.ctypes.data, uv.ctypes.data, oc.shape[0], C.byref(o), C.byref(s)))
+    if cam_const is None and pt_const is None:
+        ctxs[0]._check(ctxs[0].lib.sfmhip_ba_solve_multi(arr, len(ctxs), K4.ctypes.data, ext.ctypes.data, ext.shape[0], pts.ctypes.data, pts.shape[0],
+                                                          oc.ctypes.data, op.ctypes.data, uv.ctypes.data, oc.shape[0], C.byref(o), C.byref(s)))
+    else:
+        cm, pm = _const_mask(cam_const, ext.shape[0]), _const_mask(pt_const, pts.shape[0])
+        ctxs[0]._check(ctxs[0].lib.sfmhip_ba_solve_multi_ex(arr, len(ctxs), K4.ctypes.data, ext.ctypes.data, ext.shape[0], pts.ctypes.data,
+                                                             pts.shape[0], oc.ctypes.data, op.ctypes.data, uv.ctypes.data, oc.shape[0],
+                                                             _mask_ptr(cm), _mask_ptr(pm), C.byref(o), C.byref(s)))
     return K4, ext, pts, s.asdict()
 
 
@@ -531,10 +576,12 @@ def reconstruct(K, R1, T1, R2, T2, p1, p2, ctx=None):
     return 0, xyz
 
 
-def bundle_adjustment(intrinsic, extrinsics, correspond_struct_idx, key_points_for_all, structure, ctx=None, opts=None):
+def bundle_adjustment(intrinsic, extrinsics, correspond_struct_idx, key_points_for_all, structure, ctx=None, opts=None,
+                      const_cameras=None, const_points=None):
     """NViewReconstuct.cpp:1162-1244.  intrinsic (4,), extrinsics (n_cam,6), structure (n_pt,3) are updated IN PLACE
     (numpy float64 arrays); correspond_struct_idx[img][kp] = point id or -1; key_points_for_all[img] = KEYPOINT array
-    or (n,2) float array.  Returns the summary dict and prints the reference's statistics block."""
+    or (n,2) float array.  const_cameras / const_points: index lists of blocks held constant (on top of camera 0 while
+    opts.fix_first_camera is set; sfmhip_ba_solve_ex).  Returns the summary dict and prints the reference's statistics block."""
     ctx = ctx or default_context()
     oc, op, uv = [], [], []
     for img, ids in enumerate(correspond_struct_idx):
@@ -545,7 +592,9 @@ def bundle_adjustment(intrinsic, extrinsics, correspond_struct_idx, key_points_f
         oc.append(np.full(sel.shape[0], img, np.int32)); op.append(ids[sel].astype(np.int32))
         uv.append(xy[sel].astype(np.float32).astype(np.float64))      # Point2d observed = key_points[pt_id].pt (1199)
     oc = np.concatenate(oc); op = np.concatenate(op); uv = np.concatenate(uv)
-    K4, ext, pts, s = ctx.ba_solve(intrinsic, extrinsics, structure, oc, op, uv, opts)
+    n_cam, n_pt = len(extrinsics), len(structure)
+    K4, ext, pts, s = ctx.ba_solve(intrinsic, extrinsics, structure, oc, op, uv, opts,
+                                   cam_const=_index_mask(const_cameras, n_cam), pt_const=_index_mask(const_points, n_pt))
     np.copyto(intrinsic, K4.reshape(np.shape(intrinsic))); np.copyto(extrinsics, ext.reshape(np.shape(extrinsics)))
     np.copyto(structure, pts.reshape(np.shape(structure)))
     if s["termination"] == 2:

@@ -171,7 +171,20 @@ __global__ void fill_kernel(double* __restrict__ p, size_t n, double v)
 struct sfmhip_ba {
     sfmhip_ctx* ctx = nullptr;
     sfm_ba_options o;
-    int nc = 0, np = 0, nobs = 0, fix0 = 0, fixK = 0, ncf = 0, n = 0, npad = 0, koff = 0, nbk = 0;
+    int nc = 0, np = 0, nobs = 0, nfix = 0, fixK = 0, ncf = 0, n = 0, npad = 0, koff = 0, nbk = 0;
+    // constant blocks (sfmhip_ba_create_ex).  Cameras are numbered internally with the nfix constant ones first (each group in the
+    // caller's order): cam_order[internal] = caller's index, empty when that is the identity (always so for the legacy entry points).
+    // Points: one flag per slot (d_ptfix, null when every point is free).  Observations with a constant camera, a constant point and
+    // fixed intrinsics are dropped at create; their cost is fixed_cost, added to the summary's costs.
+    std::vector<int> cam_order;
+    unsigned char* d_ptfix = nullptr;
+    long long n_free_pts = 0;
+    int nobs_all = 0;              // observations given at create (num_residuals = 2 nobs_all), nobs = those the LM loop sees
+    double fixed_cost = 0.0;
+    // constant blocks beyond the legacy camera 0 (decided at create from this problem's masks; under an all-reduce hook OR-ed over the
+    // ranks in build_solver_plan, so that every rank agrees): the chain solver is not used under a hook, and sfmhip_ba_get_params
+    // returns constant cameras and fixed intrinsics with the bits given at create
+    bool masked = false;
     int cam_split = 1, n_pt_blocks = 0, nblk = 0, rank = 0, world = 1;
     std::vector<void*> allocs;
     // parameters
@@ -296,12 +309,12 @@ static BADev make_dev(const sfmhip_ba* h, double radius, bool at_candidate = fal
     BADev P;
     memset(&P, 0, sizeof P);
     P.nc = h->nc; P.np = h->np; P.nobs = h->nobs; P.n = h->n; P.npad = h->npad; P.koff = h->koff;
-    P.fix0 = h->fix0; P.fixK = h->fixK; P.cam_split = h->cam_split; P.world = h->world; P.rank = h->rank;
+    P.fix0 = h->nfix; P.fixK = h->fixK; P.cam_split = h->cam_split; P.world = h->world; P.rank = h->rank;
     P.huber_a = h->o.huber_delta;
     P.K = h->d_K; P.ext = h->d_ext; P.pts = h->d_pts; P.Kc = h->d_Kc; P.extc = h->d_extc; P.ptsc = h->d_ptsc;
     P.pt_start = h->d_pt_start; P.ocam = h->d_ocam; P.ouv = h->d_ouv;
     P.cam_start = h->d_cam_start; P.cam_pt = h->d_cam_pt; P.cam_uv = h->d_cam_uv; P.opt = h->d_opt; P.blk_crange = h->d_blk_crange;
-    P.cam_pos = h->d_cam_pos; P.posmask = h->d_posmask;
+    P.cam_pos = h->d_cam_pos; P.posmask = h->d_posmask; P.ptfix = h->d_ptfix;
     P.campre = h->d_campre; P.campre_c = h->d_campre_c;
     P.scale_c = h->d_scale_c; P.scale_p = h->d_scale_p;
     P.Vinv = h->d_Vinv; P.bp = h->d_bp; P.WK = h->d_WK; P.colsq_p = h->d_colsq_p;
@@ -371,7 +384,8 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
     }
     // the point pass: already there if the last back-substitution computed it at what is now the current point (ba_loop)
     if (h->pt_ready && !at_candidate) { h->pt_ready = false; h->pt_fold_err = true; }
-    else hipLaunchKernelGGL(ba_point_kernel, dim3(h->n_pt_blocks), dim3(256), 0, st, P, h->d_err);
+    else if (h->d_ptfix) hipLaunchKernelGGL(ba_point_kernel<true>, dim3(h->n_pt_blocks), dim3(256), 0, st, P, h->d_err);
+    else hipLaunchKernelGGL(ba_point_kernel<false>, dim3(h->n_pt_blocks), dim3(256), 0, st, P, h->d_err);
     // camera items and pair chunks in one launch, then their folds in one launch (ba_kernels.hpp: ba_camschur_kernel)
     const int n_cam_blocks = round_up(h->nc * h->cam_split * (h->fixK ? 1 : 2), 8);
     const int n_schur_blocks = h->nblk > 0 ? round_up(ceil_div(h->nchunk, 4), 8) : 0;
@@ -556,9 +570,15 @@ static int enqueue_back(sfmhip_ba* h, double radius, double lin_radius = 0.0)
     int* err_fold = fuse_publish && h->pt_fold_err ? h->d_err_pt + h->err_cur : nullptr;
     if (lin_radius > 0.0) {
         const PtOut O = { h->d_Vinv2, h->d_bp2, h->d_WK2, h->d_colsq_p2, h->d_part_pt2 };
-        hipLaunchKernelGGL(ba_back_kernel_lin, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1, O, lin_radius,
-                           h->d_err_pt + (h->err_cur ^ 1));
-    } else
+        if (h->d_ptfix)
+            hipLaunchKernelGGL(ba_back_lin_const_kernel, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1, O, lin_radius,
+                               h->d_err_pt + (h->err_cur ^ 1));
+        else
+            hipLaunchKernelGGL(ba_back_kernel_lin, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1, O, lin_radius,
+                               h->d_err_pt + (h->err_cur ^ 1));
+    } else if (h->d_ptfix)
+        hipLaunchKernelGGL(ba_back_const_kernel, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1);
+    else
         hipLaunchKernelGGL(ba_back_kernel, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1);
     hipLaunchKernelGGL(ba_back_reduce_kernel, dim3(1), dim3(256), 0, st, h->d_part_back, h->n_pt_blocks, h->d_back4,
                        d_scal, h->d_cam2, h->d_err, fuse_publish ? h->h_scal : (double*)nullptr, fuse_publish ? ++h->pub_seq : 0ull, err_fold);
@@ -593,19 +613,24 @@ static int solver_pick_leaves(int ncf, int w)
 static int build_solver_plan(sfmhip_ba* h)
 {
     sfmhip_ctx* ctx = h->ctx;
-    const int nc = h->nc, ncf = h->ncf, f0 = h->fix0;
-    // ---- 1. adjacency among free cameras (index i = c - fix0)
+    const int nc = h->nc, ncf = h->ncf, f0 = h->nfix;
+    // ---- 1. adjacency among free cameras (index i = c - nfix: the constant cameras are numbered first)
     std::vector<double> adj((size_t)ncf * ncf, 0.0);
     for (size_t b = 0; b + 1 < h->host_blk_cam.size(); b += 2) {
         const int a = h->host_blk_cam[b] - f0, c = h->host_blk_cam[b + 1] - f0;
         adj[(size_t)a * ncf + c] = 1.0; adj[(size_t)c * ncf + a] = 1.0;
     }
     if (h->ar_fn && ncf > 0) {
+        // one more entry: this rank's "masked" flag (a rank may hold none of the constant points), summed with the adjacency so that
+        // every rank takes the same solver
+        adj.push_back(h->masked ? 1.0 : 0.0);
         if (adj.size() > h->msg_count) { ctx->last_error = "adjacency larger than the message buffer"; return SFMHIP_E_ARG; }
         SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_msg, adj.data(), adj.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         int rc = call_allreduce(h, h->d_msg, adj.size()); if (rc) return rc;
         SFM_HIP_TRY(ctx, hipMemcpyAsync(adj.data(), h->d_msg, adj.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (adj.back() != 0.0) h->masked = true;
+        adj.pop_back();
     }
     int w = 0;
     for (int a = 0; a < ncf; ++a) for (int c = 0; c < a; ++c) if (adj[(size_t)a * ncf + c] != 0.0) w = std::max(w, a - c);
@@ -621,7 +646,9 @@ static int build_solver_plan(sfmhip_ba* h)
     ChainArgs chain_args;
     memset(&chain_args, 0, sizeof chain_args);
     bool chain_ok = false;
-    if (h->o.solver == 0 && !h->force_dense && ncf >= 12 && ncf <= 640) {
+    // Not with constant blocks under an all-reduce hook: the chain solver reads entries of S above the diagonal, which the packed
+    // all-reduce message does not carry (first finding; unmasked problems keep the selection they had).
+    if (h->o.solver == 0 && !h->force_dense && ncf >= 12 && ncf <= 640 && !(h->masked && h->ar_fn)) {
         const int npad_nat = std::max(NB, round_up(6 * ncf + (h->fixK ? 0 : 4), NB));
         chain_ok = npad_nat <= h->npad_max && chain_plan(chain_args, ncf, w, h->fixK ? 0 : 4, npad_nat, npad_nat, 0, -1, 0, (size_t)160 << 10);
     }
@@ -1025,7 +1052,7 @@ static int ba_start(sfmhip_ba* h)
         SFM_HIP_TRY(ctx, hipMemcpy(K.data(), h->d_K, 4 * sizeof(double), hipMemcpyDeviceToHost));
         SFM_HIP_TRY(ctx, hipMemcpy(ext.data(), h->d_ext, ext.size() * sizeof(double), hipMemcpyDeviceToHost));
         if (!h->fixK) for (int i = 0; i < 4; ++i) cam += K[i] * K[i];
-        for (int c = h->fix0; c < h->nc; ++c) for (int j = 0; j < 6; ++j) cam += ext[6 * c + j] * ext[6 * c + j];
+        for (int c = h->nfix; c < h->nc; ++c) for (int j = 0; j < 6; ++j) cam += ext[6 * c + j] * ext[6 * c + j];
         double pt = s - cam;
         SFM_HIP_TRY(ctx, hipMemcpy(h->d_back4, &pt, sizeof(double), hipMemcpyHostToDevice));
         int rc = call_allreduce(h, h->d_back4, 1); if (rc) return rc;
@@ -1061,6 +1088,12 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
     const sfm_ba_options& o = h->o;
+    if (h->n == 0 && h->n_free_pts == 0 && !h->ar_fn) {
+        // no free parameter (every camera and point constant, intrinsics fixed): nothing to minimise, the cost is the fixed part
+        h->iter = 0; h->nsucc = 0; h->initial_cost = 0.0; h->x_cost = 0.0; h->gmax = 0.0; h->radius = o.initial_trust_region_radius;
+        h->termination = SFMHIP_BA_CONVERGENCE;
+        return SFMHIP_OK;
+    }
     if (!h->started) { const auto ts = std::chrono::steady_clock::now(); int rc = drop_point_pass(h); if (rc) return rc; rc = ba_start(h); if (rc) return rc; h->start_ms = ms_since(ts); }
     const int it_end = h->iter + max_it;
     const size_t np2 = (size_t)h->npad * h->npad;
@@ -1194,7 +1227,7 @@ static void fill_summary(const sfmhip_ba* h, sfm_ba_summary* s, double t_s)
 {
     if (!s) return;
     s->termination = h->termination; s->iterations = h->iter; s->successful_steps = h->nsucc;
-    s->num_residuals = 2 * h->nobs; s->initial_cost = h->initial_cost < 0 ? 0.0 : h->initial_cost; s->final_cost = h->x_cost;
+    s->num_residuals = 2 * h->nobs_all; s->initial_cost = (h->initial_cost < 0 ? 0.0 : h->initial_cost) + h->fixed_cost; s->final_cost = h->x_cost + h->fixed_cost;
     s->final_radius = h->radius; s->final_gradient_max_norm = h->gmax; s->total_time_s = t_s;
     // a resident problem: the call's own share (sfmhip_ba_solve overwrites these with the whole call, as Ceres reports it)
     s->preprocessor_time_s = h->start_ms * 1e-3; s->minimizer_time_s = t_s - h->start_ms * 1e-3; s->postprocessor_time_s = 0.0;
@@ -1220,7 +1253,7 @@ struct SetupTemps {
 // from all over HBM (C4 on MI355X: linearisation 0.41 -> 0.31 ms, back-substitution 0.13 -> 0.08 ms) --, a point's
 // observations in ascending camera order (the k-th observation of every point of a run then belongs to the same camera,
 // which the run tiles rely on), the camera-ordered copy, and the camera-pair lists for the off-diagonal Schur blocks.
-static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv)
+static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, const uint8_t* pt_const)
 {
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
@@ -1293,6 +1326,12 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
         if (np) hipLaunchKernelGGL(setup_slot_kernel, dim3(gpt), dim3(256), 0, st, (const su32*)V[0], np, (const su32*)st_pt, h->d_slot, (su32*)h->d_pt_start);
         setup_enqueue_scan(st, (su32*)h->d_pt_start, (size_t)np + 1, bsum, nullptr);
     }
+    if (pt_const && np) {           // constant points: the caller's flags into slot order
+        unsigned char* d_flags_in = nullptr;
+        TRY_RC(T.get(&d_flags_in, (size_t)np)); TRY_RC(dalloc(h, &h->d_ptfix, (size_t)np));
+        TRY_RC(sfm_upload(ctx, d_flags_in, pt_const, (size_t)np));
+        hipLaunchKernelGGL(setup_slot_flags_kernel, dim3(gpt), dim3(256), 0, st, (const unsigned char*)d_flags_in, (const int*)h->d_slot, np, h->d_ptfix);
+    }
     stamp("point sort");
     // ---- observations and points into storage order, the camera-ordered copy, the camera range of every 256 points
     if (nobs) {
@@ -1317,7 +1356,7 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     TRY_RC(T.get(&npair, (size_t)np + 1));
     SFM_HIP_TRY(ctx, hipMemsetAsync(npair, 0, ((size_t)np + 1) * sizeof(su32), st));
     SFM_HIP_TRY(ctx, hipMemsetAsync(d_total + 1, 0, sizeof(su64), st));
-    if (np) hipLaunchKernelGGL(setup_pair_count_kernel, dim3(gpt), dim3(256), 0, st, (const int*)h->d_pt_start, (const int*)h->d_ocam, np, h->fix0, npair, d_total + 1);
+    if (np) hipLaunchKernelGGL(setup_pair_count_kernel, dim3(gpt), dim3(256), 0, st, (const int*)h->d_pt_start, (const int*)h->d_ocam, np, h->nfix, (const unsigned char*)h->d_ptfix, npair, d_total + 1);
     setup_enqueue_scan(st, npair, (size_t)np + 1, bsum, d_total);
     su64 total_pairs = 0;
     std::vector<int> cam_start((size_t)nc + 1);
@@ -1339,7 +1378,7 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
         for (int i = 0; i < 2; ++i) { TRY_RC(T.get(&pK[i], npairs)); TRY_RC(T.get(&pV[i], npairs)); }
         TRY_RC(T.get(&raw, npairs)); TRY_RC(T.get(&flag, npairs + 1));
         TRY_RC(T.get(&hist2, 256 * setup_rs_tiles(npairs) + 1)); TRY_RC(T.get(&bsum2, setup_scan_tiles(std::max(256 * setup_rs_tiles(npairs), npairs + 1)) + 1));
-        hipLaunchKernelGGL(setup_pair_gen_kernel, dim3(gobs), dim3(256), 0, st, (const int*)h->d_pt_start, (const int*)h->d_ocam, (const int*)h->d_opt, nobs, h->fix0, nc,
+        hipLaunchKernelGGL(setup_pair_gen_kernel, dim3(gobs), dim3(256), 0, st, (const int*)h->d_pt_start, (const int*)h->d_ocam, (const int*)h->d_opt, nobs, h->nfix, (const unsigned char*)h->d_ptfix, nc,
                            (const su32*)npair, pK[0], raw);
         stamp("pair generation");
         SetupSortBufs B = { { pK[0], pK[1] }, { pV[0], pV[1] }, hist2, bsum2 };
@@ -1397,7 +1436,8 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     // ---- run tiles (opt-in linearizer = 2): runs of points with one camera list, cut into segments of <= seg_max points (one
     // workgroup each).  Host pass over the finished tables.
     h->tsegs.clear(); h->tcams.clear(); h->n_tseg = 0; h->n_ttiles = 0; h->use_tiles = false;
-    if (h->o.linearizer == 2 && np > 0) {
+    // (not with constant points: those problems run the per-observation kernels, which store V^-1 = 0 for them)
+    if (h->o.linearizer == 2 && np > 0 && !h->d_ptfix) {
         std::vector<int> pt_start((size_t)np + 1), ocam((size_t)nobs);
         SFM_HIP_TRY(ctx, hipMemcpy(pt_start.data(), h->d_pt_start, pt_start.size() * sizeof(int), hipMemcpyDeviceToHost));
         if (nobs) SFM_HIP_TRY(ctx, hipMemcpy(ocam.data(), h->d_ocam, ocam.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -1475,21 +1515,104 @@ void sfmhip_ba_destroy(sfmhip_ba* h)
     delete h;
 }
 
-int sfmhip_ba_create(sfmhip_ctx* ctx, const double* K4, const double* ext6, int n_cam, const double* pts, int n_pt,
-                     const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
-                     const sfm_ba_options* opts, sfmhip_ba** out)
+}  // extern "C"
+
+// 1/2 rho(|r|^2) of one observation on the host (ReprojectCost, ceres::AngleAxisRotatePoint incl. its small-angle branch, Huber):
+// the fixed cost of the observations sfmhip_ba_create_ex drops.  The camera's angle, sine, cosine and axis are taken once per camera
+// (HostRot): the same values the formula derives per observation.
+struct HostRot { bool big; double c, s, w[3]; };
+static HostRot host_rot(const double* e)
+{
+    HostRot r; r.big = false; r.c = r.s = 0.0; r.w[0] = r.w[1] = r.w[2] = 0.0;
+    const double th2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
+    if (th2 > DBL_EPSILON) {
+        const double th = std::sqrt(th2);
+        r.big = true; r.c = std::cos(th); r.s = std::sin(th);
+        for (int k = 0; k < 3; ++k) r.w[k] = e[k] / th;
+    }
+    return r;
+}
+static double host_obs_cost(const double* K4, const double* e, const HostRot& R, const double* X, double u, double v, double huber_a)
+{
+    double p[3];
+    if (R.big) {
+        const double* w = R.w;
+        const double wx[3] = { w[1] * X[2] - w[2] * X[1], w[2] * X[0] - w[0] * X[2], w[0] * X[1] - w[1] * X[0] };
+        const double tmp = (w[0] * X[0] + w[1] * X[1] + w[2] * X[2]) * (1.0 - R.c);
+        for (int k = 0; k < 3; ++k) p[k] = X[k] * R.c + wx[k] * R.s + w[k] * tmp;
+    } else {
+        p[0] = X[0] + (e[1] * X[2] - e[2] * X[1]);
+        p[1] = X[1] + (e[2] * X[0] - e[0] * X[2]);
+        p[2] = X[2] + (e[0] * X[1] - e[1] * X[0]);
+    }
+    for (int k = 0; k < 3; ++k) p[k] += e[3 + k];
+    const double r0 = K4[0] * (p[0] / p[2]) + K4[2] - u, r1 = K4[1] * (p[1] / p[2]) + K4[3] - v;
+    const double sq = r0 * r0 + r1 * r1;
+    const double rho = (huber_a > 0.0 && sq > huber_a * huber_a) ? 2.0 * huber_a * std::sqrt(sq) - huber_a * huber_a : sq;
+    return 0.5 * rho;
+}
+
+// sfmhip_ba_create_ex
+static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6, int n_cam, const double* pts, int n_pt,
+                          const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                          const uint8_t* cam_const, const uint8_t* pt_const, const sfm_ba_options* opts, sfmhip_ba** out)
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_ba_create");
     SFM_ARG_CHECK(ctx, ctx && out && K4 && ext6 && n_cam > 0 && n_pt >= 0 && n_obs >= 0);
     SFM_ARG_CHECK(ctx, (pts || n_pt == 0) && ((obs_cam && obs_pt && obs_uv) || n_obs == 0));
     const auto t0 = std::chrono::steady_clock::now();
+    sfm_ba_options oo;
+    if (opts) oo = *opts; else sfmhip_ba_default_options(&oo);
+    // ---- constant blocks: the camera set (mask OR the legacy camera 0), its numbering, the constant points, the dropped observations
+    std::vector<char> cfix((size_t)n_cam, 0);
+    int nfix = 0;
+    for (int c = 0; c < n_cam; ++c) { cfix[c] = (cam_const && cam_const[c]) || (c == 0 && oo.fix_first_camera); nfix += cfix[c]; }
+    std::vector<int> order, inv;            // internal -> caller, caller -> internal (empty: identity)
+    bool identity = true;
+    for (int c = 0; c < n_cam; ++c) if (cfix[c] != (c < nfix)) identity = false;
+    if (!identity) {
+        order.reserve((size_t)n_cam); inv.assign((size_t)n_cam, 0);
+        for (int pass = 1; pass >= 0; --pass) for (int c = 0; c < n_cam; ++c) if (cfix[c] == pass) { inv[c] = (int)order.size(); order.push_back(c); }
+    }
+    long long n_pfix = 0;
+    if (pt_const) for (int p = 0; p < n_pt; ++p) n_pfix += pt_const[p] ? 1 : 0;
+    const uint8_t* ptc = n_pfix ? pt_const : nullptr;
+    std::vector<int32_t> oc2, op2; std::vector<double> uv2, ext2;
+    double fixed_cost = 0.0;
+    const bool filtered = !identity || (ptc && oo.fix_intrinsics);
+    if (filtered) {
+        std::vector<HostRot> rot;
+        if (ptc && oo.fix_intrinsics) { rot.resize((size_t)n_cam); for (int c = 0; c < n_cam; ++c) if (cfix[c]) rot[c] = host_rot(ext6 + 6 * (size_t)c); }
+        oc2.reserve((size_t)n_obs); op2.reserve((size_t)n_obs); uv2.reserve(2 * (size_t)n_obs);
+        for (int k = 0; k < n_obs; ++k) {
+            const int c = obs_cam[k], p = obs_pt[k];
+            const bool valid = c >= 0 && c < n_cam && p >= 0 && p < n_pt;        // invalid ones are kept: the device set-up rejects them
+            if (valid && ptc && oo.fix_intrinsics && cfix[c] && ptc[p]) {
+                fixed_cost += host_obs_cost(K4, ext6 + 6 * (size_t)c, rot[c], pts + 3 * (size_t)p, obs_uv[2 * (size_t)k], obs_uv[2 * (size_t)k + 1], oo.huber_delta);
+                continue;
+            }
+            oc2.push_back(valid && !identity ? inv[c] : c); op2.push_back(p);
+            uv2.push_back(obs_uv[2 * (size_t)k]); uv2.push_back(obs_uv[2 * (size_t)k + 1]);
+        }
+        if (!identity) {
+            ext2.resize(6 * (size_t)n_cam);
+            for (int i = 0; i < n_cam; ++i) std::copy(ext6 + 6 * (size_t)order[i], ext6 + 6 * (size_t)order[i] + 6, ext2.begin() + 6 * (size_t)i);
+            ext6 = ext2.data();
+        }
+        obs_cam = oc2.data(); obs_pt = op2.data(); obs_uv = uv2.data();
+    }
+    const int n_obs_all = n_obs;
+    if (filtered) n_obs = (int)oc2.size();
     sfmhip_ba* h = new sfmhip_ba();
     h->ctx = ctx;
-    if (opts) h->o = *opts; else sfmhip_ba_default_options(&h->o);
-    h->nc = n_cam; h->np = n_pt; h->nobs = n_obs;
-    h->fix0 = h->o.fix_first_camera ? 1 : 0; h->fixK = h->o.fix_intrinsics ? 1 : 0;
-    h->ncf = n_cam - h->fix0; h->koff = 6 * h->ncf; h->n = 6 * h->ncf + (h->fixK ? 0 : 4);
+    h->o = oo;
+    h->nc = n_cam; h->np = n_pt; h->nobs = n_obs; h->nobs_all = n_obs_all;
+    h->cam_order = order; h->fixed_cost = fixed_cost; h->n_free_pts = n_pt - n_pfix;
+    // masked: a constant set the legacy options cannot express (more than camera 0, or any point of this problem)
+    h->masked = n_pfix > 0 || !(nfix == 0 || (nfix == 1 && cfix[0]));
+    h->nfix = nfix; h->fixK = h->o.fix_intrinsics ? 1 : 0;
+    h->ncf = n_cam - h->nfix; h->koff = 6 * h->ncf; h->n = 6 * h->ncf + (h->fixK ? 0 : 4);
     h->npad = std::max(NB, round_up(h->n, NB)); h->nbk = h->npad / NB;
     // room for the per-node padding of the nested-dissection layout: up to solver_pmax leaves and as many separators
     h->solver_pmax = 1; while (h->solver_pmax < 64 && h->solver_pmax * 16 <= h->ncf) h->solver_pmax *= 2;
@@ -1505,7 +1628,7 @@ int sfmhip_ba_create(sfmhip_ctx* ctx, const double* K4, const double* ext6, int 
 
     int rc = SFMHIP_OK;
 #define TRY_RC(x) do { rc = (x); if (rc) { sfmhip_ba_destroy(h); return rc; } } while (0)
-    TRY_RC(ba_build_orderings(h, pts, obs_cam, obs_pt, obs_uv));
+    TRY_RC(ba_build_orderings(h, pts, obs_cam, obs_pt, obs_uv, ptc));
     TRY_RC(dupload(h, &h->d_K, K4, 4)); TRY_RC(dupload(h, &h->d_ext, ext6, 6 * (size_t)n_cam));
     TRY_RC(dupload(h, &h->d_K0, K4, 4)); TRY_RC(dupload(h, &h->d_ext0, ext6, 6 * (size_t)n_cam));
     TRY_RC(dupload(h, &h->d_Kc, K4, 4)); TRY_RC(dupload(h, &h->d_extc, ext6, 6 * (size_t)n_cam));
@@ -1557,6 +1680,25 @@ int sfmhip_ba_create(sfmhip_ctx* ctx, const double* K4, const double* ext6, int 
                h->setup_ms[1] - h->setup_ms[0], h->setup_ms[2] - h->setup_ms[1]);
     *out = h;
     return SFMHIP_OK;
+}
+
+// the fixed cost of a problem (sfmhip_ba_solve_multi_ex sums it over the shards)
+double sfm_ba_fixed_cost(const sfmhip_ba* h) { return h ? h->fixed_cost : 0.0; }
+
+extern "C" {
+
+int sfmhip_ba_create_ex(sfmhip_ctx* ctx, const double* K4, const double* ext6, int n_cam, const double* pts, int n_pt,
+                        const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                        const uint8_t* cam_const, const uint8_t* pt_const, const sfm_ba_options* opts, sfmhip_ba** out)
+{
+    return ba_create_impl(ctx, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, cam_const, pt_const, opts, out);
+}
+
+int sfmhip_ba_create(sfmhip_ctx* ctx, const double* K4, const double* ext6, int n_cam, const double* pts, int n_pt,
+                     const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                     const sfm_ba_options* opts, sfmhip_ba** out)
+{
+    return ba_create_impl(ctx, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, nullptr, nullptr, opts, out);
 }
 
 int sfmhip_ba_set_allreduce(sfmhip_ba* h, sfmhip_allreduce_fn fn, void* user, int rank, int world)
@@ -1613,12 +1755,28 @@ int sfmhip_ba_get_params(sfmhip_ba* h, double* K4, double* ext6, double* pts)
     if (!h) return SFMHIP_E_ARG;
     sfmhip_ctx* ctx = h->ctx;
     SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (K4) SFM_HIP_TRY(ctx, hipMemcpy(K4, h->d_K, 4 * sizeof(double), hipMemcpyDeviceToHost));
-    if (ext6) SFM_HIP_TRY(ctx, hipMemcpy(ext6, h->d_ext, 6 * (size_t)h->nc * sizeof(double), hipMemcpyDeviceToHost));
+    // fixed intrinsics of a masked problem: the bits given at create (see the cameras below)
+    if (K4) SFM_HIP_TRY(ctx, hipMemcpy(K4, h->masked && h->fixK ? h->d_K0 : h->d_K, 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (ext6 && !h->masked && h->cam_order.empty()) SFM_HIP_TRY(ctx, hipMemcpy(ext6, h->d_ext, 6 * (size_t)h->nc * sizeof(double), hipMemcpyDeviceToHost));
+    else if (ext6) {
+        // back into the caller's camera order; constant cameras with the bits given at create (the step's x + 0 turns a -0 into +0;
+        // problems the legacy options express keep that arithmetic, and with it the bits they always had)
+        std::vector<double> e(6 * (size_t)h->nc), e0(6 * (size_t)h->nfix);
+        SFM_HIP_TRY(ctx, hipMemcpy(e.data(), h->d_ext, e.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (h->nfix) SFM_HIP_TRY(ctx, hipMemcpy(e0.data(), h->d_ext0, e0.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (h->masked) std::copy(e0.begin(), e0.end(), e.begin());       // internal cameras [0, nfix) are the constant ones
+        for (int i = 0; i < h->nc; ++i) {
+            const int c = h->cam_order.empty() ? i : h->cam_order[i];
+            std::copy(e.begin() + 6 * (size_t)i, e.begin() + 6 * (size_t)i + 6, ext6 + 6 * (size_t)c);
+        }
+    }
     if (pts && h->np) {           // back into the caller's point order on the device, then one copy into the caller's array
         void* tmp = nullptr;
         int rc = sfm_scratch(ctx, 3 * (size_t)h->np * sizeof(double), &tmp); if (rc) return rc;
         hipLaunchKernelGGL(setup_permute_pts_kernel, dim3(ceil_div(h->np, 256)), dim3(256), 0, ctx->stream, (const double*)h->d_pts, (const int*)h->d_slot, h->np, (double*)tmp, 0);
+        if (h->d_ptfix)
+            hipLaunchKernelGGL(setup_restore_fixed_pts_kernel, dim3(ceil_div(h->np, 256)), dim3(256), 0, ctx->stream, (const double*)h->d_pts0, (const int*)h->d_slot,
+                               (const unsigned char*)h->d_ptfix, h->np, (double*)tmp);
         SFM_HIP_TRY(ctx, hipMemcpyAsync(pts, tmp, 3 * (size_t)h->np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -1701,13 +1859,20 @@ int sfmhip_ba_solve(sfmhip_ctx* ctx, double* K4, double* ext6, int n_cam, double
                     const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
                     const sfm_ba_options* opts, sfm_ba_summary* summary)
 {
+    return sfmhip_ba_solve_ex(ctx, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, nullptr, nullptr, opts, summary);
+}
+
+int sfmhip_ba_solve_ex(sfmhip_ctx* ctx, double* K4, double* ext6, int n_cam, double* pts, int n_pt,
+                       const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                       const uint8_t* cam_const, const uint8_t* pt_const, const sfm_ba_options* opts, sfm_ba_summary* summary)
+{
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_ba_solve");
     // One call = build the problem + solve + write the parameters back, like bundle_adjustment() (NView:1169-1224); the
     // summary's times cover the whole call the way Ceres' do (total_time_in_seconds includes the preprocessor, NView:1239).
     const auto t0 = std::chrono::steady_clock::now();
     sfmhip_ba* h = nullptr;
-    int rc = sfmhip_ba_create(ctx, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, opts, &h);
+    int rc = sfmhip_ba_create_ex(ctx, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, cam_const, pt_const, opts, &h);
     if (rc) return rc;
     const double create_s = ms_since(t0) * 1e-3;
     sfm_ba_summary local;

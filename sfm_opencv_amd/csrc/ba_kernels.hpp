@@ -48,12 +48,17 @@ struct BADev {
     const double* y;
     double radius, min_diag, max_diag;
     int xcd_plain;        // measurement knob (SFMHIP_EXP_XCD_PLAIN): 1 = work item = workgroup index, no XCD-aware order
+    // constant points (sfmhip_ba_create_ex): one flag per slot, null when every point is free.  The kernels that read it per point
+    // are templates on PTFIX: problems without constant points run the PTFIX = false instances, compiled as before the flag existed.
+    const unsigned char* ptfix;
 };
 
 #define SCAL_COST 0
 #define SCAL_GMAX_SLOTS 8     // scal[8 + rank] = local max |gradient| over this rank's points
 
 __device__ __forceinline__ int cam_off(const BADev& P, int c) { return P.cam_pos[c]; }
+template <bool PTFIX>
+__device__ __forceinline__ bool pt_fixed(const BADev& P, int p) { return PTFIX && P.ptfix[p]; }
 
 // Corrected residual and Jacobian blocks of one observation, column-scaled; blocks of constant parameters are 0.
 struct ObsLin {
@@ -410,15 +415,17 @@ __device__ __forceinline__ void pt_accumulate(int fixK, const ObsLin& o, PtAcc& 
         for (int j = 0; j < 3; ++j) ACC2(a.WK[3 * i + j], o.EK[0][i], o.F[0][j], o.EK[1][i], o.F[1][j]);
 #undef ACC2
 }
-// after the last observation: damping with `radius`, V^-1, and the point's share of the part_pt record
-__device__ __forceinline__ void pt_finish(const BADev& P, double radius, const double sp[3], PtAcc& a, double Vi[6], double cs[3], int* __restrict__ err)
+// after the last observation: damping with `radius`, V^-1, and the point's share of the part_pt record.  A constant point
+// (fixed) stores V^-1 = 0: no Schur term, no SKK / gK, no step; only its observations' cost and camera / intrinsic sums remain.
+__device__ __forceinline__ void pt_finish(const BADev& P, double radius, const double sp[3], PtAcc& a, double Vi[6], double cs[3], int* __restrict__ err,
+                                          bool fixed)
 {
     double* V = a.V; const double* b = a.b; const double* WK = a.WK;
     cs[0] = V[0]; cs[1] = V[2]; cs[2] = V[5];
     V[0] += fmin(fmax(cs[0], P.min_diag), P.max_diag) / radius;
     V[2] += fmin(fmax(cs[1], P.min_diag), P.max_diag) / radius;
     V[5] += fmin(fmax(cs[2], P.min_diag), P.max_diag) / radius;
-    if (!inv3_spd(V, Vi)) *err = 1;
+    if (!inv3_spd(V, Vi) && !fixed) *err = 1;
     // T = WK Vi (4x3); SKK = T WK' ; gK = T b
     double T[12];
 #pragma unroll
@@ -433,6 +440,13 @@ __device__ __forceinline__ void pt_finish(const BADev& P, double radius, const d
 #pragma unroll
     for (int i = 0; i < 4; ++i) a.acc[11 + i] = T[3 * i] * b[0] + T[3 * i + 1] * b[1] + T[3 * i + 2] * b[2];
     a.acc[15] = fmax(fabs(b[0] * rcp_nr(sp[0])), fmax(fabs(b[1] * rcp_nr(sp[1])), fabs(b[2] * rcp_nr(sp[2]))));
+    // constant point: overridden after the fact, so that the arithmetic above stays what both callers compile for a free one
+    if (fixed) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) Vi[i] = 0.0;
+#pragma unroll
+        for (int i = 1; i < 16; ++i) a.acc[i] = 0.0;
+    }
 }
 // the block's stores; stage: 4 * PT_STAGE doubles of LDS, red: 4 x 32.  Every thread of the block calls it (one barrier).
 __device__ __forceinline__ void pt_store(const BADev& P, const PtOut& O, double* __restrict__ stage, double (*red)[32],
@@ -490,6 +504,7 @@ __device__ __forceinline__ void pt_store(const BADev& P, const PtOut& O, double*
     }
 }
 
+template <bool PTFIX>
 __global__ __launch_bounds__(256) void ba_point_kernel(BADev P, int* __restrict__ err)
 {
     __shared__ double red[4][32];
@@ -510,7 +525,7 @@ __global__ __launch_bounds__(256) void ba_point_kernel(BADev P, int* __restrict_
                           P.fixK ? nullptr : P.scale_c + P.koff, nullptr, sp, o);
             pt_accumulate(P.fixK, o, a);
         }
-        pt_finish(P, P.radius, sp, a, Vi, cs, err);
+        pt_finish(P, P.radius, sp, a, Vi, cs, err, pt_fixed<PTFIX>(P, p));
     }
     const PtOut O = { P.Vinv, P.bp, P.WK, P.colsq_p, P.part_pt };
     pt_store(P, O, stage, red, a, Vi, cs);
@@ -1006,7 +1021,7 @@ struct BackCam { const double *pre, *t, *pre_c, *t_c, *sc, *y; };     // one cam
 // pass, sharing the projection, its 36 accumulators on top of that pass's live values spilled 240 registers at three waves per
 // SIMD; the separate loop: 10, outside the loops.)  next_radius damps it; Vi_n / cs_n return V^-1 and the raw column norms,
 // a the sums (pt_store writes them).
-template <bool LIN, typename CamAt>
+template <bool LIN, bool PTFIX, typename CamAt>
 __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_at, double acc[4], double (*esave)[256][2],
                                               PtAcc* a, double* Vi_n, double* cs_n, double next_radius, int* __restrict__ err_n)
 {
@@ -1037,6 +1052,8 @@ __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_a
         for (int j = 0; j < 3; ++j) t[j] -= o.F[0][j] * e0 + o.F[1][j] * e1;
         if (k - s0 < BACK_ESAVE) { esave[k - s0][tid][0] = e0; esave[k - s0][tid][1] = e1; }
     }
+    // a constant point has V^-1 = 0: its step is +-0, so Xc == X (up to the sign of a zero: sfmhip_ba_get_params returns the
+    // given bits) and |dx|^2 gets 0; |x|^2 runs over the free parameters only (the PTFIX instances below)
     double yp[3];
     symv3(Vi, t, yp);
     const double d[3] = { -yp[0] * sp[0], -yp[1] * sp[1], -yp[2] * sp[2] };
@@ -1044,6 +1061,7 @@ __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_a
     P.ptsc[3 * (size_t)p] = Xc[0]; P.ptsc[3 * (size_t)p + 1] = Xc[1]; P.ptsc[3 * (size_t)p + 2] = Xc[2];
     acc[2] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
     acc[3] = Xc[0] * Xc[0] + Xc[1] * Xc[1] + Xc[2] * Xc[2];
+    if (pt_fixed<PTFIX>(P, p)) acc[3] = 0.0;
     for (int k = s0; k < s1; ++k) {
         const int c = P.ocam[k];
         const bool free_cam = cam_off(P, c) >= 0;
@@ -1075,7 +1093,7 @@ __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_a
             obs_linearize(P.Kc, rec.pre_c, rec.t_c, Xc, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a, sK, nullptr, sp, oc);
             pt_accumulate(P.fixK, oc, *a);
         }
-        pt_finish(P, next_radius, sp, *a, Vi_n, cs_n, err_n);
+        pt_finish(P, next_radius, sp, *a, Vi_n, cs_n, err_n, pt_fixed<PTFIX>(P, p));
     }
 }
 
@@ -1096,7 +1114,7 @@ __device__ __forceinline__ double back_rec_value(const BADev& P, int c, int f)
 // rank the reduced system S and the solver's private buffers, which the factorisation has consumed by now and the next
 // linearisation expects empty -- as two hipMemsetAsync calls behind the step's last kernel they sat on the critical path.
 #define BACK_ZERO_BLOCKS 512
-template <bool LIN>
+template <bool LIN, bool PTFIX>
 __device__ __forceinline__ void ba_back_body(const BADev& P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1,
                                              const PtOut& O, double next_radius, int* __restrict__ err_n)
 {
@@ -1132,11 +1150,11 @@ __device__ __forceinline__ void ba_back_body(const BADev& P, int n_pt_blocks, do
     if (LIN) pt_zero(a);
     if (p < P.np) {
         if (staged) {
-            ba_back_point<LIN>(P, p, [&](int c) {
+            ba_back_point<LIN, PTFIX>(P, p, [&](int c) {
                 const double* r = &cam[c - cmin][0];
                 return BackCam{ r, r + 20, r + 23, r + 43, r + 46, r + 52 }; }, acc, esave, &a, Vi_n, cs_n, next_radius, err_n);
         } else {            // the block's points span too many cameras: straight from the global arrays
-            ba_back_point<LIN>(P, p, [&](int c) {
+            ba_back_point<LIN, PTFIX>(P, p, [&](int c) {
                 const int co = cam_off(P, c);
                 return BackCam{ P.campre + CAMPRE * (size_t)c, P.ext + 6 * c + 3, P.campre_c + CAMPRE * (size_t)c, P.extc + 6 * c + 3,
                                 P.scale_c + (co < 0 ? 0 : co), P.y + (co < 0 ? 0 : co) }; }, acc, esave, &a, Vi_n, cs_n, next_radius, err_n);
@@ -1160,7 +1178,13 @@ __device__ __forceinline__ void ba_back_body(const BADev& P, int n_pt_blocks, do
 }
 __global__ __launch_bounds__(256, 3) void ba_back_kernel(BADev P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1)
 {
-    ba_back_body<false>(P, n_pt_blocks, z0, n0, z1, n1, PtOut{}, 0.0, nullptr);
+    ba_back_body<false, false>(P, n_pt_blocks, z0, n0, z1, n1, PtOut{}, 0.0, nullptr);
+}
+// ... for a problem with constant points (P.ptfix): they stay out of |x_cand|^2.  A kernel of its own, so that ba_back_kernel stays the
+// instruction sequence it was.
+__global__ __launch_bounds__(256, 3) void ba_back_const_kernel(BADev P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1)
+{
+    ba_back_body<false, true>(P, n_pt_blocks, z0, n0, z1, n1, PtOut{}, 0.0, nullptr);
 }
 // The same + the point pass of the next linearisation at the candidate, damped with next_radius (the radius an accepted step
 // with rho >= 0.937 leads to), into the point-side buffer set O; a non-SPD V there raises *err_n, a flag of its own that
@@ -1168,7 +1192,14 @@ __global__ __launch_bounds__(256, 3) void ba_back_kernel(BADev P, int n_pt_block
 __global__ __launch_bounds__(256, 3) void ba_back_kernel_lin(BADev P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1,
                                                              PtOut O, double next_radius, int* __restrict__ err_n)
 {
-    ba_back_body<true>(P, n_pt_blocks, z0, n0, z1, n1, O, next_radius, err_n);
+    ba_back_body<true, false>(P, n_pt_blocks, z0, n0, z1, n1, O, next_radius, err_n);
+}
+// ... for a problem with constant points (P.ptfix): they stay out of |x_cand|^2, and their next point pass stores V^-1 = 0 (pt_finish).  A kernel of its own, so that
+// ba_back_kernel_lin stays the instruction sequence it was.
+__global__ __launch_bounds__(256, 3) void ba_back_lin_const_kernel(BADev P, int n_pt_blocks, double* __restrict__ z0, size_t n0, double* __restrict__ z1, size_t n1,
+                                                                   PtOut O, double next_radius, int* __restrict__ err_n)
+{
+    ba_back_body<true, true>(P, n_pt_blocks, z0, n0, z1, n1, O, next_radius, err_n);
 }
 
 // out4 = sum over blocks of part_back
@@ -1228,7 +1259,7 @@ __global__ __launch_bounds__(256) void ba_xnorm_kernel(BADev P, double* __restri
         double v;
         if (i < 4) v = P.fixK ? 0.0 : P.K[i];
         else if (i < 4 + 6 * (size_t)P.nc) { const int c = (int)((i - 4) / 6); v = cam_off(P, c) < 0 ? 0.0 : P.ext[i - 4]; }
-        else v = P.pts[i - 4 - 6 * (size_t)P.nc];
+        else { const size_t j = i - 4 - 6 * (size_t)P.nc; v = (P.ptfix && P.ptfix[j / 3]) ? 0.0 : P.pts[j]; }
         s += v * v;
     }
     s = wave_sum(s);

@@ -300,25 +300,27 @@ __global__ __launch_bounds__(256) void setup_cam_copy_kernel(const su32* __restr
     cam_pt[at] = opt[q]; cam_uv[at] = ouv[q];
 }
 
-// observation pairs of a point between free cameras: a point's observations are in ascending camera order, so those of the
-// constant camera 0 (if any) lead; with m others there are m (m - 1) / 2 pairs
-__device__ __forceinline__ int setup_lead_fixed(const int* __restrict__ ocam, int lo, int hi, int fix0)
+// observation pairs of a point between free cameras: a point's observations are in ascending camera order and the constant
+// cameras are numbered first (sfmhip_ba_create_ex renumbers them), so those of constant cameras lead; with m others there are
+// m (m - 1) / 2 pairs.  A constant point (ptfix, per slot; null: none) has no pairs at all.
+__device__ __forceinline__ int setup_lead_fixed(const int* __restrict__ ocam, int lo, int hi, int nfix, const unsigned char* __restrict__ ptfix, int s)
 {
+    if (ptfix && ptfix[s]) return hi - lo;
     int z = 0;
-    if (fix0) while (lo + z < hi && ocam[lo + z] == 0) ++z;
+    if (nfix) while (lo + z < hi && ocam[lo + z] < nfix) ++z;
     return z;
 }
 // total64 (zeroed by the caller): the number of pairs in 64 bits.  The per-point counters and the tile sums of the scan behind them are
 // 32 bits wide and WRAP for absurd inputs (4096 points of 1449 observations each in one tile); the caller rejects the problem on this
 // sum before it looks at anything the scan produced.
-__global__ __launch_bounds__(256) void setup_pair_count_kernel(const int* __restrict__ pt_start, const int* __restrict__ ocam, int np, int fix0, su32* __restrict__ npair,
-                                                               su64* __restrict__ total64)
+__global__ __launch_bounds__(256) void setup_pair_count_kernel(const int* __restrict__ pt_start, const int* __restrict__ ocam, int np, int nfix,
+                                                               const unsigned char* __restrict__ ptfix, su32* __restrict__ npair, su64* __restrict__ total64)
 {
     const int s = blockIdx.x * 256 + threadIdx.x;
     su64 c = 0;
     if (s < np) {
         const int lo = pt_start[s], hi = pt_start[s + 1];
-        const su64 m = (su64)(hi - lo - setup_lead_fixed(ocam, lo, hi, fix0));
+        const su64 m = (su64)(hi - lo - setup_lead_fixed(ocam, lo, hi, nfix, ptfix, s));
         c = m * (m - (m ? 1 : 0)) / 2;
         npair[s] = c > 0xffffffffull ? 0xffffffffu : (su32)c;
     }
@@ -334,12 +336,13 @@ __global__ __launch_bounds__(256) void setup_pair_count_kernel(const int* __rest
 // thread per observation i: its pairs (i, j > i) in the order "for i, for j" of the point -- key = ca * nc + cb with ca >= cb,
 // raw = (observation of ca, observation of cb)
 __global__ __launch_bounds__(256) void setup_pair_gen_kernel(const int* __restrict__ pt_start, const int* __restrict__ ocam, const int* __restrict__ opt, int nobs,
-                                                             int fix0, int nc, const su32* __restrict__ pair_off, su64* __restrict__ keys, int2* __restrict__ raw)
+                                                             int nfix, const unsigned char* __restrict__ ptfix, int nc, const su32* __restrict__ pair_off,
+                                                             su64* __restrict__ keys, int2* __restrict__ raw)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= nobs) return;
     const int s = opt[q], lo = pt_start[s], hi = pt_start[s + 1];
-    const int z = setup_lead_fixed(ocam, lo, hi, fix0);
+    const int z = setup_lead_fixed(ocam, lo, hi, nfix, ptfix, s);
     const long long a = (long long)q - (lo + z), m = (long long)hi - lo - z;
     if (a < 0) return;
     size_t id = (size_t)pair_off[s] + (size_t)(a * (2 * m - a - 1) / 2);
@@ -349,6 +352,23 @@ __global__ __launch_bounds__(256) void setup_pair_gen_kernel(const int* __restri
         if (ci < cj) { keys[id] = (su64)cj * (su64)nc + (su64)ci; raw[id] = make_int2(j, q); }
         else         { keys[id] = (su64)ci * (su64)nc + (su64)cj; raw[id] = make_int2(q, j); }
     }
+}
+
+// constant points back into the caller's order with the bits given at create (the LM state may hold a -0 as +0): out[p] = pts0[slot[p]]
+__global__ __launch_bounds__(256) void setup_restore_fixed_pts_kernel(const double* __restrict__ pts0, const int* __restrict__ slot, const unsigned char* __restrict__ ptfix,
+                                                                      int np, double* __restrict__ out)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= np) return;
+    const int s = slot[p];
+    if (ptfix[s]) { out[3 * (size_t)p] = pts0[3 * (size_t)s]; out[3 * (size_t)p + 1] = pts0[3 * (size_t)s + 1]; out[3 * (size_t)p + 2] = pts0[3 * (size_t)s + 2]; }
+}
+
+// per-slot constant-point flags from the caller's order: flags_slot[slot[p]] = flags[p]
+__global__ __launch_bounds__(256) void setup_slot_flags_kernel(const unsigned char* __restrict__ flags, const int* __restrict__ slot, int np, unsigned char* __restrict__ flags_slot)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < np) flags_slot[slot[p]] = flags[p] ? 1 : 0;
 }
 
 // run starts of the sorted pair keys: flag -> (scan) -> compaction

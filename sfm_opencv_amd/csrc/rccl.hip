@@ -15,6 +15,9 @@
 #include <memory>
 #include <sched.h>
 
+// ba.hip: a problem's fixed cost
+double sfm_ba_fixed_cost(const sfmhip_ba* h);
+
 namespace {
 
 // the handful of RCCL declarations used (rccl.h: ncclUniqueId is 128 opaque bytes, ncclDouble = 8, ncclSum = 0, ncclSuccess = 0)
@@ -333,12 +336,28 @@ extern "C" int sfmhip_ba_solve_multi(sfmhip_ctx* const* ctxs, int n_ctx, double*
                                      const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
                                      const sfm_ba_options* opts, sfm_ba_summary* summary)
 {
+    return sfmhip_ba_solve_multi_ex(ctxs, n_ctx, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, nullptr, nullptr, opts, summary);
+}
+
+extern "C" int sfmhip_ba_solve_multi_ex(sfmhip_ctx* const* ctxs, int n_ctx, double* K4, double* ext6, int n_cam, double* pts, int n_pt,
+                                        const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs,
+                                        const uint8_t* cam_const, const uint8_t* pt_const, const sfm_ba_options* opts, sfm_ba_summary* summary)
+{
     if (!ctxs || n_ctx < 1 || n_ctx > 64 || !ctxs[0]) return SFMHIP_E_ARG;
     sfmhip_ctx* c0 = ctxs[0];
-    if (n_ctx == 1) return sfmhip_ba_solve(c0, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, opts, summary);
+    if (n_ctx == 1) return sfmhip_ba_solve_ex(c0, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, cam_const, pt_const, opts, summary);
     SFM_RANGE("sfmhip_ba_solve_multi");
     SFM_ARG_CHECK(c0, K4 && ext6 && n_cam > 0 && n_pt >= 0 && n_obs >= 0 && (pts || n_pt == 0) && ((obs_cam && obs_pt && obs_uv) || n_obs == 0));
     for (int r = 0; r < n_ctx; ++r) SFM_ARG_CHECK(c0, ctxs[r] != nullptr);
+    // constant blocks: with no free parameter at all there is nothing to shard (the ranks agree on the solver among themselves:
+    // build_solver_plan)
+    sfm_ba_options oo;
+    if (opts) oo = *opts; else sfmhip_ba_default_options(&oo);
+    int nfix = 0; long long n_pfix = 0;
+    for (int c = 0; c < n_cam; ++c) nfix += ((cam_const && cam_const[c]) || (c == 0 && oo.fix_first_camera)) ? 1 : 0;
+    if (pt_const) for (int p = 0; p < n_pt; ++p) n_pfix += pt_const[p] ? 1 : 0;
+    if (nfix == n_cam && oo.fix_intrinsics && n_pfix == n_pt)
+        return sfmhip_ba_solve_ex(c0, K4, ext6, n_cam, pts, n_pt, obs_cam, obs_pt, obs_uv, n_obs, cam_const, pt_const, opts, summary);
     const auto t0 = std::chrono::steady_clock::now();
     // ---- shards.  A point belongs to the rank of the FIRST camera that sees it; the cameras are cut into n_ctx consecutive ranges of
     // (nearly) equal observation count.  A few parallel passes over the observations / points on the context's copy threads (persistent:
@@ -400,6 +419,8 @@ extern "C" int sfmhip_ba_solve_multi(sfmhip_ctx* const* ctxs, int n_ctx, double*
         for (int t = 0; t < NT; ++t) { const long long a = pcount[t][r], b = ocount[t][r]; pcount[t][r] = n_local[r]; ocount[t][r] = n_lobs[r]; n_local[r] += a; n_lobs[r] += b; }
     //  4. scatter: points (their local index = the caller's order inside the shard) and observations into the shards' arrays, order kept
     std::vector<double*> pl((size_t)n_ctx), uvl((size_t)n_ctx);
+    std::vector<std::vector<uint8_t>> pcl((size_t)n_ctx);          // the shards' constant-point flags
+    if (pt_const) for (int r = 0; r < n_ctx; ++r) pcl[r].assign((size_t)n_local[r], 0);
     std::vector<int32_t*> ocl((size_t)n_ctx), opl((size_t)n_ctx);
     for (int r = 0; r < n_ctx; ++r) {
         pl[r] = (double*)arena; arena += align64(3 * (size_t)n_local[r] * sizeof(double));
@@ -413,6 +434,7 @@ extern "C" int sfmhip_ba_solve_multi(sfmhip_ctx* const* ctxs, int n_ctx, double*
             const int r = rank_of[p]; const long long l = at[r]++;
             local_of[p] = (int)l;
             for (int d = 0; d < 3; ++d) pl[r][3 * (size_t)l + d] = pts[3 * (size_t)p + d];
+            if (pt_const) pcl[r][(size_t)l] = pt_const[p] ? 1 : 0;
         }
     });
     sfm_parallel(c0, [&](int t, int nt) {
@@ -433,12 +455,14 @@ extern "C" int sfmhip_ba_solve_multi(sfmhip_ctx* const* ctxs, int n_ctx, double*
     std::vector<int> rcs((size_t)n_ctx, SFMHIP_OK);
     std::vector<sfm_ba_summary> sums((size_t)n_ctx);
     std::vector<std::vector<double>> Kr((size_t)n_ctx, std::vector<double>(4)), extr((size_t)n_ctx);
-    std::vector<double> create_s((size_t)n_ctx, 0.0);
+    std::vector<double> create_s((size_t)n_ctx, 0.0), fixed_cost((size_t)n_ctx, 0.0);
     auto work = [&](int r) {
         sfmhip_ctx* ctx = ctxs[r];
         sfmhip_ba* h = nullptr;
         const auto tc = std::chrono::steady_clock::now();
-        int rc = sfmhip_ba_create(ctx, K4, ext6, n_cam, pl[r], (int)n_local[r], ocl[r], opl[r], uvl[r], (int)n_lobs[r], opts, &h);
+        int rc = sfmhip_ba_create_ex(ctx, K4, ext6, n_cam, pl[r], (int)n_local[r], ocl[r], opl[r], uvl[r], (int)n_lobs[r], cam_const,
+                                     pt_const ? pcl[r].data() : nullptr, opts, &h);
+        if (rc == SFMHIP_OK) fixed_cost[r] = sfm_ba_fixed_cost(h);
         if (rc == SFMHIP_OK) {
             if (use_rccl) rc = sfmhip_ba_set_rccl(h, cset->comms[r], r, n_ctx);
             else { lranks[r].comm = &local; lranks[r].rank = r; rc = sfmhip_ba_set_allreduce(h, local_allreduce_hook, &lranks[r], r, n_ctx); }
@@ -485,6 +509,8 @@ extern "C" int sfmhip_ba_solve_multi(sfmhip_ctx* const* ctxs, int n_ctx, double*
     if (summary) {
         *summary = sums[0];
         summary->num_residuals = 2 * n_obs;
+        double fc = 0.0; for (double v : fixed_cost) fc += v;          // every shard's fixed cost, where sums[0] holds rank 0's
+        summary->initial_cost += fc - fixed_cost[0]; summary->final_cost += fc - fixed_cost[0];
         summary->total_time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         // like sfmhip_ba_solve: everything before the first LM iteration (sharding on the host threads + the slowest shard's construction + plan)
         double slowest = 0.0; for (double v : create_s) slowest = std::max(slowest, v);

@@ -341,8 +341,12 @@ inline void Rodrigues_vec(const Mat& rvec, Mat& R)
 }
 
 // ---- bundle adjustment (NView:1162-1244): in place on intrinsic (4x1), extrinsics (6x1 each), structure -----------
+// const_cameras / const_points: indices of blocks held constant (ceres::Problem::SetParameterBlockConstant; camera 0 stays constant
+// as in the reference unless the options say otherwise) -- local / windowed BA, motion-only, structure-only (sfmhip_ba_solve_ex).
+// Empty sets: the reference's problem.  An index out of range is an error: "[Err]" line, nothing optimised, parameters unchanged.
 inline void bundle_adjustment(Mat& intrinsic, std::vector<Mat>& extrinsics, std::vector<std::vector<int>>& inds_2d_to_3d,
-                              std::vector<std::vector<KeyPoint>>& key_points_for_all, std::vector<Point3d>& pts3d)
+                              std::vector<std::vector<KeyPoint>>& key_points_for_all, std::vector<Point3d>& pts3d,
+                              const std::vector<int>& const_cameras, const std::vector<int>& const_points)
 {
     sfmhip_ctx* ctx = context();
     if (!ctx) { printf("Bundle Adjustment failed.\n"); return; }
@@ -357,20 +361,36 @@ inline void bundle_adjustment(Mat& intrinsic, std::vector<Mat>& extrinsics, std:
     const int nc = (int)extrinsics.size();
     std::vector<double> ext((size_t)6 * nc);
     for (int c = 0; c < nc; ++c) std::memcpy(&ext[6 * (size_t)c], extrinsics[c].ptr<double>(), 6 * sizeof(double));
+    std::vector<uint8_t> cmask, pmask;          // empty set: NULL mask
+    for (int c : const_cameras) {
+        if (c < 0 || c >= nc) { printf("[Err]: bundle_adjustment: constant camera %d out of range (%d cameras).\n", c, nc); return; }
+        cmask.resize((size_t)nc, 0); cmask[c] = 1;
+    }
+    for (int p : const_points) {
+        if (p < 0 || p >= (int)pts3d.size()) { printf("[Err]: bundle_adjustment: constant point %d out of range (%d points).\n", p, (int)pts3d.size()); return; }
+        pmask.resize(pts3d.size(), 0); pmask[p] = 1;
+    }
+    const uint8_t* cm = cmask.empty() ? nullptr : cmask.data();
+    const uint8_t* pm = pmask.empty() ? nullptr : pmask.data();
     sfm_ba_options o; sfmhip_ba_default_options(&o);
     sfm_ba_summary s; std::memset(&s, 0, sizeof s);
     const std::vector<sfmhip_ctx*>& many = ba_contexts();
     const int rc = many.size() > 1
-        ? sfmhip_ba_solve_multi(many.data(), (int)many.size(), intrinsic.ptr<double>(), ext.data(), nc, pts3d.empty() ? nullptr : &pts3d[0].x,
-                                (int)pts3d.size(), oc.data(), op.data(), uv.data(), (int)oc.size(), &o, &s)
-        : sfmhip_ba_solve(ctx, intrinsic.ptr<double>(), ext.data(), nc, pts3d.empty() ? nullptr : &pts3d[0].x, (int)pts3d.size(),
-                          oc.data(), op.data(), uv.data(), (int)oc.size(), &o, &s);
+        ? sfmhip_ba_solve_multi_ex(many.data(), (int)many.size(), intrinsic.ptr<double>(), ext.data(), nc, pts3d.empty() ? nullptr : &pts3d[0].x,
+                                   (int)pts3d.size(), oc.data(), op.data(), uv.data(), (int)oc.size(), cm, pm, &o, &s)
+        : sfmhip_ba_solve_ex(ctx, intrinsic.ptr<double>(), ext.data(), nc, pts3d.empty() ? nullptr : &pts3d[0].x, (int)pts3d.size(),
+                             oc.data(), op.data(), uv.data(), (int)oc.size(), cm, pm, &o, &s);
     if (rc != SFMHIP_OK || s.termination == SFMHIP_BA_FAILURE) { printf("Bundle Adjustment failed.\n"); return; }
     for (int c = 0; c < nc; ++c) std::memcpy(extrinsics[c].ptr<double>(), &ext[6 * (size_t)c], 6 * sizeof(double));
     printf("\nBundle Adjustment statistics (approximated RMSE):\n #views: %d\n #residuals: %d\n Initial RMSE(pixel): %g\n"
            " Final   RMSE(pixel): %g\n Time (s): %g\n\n", nc, s.num_residuals,
            std::sqrt(s.initial_cost / (s.num_residuals > 0 ? s.num_residuals : 1)),
            std::sqrt(s.final_cost / (s.num_residuals > 0 ? s.num_residuals : 1)), s.total_time_s);
+}
+inline void bundle_adjustment(Mat& intrinsic, std::vector<Mat>& extrinsics, std::vector<std::vector<int>>& inds_2d_to_3d,
+                              std::vector<std::vector<KeyPoint>>& key_points_for_all, std::vector<Point3d>& pts3d)
+{
+    bundle_adjustment(intrinsic, extrinsics, inds_2d_to_3d, key_points_for_all, pts3d, std::vector<int>(), std::vector<int>());
 }
 
 // ---- normals (NView:551-599) ------------------------------------------------------------------------------------
