@@ -377,7 +377,9 @@ int  sfmhip_ba_reduced_system(sfmhip_ba*, double radius, double* S, double* rhs,
  * hands the same observation list to ceres::Problem): "pt_slot" (caller's point -> storage slot), "pt_start", "ocam", "opt",
  * "ouv" (observations by slot, then camera), "cam_start", "cam_pt", "cam_uv" (camera-ordered copy), "blk_crange", "blk_cam",
  * "blk_chunk", "chunk_desc", "items" (camera-pair lists; int32 except the double pixel arrays), "setup_ms" (4 doubles: host
- * clock of sfmhip_ba_create, cumulative: inputs + observation sort, + orderings, + pair lists, whole call).
+ * clock of sfmhip_ba_create, cumulative: inputs + observation sort, + orderings, + pair lists, whole call), "solver_plan" (4 int32,
+ * valid once an iteration has run: leaves of the dissection (1: none), parallel separator levels, panels of the top node, 1 if the
+ * backward sweep below the top is one launch).
  * out == NULL: only *n_bytes is set.  Synchronises. */
 int  sfmhip_ba_debug_table(sfmhip_ba*, const char* name, void* out, size_t cap_bytes, size_t* n_bytes);
 /* average device time (ms) per LM iteration of the last sfmhip_ba_iterate call, measured with HIP events on the

@@ -168,6 +168,7 @@ __global__ void fill_kernel(double* __restrict__ p, size_t n, double v)
 // ------------------------------------------------------------------------------------------------
 // host-side problem
 // ------------------------------------------------------------------------------------------------
+enum { SEAM_LIN_IN_BACK = 4, SEAM_INTR_FRONT = 8, SEAM_CAMSTEP_ROLES = 16, SEAM_TREE_BACKWARD = 32, SEAM_BACK_REDUCE = 64, SEAM_ALL = 4 | 8 | 16 | 32 | 64 };
 struct sfmhip_ba {
     sfmhip_ctx* ctx = nullptr;
     sfm_ba_options o;
@@ -259,7 +260,12 @@ struct sfmhip_ba {
     // SFMHIP_BA_SEAM (read per handle in sfmhip_ba_create): bit 2 (value 4) = the back-substitution also runs the point pass of the
     // next linearisation at the candidate (ba_back_kernel_lin), into the second point-side buffer set below.  An accepted step
     // whose new radius is the one that pass was damped with swaps the sets, and the next build skips ba_point_kernel.
-    int seam = 4;
+    // Bits 3..6: the one-workgroup reductions off the critical path.  8: the intrinsic block + scalars of the fold (ba_finalize_intr_role)
+    // run as a front group of ba_camschur_kernel; 16: ba_camstep_kernel with the gradient maximum in a workgroup of its own and block 0's
+    // loads in flight; 32: one backward launch for the tree below the top (chol_tree_backward_kernel); 64: ba_back_reduce_kernel with
+    // its loads in flight.  0 = every piece a launch / a loop of its own.
+    int seam = SEAM_ALL;
+    int* d_tree_path = nullptr; size_t tree_path_cap = 0; bool tree_ok = false;      // per-leaf ancestor lists of the solver plan (bit 5)
     double *d_Vinv2 = nullptr, *d_bp2 = nullptr, *d_WK2 = nullptr, *d_colsq_p2 = nullptr, *d_part_pt2 = nullptr;
     int* d_err_pt = nullptr;       // [2]: non-SPD flag of the point pass held by [0] the current set (if it was adopted), [1] the second set
     int err_cur = 0;               // which of the two flags belongs to the current set
@@ -392,7 +398,7 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
     // Up to a few thousand workgroups one launch is ahead (C3: 0.190 -> 0.169 ms per iteration, C4: 0.314 -> 0.306: the fork /
     // join events cost 5-7 us of stream gap each); beyond that the two kernels on two queues run 15 % faster than the shared
     // launch (C5: 0.44 || 0.48 ms against 0.56), so large problems keep the auxiliary stream.
-    bool folded = false;
+    bool folded = false, intr_in_front = false;
     if (n_schur_blocks > 0 && n_cam_blocks + n_schur_blocks > h->fuse_max_blocks) {
         SFM_HIP_TRY(ctx, hipEventRecord(h->ev_fork, st));
         SFM_HIP_TRY(ctx, hipStreamWaitEvent(h->aux, h->ev_fork, 0));
@@ -404,17 +410,20 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
         if (tv) (void)hipEventRecord(tv[1], st);
         hipLaunchKernelGGL(ba_camera_kernel, dim3(n_cam_blocks), dim3(256), 0, st, P);
         if (tv) (void)hipEventRecord(tv[2], st);
-        hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + 1), dim3(256), 0, st, P, h->n_pt_blocks, h->d_blk_cam, h->d_blk_chunk, 0, h->d_part_schur);      // each stream folds its own kernel's partials
+        hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + 1), dim3(256), 0, st, P, h->n_pt_blocks, h->d_blk_cam, h->d_blk_chunk, 0, h->d_part_schur, 1);      // each stream folds its own kernel's partials
         SFM_HIP_TRY(ctx, hipStreamWaitEvent(st, h->ev_join, 0));
         folded = true;
     } else {
         if (tv) { (void)hipEventRecord(tv[1], st); (void)hipEventRecord(tv[3], st); h->build_fused[h->build_parity] = true; }
-        hipLaunchKernelGGL(ba_camschur_kernel, dim3(n_cam_blocks + n_schur_blocks), dim3(256), 0, st, P, n_cam_blocks, h->d_chunk_desc, h->nchunk, h->d_items, h->d_part_schur);
+        // the intrinsic block + scalars need only the point pass: a front group of this launch reduces them (SFMHIP_BA_SEAM bit 3)
+        intr_in_front = (h->seam & SEAM_INTR_FRONT) != 0;
+        hipLaunchKernelGGL(ba_camschur_kernel, dim3(n_cam_blocks + n_schur_blocks + (intr_in_front ? 8 : 0)), dim3(256), 0, st, P, n_cam_blocks, h->d_chunk_desc, h->nchunk,
+                           h->d_items, h->d_part_schur, intr_in_front ? h->n_pt_blocks : 0);
         if (tv) { (void)hipEventRecord(tv[2], st); (void)hipEventRecord(tv[4], st); }
     }
     if (!folded)
-        hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + 1 + (h->nblk > 0 ? ceil_div(h->nblk * 36, 256) : 0)), dim3(256), 0, st, P, h->n_pt_blocks,
-                           h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur);
+        hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + (intr_in_front ? 0 : 1) + (h->nblk > 0 ? ceil_div(h->nblk * 36, 256) : 0)), dim3(256), 0, st, P, h->n_pt_blocks,
+                           h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, intr_in_front ? 0 : 1);
     if (h->n_diag_blk > 0)
         hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3(ceil_div(h->nblk * 36, 256)), dim3(256), 0, st, P, h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, 1);
     SFM_HIP_TRY(ctx, hipGetLastError());
@@ -526,7 +535,10 @@ static int enqueue_solve(sfmhip_ba* h)
                 if (l == 0 && ctx->timing) (void)hipEventRecord(h->evi[h->iter_parity][4], st);
             }
             hipLaunchKernelGGL(chol_top_kernel, dim3(1), dim3(STHREADS), 0, st, S, ld, pl, h->d_nodes, h->top_node, rhs_rw, h->d_ents, h->d_y, h->d_err);
-            for (int l = nlev - 1; l >= 0; --l)
+            if ((h->seam & SEAM_TREE_BACKWARD) && h->tree_ok && nlev > 1)       // every level below the top in one launch, a workgroup per leaf
+                hipLaunchKernelGGL(chol_tree_backward_kernel, dim3(h->lvl_first[1] - h->lvl_first[0]), dim3(STHREADS), 0, st, S, ld, pl, h->d_nodes, h->d_tree_path,
+                                   h->top_blk, nb, rhs_rw, h->d_y);
+            else for (int l = nlev - 1; l >= 0; --l)
                 hipLaunchKernelGGL(chol_node_backward_kernel, dim3(h->lvl_first[l + 1] - h->lvl_first[l]), dim3(STHREADS), 0, st, S, ld, pl, h->d_nodes, h->lvl_first[l], rhs_rw, h->d_y);
         }
         SFM_HIP_TRY(ctx, hipGetLastError());
@@ -552,7 +564,9 @@ static int enqueue_back(sfmhip_ba* h, double radius, double lin_radius = 0.0)
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
     BADev P = make_dev(h, radius);
-    hipLaunchKernelGGL(ba_camstep_kernel, dim3(1 + ceil_div(h->nc, 256)), dim3(256), 0, st, P, h->d_cam2);     // block 0: the step; the others: candidate rotation blocks
+    // block 0: the step; the others: candidate rotation blocks; SFMHIP_BA_SEAM bit 4: one more for the gradient maximum
+    const int step_roles = (h->seam & SEAM_CAMSTEP_ROLES) ? 1 : 0;
+    hipLaunchKernelGGL(ba_camstep_kernel, dim3(1 + ceil_div(h->nc, 256) + step_roles), dim3(256), 0, st, P, h->d_cam2, step_roles);
     // single rank: the reduction also publishes the decision scalars (ba_loop then skips ba_publish_kernel), and extra
     // workgroups of the back-substitution zero-fill S and the solver's private buffers for the next linearisation.  (The tail
     // [rhs | diagU | graw | scalars] needs no refill there: the finalisation stores every real entry and the padding
@@ -581,7 +595,8 @@ static int enqueue_back(sfmhip_ba* h, double radius, double lin_radius = 0.0)
     else
         hipLaunchKernelGGL(ba_back_kernel, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1);
     hipLaunchKernelGGL(ba_back_reduce_kernel, dim3(1), dim3(256), 0, st, h->d_part_back, h->n_pt_blocks, h->d_back4,
-                       d_scal, h->d_cam2, h->d_err, fuse_publish ? h->h_scal : (double*)nullptr, fuse_publish ? ++h->pub_seq : 0ull, err_fold);
+                       d_scal, h->d_cam2, h->d_err, fuse_publish ? h->h_scal : (double*)nullptr, fuse_publish ? ++h->pub_seq : 0ull, err_fold,
+                       (h->seam & SEAM_BACK_REDUCE) ? 1 : 0);
     if (err_fold) h->pt_fold_err = false;
     h->published = fuse_publish;
     SFM_HIP_TRY(ctx, hipGetLastError());
@@ -866,6 +881,41 @@ static int build_solver_plan(sfmhip_ba* h)
             }
             if (!valid) continue;
         }
+        // ---- per-leaf ancestor lists for the one-launch backward sweep (chol_tree_backward_kernel): the parallel separators a leaf's
+        // panels reach, directly or through another listed separator, from the highest level down.  Checked like the independence above:
+        // every outside block of a listed node belongs to the top or to a node listed before it; the lowest-numbered leaf stores.
+        std::vector<int> tree_path;
+        bool tree_ok = false;
+        if (P > 1 && first_of_level.size() > 2 && h->use_sparse) {
+            tree_ok = true;
+            tree_path.assign((size_t)P * TREE_PATH, 0);
+            std::vector<char> stored((size_t)n_par, 0);
+            for (int leaf = 0; leaf < P && tree_ok; ++leaf) {
+                std::vector<int> list, todo(1, leaf);
+                while (!todo.empty()) {
+                    const int nd = todo.back(); todo.pop_back();
+                    for (int b : anc[nd]) {
+                        const int o = blk_node[b];
+                        if (o < n_par && std::find(list.begin(), list.end(), o) == list.end()) { list.push_back(o); todo.push_back(o); }
+                    }
+                }
+                std::sort(list.begin(), list.end(), [&](int x, int y) { return node_level[x] != node_level[y] ? node_level[x] > node_level[y] : x > y; });
+                if ((int)list.size() > TREE_PATH - 2) { tree_ok = false; break; }
+                for (size_t a = 0; a < list.size() && tree_ok; ++a) {
+                    if (node_level[list[a]] < 1) tree_ok = false;
+                    for (int b : anc[list[a]]) {
+                        const int o = blk_node[b];
+                        if (o < n_par && std::find(list.begin(), list.begin() + a, o) == list.begin() + a) tree_ok = false;
+                    }
+                }
+                for (int b : anc[leaf]) { const int o = blk_node[b]; if (o < n_par && std::find(list.begin(), list.end(), o) == list.end()) tree_ok = false; }
+                int* rec = &tree_path[(size_t)leaf * TREE_PATH];
+                rec[0] = (int)list.size();
+                for (size_t a = 0; a < list.size(); ++a) { rec[2 + a] = list[a]; if (!stored[list[a]]) { stored[list[a]] = 1; rec[1] |= 1 << a; } }
+            }
+            // every parallel separator must be solved (and stored) by some leaf
+            for (int nd = P; nd < n_par && tree_ok; ++nd) if (!stored[nd]) tree_ok = false;
+        }
         // ---- upload
         std::vector<int> mask((size_t)h->npad_max, 0);
         for (int i = 0; i < npad; ++i) mask[i] = h->pos_param[i] >= 0;
@@ -882,6 +932,11 @@ static int build_solver_plan(sfmhip_ba* h)
                 SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_nodes, nodes.data(), nodes.size() * sizeof(NodeDesc), hipMemcpyHostToDevice, ctx->stream));
                 if (!ents.empty()) SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_ents, ents.data(), ents.size() * sizeof(FoldEnt), hipMemcpyHostToDevice, ctx->stream));
                 h->lvl_first = first_of_level; h->top_node = n_par;
+                h->tree_ok = tree_ok;
+                if (tree_ok) {
+                    if (tree_path.size() > h->tree_path_cap) { rc = dalloc(h, &h->d_tree_path, tree_path.size()); if (rc) return rc; h->tree_path_cap = tree_path.size(); }
+                    SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_tree_path, tree_path.data(), tree_path.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+                }
                 h->top_cleared = false;
             }
         }
@@ -909,7 +964,7 @@ static int build_solver_plan(sfmhip_ba* h)
         SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (h->o.verbose)
             printf("[sfmhip_ba] reduced system: %d unknowns (%d free cameras, band %d cameras); solver: %s\n", h->n, ncf, w,
-                   h->use_chain ? "chain (fronts in LDS)" : h->use_sparse ? (P > 1 ? "nested dissection, a launch per level" : "one workgroup, sparse panels") : "dense blocked");
+                   h->use_chain ? "chain (fronts in LDS)" : h->use_sparse ? (P > 1 ? (h->tree_ok && (h->seam & SEAM_TREE_BACKWARD) ? "nested dissection, a launch per level forward, one launch backward" : "nested dissection, a launch per level") : "one workgroup, sparse panels") : "dense blocked");
         if (h->use_chain && h->o.verbose)
             printf("[sfmhip_ba] chain solver: %d leaves of %d-%d cameras, %d waves each, %d tree level(s) in the first kernel, %d in the second\n",
                    h->chain.P, h->chain.q, h->chain.q + (h->chain.r ? 1 : 0), h->chain.G, h->chain.a, h->chain.m - h->chain.a);
@@ -1132,7 +1187,7 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
         // rho >= 0.937 (the normal case while LM is making progress) grows it by exactly 1 / (1/3)
         const double spec_radius = std::min(o.max_trust_region_radius, h->radius / (1.0 / 3.0));
         // single rank, per-observation lineariser: the back-substitution carries the next point pass (SFMHIP_BA_SEAM bit 2)
-        const bool lin_in_back = (h->seam & 4) && !h->ar_fn && !h->use_tiles && !speculate && h->d_Vinv2;
+        const bool lin_in_back = (h->seam & SEAM_LIN_IN_BACK) && !h->ar_fn && !h->use_tiles && !speculate && h->d_Vinv2;
         h->publish_in_back = true; h->fold_step_scalars = folded;
         rc = enqueue_back(h, h->radius, lin_in_back ? spec_radius : 0.0); h->publish_in_back = false; h->fold_step_scalars = false; if (rc) return rc;
         if (timing) SFM_HIP_TRY(ctx, hipEventRecord(ti[2], st));
@@ -1620,7 +1675,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     h->n_pt_blocks = std::max(1, ceil_div(n_pt, 256));
     // one arena for the many small and medium device arrays of a problem (a hipMalloc each cost more than the uploads)
     h->arena_chunk = (size_t)n_pt * 360 + (size_t)n_obs * 72 + (size_t)n_cam * 4096 + (1u << 20);
-    if (const char* e = getenv("SFMHIP_BA_SEAM")) h->seam = atoi(e) & 4;      // per handle: 0 = the launch sequence without any fused piece
+    if (const char* e = getenv("SFMHIP_BA_SEAM")) h->seam = atoi(e) & SEAM_ALL;      // per handle: 0 = the launch sequence without any fused piece
 #ifdef SFMHIP_EXPERIMENTS
     h->force_dense = getenv("SFMHIP_DENSE_SOLVER") != nullptr;
     if (const char* e = getenv("SFMHIP_FUSE_MAX_BLOCKS")) h->fuse_max_blocks = atoi(e);      // measurement knob: 0 = always two launches on two streams
@@ -1649,7 +1704,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     // Second point-side set: the point pass the back-substitution computes ahead.  Only while both sets (2 x 192 B per point) fit the
     // 256 MB last-level cache: measured faster at 80k and 300k points (C3 0.164 -> 0.161, C4 0.299 -> 0.290 ms per iteration), slower
     // at 2M (C5 1.16 -> 1.29 ms), where neither set stays on chip and the separate, purely streaming ba_point_kernel is ahead.
-    if ((h->seam & 4) && !h->use_tiles && 2 * 192 * (size_t)n_pt <= ((size_t)256 << 20)) {
+    if ((h->seam & SEAM_LIN_IN_BACK) && !h->use_tiles && 2 * 192 * (size_t)n_pt <= ((size_t)256 << 20)) {
         TRY_RC(dalloc(h, &h->d_Vinv2, 6 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_bp2, 3 * (size_t)n_pt));
         TRY_RC(dalloc(h, &h->d_WK2, 12 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_colsq_p2, 3 * (size_t)n_pt));
         TRY_RC(dalloc(h, &h->d_part_pt2, 32 * (size_t)h->n_pt_blocks)); TRY_RC(dalloc(h, &h->d_err_pt, 2));
@@ -1674,7 +1729,12 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { sfmhip_ba_destroy(h); ctx->last_error = "upload failed"; return SFMHIP_E_HIP; }
     h->setup_ms[3] = ms_since(t0);
     if (h->o.verbose)
-        printf("[sfmhip_ba] seam %d: the next point pass %s\n", h->seam, h->d_Vinv2 ? "rides in the back-substitution (ba_back_kernel_lin)" : "is a launch of its own (ba_point_kernel)");
+        printf("[sfmhip_ba] seam %d: the next point pass %s; intrinsic block + scalars %s; gradient maximum %s; backward sweep below the top %s; ba_back_reduce_kernel's loads %s\n", h->seam,
+               h->d_Vinv2 ? "rides in the back-substitution (ba_back_kernel_lin)" : "is a launch of its own (ba_point_kernel)",
+               (h->seam & SEAM_INTR_FRONT) && !h->use_tiles ? "in ba_camschur_kernel's front group (where camera items and pair chunks share that launch)" : "in ba_fold_kernel",
+               (h->seam & SEAM_CAMSTEP_ROLES) ? "in a workgroup of its own" : "behind the step in block 0",
+               (h->seam & SEAM_TREE_BACKWARD) ? "in one launch (if the plan has parallel separator levels)" : "a launch per level",
+               (h->seam & SEAM_BACK_REDUCE) ? "in flight together" : "trip by trip");
     if (h->o.verbose)
         printf("[sfmhip_ba] create %.2f ms (inputs + observation sort %.2f, orderings %.2f, pair lists %.2f)\n", h->setup_ms[3], h->setup_ms[0],
                h->setup_ms[1] - h->setup_ms[0], h->setup_ms[2] - h->setup_ms[1]);
@@ -1836,6 +1896,16 @@ int sfmhip_ba_debug_table(sfmhip_ba* h, const char* name, void* out, size_t cap_
         int4 last = make_int4(0, 0, 0, 0);
         if (h->nchunk) SFM_HIP_TRY(ctx, hipMemcpy(&last, h->d_chunk_desc + (h->nchunk - 1), sizeof last, hipMemcpyDeviceToHost));
         src = h->d_items; bytes = (size_t)last.w * 16;
+    }
+    else if (nm == "solver_plan") {
+        // the plan of the reduced solve (built by the first iteration): [leaves of the dissection (1: none), parallel separator levels,
+        // panels of the top node, 1 if the backward sweep below the top is one launch]
+        const bool tree = h->use_sparse && h->nseg > 1;
+        const int nlev = tree ? (int)h->lvl_first.size() - 1 : 0;
+        const int v[4] = { tree ? h->nseg : 1, tree ? nlev - 1 : 0, tree ? h->nbk - h->top_blk : 0, tree && nlev > 1 && h->tree_ok && (h->seam & SEAM_TREE_BACKWARD) ? 1 : 0 };
+        if (n_bytes) *n_bytes = sizeof v;
+        if (out && cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
+        return SFMHIP_OK;
     }
     else if (nm == "setup_ms") { if (n_bytes) *n_bytes = sizeof h->setup_ms; if (out && cap_bytes >= sizeof h->setup_ms) memcpy(out, h->setup_ms, sizeof h->setup_ms); return SFMHIP_OK; }
     else { ctx->last_error = "sfmhip_ba_debug_table: unknown table"; return SFMHIP_E_ARG; }

@@ -669,49 +669,56 @@ __device__ __forceinline__ void ba_camera_role(const BADev& P, double (*red)[CAM
 // K_finalize: block c < nc sums camera c's split partials and writes its S blocks / rhs / diagU / graw;
 // block nc reduces the intrinsic terms: S_KK = sum_c UKK - sum_blocks SKK, rhs_K, cost, local gmax.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ba_finalize_role(const BADev& P, int n_pt_blocks, int blk)
+__device__ __forceinline__ void ba_finalize_cam_role(const BADev& P, int blk)
 {
-    __shared__ double sh[256];
+    __shared__ double sh[CAMACC];
     const int tid = threadIdx.x;
     const int ld = P.npad;
-    if (blk < P.nc) {
-        const int c = blk, co = cam_off(P, c);
-        if (co < 0) return;
-        if (tid < CAMACC) {
-            double v = 0.0;
-            for (int s = 0; s < P.cam_split; ++s) v += P.part_cam[((size_t)c * P.cam_split + s) * CAMACC + tid];
-            sh[tid] = v;
-        }
-        __syncthreads();
-        if (tid < 36) {
-            const int i = tid / 6, j = tid % 6;
-            const int hi = i > j ? i : j, lo = i > j ? j : i;
-            P.S[(size_t)(co + i) * ld + co + j] = sh[hi * (hi + 1) / 2 + lo];
-        } else if (tid < 60 && !P.fixK) {
-            const int q = tid - 36, i = q / 4, j = q % 4;
-            const double v = sh[21 + q];
-            P.S[(size_t)(co + i) * ld + P.koff + j] = v;
-            P.S[(size_t)(P.koff + j) * ld + co + i] = v;
-        } else if (tid >= 64 && tid < 70) {
-            const int i = tid - 64;
-            P.rhs[co + i] = sh[45 + i];
-            P.diagU[co + i] = sh[65 + i];
-            P.graw[co + i] = sh[71 + i];
-        }
-        return;
+    const int c = blk, co = cam_off(P, c);
+    if (co < 0) return;
+    if (tid < CAMACC) {
+        double v = 0.0;
+        for (int s = 0; s < P.cam_split; ++s) v += P.part_cam[((size_t)c * P.cam_split + s) * CAMACC + tid];
+        sh[tid] = v;
     }
-    // intrinsic block + scalars: thread (value i = tid & 31, slice = tid >> 5) sums value i over the point blocks of its slice --
-    // a wave reads whole 256-byte records, no cross-lane step -- then the eight slices are folded in a fixed order
+    __syncthreads();
+    if (tid < 36) {
+        const int i = tid / 6, j = tid % 6;
+        const int hi = i > j ? i : j, lo = i > j ? j : i;
+        P.S[(size_t)(co + i) * ld + co + j] = sh[hi * (hi + 1) / 2 + lo];
+    } else if (tid < 60 && !P.fixK) {
+        const int q = tid - 36, i = q / 4, j = q % 4;
+        const double v = sh[21 + q];
+        P.S[(size_t)(co + i) * ld + P.koff + j] = v;
+        P.S[(size_t)(P.koff + j) * ld + co + i] = v;
+    } else if (tid >= 64 && tid < 70) {
+        const int i = tid - 64;
+        P.rhs[co + i] = sh[45 + i];
+        P.diagU[co + i] = sh[65 + i];
+        P.graw[co + i] = sh[71 + i];
+    }
+}
+// The intrinsic block + scalars.  Everything here comes out of part_pt, the point pass's per-block records: it needs no camera
+// partial, so it may run anywhere between the point pass and the solve (ba_camschur_kernel's front group, or block nc of ba_fold_kernel).
+// Thread (value i = tid & 31, slice = tid >> 5) sums value i over the point blocks of its slice -- a wave reads whole 256-byte
+// records, no cross-lane step -- then the eight slices are folded in a fixed order.
+template <int FINALIZE_INFLIGHT>
+__device__ __forceinline__ void ba_finalize_intr_role(const BADev& P, int n_pt_blocks)
+{
+    __shared__ double sh[32];
+    const int tid = threadIdx.x;
+    const int ld = P.npad;
     {
         __shared__ double red[8][32];
         const int i = tid & 31, slice = tid >> 5;
         double a = 0.0;
-        for (int b0 = slice; b0 < n_pt_blocks; b0 += 8 * 16) {      // sixteen records in flight per thread, folded in order
-            double v[16];
+        // FINALIZE_INFLIGHT records in flight per thread, folded in order (1,172 blocks at forty: four dependent trips; at sixteen: ten)
+        for (int b0 = slice; b0 < n_pt_blocks; b0 += 8 * FINALIZE_INFLIGHT) {
+            double v[FINALIZE_INFLIGHT];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) { const int b = b0 + 8 * u; v[u] = b < n_pt_blocks ? P.part_pt[32 * (size_t)b + i] : (i == 15 ? 0.0 : 0.0); }
+            for (int u = 0; u < FINALIZE_INFLIGHT; ++u) { const int b = b0 + 8 * u; v[u] = b < n_pt_blocks ? P.part_pt[32 * (size_t)b + i] : 0.0; }
 #pragma unroll
-            for (int u = 0; u < 16; ++u) a = (i == 15) ? fmax(a, v[u]) : a + v[u];
+            for (int u = 0; u < FINALIZE_INFLIGHT; ++u) a = (i == 15) ? fmax(a, v[u]) : a + v[u];
         }
         red[slice][i] = a;
         __syncthreads();
@@ -845,15 +852,22 @@ __device__ __forceinline__ void ba_schur_reduce_role(const BADev& P, const int* 
 // gap each.  Likewise the two folds: K_finalize's workgroups and the off-diagonal pass of K_schur_reduce write disjoint parts
 // of the message; the rare (a, a) blocks add onto what K_finalize wrote and keep their own launch (diag_pass = 1).
 __global__ __launch_bounds__(256, 3) void ba_camschur_kernel(BADev P, int n_cam_blocks, const int4* __restrict__ chunk_desc, int n_chunk,
-                                                          const int4* __restrict__ items, double* __restrict__ part)
+                                                          const int4* __restrict__ items, double* __restrict__ part, int front)      // front: 0, or the number of point blocks
 {
     __shared__ double red[4][CAMACC];
+    // front > 0: one more group of 8 in front of the grid, whose first workgroup reduces the point pass's records into the intrinsic
+    // block and the scalars (ba_finalize_intr_role: dispatched in the first round, it has the whole launch to hide in); the others
+    // return.  Every camera item and pair chunk keeps its XCD (blockIdx.x % 8) and its place in the order.
+    const int bx = (int)blockIdx.x - (front ? 8 : 0), nbx = (int)gridDim.x - (front ? 8 : 0);
     // groups of 8 workgroups (one per XCD) alternate between the roles in proportion, so that both kinds are resident together
     // from the first wave of dispatches to the last (camera items first, then pair chunks: 89 us; mixed: see profiles/README.md)
-    const int G = gridDim.x >> 3, Gc = n_cam_blocks >> 3, g = blockIdx.x >> 3;
+    const int G = nbx >> 3, Gc = n_cam_blocks >> 3, g = bx >> 3;
     const int before = (int)(((long long)g * Gc) / G), upto = (int)(((long long)(g + 1) * Gc) / G);      // camera groups in [0, g) and [0, g]
-    if (upto > before) ba_camera_role(P, red, before * 8 + (blockIdx.x & 7), n_cam_blocks);
-    else ba_schur_role(P, chunk_desc, n_chunk, items, part, (g - before) * 8 + (blockIdx.x & 7), gridDim.x - n_cam_blocks);
+    // (the front group as the first branch of this chain, not as an early return in front of it: that form cost the camera role its
+    // register allocation -- 109 spilled registers instead of 10)
+    if (bx < 0) { if (blockIdx.x == 0) ba_finalize_intr_role<40>(P, front); }
+    else if (upto > before) ba_camera_role(P, red, before * 8 + (bx & 7), n_cam_blocks);
+    else ba_schur_role(P, chunk_desc, n_chunk, items, part, (g - before) * 8 + (bx & 7), nbx - n_cam_blocks);
 }
 // the two roles as launches of their own: large problems run them on two streams (see enqueue_build).  Compiled for TWO waves per SIMD
 // (256 registers, nothing spilled), unlike the one-launch form above: at C5, where the gathers miss the L2s, the linearisation phase
@@ -870,10 +884,12 @@ __global__ __launch_bounds__(256, 2) void ba_schur_kernel(BADev P, const int4* _
     ba_schur_role(P, chunk_desc, n_chunk, items, part, blockIdx.x, gridDim.x);
 }
 __global__ __launch_bounds__(256) void ba_fold_kernel(BADev P, int n_pt_blocks, const int* __restrict__ blk_cam, const int* __restrict__ blk_chunk,
-                                                      int n_blk, const double* __restrict__ part)
+                                                      int n_blk, const double* __restrict__ part, int intr)
 {
-    if ((int)blockIdx.x <= P.nc) ba_finalize_role(P, n_pt_blocks, blockIdx.x);
-    else ba_schur_reduce_role(P, blk_cam, blk_chunk, n_blk, part, 0, blockIdx.x - (P.nc + 1));
+    // blocks [0, nc): a camera each; intr = 1: block nc is the intrinsic block + scalars (0: an earlier launch has done it); then the pair-block sums
+    if ((int)blockIdx.x < P.nc) ba_finalize_cam_role(P, blockIdx.x);
+    else if (intr && (int)blockIdx.x == P.nc) ba_finalize_intr_role<40>(P, n_pt_blocks);
+    else ba_schur_reduce_role(P, blk_cam, blk_chunk, n_blk, part, 0, blockIdx.x - (P.nc + intr));
 }
 __global__ __launch_bounds__(256) void ba_schur_reduce_kernel(BADev P, const int* __restrict__ blk_cam, const int* __restrict__ blk_chunk,
                                                               int n_blk, const double* __restrict__ part, int diag_pass)
@@ -919,9 +935,45 @@ __global__ void ba_scale_kernel(const double* __restrict__ colsq, double* __rest
 // ------------------------------------------------------------------------------------------------
 // K_camstep: candidate intrinsics / cameras = x + scale * (-y); out[0] = |delta_cam|^2, out[1] = |x_cand,cam|^2
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ba_camstep_kernel(BADev P, double* __restrict__ out2)
+// max |gradient| (what ba_damp_kernel reports when it runs; the sparse solvers damp S themselves): camera-side columns
+// folded with the per-rank point maxima.  graw is not touched by the factorisation.  STAGED: every mask of up to eight trips
+// requested first, then every graw / scale_c pair, then the divisions (a maximum may be taken in any order).
+template <bool STAGED>
+__device__ __forceinline__ void ba_gmax_role(const BADev& P)
+{
+    __shared__ double gred[4];
+    double g = 0.0;
+    if (STAGED) {
+        for (int i0 = threadIdx.x; i0 < P.npad; i0 += 256 * 8) {
+            int m[8]; double gr[8], sc[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const int i = i0 + 256 * u; m[u] = i < P.npad ? P.posmask[i] : 0; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const int i = i0 + 256 * u; gr[u] = 0.0; sc[u] = 1.0; if (m[u]) { gr[u] = P.graw[i]; sc[u] = P.scale_c[i]; } }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) if (m[u]) g = fmax(g, fabs(gr[u] / sc[u]));
+        }
+    } else {
+        for (int i = threadIdx.x; i < P.npad; i += 256)
+            if (P.posmask[i]) g = fmax(g, fabs(P.graw[i] / P.scale_c[i]));
+    }
+    g = wave_max(g);
+    if ((threadIdx.x & 63) == 0) gred[threadIdx.x >> 6] = g;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = fmax(fmax(gred[0], gred[1]), fmax(gred[2], gred[3]));
+        for (int r = 0; r < P.world; ++r) m = fmax(m, P.scal[SCAL_GMAX_SLOTS + r]);
+        P.scal[1] = m;
+    }
+}
+
+// roles = 0: block 0 computes the step, then the gradient maximum; blocks 1..: the candidate rotation blocks.
+// roles = 1: the gradient maximum (it depends on neither the step nor the solve) is the LAST block's, and block 0 requests the
+// loads of all its trips (cam_pos, then y and scale_c) before the first add; per-thread order of the sums unchanged.
+__global__ __launch_bounds__(256) void ba_camstep_kernel(BADev P, double* __restrict__ out2, int roles)
 {
 #pragma clang fp contract(off)          // x + (-y * scale) must round the same way in block 0 and in the other blocks
+    if (roles && blockIdx.x + 1 == gridDim.x) { ba_gmax_role<true>(P); return; }
     if (blockIdx.x > 0) {
         // blocks 1..: the candidate cameras' rotation blocks (what ba_campre_kernel computes), each thread from its own copy
         // of the candidate extrinsics (same arithmetic as block 0's, so nothing waits for block 0)
@@ -941,7 +993,31 @@ __global__ __launch_bounds__(256) void ba_camstep_kernel(BADev P, double* __rest
     }
     __shared__ double red[4][2];
     double dn = 0.0, xn = 0.0;
-    for (int i = threadIdx.x; i < 6 * P.nc + 4; i += 256) {
+    const int n = 6 * P.nc + 4;
+    if (roles) {
+        for (int i0 = threadIdx.x; i0 < n; i0 += 256 * 8) {
+            int co[8]; double x[8], yv[8], sc[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {          // position of the unknown in the reduced system (-1: constant) and the parameter
+                const int i = i0 + 256 * u;
+                co[u] = -1; x[u] = 0.0;
+                if (i < 4) { x[u] = P.K[i]; if (!P.fixK) co[u] = P.koff + i; }
+                else if (i < n) { const int cp = cam_off(P, (i - 4) / 6); if (cp >= 0) co[u] = cp + (i - 4) % 6; x[u] = P.ext[i - 4]; }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { yv[u] = 0.0; sc[u] = 0.0; if (co[u] >= 0) { yv[u] = P.y[co[u]]; sc[u] = P.scale_c[co[u]]; } }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + 256 * u;
+                if (i >= n) continue;
+                double d = 0.0;
+                if (co[u] >= 0) d = -yv[u] * sc[u];
+                if (i < 4) P.Kc[i] = x[u] + d; else P.extc[i - 4] = x[u] + d;
+                if (co[u] >= 0) { dn += d * d; xn += (x[u] + d) * (x[u] + d); }
+            }
+        }
+    } else
+    for (int i = threadIdx.x; i < n; i += 256) {
         double x, d = 0.0;
         if (i < 4) {
             x = P.K[i];
@@ -964,22 +1040,7 @@ __global__ __launch_bounds__(256) void ba_camstep_kernel(BADev P, double* __rest
         out2[0] = red[0][0] + red[1][0] + red[2][0] + red[3][0];
         out2[1] = red[0][1] + red[1][1] + red[2][1] + red[3][1];
     }
-    // max |gradient| (what ba_damp_kernel reports when it runs; the sparse solvers damp S themselves): camera-side columns
-    // folded with the per-rank point maxima.  graw is not touched by the factorisation.
-    {
-        __shared__ double gred[4];
-        double g = 0.0;
-        for (int i = threadIdx.x; i < P.npad; i += 256)
-            if (P.posmask[i]) g = fmax(g, fabs(P.graw[i] / P.scale_c[i]));
-        g = wave_max(g);
-        if ((threadIdx.x & 63) == 0) gred[threadIdx.x >> 6] = g;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double m = fmax(fmax(gred[0], gred[1]), fmax(gred[2], gred[3]));
-            for (int r = 0; r < P.world; ++r) m = fmax(m, P.scal[SCAL_GMAX_SLOTS + r]);
-            P.scal[1] = m;
-        }
-    }
+    if (!roles) ba_gmax_role<false>(P);
 }
 
 // The scalars the host needs to accept or reject the step, gathered into pinned host memory by one wave, then a sequence
@@ -1207,10 +1268,24 @@ __global__ __launch_bounds__(256, 3) void ba_back_lin_const_kernel(BADev P, int 
 // i.e. does ba_publish_kernel's job in the same launch.
 __global__ __launch_bounds__(256) void ba_back_reduce_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ out4,
                                                              const double* __restrict__ scal2, const double* __restrict__ cam2, int* __restrict__ err,
-                                                             double* __restrict__ host_out, unsigned long long seq, int* __restrict__ err_fold)
+                                                             double* __restrict__ host_out, unsigned long long seq, int* __restrict__ err_fold, int staged)
 {
     __shared__ double red[4][4];
     double acc[4] = { 0, 0, 0, 0 };
+    if (staged) {
+        // the records of up to eight trips requested (two 16-byte loads each) before the first add; the adds in the same order
+        for (int b0 = threadIdx.x; b0 < nblocks; b0 += 256 * 8) {
+            double2 v[8][2];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int b = b0 + 256 * u;
+                if (b < nblocks) { v[u][0] = *(const double2*)(part + 4 * (size_t)b); v[u][1] = *(const double2*)(part + 4 * (size_t)b + 2); }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (b0 + 256 * u < nblocks) { acc[0] += v[u][0].x; acc[1] += v[u][0].y; acc[2] += v[u][1].x; acc[3] += v[u][1].y; }
+        }
+    } else
     for (int b = threadIdx.x; b < nblocks; b += 256)
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i] += part[4 * (size_t)b + i];

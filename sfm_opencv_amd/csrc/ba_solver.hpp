@@ -730,3 +730,30 @@ __global__ __launch_bounds__(STHREADS) void chol_node_backward_kernel(const doub
     backward_panels(s, A, ld, nd.k0, nd.k1, pl, sy);
     for (int i = nd.k0 * SNB + tid; i < nd.k1 * SNB; i += STHREADS) y[i] = sy[i];
 }
+
+// The whole backward sweep below the top in ONE launch: a workgroup per leaf.  It first solves its ancestors among the parallel
+// separators, from the highest level down -- the highest needs only the top's y (chol_top_kernel wrote it), each lower one also the
+// ones above it, which are in sy by then --, then its own panels.  Sibling leaves repeat a separator's panels with the same
+// instructions on the same inputs (same bits); the lowest-numbered leaf below a separator stores its y.  No workgroup waits for
+// another.  path: TREE_PATH ints per leaf = { count, store mask, node indices from the highest level down }; the host checked that
+// every outside block of a listed node lies in the top or in a node listed before it (build_solver_plan).
+#define TREE_PATH 16
+__global__ __launch_bounds__(STHREADS) void chol_tree_backward_kernel(const double* __restrict__ A, int ld, SolverPlan pl, const NodeDesc* __restrict__ nodes,
+                                                                      const int* __restrict__ path, int top_k0, int top_k1,
+                                                                      const double* __restrict__ rhs, double* __restrict__ y)
+{
+    __shared__ SolverLds s;
+    const int tid = threadIdx.x;
+    double* sy = &s.B[0][0];
+    const int* pt = path + TREE_PATH * blockIdx.x;
+    const int n_anc = pt[0], store = pt[1];
+    for (int i = top_k0 * SNB + tid; i < top_k1 * SNB; i += STHREADS) sy[i] = y[i];
+    for (int a = 0; a <= n_anc; ++a) {
+        const NodeDesc nd = nodes[a < n_anc ? pt[2 + a] : (int)blockIdx.x];       // leaves are nodes [0, gridDim.x)
+        for (int i = nd.k0 * SNB + tid; i < nd.k1 * SNB; i += STHREADS) sy[i] = rhs[i];
+        __syncthreads();
+        backward_panels(s, A, ld, nd.k0, nd.k1, pl, sy);
+        if (a == n_anc || ((store >> a) & 1))
+            for (int i = nd.k0 * SNB + tid; i < nd.k1 * SNB; i += STHREADS) y[i] = sy[i];
+    }
+}
