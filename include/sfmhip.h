@@ -399,6 +399,32 @@ int  sfmhip_ba_phase_ms(sfmhip_ba*, double out_ms[8]);
 /* ------------------------------------------------------------------------------------------ */
 int sfmhip_estimate_normals(sfmhip_ctx*, const double* pts, int n, int K, double* normals);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Neighbour search over a 3-D point cloud (exact), and what is built on it.                    */
+/* d(i,j) = sqrt((dx*dx + dy*dy) + dz*dz) in fp64, no contraction.  Neighbours are ordered by   */
+/* (d, j) ascending; point i itself is excluded by index (a duplicate at distance 0 IS a         */
+/* neighbour); a slot without a neighbour is idx -1 / dist +inf (n - 1 < K); a point with a     */
+/* non-finite coordinate is nobody's neighbour and has none.  1 <= K <= 16.  n == 0: OK, no      */
+/* pointer touched.  Every method gives the same bits:                                          */
+/* ------------------------------------------------------------------------------------------ */
+#define SFMHIP_POINTS_AUTO  0   /* brute force or grid by n (the measured crossover) */
+#define SFMHIP_POINTS_BRUTE 1   /* all pairs */
+#define SFMHIP_POINTS_GRID  2   /* cell grid built on the device; certified exact, brute-force pass for what it cannot certify */
+/* K nearest OTHER points of every point.  pts: n x 3 double.  idx: n x K int32, dist: n x K double (either may be NULL). */
+int sfmhip_knn_points    (sfmhip_ctx*, const double* pts,   int n, int K, int method, int32_t* idx,   double* dist);
+/* the same on device arrays: enqueues on the context's stream, never synchronises */
+int sfmhip_knn_points_dev(sfmhip_ctx*, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist);
+/* sfmhip_estimate_normals on the neighbours of the chosen method (same bits for every method) */
+int sfmhip_estimate_normals_ex(sfmhip_ctx*, const double* pts, int n, int K, int method, double* normals);
+/* Statistical outlier removal (PCL StatisticalOutlierRemoval, Open3D remove_statistical_outlier): mean_dist[i] = ((d_0 + d_1) + ... +
+ * d_{K-1}) / K over the K neighbours in order (+inf for a point with fewer than K); mu, sigma = mean and population standard deviation
+ * (two passes) of the finite mean_dist; keep[i] = 1 iff mean_dist[i] <= thr;  stats = {mu, sigma, thr}, thr = mu + std_ratio * sigma.
+ * No finite value: stats NaN, keep all 0.  The sums are fixed-order trees on the device: a rerun gives the same bits. */
+int sfmhip_statistical_outliers(sfmhip_ctx*, const double* pts, int n, int K, double std_ratio, int method,
+                                uint8_t* keep, double* mean_dist /* may be NULL */, double stats[3] /* may be NULL */);
+/* diagnostic: how many queries the context's last SFMHIP_POINTS_GRID search handed to its brute-force pass.  Synchronises. */
+int sfmhip_points_fallback_count(sfmhip_ctx*, int* count);
+
 #ifdef __cplusplus
 }
 #endif

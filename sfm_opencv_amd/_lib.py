@@ -62,9 +62,12 @@ SYMBOLS = [
     "sfmhip_ba_set_rccl", "sfmhip_rccl_allreduce_f64", "sfmhip_ba_solve_multi", "sfmhip_match_pairs_multi", "sfmhip_debug_fail_allocations",
     "sfmhip_knn2_mutual_dev", "sfmhip_match_pairs_ex_dev", "sfmhip_match_pairs_ex", "sfmhip_match_pairs_multi_ex",
     "sfmhip_ba_create_ex", "sfmhip_ba_solve_ex", "sfmhip_ba_solve_multi_ex",
+    "sfmhip_knn_points", "sfmhip_knn_points_dev", "sfmhip_estimate_normals_ex", "sfmhip_statistical_outliers",
+    "sfmhip_points_fallback_count",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
+POINTS_METHODS = {"auto": 0, "brute": 1, "grid": 2}      # SFMHIP_POINTS_*
 
 _lib = None
 
@@ -149,6 +152,11 @@ def load():
         "sfmhip_ba_create_ex": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(BAOptions), C.POINTER(vp)]),
         "sfmhip_ba_solve_ex": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(BAOptions), C.POINTER(BASummary)]),
         "sfmhip_ba_solve_multi_ex": (i32, [C.POINTER(vp), i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, C.POINTER(BAOptions), C.POINTER(BASummary)]),
+        "sfmhip_knn_points": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "sfmhip_knn_points_dev": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        "sfmhip_estimate_normals_ex": (i32, [vp, vp, i32, i32, i32, vp]),
+        "sfmhip_statistical_outliers": (i32, [vp, vp, i32, i32, f64, i32, vp, vp, vp]),
+        "sfmhip_points_fallback_count": (i32, [vp, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

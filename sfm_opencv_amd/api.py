@@ -322,12 +322,51 @@ class Context:
                                                     _mask_ptr(cm), _mask_ptr(pm), C.byref(o), C.byref(s)))
         return K4, ext, pts, s.asdict()
 
-    # ---------------------------------------------------------------- normals
-    def estimate_normals(self, pts, K=10):
+    # ---------------------------------------------------------------- point clouds: neighbours, normals, outlier filter
+    @staticmethod
+    def _points_method(method):
+        """"auto" / "brute" / "grid" or the SFMHIP_POINTS_* number"""
+        if isinstance(method, str):
+            if method not in _lib.POINTS_METHODS:
+                raise ValueError(f"method {method!r}: one of {sorted(_lib.POINTS_METHODS)}")
+            return _lib.POINTS_METHODS[method]
+        return int(method)
+
+    def knn_points(self, pts, K=10, method="auto"):
+        """(idx n x K int32, dist n x K float64): the K nearest OTHER points of every point, ordered by (distance, index);
+        -1 / inf where a point has fewer (sfmhip_knn_points).  Exact for every method."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n, K = pts.shape[0], int(K)
+        idx = np.empty((n, max(K, 0)), np.int32); dist = np.empty((n, max(K, 0)), np.float64)
+        self._check(self.lib.sfmhip_knn_points(self.h, pts.ctypes.data, n, K, self._points_method(method), idx.ctypes.data, dist.ctypes.data))
+        return idx, dist
+
+    def knn_points_dev(self, d_pts, n, K, d_idx, d_dist, method="auto"):
+        """the same on device pointers (integers; 0: not wanted): enqueues on the context's stream, never synchronises"""
+        self._check(self.lib.sfmhip_knn_points_dev(self.h, C.c_void_p(int(d_pts)), int(n), int(K), self._points_method(method),
+                                                   C.c_void_p(int(d_idx)) if d_idx else None, C.c_void_p(int(d_dist)) if d_dist else None))
+
+    def estimate_normals(self, pts, K=10, method="auto"):
         pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
         out = np.empty_like(pts)
-        self._check(self.lib.sfmhip_estimate_normals(self.h, pts.ctypes.data, pts.shape[0], int(K), out.ctypes.data))
+        self._check(self.lib.sfmhip_estimate_normals_ex(self.h, pts.ctypes.data, pts.shape[0], int(K), self._points_method(method), out.ctypes.data))
         return out
+
+    def statistical_outliers(self, pts, K=10, std_ratio=2.0, method="auto"):
+        """(keep bool n, mean_dist float64 n, stats = [mu, sigma, thr]): statistical outlier removal as in PCL / Open3D
+        (sfmhip_statistical_outliers); keep == (mean_dist <= thr), thr = mu + std_ratio * sigma over the finite mean distances"""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        keep = np.zeros(n, np.uint8); mean_dist = np.empty(n, np.float64); stats = np.full(3, np.nan)
+        self._check(self.lib.sfmhip_statistical_outliers(self.h, pts.ctypes.data, n, int(K), float(std_ratio), self._points_method(method),
+                                                         keep.ctypes.data, mean_dist.ctypes.data, stats.ctypes.data))
+        return keep.astype(bool), mean_dist, stats
+
+    def points_fallback_count(self):
+        """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
+        c = C.c_int(0)
+        self._check(self.lib.sfmhip_points_fallback_count(self.h, C.byref(c)))
+        return c.value
 
 
 def _const_mask(m, n):

@@ -1958,3 +1958,15 @@ int sfmhip_ba_solve_ex(sfmhip_ctx* ctx, double* K4, double* ext6, int n_cam, dou
 }
 
 }  // extern "C"
+
+// The stable radix sort of ba_setup.hpp for the other translation units of the library (points.hip bins a cloud with it).  The kernels of
+// that header have external linkage, so it stays included here only and these two functions are its door (common.hpp declares them).
+size_t sfm_radix_sort_hist_words(size_t n) { return (size_t)256 * setup_rs_tiles(n); }
+size_t sfm_radix_sort_bsum_words(size_t n) { return setup_scan_tiles((size_t)256 * setup_rs_tiles(n)); }
+int sfm_enqueue_radix_sort(hipStream_t st, unsigned long long* k0, unsigned long long* k1, unsigned* v0, unsigned* v1, unsigned* hist, unsigned* bsum,
+                           size_t n, int bits, bool identity_vals)
+{
+    SetupSortBufs B;
+    B.k[0] = k0; B.k[1] = k1; B.v[0] = v0; B.v[1] = v1; B.hist = hist; B.bsum = bsum;
+    return setup_radix_sort(st, B, n, bits, identity_vals);
+}

@@ -50,6 +50,7 @@ struct sfmhip_ctx {
     int    num_cus = 256;
     // grow-only host block for the shards' arrays of sfmhip_ba_solve_multi (fresh allocations of that size cost a page fault per 4 KB: 60 ms at C5)
     void*  host_scratch = nullptr; size_t host_scratch_bytes = 0;
+    unsigned* d_points_fallback = nullptr;      // points.hip: length of the last grid search's fallback list (a pool block taken on first use and kept)
     int    inject_alloc_failures = 0;      // sfmhip_debug_fail_allocations: the next N sfm_pool_get calls fail (tests of the error paths)
     // optional per-kernel timing of the matching path (sfmhip_set_kernel_timing): event triples
     // [before kNN kernel, after it, after merge / re-score] for up to TIMING_SLOTS calls since the last query
@@ -168,6 +169,34 @@ void sfm_pool_put(sfmhip_ctx* ctx, void* p);
 void sfm_pool_trim(sfmhip_ctx* ctx);
 // rccl.hip: communicators cached for sets of contexts go when one of their contexts does
 void sfm_rccl_forget_ctx(sfmhip_ctx* ctx);
+
+// ba.hip: the stable LSD radix sort of ba_setup.hpp on (64-bit key, 32-bit value) pairs, for the other translation units.  Keys in k0,
+// values in v0 (or the element index where identity_vals); k1 / v1: ping-pong buffers of n entries; hist / bsum: scratch of
+// sfm_radix_sort_hist_words(n) / sfm_radix_sort_bsum_words(n) 32-bit words.  Sorts by the low `bits` bits, enqueues only, returns the
+// index (0 / 1) of the buffers that hold the result.
+size_t sfm_radix_sort_hist_words(size_t n);
+size_t sfm_radix_sort_bsum_words(size_t n);
+int sfm_enqueue_radix_sort(hipStream_t st, unsigned long long* k0, unsigned long long* k1, unsigned* v0, unsigned* v1, unsigned* hist, unsigned* bsum,
+                           size_t n, int bits, bool identity_vals);
+
+// points.hip: K nearest other points of every point of a device cloud (n x 3 double) into d_idx (n x K int32) / d_dist (n x K double),
+// either may be null; method: SFMHIP_POINTS_*.  Enqueues on the context's stream, never synchronises.  The grid leaves the number of
+// queries it handed to its brute-force pass in ctx->d_points_fallback.
+int sfm_points_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist);
+// normals.hip: plane fit on the K neighbours listed in d_idx (n x K, -1 = none), the fit of normals_kernel
+int sfm_normals_from_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, const int32_t* d_idx, int n, int K, double* d_normals);
+// the method SFMHIP_POINTS_AUTO stands for at n points
+int sfm_points_auto_method(int n);
+
+// device blocks of the context's cache that go back to it when the holder leaves scope
+struct SfmPoolHold {
+    sfmhip_ctx* ctx; std::vector<void*> blocks;
+    explicit SfmPoolHold(sfmhip_ctx* c) : ctx(c) {}
+    ~SfmPoolHold() { for (void* p : blocks) sfm_pool_put(ctx, p); }
+    int get(size_t bytes, void** out) { const int rc = sfm_pool_get(ctx, bytes, out); if (rc == SFMHIP_OK) blocks.push_back(*out); return rc; }
+    SfmPoolHold(const SfmPoolHold&) = delete;
+    SfmPoolHold& operator=(const SfmPoolHold&) = delete;
+};
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline int ceil_div(int x, int m) { return (x + m - 1) / m; }

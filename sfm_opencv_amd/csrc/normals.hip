@@ -44,6 +44,38 @@ __device__ __forceinline__ void eig3_min(const double Cin[9], double v[3])
     if (A[2][2] < best) { best = A[2][2]; v[0] = V[0][2]; v[1] = V[1][2]; v[2] = V[2][2]; }
 }
 
+// plane fit of point i on the neighbours bi[0 .. K) (-1: none), in that order
+__device__ __forceinline__ void plane_fit(const double* __restrict__ pts, const int (&bi)[KMAX], int K, int i, double* __restrict__ normals)
+{
+    int cnt = 0;
+    double mean[3] = { 0, 0, 0 };
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (k < K && bi[k] >= 0) {
+            mean[0] += pts[3 * (size_t)bi[k]]; mean[1] += pts[3 * (size_t)bi[k] + 1]; mean[2] += pts[3 * (size_t)bi[k] + 2];
+            ++cnt;
+        }
+    if (cnt == 0) { normals[3 * (size_t)i] = NAN; normals[3 * (size_t)i + 1] = NAN; normals[3 * (size_t)i + 2] = NAN; return; }
+    mean[0] /= (double)cnt; mean[1] /= (double)cnt; mean[2] /= (double)cnt;
+    double C[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (k < K && bi[k] >= 0) {
+            const double d[3] = { pts[3 * (size_t)bi[k]] - mean[0], pts[3 * (size_t)bi[k] + 1] - mean[1], pts[3 * (size_t)bi[k] + 2] - mean[2] };
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) C[3 * a + b] += d[a] * d[b];
+        }
+#pragma unroll
+    for (int a = 0; a < 9; ++a) C[a] /= (double)cnt;
+    double v[3];
+    eig3_min(C, v);
+    if (v[0] * mean[0] + v[1] * mean[1] + v[2] * mean[2] > 0.0) { v[0] = -v[0]; v[1] = -v[1]; v[2] = -v[2]; }
+    const double nn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    normals[3 * (size_t)i] = v[0] / nn; normals[3 * (size_t)i + 1] = v[1] / nn; normals[3 * (size_t)i + 2] = v[2] / nn;
+}
+
 __global__ __launch_bounds__(NTILE) void normals_kernel(const double* __restrict__ pts, int n, int K, double* __restrict__ normals)
 {
     __shared__ double tx[NTILE], ty[NTILE], tz[NTILE];
@@ -83,53 +115,59 @@ __global__ __launch_bounds__(NTILE) void normals_kernel(const double* __restrict
         }
     }
     if (!active) return;
-    int cnt = 0;
-    double mean[3] = { 0, 0, 0 };
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-        if (k < K && bi[k] >= 0) {
-            mean[0] += pts[3 * (size_t)bi[k]]; mean[1] += pts[3 * (size_t)bi[k] + 1]; mean[2] += pts[3 * (size_t)bi[k] + 2];
-            ++cnt;
-        }
-    if (cnt == 0) { normals[3 * (size_t)i] = NAN; normals[3 * (size_t)i + 1] = NAN; normals[3 * (size_t)i + 2] = NAN; return; }
-    mean[0] /= (double)cnt; mean[1] /= (double)cnt; mean[2] /= (double)cnt;
-    double C[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-        if (k < K && bi[k] >= 0) {
-            const double d[3] = { pts[3 * (size_t)bi[k]] - mean[0], pts[3 * (size_t)bi[k] + 1] - mean[1], pts[3 * (size_t)bi[k] + 2] - mean[2] };
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = 0; b < 3; ++b) C[3 * a + b] += d[a] * d[b];
-        }
-#pragma unroll
-    for (int a = 0; a < 9; ++a) C[a] /= (double)cnt;
-    double v[3];
-    eig3_min(C, v);
-    if (v[0] * mean[0] + v[1] * mean[1] + v[2] * mean[2] > 0.0) { v[0] = -v[0]; v[1] = -v[1]; v[2] = -v[2]; }
-    const double nn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    normals[3 * (size_t)i] = v[0] / nn; normals[3 * (size_t)i + 1] = v[1] / nn; normals[3 * (size_t)i + 2] = v[2] / nn;
+    plane_fit(pts, bi, K, i, normals);
 }
 
-extern "C" int sfmhip_estimate_normals(sfmhip_ctx* ctx, const double* pts, int n, int K, double* normals)
+// the same fit on a neighbour table (sfm_points_knn_enqueue): the grid search finds the K-sets, in the order of the sweep above
+__global__ __launch_bounds__(NTILE) void normals_from_knn_kernel(const double* __restrict__ pts, const int32_t* __restrict__ idx, int n, int K, double* __restrict__ normals)
+{
+    const int i = blockIdx.x * NTILE + threadIdx.x;
+    if (i >= n) return;
+    int bi[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) bi[k] = k < K ? idx[(size_t)i * K + k] : -1;
+    plane_fit(pts, bi, K, i, normals);
+}
+
+int sfm_normals_from_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, const int32_t* d_idx, int n, int K, double* d_normals)
+{
+    hipLaunchKernelGGL(normals_from_knn_kernel, dim3(ceil_div(n, NTILE)), dim3(NTILE), 0, ctx->stream, d_pts, d_idx, n, K, d_normals);
+    SFM_HIP_TRY(ctx, hipGetLastError());
+    return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_estimate_normals_ex(sfmhip_ctx* ctx, const double* pts, int n, int K, int method, double* normals)
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_estimate_normals");
     SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX);
+    SFM_ARG_CHECK(ctx, method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID);
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, pts && normals);
-    double *d_p = nullptr, *d_n = nullptr;
-    SFM_HIP_TRY(ctx, hipMalloc((void**)&d_p, (size_t)n * 24));
-    hipError_t e = hipMalloc((void**)&d_n, (size_t)n * 24);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    if (method == SFMHIP_POINTS_AUTO) method = sfm_points_auto_method(n);
+    SfmPoolHold hold(ctx);
+    double *d_p = nullptr, *d_n = nullptr; int32_t* d_idx = nullptr;
+    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_n);
+    if (rc == SFMHIP_OK && method == SFMHIP_POINTS_GRID) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_idx);
+    if (rc != SFMHIP_OK) return rc;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+    if (method == SFMHIP_POINTS_GRID) {
+        rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_idx, nullptr);
+        if (rc == SFMHIP_OK) rc = sfm_normals_from_knn_enqueue(ctx, d_p, d_idx, n, K, d_n);
+        if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    } else {
         hipLaunchKernelGGL(normals_kernel, dim3(ceil_div(n, NTILE)), dim3(NTILE), 0, ctx->stream, d_p, n, K, d_n);
-        e = hipGetLastError();
+        SFM_HIP_TRY(ctx, hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_p); (void)hipFree(d_n);
+    hipError_t e = hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);        // also on an error: the blocks go back to the cache behind this call
+    if (e == hipSuccess) e = e2;
     if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
     return SFMHIP_OK;
+}
+
+extern "C" int sfmhip_estimate_normals(sfmhip_ctx* ctx, const double* pts, int n, int K, double* normals)
+{
+    return sfmhip_estimate_normals_ex(ctx, pts, n, K, SFMHIP_POINTS_AUTO, normals);
 }

@@ -1,0 +1,526 @@
+// points.hip -- neighbour search over a 3-D point cloud: the K nearest OTHER points of every point, exact, and what is built on
+// it (statistical outlier removal; normals.hip fits its planes on the same table).
+//
+// Semantics, the same for every method (they are what normals_kernel has always done):
+//   d(i, j) = sqrt((dx*dx + dy*dy) + dz*dz) in fp64 without contraction; neighbours ordered by (d, j) ascending; i itself excluded by
+//   index (a duplicate at distance 0 is a neighbour); a slot without a neighbour is idx -1 / dist +inf; a point with a non-finite
+//   coordinate is nobody's neighbour and has none.
+//
+// SFMHIP_POINTS_BRUTE: one thread per query streams the whole cloud through LDS tiles (the sweep of normals_kernel).
+// SFMHIP_POINTS_GRID : the cloud is binned into cubic cells on the device (64-bit key, 21 bits per axis, stable radix sort of
+//   ba_setup.hpp), a query visits the cells within Chebyshev ring r = 0, 1, .. RMAX of its own and stops as soon as its K-th distance
+//   is CERTIFIED final (see points_knn_grid_kernel); a query not certified by RMAX goes on a list that the brute-force sweep finishes.
+//   Nothing here needs the host: cell size, origin, list length all stay on the device.
+#include "common.hpp"
+#pragma clang fp contract(off)
+
+#define KMAX 16
+#define NTILE 256
+#define CELL_BITS 21
+#define CELL_MAX ((1 << CELL_BITS) - 1)
+#define RMAX 2
+#define NSAMPLE 1024
+
+typedef unsigned long long pu64;
+typedef unsigned int pu32;
+
+// ------------------------------------------------------------------------------------------------
+// the sorted top-16 of a query, in registers.  (d, j) < (bd[k], bi[k]) lexicographically; an empty slot is (+inf, -1) and never beats
+// anything.  dk / ik: the K-th entry (the only one a candidate has to beat), kept beside the list so that no register is indexed by K.
+// ------------------------------------------------------------------------------------------------
+struct TopK {
+    double bd[KMAX]; int bi[KMAX];
+    double dk; int ik;        // bd[K - 1], bi[K - 1]
+    double gate2;             // no candidate with d2 > gate2 can have sqrt(d2) <= dk (see normals_kernel)
+    __device__ __forceinline__ void init()
+    {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) { bd[k] = INFINITY; bi[k] = -1; }
+        dk = INFINITY; ik = -1; gate2 = INFINITY;
+    }
+    // candidate j at squared distance d2 (cells are not visited in index order: the tie rule is explicit)
+    __device__ __forceinline__ void offer(double d2, int j, int K)
+    {
+        if (!(d2 <= gate2)) return;
+        const double d = sqrt(d2);
+        if (!(d < dk || (d == dk && j < ik))) return;
+        bd[KMAX - 1] = d; bi[KMAX - 1] = j;           // replaces the 16th: never one of the first K
+#pragma unroll
+        for (int k = KMAX - 1; k > 0; --k) {
+            if (bd[k] < bd[k - 1] || (bd[k] == bd[k - 1] && bi[k] < bi[k - 1])) {
+                const double td = bd[k]; bd[k] = bd[k - 1]; bd[k - 1] = td;
+                const int ti = bi[k]; bi[k] = bi[k - 1]; bi[k - 1] = ti;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) if (k == K - 1) { dk = bd[k]; ik = bi[k]; }
+        gate2 = dk * dk * (1.0 + 0x1p-50);            // inf while the list is not full
+    }
+    __device__ __forceinline__ void store(int K, size_t row, int32_t* __restrict__ idx, double* __restrict__ dist) const
+    {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (k < K) {
+                if (idx) idx[row * K + k] = bi[k];
+                if (dist) dist[row * K + k] = bd[k];
+            }
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
+// brute force: query t of the list (or point t where there is no list) against every point, LDS tiles of NTILE points.  Scanning j
+// ascending with a strict (d, j) test is the order of normals_kernel.  The grid's fallback pass is this kernel on its list: the
+// launch covers n queries and the workgroups beyond the list's length (read from the device) leave at once.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NTILE) void points_knn_brute_kernel(const double* __restrict__ pts, int n, int K, const pu32* __restrict__ list,
+                                                                 const pu32* __restrict__ list_len, int32_t* __restrict__ idx, double* __restrict__ dist)
+{
+    __shared__ double tx[NTILE], ty[NTILE], tz[NTILE];
+    const int m = list ? (int)min(*list_len, (pu32)n) : n;
+    if (blockIdx.x * NTILE >= m) return;                           // uniform over the workgroup
+    const int t = blockIdx.x * NTILE + threadIdx.x;
+    const bool active = t < m;
+    const int i = active ? (list ? (int)list[t] : t) : -1;
+    const double px = active ? pts[3 * (size_t)i] : 0.0, py = active ? pts[3 * (size_t)i + 1] : 0.0, pz = active ? pts[3 * (size_t)i + 2] : 0.0;
+    TopK top; top.init();
+    for (int base = 0; base < n; base += NTILE) {
+        const int j0 = base + threadIdx.x;
+        __syncthreads();
+        if (j0 < n) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; }
+        __syncthreads();
+        const int cnt = n - base < NTILE ? n - base : NTILE;
+        for (int s = 0; s < cnt; ++s) {
+            const int j = base + s;
+            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            if (j != i) top.offer(d2, j, K);
+        }
+    }
+    if (active) top.store(K, (size_t)i, idx, dist);
+}
+
+// ------------------------------------------------------------------------------------------------
+// cell size and origin from robust statistics of a strided sample (one workgroup).  A bounding box is useless for SfM clouds: one point
+// at 4e4 beside a cloud of unit size would put everything else into one cell.  Instead: the per-axis MEDIAN of the sample is the centre
+// of the 2^21-cell range, and the cell size comes from neighbour distances inside the sample: with the sample a 1-in-f thinning of the
+// cloud, the distance r_m to a sample point's m-th nearest sample point holds about m f points of the cloud, and between m = 2 and
+// m = 8 the growth of r_m tells the local dimension D of the cloud (a surface: 2, a volume: 3), so the radius that holds T = 2K points
+// is r_8 (T / (8 f))^(1/D).  Medians over the sample points throughout.  The cell size only steers speed: whatever comes out, the
+// certificate and the fallback keep the result exact.  params: [0..2] origin, [3] 1/h, [4] h_lo (a lower bound of h, see the certificate)
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void lds_bitonic_sort(double* a, int len)       // len: power of two, NTILE threads
+{
+    for (int k = 2; k <= len; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int t = threadIdx.x; t < len; t += NTILE) {
+                const int u = t ^ j;
+                if (u > t) {
+                    const double x = a[t], y = a[u];
+                    const bool up = (t & k) == 0;
+                    if ((x > y) == up) { a[t] = y; a[u] = x; }
+                }
+            }
+        }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(NTILE) void points_cell_stats_kernel(const double* __restrict__ pts, int n, int K, double* __restrict__ params)
+{
+    __shared__ double sx[NSAMPLE], sy[NSAMPLE], sz[NSAMPLE], srt[NSAMPLE];
+    __shared__ double med[3];
+    __shared__ int s_valid;
+    const int ns = n < NSAMPLE ? n : NSAMPLE;
+    if (threadIdx.x == 0) s_valid = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int s = threadIdx.x; s < NSAMPLE; s += NTILE) {
+        double x = INFINITY, y = INFINITY, z = INFINITY;
+        if (s < ns) {
+            const size_t i = (size_t)((pu64)s * (pu64)n / (pu64)ns);
+            const double a = pts[3 * i], b = pts[3 * i + 1], c = pts[3 * i + 2];
+            if (isfinite(a) && isfinite(b) && isfinite(c)) { x = a; y = b; z = c; ++mine; }
+        }
+        sx[s] = x; sy[s] = y; sz[s] = z;
+    }
+    if (mine) atomicAdd(&s_valid, mine);
+    __syncthreads();
+    const int nv = s_valid;
+    // per-axis medians (the invalid entries are +inf and sort last)
+    for (int a = 0; a < 3; ++a) {
+        const double* src = a == 0 ? sx : a == 1 ? sy : sz;
+        for (int s = threadIdx.x; s < NSAMPLE; s += NTILE) srt[s] = src[s];
+        lds_bitonic_sort(srt, NSAMPLE);
+        if (threadIdx.x == 0) med[a] = nv > 0 ? srt[nv / 2] : 0.0;
+        __syncthreads();
+    }
+    // thread t: sample point 4 t against the sample; its 2nd and 8th smallest squared distances
+    double best[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) best[k] = INFINITY;
+    const int q = 4 * threadIdx.x;
+    const double qx = sx[q], qy = sy[q], qz = sz[q];
+    const bool qok = qx < INFINITY;
+    for (int s = 0; s < NSAMPLE; ++s) {
+        const double dx = qx - sx[s], dy = qy - sy[s], dz = qz - sz[s];
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        if (s != q && d2 < best[7]) {
+            best[7] = d2;
+#pragma unroll
+            for (int k = 7; k > 0; --k) if (best[k] < best[k - 1]) { const double t = best[k]; best[k] = best[k - 1]; best[k - 1] = t; }
+        }
+    }
+    __syncthreads();
+    const bool ok = qok && best[7] < INFINITY;
+    srt[threadIdx.x] = ok ? best[1] : INFINITY;
+    srt[NTILE + threadIdx.x] = ok ? best[7] : INFINITY;
+    __syncthreads();
+    lds_bitonic_sort(srt, NTILE);
+    lds_bitonic_sort(srt + NTILE, NTILE);
+    if (threadIdx.x == 0) {
+        int nq = 0;
+        for (int t = 0; t < NTILE; ++t) nq += srt[NTILE + t] < INFINITY ? 1 : 0;
+        double h = 1.0;
+        if (nq > 0) {
+            const double r2 = sqrt(srt[nq / 2]), r8 = sqrt(srt[NTILE + nq / 2]);
+            double D = 2.0;
+            if (r2 > 0.0 && r8 > r2) D = log(4.0) / log(r8 / r2);
+            D = D < 1.0 ? 1.0 : D > 3.0 ? 3.0 : D;
+            const double f = (double)n / (double)ns, T = 2.0 * (double)K;
+            if (r8 > 0.0) h = r8 * pow(T / (8.0 * f), 1.0 / D);
+        }
+        if (!(h >= 1e-100 && h <= 1e100)) h = 1.0;
+        const double inv_h = 1.0 / h;
+        params[0] = med[0] - 0x1p20 * h; params[1] = med[1] - 0x1p20 * h; params[2] = med[2] - 0x1p20 * h;
+        params[3] = inv_h;
+        params[4] = (1.0 / inv_h) * (1.0 - 0x1p-40);
+    }
+}
+
+// position of a coordinate in cell units, and the cell it is binned into.  The ONE definition used by the binning and by the
+// certificate: what matters is not where a point "really" lies but what this function says.
+__device__ __forceinline__ double cell_pos(double x, double origin, double inv_h) { return (x - origin) * inv_h; }
+__device__ __forceinline__ int cell_of(double t) { return t < 1.0 ? 0 : !(t < (double)CELL_MAX) ? CELL_MAX : (int)t; }
+__device__ __forceinline__ pu64 cell_key(int cx, int cy, int cz) { return ((pu64)cx << (2 * CELL_BITS)) | ((pu64)cy << CELL_BITS) | (pu64)cz; }
+
+// key of every point; a point with a non-finite coordinate gets the all-ones key: it sorts behind every cell and no search looks there
+__global__ __launch_bounds__(256) void points_cell_key_kernel(const double* __restrict__ pts, int n, const double* __restrict__ params, pu64* __restrict__ keys)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    pu64 key = ~0ull;
+    if (isfinite(x) && isfinite(y) && isfinite(z)) {
+        const double inv_h = params[3];
+        key = cell_key(cell_of(cell_pos(x, params[0], inv_h)), cell_of(cell_pos(y, params[1], inv_h)), cell_of(cell_pos(z, params[2], inv_h)));
+    }
+    keys[i] = key;
+}
+
+// the cloud in cell order (a query's candidates are then runs of neighbouring records)
+__global__ __launch_bounds__(256) void points_gather_kernel(const double* __restrict__ pts, const pu32* __restrict__ order, int n, double* __restrict__ spts)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const size_t i = order[p];
+    spts[3 * (size_t)p] = pts[3 * i]; spts[3 * (size_t)p + 1] = pts[3 * i + 1]; spts[3 * (size_t)p + 2] = pts[3 * i + 2];
+}
+
+// first position of the sorted keys with keys[pos] >= key, in [lo, n): at most 32 halvings
+__device__ __forceinline__ int keys_lower_bound(const pu64* __restrict__ keys, int lo, int n, pu64 key)
+{
+    int hi = n;
+    for (int it = 0; it < 32 && lo < hi; ++it) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid search.  Thread p handles the p-th point in cell order (a wave walks the same cells) and writes to the row of its point.
+//
+// Ring r visits the cells of the cube [c - r, c + r]^3 (clipped to [0, CELL_MAX]) that ring r - 1 has not visited; cells with the same
+// (x, y) and consecutive z are consecutive keys, so a column of the cube is ONE run of the sorted keys, found by two binary searches.
+//
+// The certificate.  Let t_q = cell_pos(q_a) on axis a, c = cell_of(t_q) with 0 < c < CELL_MAX on every axis (a query in a border cell is
+// not searched at all: border cells are unbounded outward and hold whatever was clamped into them).  A point p that the cube has NOT
+// visited has, on some axis, cell_of(t_p) >= m with m = c + r + 1 <= CELL_MAX, or cell_of(t_p) <= m' - 1 with m' = c - r >= 1.  By the
+// definition of cell_of that means t_p >= m, resp. t_p < m', also where p was clamped (clamping from above only yields CELL_MAX, from
+// below only 0), while c <= t_q < c + 1.  cell_pos rounds twice: t = (x - o)(1 + e1) inv_h (1 + e2), |e| <= 2^-53, so x - o = t / (inv_h
+// (1 + e)) with |e| < 2^-51 (a subnormal product is off by less than 1e-323, far inside the slack below), and therefore
+//     p_a - q_a >= (m - t_q - (m + |t_q|) 2^-51) / inv_h        resp.        q_a - p_a >= (t_q - m' - (m' + |t_q|) 2^-51) / inv_h.
+// The code evaluates these gaps with 2^-48 in place of 2^-51, which covers the roundings of the evaluation itself, takes the smallest
+// gap over the faces that exist (a face beyond the clamped range has nothing behind it) and multiplies by h_lo = fl(1 / inv_h) (1 - 2^-40):
+// `bound` is then below the true distance from q to any unvisited point by a relative 2^-41, while the distance the kernels COMPUTE for
+// a pair is below the true one by at most a relative 2^-50 (h >= 1e-100 keeps the squares of such gaps from underflowing).  Hence every unvisited p has
+// computed d(q, p) >= bound, and with dk < bound -- STRICTLY: at d == dk a lower index would still enter -- no unvisited point can be
+// among the first K by (d, j).  A non-finite gap (t_q overflowed) compares false and certifies nothing.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NTILE) void points_knn_grid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ spts,
+                                                                int n, int K, const double* __restrict__ params, int32_t* __restrict__ idx,
+                                                                double* __restrict__ dist, pu32* __restrict__ fb_list, pu32* __restrict__ fb_len)
+{
+    const int p = blockIdx.x * NTILE + threadIdx.x;
+    if (p >= n) return;
+    const pu64 key = keys[p];
+    const int i = (int)order[p];
+    TopK top; top.init();
+    if (key >> 63) { top.store(K, (size_t)i, idx, dist); return; }        // non-finite: no neighbours
+    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
+    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
+    const double inv_h = params[3], h_lo = params[4];
+    const double tq[3] = { cell_pos(qx, params[0], inv_h), cell_pos(qy, params[1], inv_h), cell_pos(qz, params[2], inv_h) };
+    const int c[3] = { cx, cy, cz };
+    bool certified = false;
+    const bool border = cx == 0 || cx == CELL_MAX || cy == 0 || cy == CELL_MAX || cz == 0 || cz == CELL_MAX;
+    if (!border) {
+        for (int r = 0; r <= RMAX; ++r) {
+            for (int dx = -r; dx <= r; ++dx) {
+                const int X = cx + dx;
+                if (X < 0 || X > CELL_MAX) continue;
+                for (int dy = -r; dy <= r; ++dy) {
+                    const int Y = cy + dy;
+                    if (Y < 0 || Y > CELL_MAX) continue;
+                    const bool shell = dx == -r || dx == r || dy == -r || dy == r;
+                    // a column of the shell: z in [cz - r, cz + r]; an inner column: its two ends only (the same cell where r = 0: shell)
+                    const int nrun = shell ? 1 : 2;
+                    for (int run = 0; run < nrun; ++run) {
+                        int z0 = shell ? cz - r : run == 0 ? cz - r : cz + r;
+                        int z1 = shell ? cz + r : z0;
+                        if (z1 < 0 || z0 > CELL_MAX) continue;
+                        z0 = z0 < 0 ? 0 : z0; z1 = z1 > CELL_MAX ? CELL_MAX : z1;
+                        const int a = keys_lower_bound(keys, 0, n, cell_key(X, Y, z0));
+                        if (a >= n || keys[a] > cell_key(X, Y, z1)) continue;             // an empty run
+                        const int b = keys_lower_bound(keys, a, n, cell_key(X, Y, z1) + 1ull);
+                        for (int s = a; s < b; ++s) {
+                            const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
+                            const double d2 = ex * ex + ey * ey + ez * ez;
+                            if (s != p) top.offer(d2, (int)order[s], K);
+                        }
+                    }
+                }
+            }
+            double gmin = INFINITY;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const int m_hi = c[a] + r + 1, m_lo = c[a] - r;
+                if (m_hi <= CELL_MAX) { const double g = ((double)m_hi - tq[a]) - ((double)m_hi + fabs(tq[a])) * 0x1p-48; gmin = g < gmin || !(g == g) ? g : gmin; }
+                if (m_lo >= 1)        { const double g = (tq[a] - (double)m_lo) - ((double)m_lo + fabs(tq[a])) * 0x1p-48; gmin = g < gmin || !(g == g) ? g : gmin; }
+            }
+            const double bound = gmin * h_lo;
+            if (top.dk < bound) { certified = true; break; }
+        }
+    }
+    if (!certified) { fb_list[atomicAdd(fb_len, 1u)] = (pu32)i; return; }
+    top.store(K, (size_t)i, idx, dist);
+}
+
+// SFMHIP_POINTS_AUTO.  Measured (profiles/r09_time_points.log: normals, K = 10, noisy sphere / that sphere with 1 % far outliers / a
+// volume cloud): 300,000 is the smallest size from which the grid is faster by at least 10 % on all three; below it the brute-force
+// pass over the fallback list (one sweep of the cloud at one-workgroup speed, 13 ms at 100k) can cost more than the whole all-pairs sweep.
+#define POINTS_AUTO_GRID_FROM 300000
+int sfm_points_auto_method(int n) { return n >= POINTS_AUTO_GRID_FROM ? SFMHIP_POINTS_GRID : SFMHIP_POINTS_BRUTE; }
+
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int sfm_points_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist)
+{
+    if (method == SFMHIP_POINTS_AUTO) method = sfm_points_auto_method(n);
+    hipStream_t st = ctx->stream;
+    const int nb = ceil_div(n, NTILE);
+    if (method == SFMHIP_POINTS_BRUTE) {
+        hipLaunchKernelGGL(points_knn_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, K, (const pu32*)nullptr, (const pu32*)nullptr, d_idx, d_dist);
+        SFM_HIP_TRY(ctx, hipGetLastError());
+        return SFMHIP_OK;
+    }
+    if (!ctx->d_points_fallback) {
+        void* q = nullptr;
+        const int rc = sfm_pool_get(ctx, 256, &q);            // kept for the life of the context
+        if (rc != SFMHIP_OK) return rc;
+        ctx->d_points_fallback = (unsigned*)q;
+    }
+    // one block of the cache, carved up
+    const size_t N = (size_t)n, hist_w = sfm_radix_sort_hist_words(N), bsum_w = sfm_radix_sort_bsum_words(N);
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_par = carve(8 * sizeof(double)), o_k0 = carve(N * 8), o_k1 = carve(N * 8), o_v0 = carve(N * 4), o_v1 = carve(N * 4),
+                 o_hist = carve(hist_w * 4), o_bsum = carve(bsum_w * 4), o_spts = carve(N * 24), o_list = carve(N * 4);
+    SfmPoolHold hold(ctx);
+    char* w = nullptr;
+    const int rc = hold.get(off, (void**)&w);
+    if (rc != SFMHIP_OK) return rc;
+    double* params = (double*)(w + o_par);
+    pu64* k[2] = { (pu64*)(w + o_k0), (pu64*)(w + o_k1) };
+    pu32* v[2] = { (pu32*)(w + o_v0), (pu32*)(w + o_v1) };
+    double* spts = (double*)(w + o_spts);
+    pu32* list = (pu32*)(w + o_list);
+    SFM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_points_fallback, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(points_cell_stats_kernel, dim3(1), dim3(NTILE), 0, st, d_pts, n, K, params);
+    hipLaunchKernelGGL(points_cell_key_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, n, (const double*)params, k[0]);
+    const int cur = sfm_enqueue_radix_sort(st, k[0], k[1], v[0], v[1], (pu32*)(w + o_hist), (pu32*)(w + o_bsum), N, 64, true);
+    hipLaunchKernelGGL(points_gather_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, (const pu32*)v[cur], n, spts);
+    hipLaunchKernelGGL(points_knn_grid_kernel, dim3(nb), dim3(NTILE), 0, st, (const pu64*)k[cur], (const pu32*)v[cur], (const double*)spts, n, K,
+                       (const double*)params, d_idx, d_dist, list, ctx->d_points_fallback);
+    hipLaunchKernelGGL(points_knn_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, K, (const pu32*)list, (const pu32*)ctx->d_points_fallback, d_idx, d_dist);
+    SFM_HIP_TRY(ctx, hipGetLastError());
+    return SFMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// statistical outlier removal (PCL StatisticalOutlierRemoval / Open3D remove_statistical_outlier): mean distance to the K nearest
+// neighbours, then keep what lies within mu + std_ratio * sigma of the finite means.  The sums are fixed-order trees (a tile per
+// workgroup, then one workgroup over the tiles), so a rerun gives the same bits.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void points_mean_dist_kernel(const int32_t* __restrict__ idx, const double* __restrict__ dist, int n, int K, double* __restrict__ mean_dist)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    bool full = true;
+    for (int k = 0; k < K; ++k) { s += dist[(size_t)i * K + k]; full = full && idx[(size_t)i * K + k] >= 0; }
+    mean_dist[i] = full ? s / (double)K : INFINITY;
+}
+
+#define RED_TILE 4096
+// 256 threads: tree sum of (v, c) over the workgroup, valid in thread 0
+__device__ __forceinline__ void block_tree_sum(double& v, double& c, double* sv, double* sc)
+{
+    sv[threadIdx.x] = v; sc[threadIdx.x] = c;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) { sv[threadIdx.x] += sv[threadIdx.x + off]; sc[threadIdx.x] += sc[threadIdx.x + off]; }
+        __syncthreads();
+    }
+    v = sv[0]; c = sc[0];
+}
+// pass 0: partial[b] = (sum, count) of the finite m of tile b;  pass 1: (sum of (m - mu)^2, count), mu = stats[0]
+__global__ __launch_bounds__(256) void points_stat_tile_kernel(const double* __restrict__ m, int n, int pass, const double* __restrict__ stats, double* __restrict__ partial)
+{
+    __shared__ double sv[256], sc[256];
+    const double mu = pass ? stats[0] : 0.0;
+    double v = 0.0, c = 0.0;
+    for (int r = 0; r < RED_TILE / 256; ++r) {
+        const size_t i = (size_t)blockIdx.x * RED_TILE + (size_t)r * 256 + threadIdx.x;
+        if (i < (size_t)n) {
+            const double x = m[i];
+            if (isfinite(x)) { const double e = x - mu; v += pass ? e * e : x; c += 1.0; }
+        }
+    }
+    block_tree_sum(v, c, sv, sc);
+    if (threadIdx.x == 0) { partial[2 * (size_t)blockIdx.x] = v; partial[2 * (size_t)blockIdx.x + 1] = c; }
+}
+// one workgroup over the tiles.  pass 0: stats[0] = mu;  pass 1: stats[1] = sigma, stats[2] = thr = mu + ratio * sigma
+__global__ __launch_bounds__(256) void points_stat_top_kernel(const double* __restrict__ partial, int nt, int pass, double ratio, double* __restrict__ stats)
+{
+    __shared__ double sv[256], sc[256];
+    double v = 0.0, c = 0.0;
+    for (int t = threadIdx.x; t < nt; t += 256) { v += partial[2 * (size_t)t]; c += partial[2 * (size_t)t + 1]; }
+    block_tree_sum(v, c, sv, sc);
+    if (threadIdx.x == 0) {
+        if (pass == 0) stats[0] = v / c;                          // no finite value: 0 / 0 = NaN
+        else { const double sigma = sqrt(v / c); stats[1] = sigma; stats[2] = stats[0] + ratio * sigma; }
+    }
+}
+__global__ __launch_bounds__(256) void points_keep_kernel(const double* __restrict__ m, int n, const double* __restrict__ stats, uint8_t* __restrict__ keep)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) keep[i] = m[i] <= stats[2] ? 1 : 0;               // false for an infinite mean and for a NaN threshold
+}
+
+static inline bool points_method_ok(int method) { return method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID; }
+
+// after an error with work possibly in flight: drain the stream (the caller's host buffers may be targets of copies), keep the first error
+static int points_finish(sfmhip_ctx* ctx, hipError_t e)
+{
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
+    return SFMHIP_OK;
+}
+
+extern "C" {
+
+int sfmhip_knn_points_dev(sfmhip_ctx* ctx, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_knn_points_dev");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && points_method_ok(method));
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, d_pts);
+    if (!d_idx && !d_dist) return SFMHIP_OK;
+    return sfm_points_knn_enqueue(ctx, d_pts, n, K, method, d_idx, d_dist);
+}
+
+int sfmhip_knn_points(sfmhip_ctx* ctx, const double* pts, int n, int K, int method, int32_t* idx, double* dist)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_knn_points");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && points_method_ok(method));
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, pts);
+    if (!idx && !dist) return SFMHIP_OK;
+    SfmPoolHold hold(ctx);
+    double *d_p = nullptr, *d_d = nullptr; int32_t* d_i = nullptr;
+    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc == SFMHIP_OK && idx) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_i);
+    if (rc == SFMHIP_OK && dist) rc = hold.get((size_t)n * K * sizeof(double), (void**)&d_d);
+    if (rc != SFMHIP_OK) return rc;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+    rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
+    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    hipError_t e = hipSuccess;
+    if (idx) e = hipMemcpyAsync(idx, d_i, (size_t)n * K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, d_d, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    return points_finish(ctx, e);
+}
+
+int sfmhip_statistical_outliers(sfmhip_ctx* ctx, const double* pts, int n, int K, double std_ratio, int method, uint8_t* keep, double* mean_dist, double stats[3])
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_statistical_outliers");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && points_method_ok(method));
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, pts && keep);
+    const int nt = ceil_div(n, RED_TILE);
+    SfmPoolHold hold(ctx);
+    double *d_p = nullptr, *d_d = nullptr, *d_m = nullptr, *d_part = nullptr; int32_t* d_i = nullptr; uint8_t* d_keep = nullptr;
+    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_i);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * K * sizeof(double), (void**)&d_d);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(double), (void**)&d_m);
+    if (rc == SFMHIP_OK) rc = hold.get(((size_t)2 * nt + 4) * sizeof(double), (void**)&d_part);       // tile sums, then stats[3]
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n, (void**)&d_keep);
+    if (rc != SFMHIP_OK) return rc;
+    double* d_stats = d_part + 2 * (size_t)nt;
+    hipStream_t st = ctx->stream;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
+    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    hipLaunchKernelGGL(points_mean_dist_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const int32_t*)d_i, (const double*)d_d, n, K, d_m);
+    for (int pass = 0; pass < 2; ++pass) {
+        hipLaunchKernelGGL(points_stat_tile_kernel, dim3(nt), dim3(256), 0, st, (const double*)d_m, n, pass, (const double*)d_stats, d_part);
+        hipLaunchKernelGGL(points_stat_top_kernel, dim3(1), dim3(256), 0, st, (const double*)d_part, nt, pass, std_ratio, d_stats);
+    }
+    hipLaunchKernelGGL(points_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const double*)d_m, n, (const double*)d_stats, d_keep);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mean_dist) e = hipMemcpyAsync(mean_dist, d_m, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, 3 * sizeof(double), hipMemcpyDeviceToHost, st);
+    return points_finish(ctx, e);
+}
+
+int sfmhip_points_fallback_count(sfmhip_ctx* ctx, int* count)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_ARG_CHECK(ctx, ctx && count);
+    *count = 0;
+    if (!ctx->d_points_fallback) return SFMHIP_OK;
+    unsigned c = 0;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(&c, ctx->d_points_fallback, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *count = (int)c;
+    return SFMHIP_OK;
+}
+
+}  // extern "C"

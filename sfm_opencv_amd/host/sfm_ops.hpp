@@ -403,6 +403,24 @@ inline int estimate_normals(const std::vector<Point3d>& pts3d, const int K, std:
     return sfmhip_estimate_normals(ctx, &pts3d[0].x, (int)pts3d.size(), K, &normals[0].x) == SFMHIP_OK ? 0 : -1;
 }
 
+// ---- statistical outlier removal (extension, NOT reference behaviour: pcl::StatisticalOutlierRemoval / Open3D's
+// remove_statistical_outlier) -- keep[i] = 1 where the mean distance of point i to its K nearest neighbours is at most
+// mean + std_ratio * standard deviation of those means over the cloud.  Returns the number of points kept, -1 on error.
+inline int filter_outliers(const std::vector<Point3d>& pts3d, const int K, const double std_ratio, std::vector<unsigned char>& keep)
+{
+    sfmhip_ctx* ctx = context();
+    keep.assign(pts3d.size(), 0);
+    if (!ctx) return -1;
+    if (pts3d.empty()) return 0;
+    if (sfmhip_statistical_outliers(ctx, &pts3d[0].x, (int)pts3d.size(), K, std_ratio, SFMHIP_POINTS_AUTO, keep.data(), nullptr, nullptr) != SFMHIP_OK) {
+        printf("[Err]: filter_outliers: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    int kept = 0;
+    for (unsigned char k : keep) kept += k ? 1 : 0;
+    return kept;
+}
+
 // ---- outputs (NView:186-338) ------------------------------------------------------------------------------------
 namespace detail {
 // fs::doubleToString [3P] + the "%.16e" of the Windows CRT the reference's files were written with (exact decimal ties

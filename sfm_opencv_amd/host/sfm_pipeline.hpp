@@ -230,6 +230,7 @@ struct PipelineOptions {
                                            // TwoView:112).  driver_main sets the default per program: NViewReconstruct AKAZE, TwoViewReconstruct SIFT
     double refine_px = 0.0;                // > 0: after BA, refine_structure(max_px) + a second BA (extension, not reference behaviour)
     bool cross_check = false;              // mutual nearest neighbours only, after the ratio test (extension, not reference behaviour)
+    double filter_outliers_ratio = 0.0;    // > 0: structure_ba.ply holds only the points that pass filter_outliers(K = 10, ratio) (extension, not reference behaviour)
 };
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
@@ -311,8 +312,19 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         for (size_t i = 0; i < pts3d.size(); ++i)
             printf("Point3d %zu offset: [%.17g, %.17g, %.17g]\n", i, pts3d[i].x - pts3d_old[i].x, pts3d[i].y - pts3d_old[i].y, pts3d[i].z - pts3d_old[i].z);
 
-    std::vector<Point3d> normals(pts3d.size());
-    estimate_normals(pts3d, 10, normals);
+    // the cloud of the .ply: every point, or (--filter-outliers) what the statistical filter keeps, with normals of THAT cloud
+    std::vector<Point3d> ply_pts = pts3d;
+    std::vector<Vec3b> ply_colors = colors;
+    if (opt.filter_outliers_ratio > 0.0) {
+        std::vector<unsigned char> keep;
+        if (filter_outliers(pts3d, 10, opt.filter_outliers_ratio, keep) < 0) return -1;
+        ply_pts.clear(); ply_colors.clear();
+        for (size_t i = 0; i < pts3d.size(); ++i)
+            if (keep[i]) { ply_pts.push_back(pts3d[i]); if (i < colors.size()) ply_colors.push_back(colors[i]); }
+        printf("outlier filter: kept %zu of %zu points\n", ply_pts.size(), pts3d.size());
+    }
+    std::vector<Point3d> normals(ply_pts.size());
+    estimate_normals(ply_pts, 10, normals);
 
     if (opt.write_back_poses)
         for (size_t i = 0; i < extrinsics.size(); ++i) {
@@ -324,7 +336,7 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
     printf("structure_ba.yml saved.\n");
     printf("Saving structure to ply...\n");
     std::vector<Pt3DPly> pts3dply;
-    get_ply_pts3d(pts3d, normals, colors, pts3dply);
+    get_ply_pts3d(ply_pts, normals, ply_colors, pts3dply);
     write_ply_binary(opt.out_dir + "/structure_ba.ply", pts3dply);
     printf("%s/structure_ba.ply saved.\n", opt.out_dir.c_str());
     std::cout << "Save structure done." << std::endl;
@@ -364,7 +376,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -389,6 +401,8 @@ inline int driver_main(int argc, char** argv, bool nview)
         else if (a == "--cross-check") opt.cross_check = true;
         else if (a == "--refine") opt.refine_px = 4.0;
         else if (a.rfind("--refine=", 0) == 0) opt.refine_px = std::atof(a.c_str() + 9);
+        else if (a == "--filter-outliers") opt.filter_outliers_ratio = 2.0;
+        else if (a.rfind("--filter-outliers=", 0) == 0) opt.filter_outliers_ratio = std::atof(a.c_str() + 18);
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
         else if (positional++ == 0) opt.out_dir = a;
     }
