@@ -325,199 +325,15 @@ __device__ __forceinline__ long long shfl_xor_ll(long long v, int off)
 // ------------------------------------------------------------------------------------------------
 #define QV_PAD (3 << 29)              // pad query rows: their keys stay in [QV_PAD - 2^22, QV_PAD + 2^22], real keys below 2^30 + 2^15
 #define QV_REAL_MAX ((1 << 30) + (1 << 28))
-template <int KS>
-__global__ __launch_bounds__(256, KNN_WGS_PER_CU) void knn2_i8_kernel(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs)
-{
-    constexpr int DP = 32 * KS;          // bytes per row
-    constexpr int CH = DP / 16;          // 16-byte chunks per row
-    constexpr int TROWS = KNN_STAGE_ROWS, TILES = TROWS / 32;     // train rows staged per barrier
-    constexpr int PASSES = (TROWS * CH) / 256;
-    constexpr int BUF_BYTES = TROWS * DP, NORM_OFF = 2 * BUF_BYTES;
-    constexpr int STAGE_BYTES = 2 * BUF_BYTES + 2 * TROWS * 4, MERGE_BYTES = 4 * 32 * 33 * 8;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES];
-    // XCD-aware work mapping (speed only, any mapping is correct): consecutive workgroup ids go round-robin to the 8 XCDs,
-    // each with its own L2, so pair 8g + k is given to the workgroups with id = k (mod 8): one XCD streams one train
-    // image instead of all eight fetching every image (TCC FETCH_SIZE of the C4 launch: 1.06 GB -> see profiles/).
-    // The grid's z extent is padded to a multiple of 8.
-    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int per_pair = gridDim.x * gridDim.y, slot = lin >> 3;
-    const int pair = (slot / per_pair) * 8 + (lin & 7), rest = slot % per_pair;
-    if (pair >= n_pairs) return;
-    const PairDesc pd = pairs[pair];
-    const int qb = rest % gridDim.x, chunk = rest / gridDim.x;
-    if (qb * 128 >= pd.nq_pad || chunk >= pd.nchunks) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform by construction: keep it (and every address built from it) in SGPRs
-    const int l31 = lane & 31, half = lane >> 5;
-    // pointers that come out of the PairDesc table are generic to the compiler: without the address-space casts the
-    // train prefetch becomes flat_load, which also counts in lgkmcnt -- every LDS wait then waits for HBM as well
-    typedef const int8_t __attribute__((address_space(1)))* gi8;
-    typedef const int32_t __attribute__((address_space(1)))* gi32;
-    typedef const v4i __attribute__((address_space(1)))* gv4;
-    const gi8 Q = (gi8)(uintptr_t)pd.q;
-    const gi8 T = (gi8)(uintptr_t)pd.t;
-    const gi32 TN = (gi32)(uintptr_t)pd.tn;
-    const int t_begin = chunk * pd.chunk_rows;
-    int t_end = t_begin + pd.chunk_rows; if (t_end > pd.nt_pad) t_end = pd.nt_pad;
-    const int nblocks = (t_end - t_begin) / TROWS;
-    const int q0 = qb * 128 + wave * 32;
-
-    // stationary operand: 32 query rows per wave, lane holds row l31, k bytes [32 ks + 16 half, +16), COMPLEMENTED:
-    // ~a = -a - 1 stays in int8 range, and with S = sum (~a) b = -a.b - sum b the partial key
-    //     (|b|^2 - 2 a.b) * 128 + slot = (|b|^2 + 2 sum b) * 128 + slot + (S << 8)
-    // is one v_lshl_add_u32 per accumulator (the train-side term comes from the prep kernel).  Zero padding stays
-    // neutral: padded query bytes become -1 but meet zero train bytes.
-    v4i afrag[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        afrag[ks] = ~*(gv4)(Q + (size_t)(q0 + l31) * DP + 32 * ks + 16 * half);
-        asm volatile("" : "+v"(afrag[ks]));      // opaque: hipcc otherwise re-derives the complement inside the loop
-    }
-
-    int best1[16], best2[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { best1[i] = INT_MAX; best2[i] = INT_MAX; }
-
-    // Staging is LDS-DMA (global_load_lds_dwordx4: 64 lanes x 16 B land at M0 + lane*16, no staging registers and no
-    // ds_write): wave w's p-th instruction fills the 1 KB segment seg = 4p + w of the buffer, i.e. LDS chunk position
-    // (row r = 8 seg + lane/8, slot = lane%8); the XOR swizzle is applied on the GLOBAL side -- the lane fetches chunk
-    // c = slot ^ ((r >> 1) & (CH-1)) of row r -- so the operand reads below find chunk c of row r at slot c ^ ((r>>1)&(CH-1)).
-    // (r >> 1) & (CH-1) does not depend on p, so pass p is a uniform +p*4096 on both sides.
-    // Everything the loop addresses is a per-thread constant plus a compile-time offset: the VALU is the busiest unit of
-    // this kernel (PMC: SQ_ACTIVE_INST_VALU 74 % of the wall time), so the loop spends it on the top-2 epilogue only.
-    static_assert(DP == 128 || PASSES == 1 || (1024 / DP) % (2 * CH) == 0, "staging swizzle must repeat per pass");
-    typedef const char __attribute__((address_space(1)))* gbytes;
-    typedef char __attribute__((address_space(3)))* lbytes;
-    int rd_off[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) rd_off[ks] = l31 * DP + 16 * ((2 * ks + half) ^ ((l31 >> 1) & (CH - 1)));
-    const int seg_row = (wave * 1024 + lane * 16) / DP, seg_slot = ((wave * 1024 + lane * 16) % DP) / 16;
-    const unsigned st_goff = (unsigned)(seg_row * DP + 16 * (seg_slot ^ ((seg_row >> 1) & (CH - 1))));     // unsigned: lets hipcc use the SGPR-base + 32-bit VGPR-offset form
-    const int nrm_off = NORM_OFF + 4 * l31;
-
-    auto g_stage = [&](auto bufc, int blk) {
-        constexpr int buf = decltype(bufc)::value;
-        const gbytes blk_base = (gbytes)(T + (size_t)(t_begin + blk * TROWS) * DP);      // wave-uniform
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p)
-        {
-            unsigned long long pb = (unsigned long long)(uintptr_t)(blk_base + p * 4096);
-            asm volatile("" : "+s"(pb));          // keep the per-pass base in SGPRs: one VGPR offset serves all passes
-            __builtin_amdgcn_global_load_lds((gbytes)pb + st_goff, (lbytes)(lds + buf * BUF_BYTES + p * 4096 + wave * 1024), 16, 0, 0);
-        }
-        // train-side key terms (|b|^2 + 2 sum b), one dword per row
-        if (wave < TROWS / 64)
-        {
-            unsigned long long nb = (unsigned long long)(uintptr_t)(TN + t_begin + blk * TROWS + wave * 64);
-            asm volatile("" : "+s"(nb));
-            __builtin_amdgcn_global_load_lds((gbytes)nb + (unsigned)(4 * lane), (lbytes)(lds + NORM_OFF + buf * (4 * TROWS) + wave * 256), 4, 0, 0);
-        }
-    };
-    // one block of TROWS trains out of LDS buffer `buf`
-    auto compute = [&](auto bufc, int blk) {
-        constexpr int buf = decltype(bufc)::value;
-        // One tile at a time: 4 fragments, KS MFMAs, then the epilogue on the finished accumulator.  Nothing overlaps inside
-        // the wave on purpose -- this form needs <= 128 VGPRs, and FOUR resident waves per SIMD overlap each other's MFMA,
-        // VALU and LDS phases better than the software-pipelined 180-register form did with two (the epilogue mix issues at
-        // 2.0 ns per instruction per SIMD with 4 waves against 2.3 with 2, experiments/valu_bench.hip).  Round 3 re-tried it the way the
-        // FP4 Hamming2 kernel does it -- tile t - 1's update dealt out behind the four MFMAs of tile t, two accumulator sets, 167
-        // registers = three waves per SIMD: 0.850-0.861 ms against 0.874-0.877 in the same call (2 %): not kept.
-#pragma unroll
-        for (int tile = 0; tile < TILES; ++tile) {
-            v4i bf[KS];
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) bf[ks] = *(const v4i*)(lds + rd_off[ks] + (buf * BUF_BYTES + tile * 32 * DP));
-            const int nbt = (*(const int*)(lds + nrm_off + (buf * (4 * TROWS) + tile * 128)) << 7) + (blk * TILES + tile);
-            v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afrag[ks], bf[ks], acc, 0, 0, 0);
-            // C[row = query (reg), col = train (lane&31)].  key = (|b|^2 - 2 a.b) * 128 + local tile index.
-            // Three VALU ops per accumulator: v_lshl_add_u32, v_med3_i32 (second smallest of {best1 <= best2, key}), v_min_i32.
-            // (Round 3 tried compare-and-skip -- a key only matters below the runner-up, ~2 / j of the time for the j-th train: key +
-            // v_cmp + s_cbranch_vccnz to an out-of-line update per register, 2.2 instructions per distance -- and measured 1.20 ms
-            // against 0.87: sixteen dependent compare -> branch waits per tile cost more than the sixteen instructions saved.)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int key = (int)(((unsigned)acc[i] << 8) + (unsigned)nbt);
-                const int lo = best1[i] < best2[i] ? best1[i] : best2[i], hi = best1[i] < best2[i] ? best2[i] : best1[i];
-                const int t = hi < key ? hi : key;
-                best2[i] = lo > t ? lo : t;                                  // max(min(a,b), min(max(a,b), c)) = med3
-                best1[i] = best1[i] < key ? best1[i] : key;
-                asm volatile("" : "+v"(best1[i]), "+v"(best2[i]));          // pin here: LLVM otherwise sinks the whole epilogue below the barrier
-            }
-        }
-    };
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-
 #if !defined(KNN_EXP) || !defined(SFMHIP_EXPERIMENTS)
 #undef KNN_EXP
 #define KNN_EXP 0              // timing experiments only (SFMHIP_EXPERIMENTS builds; wrong results): 1 = no staging / barriers after the first block
 #endif
-    if (nblocks > 0) g_stage(B0{}, 0);
-    __syncthreads();
-    for (int blk = 0; blk < nblocks; blk += 2) {
-        if (blk + 1 < nblocks && !(KNN_EXP & 1)) g_stage(B1{}, blk + 1);
-        compute(B0{}, blk);
-        if (!(KNN_EXP & 1)) __syncthreads();
-        if (blk + 1 >= nblocks) break;
-        if (blk + 2 < nblocks && !(KNN_EXP & 1)) g_stage(B0{}, blk + 2);
-        compute(B1{}, blk + 1);
-        if (!(KNN_EXP & 1)) __syncthreads();
-    }
-
-    // Merge across the 32 lanes that share a query row, through LDS (the staging buffers are free after the last
-    // barrier): every lane parks its 16 (best1, best2) pairs, then lane L scans half of row L>>1's 32 parked pairs
-    // in ascending lane order with 32-bit compares -- (key, lane) ordering IS (distance, train index) ordering, and a
-    // strict < keeps the lower lane on ties -- and only the two winners are widened to 64-bit global keys.
-    // (The previous 5-level xor-shuffle merge on 64-bit keys was ~2000 instructions per wave, a third of the kernel.)
-    {
-        int2* wk = (int2*)lds + wave * (32 * 33);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
-            wk[row * 33 + l31] = make_int2(best1[i], best2[i]);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int row = lane >> 1, side = lane & 1;
-        int m1 = INT_MAX, m2 = INT_MAX, i1 = 0, i2 = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int l = side * 16 + j;
-            const int2 v = wk[row * 33 + l];
-            const bool c1 = v.x < m1, c2 = v.x < m2;
-            m2 = c1 ? m1 : (c2 ? v.x : m2); i2 = c1 ? i1 : (c2 ? l : i2);
-            m1 = c1 ? v.x : m1;             i1 = c1 ? l : i1;
-            const bool c3 = v.y < m2;        // v.y >= v.x: it can only displace the runner-up
-            m2 = c3 ? v.y : m2;             i2 = c3 ? l : i2;
-        }
-        // fold the odd lane (upper 16 source lanes) into the even one; ties stay with the even lane's lower source lanes
-        const int o1 = __shfl_xor(m1, 1), oi1 = __shfl_xor(i1, 1), o2 = __shfl_xor(m2, 1), oi2 = __shfl_xor(i2, 1);
-        {
-            const bool c1 = o1 < m1, c2 = o1 < m2;
-            m2 = c1 ? m1 : (c2 ? o1 : m2); i2 = c1 ? i1 : (c2 ? oi1 : i2);
-            m1 = c1 ? o1 : m1;             i1 = c1 ? oi1 : i1;
-            const bool c3 = o2 < m2;
-            m2 = c3 ? o2 : m2;             i2 = c3 ? oi2 : i2;
-        }
-        if (side == 0) {
-            const int qrow = q0 + row;
-            const int qn = ((const int32_t __attribute__((address_space(1)))*)(uintptr_t)pd.qn)[qrow];
-            long long k1 = KEY_INVALID, k2 = KEY_INVALID;
-            if (m1 != INT_MAX) k1 = ((long long)((m1 >> 7) + qn) << 32) | (unsigned int)(t_begin + (m1 & 127) * 32 + i1);
-            if (m2 != INT_MAX) k2 = ((long long)((m2 >> 7) + qn) << 32) | (unsigned int)(t_begin + (m2 & 127) * 32 + i2);
-            long long* o = part + 2 * (pd.part_off + (long long)qrow * pd.nchunks + chunk);
-            o[0] = k1; o[1] = k2;
-        }
-    }
-}
-
-// the 16 query-side constants do not fit beside the plain kernel's 128 registers: three workgroups per CU (168 registers)
-template <int KS>
-__global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs,
-                                                                             unsigned long long* __restrict__ rev, const long long* __restrict__ rev_off)
+// One body for both kernels: knn2_i8_kernel and knn2_i8_mutual_kernel below are wrappers, and the statements of the column pass sit
+// under if constexpr (MUTUAL), so the plain kernel compiles to what it was without them (see the note at the wrappers).
+template <int KS, bool MUTUAL>
+__device__ __forceinline__ void knn2_i8_body(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs,
+                                             unsigned long long* __restrict__ rev, const long long* __restrict__ rev_off)
 {
     constexpr int DP = 32 * KS;          // bytes per row
     constexpr int CH = DP / 16;          // 16-byte chunks per row
@@ -526,8 +342,8 @@ __global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* 
     constexpr int BUF_BYTES = TROWS * DP, NORM_OFF = 2 * BUF_BYTES;
     constexpr int STAGE_BYTES = 2 * BUF_BYTES + 2 * TROWS * 4, MERGE_BYTES = 4 * 32 * 33 * 8;
     constexpr int MAIN_BYTES = STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES;
-    constexpr int COL_BYTES = 2 * 4 * TROWS * 4;            // column minima: [buffer][wave][train row of the stage]
-    __shared__ __attribute__((aligned(16))) unsigned char lds[MAIN_BYTES + COL_BYTES];
+    constexpr int COL_BYTES = 2 * 4 * TROWS * 4;            // MUTUAL: column minima, [buffer][wave][train row of the stage]
+    __shared__ __attribute__((aligned(16))) unsigned char lds[MAIN_BYTES + (MUTUAL ? COL_BYTES : 0)];
     // XCD-aware work mapping (speed only, any mapping is correct): consecutive workgroup ids go round-robin to the 8 XCDs,
     // each with its own L2, so pair 8g + k is given to the workgroups with id = k (mod 8): one XCD streams one train
     // image instead of all eight fetching every image (TCC FETCH_SIZE of the C4 launch: 1.06 GB -> see profiles/).
@@ -570,8 +386,8 @@ __global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* 
     int best1[16], best2[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) { best1[i] = INT_MAX; best2[i] = INT_MAX; }
-    int qv[16];
-    {
+    int qv[MUTUAL ? 16 : 1];             // MUTUAL: the query-side term of the column key, one per accumulator register
+    if constexpr (MUTUAL) {
         const gi32 QN = (gi32)(uintptr_t)pd.qn;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -618,8 +434,13 @@ __global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* 
     // one block of TROWS trains out of LDS buffer `buf`
     auto compute = [&](auto bufc, int blk) {
         constexpr int buf = decltype(bufc)::value;
-        // One tile at a time, as in knn2_i8_kernel (see there); with the column pass this copy needs up to 150 registers and runs
-        // three waves per SIMD instead of four.
+        // One tile at a time: 4 fragments, KS MFMAs, then the epilogue on the finished accumulator.  Nothing overlaps inside
+        // the wave on purpose -- this form needs <= 128 VGPRs, and FOUR resident waves per SIMD overlap each other's MFMA,
+        // VALU and LDS phases better than the software-pipelined 180-register form did with two (the epilogue mix issues at
+        // 2.0 ns per instruction per SIMD with 4 waves against 2.3 with 2, experiments/valu_bench.hip).  Round 3 re-tried it the way the
+        // FP4 Hamming2 kernel does it -- tile t - 1's update dealt out behind the four MFMAs of tile t, two accumulator sets, 167
+        // registers = three waves per SIMD: 0.850-0.861 ms against 0.874-0.877 in the same call (2 %): not kept.
+        // MUTUAL: with the column pass the kernel needs up to 150 registers and runs three waves per SIMD instead of four.
 #pragma unroll
         for (int tile = 0; tile < TILES; ++tile) {
             v4i bf[KS];
@@ -643,7 +464,7 @@ __global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* 
                 best1[i] = best1[i] < key ? best1[i] : key;
                 asm volatile("" : "+v"(best1[i]), "+v"(best2[i]));          // pin here: LLVM otherwise sinks the whole epilogue below the barrier
             }
-            {
+            if constexpr (MUTUAL) {      // the wave's column minimum of the tile (see the header), into this buffer's LDS area
                 int cm = INT_MAX;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -659,7 +480,7 @@ __global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* 
     // MUTUAL: after the barrier that closes block blk (buffer buf), fold the four waves' column minima into rev[].  The area is
     // next written by the compute of block blk + 2, behind another barrier.
     auto col_flush = [&](int buf, int blk) {
-        {
+        if constexpr (MUTUAL) {
             if (tid >= 256 - TROWS) {
                 const int c = tid - (256 - TROWS);
                 const int* cb = (const int*)(lds + MAIN_BYTES) + buf * 4 * TROWS + c;
@@ -678,10 +499,6 @@ __global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* 
     using B0 = std::integral_constant<int, 0>;
     using B1 = std::integral_constant<int, 1>;
 
-#if !defined(KNN_EXP) || !defined(SFMHIP_EXPERIMENTS)
-#undef KNN_EXP
-#define KNN_EXP 0              // timing experiments only (SFMHIP_EXPERIMENTS builds; wrong results): 1 = no staging / barriers after the first block
-#endif
     if (nblocks > 0) g_stage(B0{}, 0);
     __syncthreads();
     for (int blk = 0; blk < nblocks; blk += 2) {
@@ -742,6 +559,24 @@ __global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* 
             o[0] = k1; o[1] = k2;
         }
     }
+}
+
+// The kernels are wrappers around the one body.  The pairs used to be kept copies, because an earlier attempt at a template flag had
+// changed the plain kernels' register allocation; with the body as a __forceinline__ function template and the column pass under
+// if constexpr, the gfx950 assembly of all three knn2_i8_kernel, all three knn2_i8_mutual_kernel and knn2_hamming2_fp4_kernel<8> has
+// the parent's resource numbers, instruction counts and opcode histograms (profiles/r10_knn_one_body_asm.log), and
+// tests/test_match_mutual_cpu.py pins the resource numbers of all eight instantiations.
+template <int KS>
+__global__ __launch_bounds__(256, KNN_WGS_PER_CU) void knn2_i8_kernel(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs)
+{
+    knn2_i8_body<KS, false>(pairs, part, n_pairs, nullptr, nullptr);
+}
+// the 16 query-side constants do not fit beside the plain kernel's 128 registers: three workgroups per CU (168 registers)
+template <int KS>
+__global__ __launch_bounds__(256, 3) void knn2_i8_mutual_kernel(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs,
+                                                                             unsigned long long* __restrict__ rev, const long long* __restrict__ rev_off)
+{
+    knn2_i8_body<KS, true>(pairs, part, n_pairs, rev, rev_off);
 }
 
 #define DISTMAT_WAVES 4
@@ -1111,28 +946,47 @@ __global__ __launch_bounds__(256) void knn2_hamming2_kernel(const PairDesc* __re
 //     fragment itself): keys above 3e6, never selected while a real row is left.  Two VALU ops per distance (below).
 //   * chunks are power-of-two sized and aligned, <= 8192 rows, so the 8-bit tile index is monotone inside a chunk.
 // Partial output as knn2_hamming2_kernel: two keys (distance << 32 | train index) per (query row, chunk).
+// MUTUAL (knn2_hamming2_fp4_mutual_kernel): the same pass also finds the reverse best of every train row (knn2_i8_mutual_kernel's
+// scheme, see there).  Along a column the train tile index and off_k are constant, so the accumulator orders the queries directly:
+// (value + row in the wave) is compared as a float (exact: |value| < 2^16) beside each top-2 update.  Pad query rows (and the rows of
+// waves that only repeat the block's first rows) are the rows r >= nq - q0, a suffix of every lane's registers: a compare and a select
+// per value put H4_QPAD in their place (four VALU ops per distance for the column, beside the top-2's two).  A tile's column minimum
+// is complete at K-step 11 of the NEXT tile (where the top-2 update of the finished tile ends): one lane swap across the halves, one
+// LDS store per lane of the lower half; the stage's minima meet after the following barrier (three buffers: a stage's second tile
+// lands one stage late), where the last wave decodes (distance, row), takes the minimum over the waves and folds
+// (distance << 32 | query) into rev[] with a 64-bit atomicMin.
 // ------------------------------------------------------------------------------------------------
 typedef int   v8i  __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-template <int NW>        // waves per workgroup (4 or 8), 64 query rows each
-__global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs)
-{
-#ifdef __HIP_DEVICE_COMPILE__      // the host pass only needs the launch stub: instantiating a TEMPLATE body with gfx950 builtins there drops the stub
 #ifndef H4_TROWS
 #define H4_TROWS 64
 #endif
-    constexpr int RB = H4_ROW_BYTES, TROWS = H4_TROWS, BUF_BYTES = TROWS * RB, BUF_STRIDE = TROWS * 512, TILE_BYTES = 32 * RB, QB = 64 * NW;
-    constexpr int NG = 12 * (TROWS / 32);                    // K-steps per stage
+#ifndef H4_AHEAD
+#define H4_AHEAD 1             // K-steps a train fragment is read ahead of its MFMAs: 1, 2 and 3 measured the same (1.36-1.37 ms), 1 leaves 8 registers of margin
+#endif
 #if !defined(H4_EXP) || !defined(SFMHIP_EXPERIMENTS)
 #undef H4_EXP
 #define H4_EXP 0               // timing experiments only (SFMHIP_EXPERIMENTS builds; wrong results): 1 = no staging after the first stage, 2 = no barriers, 4 = no top-2 updates, 8 = no fragment reads after the first three, 32 = one stage per workgroup, 64 = no merge epilogue, 128 = no query loads
 #endif
+#define H4_QPAD 4.0e6f
+#define H4_TOP2(B1v, B2v, KEY) asm volatile("v_med3_f32 %1, %0, %1, %2\n\tv_med3_f32 %0, %0, %2, %3" : "+v"(B1v), "+v"(B2v) : "v"(KEY), "s"(neg_inf))
+#define H4_COLMIN(CM, X) asm volatile("v_min_f32 %0, %0, %1" : "+v"(CM) : "v"(X))
+
+// One body for both kernels (the wrappers follow it): the statements of the column pass sit under if constexpr (MUTUAL).
+template <int NW, bool MUTUAL>        // waves per workgroup (4 or 8), 64 query rows each
+__device__ __forceinline__ void knn2_hamming2_fp4_body(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs,
+                                                       unsigned long long* __restrict__ rev, const long long* __restrict__ rev_off)
+{
+#ifdef __HIP_DEVICE_COMPILE__      // the host pass only needs the launch stubs: instantiating a TEMPLATE body with gfx950 builtins there drops the stub
+    constexpr int RB = H4_ROW_BYTES, TROWS = H4_TROWS, BUF_BYTES = TROWS * RB, BUF_STRIDE = TROWS * 512, TILE_BYTES = 32 * RB, QB = 64 * NW;
+    constexpr int NG = 12 * (TROWS / 32);                    // K-steps per stage
 
     constexpr int PASSES = BUF_BYTES / (1024 * NW);          // LDS-DMA instructions per wave and stage: 6 (4 waves) / 3 (8 waves)
     constexpr int MERGE_BYTES = NW * 32 * 33 * 8, STAGE_BYTES = BUF_STRIDE + BUF_BYTES;
     static_assert(BUF_BYTES % (1024 * NW) == 0 && BUF_BYTES <= BUF_STRIDE, "whole 1 KB pieces per wave");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES];
+    constexpr int MAIN_BYTES = STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[MAIN_BYTES + (MUTUAL ? 3 * NW * TROWS * 4 : 0)];      // MUTUAL: + column minima [stage % 3][wave][train row]
     const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     const int per_pair = gridDim.x * gridDim.y, slot = lin >> 3;
     const int pair = (slot / per_pair) * 8 + (lin & 7), rest = slot % per_pair;       // pair -> XCD, as knn2_i8_kernel
@@ -1185,6 +1039,10 @@ __global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const Pai
     for (int at = 0; at < 2; ++at)
 #pragma unroll
         for (int i = 0; i < 16; ++i) { best1[at][i] = 1.0e9f; best2[at][i] = 1.0e9f; }
+    // MUTUAL: rows r = 32 at + (i & 3) + 8 (i >> 2) + 4 half of the wave are real iff r < pd.nq - q0 (q0, not q0r: a wave without rows has none)
+    const float lim = (float)(pd.nq - q0 - 4 * half), hoff = half ? 4.0f : 0.0f;
+    float cm = 1.0e9f;                         // running column minimum of the pending tile
+    float* colbuf = (float*)(lds + MAIN_BYTES);
 
     // staging: the buffer is the stage's 64 rows back to back (24 KB); piece NW p + w (1 KB, one LDS-DMA instruction of wave w) covers
     // LDS bytes [1024 (NW p + w), +1024): the lane's 16 bytes are slot (pos % 384) / 16 of row pos / 384, which holds chunk
@@ -1228,16 +1086,51 @@ __global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const Pai
     v16f accA0, accA1, accB0, accB1;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { accB0[i] = 1.0e9f; accB1[i] = 1.0e9f; }
-#define H4_TOP2(B1v, B2v, KEY) asm volatile("v_med3_f32 %1, %0, %1, %2\n\tv_med3_f32 %0, %0, %2, %3" : "+v"(B1v), "+v"(B2v) : "v"(KEY), "s"(neg_inf))
-    auto top2_of = [&](v16f& p0, v16f& p1, int v) {          // value v = 0..31 of a finished tile's two accumulators
-        if (v < 16) H4_TOP2(best1[0][v], best2[0][v], p0[v]);
-        else if (v < 32) H4_TOP2(best1[1][v - 16], best2[1][v - 16], p1[v - 16]);
+    // MUTUAL: column update of one value: its row r in the wave (less 4 half) as the tie-break, pad query rows (r >= lim) out of the race
+    auto col_of = [&](float p, int r) {
+        if constexpr (MUTUAL) {
+            float x = p + (float)r;
+            x = (float)r < lim ? x : H4_QPAD;
+            H4_COLMIN(cm, x);
+        }
     };
-    auto compute = [&]() {
+    auto top2_of = [&](v16f& p0, v16f& p1, int v) {          // value v = 0..31 of a finished tile's two accumulators
+        if (v < 16) { H4_TOP2(best1[0][v], best2[0][v], p0[v]); col_of(p0[v], (v & 3) + 8 * (v >> 2)); }
+        else if (v < 32) { const int i = v - 16; H4_TOP2(best1[1][i], best2[1][i], p1[i]); col_of(p1[i], 32 + (i & 3) + 8 * (i >> 2)); }
+    };
+    // MUTUAL: the finished tile's column minima (stage sb, tile position tp) into LDS
+    auto col_emit = [&](int sb, int tp) {
+        if constexpr (MUTUAL) {
+            float c2 = cm + hoff;
+            const float o = __shfl_xor(c2, 32);
+            c2 = c2 < o ? c2 : o;
+            if (half == 0) colbuf[((sb % 3) * NW + wave) * TROWS + tp * 32 + l31] = c2;
+            cm = 1.0e9f;
+        }
+    };
+    const int off_k = 768 * pd.dim;
+    // MUTUAL: after the barrier that follows the stage after sb (where sb's second tile was stored): fold the waves' minima into rev[]
+    auto col_flush = [&](int sb) {
+        if constexpr (MUTUAL) {
+            if (tid >= 64 * NW - TROWS) {
+                const int c = tid - (64 * NW - TROWS), j = t_begin + sb * TROWS + c;
+                if (j < pd.nt) {
+                    const int tix = (j >> 5) & 255;
+                    int best = INT_MAX;
+                    for (int w = 0; w < NW; ++w) {
+                        const int x = (int)colbuf[((sb % 3) * NW + w) * TROWS + c] + off_k - tix;      // 256 distance + row
+                        const int d = x >> 8, r = x & 255;
+                        const int key = (d >= 0 && d <= 4 * pd.dim && r < 64) ? (d << 9) | (w * 64 + r) : INT_MAX;
+                        best = key < best ? key : best;
+                    }
+                    if (best != INT_MAX)
+                        atomicMin(rev + rev_off[pair] + j, ((unsigned long long)(unsigned)(best >> 9) << 32) | (unsigned)(qb * QB + (best & 511)));
+                }
+            }
+        }
+    };
+    auto compute = [&](int blk) {
         auto rd = [&](int g) { return *(const v4i*)(lds + rd_off[(g % 12) & 3] + ((g / 12) * TILE_BYTES + 128 * ((g % 12) >> 2))); };
-#ifndef H4_AHEAD
-#define H4_AHEAD 1             // K-steps a train fragment is read ahead of its MFMAs: 1, 2 and 3 measured the same (1.36-1.37 ms), 1 leaves 8 registers of margin
-#endif
         v4i bq[H4_AHEAD + 1];
 #pragma unroll
         for (int g = 0; g < H4_AHEAD; ++g) bq[g] = rd(g);
@@ -1266,6 +1159,8 @@ __global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const Pai
                 c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a0, b8, c0, 4, 4, 0, sa, 0, sbv);
                 c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a1, b8, c1, 4, 4, 0, sa, 0, sbv);
                 if (!(H4_EXP & 4)) { top2_of(p0, p1, 3 * (s - 1)); top2_of(p0, p1, 3 * (s - 1) + 1); top2_of(p0, p1, 3 * (s - 1) + 2); }
+                // MUTUAL: the pending tile is done: tile 1 of the previous stage (nothing before stage 0) or tile 0 of this one
+                if (s == 11) { if (tile == 1) col_emit(blk, 0); else if (blk > 0) col_emit(blk - 1, 1); }
             }
             // pin the pair here: set B's second chain has no reader before the next trip of the loop, and LLVM sank all twelve of
             // its MFMAs (and their twelve train fragments: 48 registers) below the stage's last step
@@ -1279,17 +1174,24 @@ __global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const Pai
     __syncthreads();
     for (int blk = 0; blk < nblocks; ++blk) {
         if (blk + 1 < nblocks && !(H4_EXP & 1)) g_stage((blk + 1) & 1, blk + 1);
-        compute();
+        compute(blk);
 #pragma unroll
         for (int j = 0; j < 4; ++j) rd_off[j] ^= BUF_STRIDE;
         if (!(H4_EXP & 2)) __syncthreads();
+        if (blk > 0) col_flush(blk - 1);
     }
     if (H4_EXP & 2) __syncthreads();
     // flush: the last tile's accumulators (set B)
     asm volatile("s_nop 11");
 #pragma unroll
     for (int v = 0; v < 32; ++v) top2_of(accB0, accB1, v);
-#undef H4_TOP2
+    if constexpr (MUTUAL) {
+        if (nblocks > 0) {
+            col_emit(nblocks - 1, 1);
+            __syncthreads();
+            col_flush(nblocks - 1);
+        }
+    }
 
     // merge across the 32 lanes that share a query row (as knn2_i8_kernel), one query tile at a time, on integer keys
     // K = key + 192 cells = 256 distance + tile for a real train (< 2^16); a pad row or the initial value is above 2^20
@@ -1300,7 +1202,7 @@ __global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const Pai
     // tests/test_match_gpu.py::test_knn2_hamming2_matrix_core_kernel_pad_rows_never_beat_the_worst_real_row the outcome.
     static_assert(256 * (4 * H4_MAX_NBYTES) + 255 < (1 << 16), "real Hamming2 keys must stay below 2^16");
     static_assert(27 * 36 * 1024 + 768 >= (1 << 20) - (1 << 16), "pad-row keys must clear every real key by the tested margin");
-    const int off_k = 768 * pd.dim, k_pad = 1 << 20;
+    const int k_pad = 1 << 20;
     const int win_base = t_begin & ~8191;
     if (H4_EXP & 64) {            // 64: no merge (one store per lane keeps the registers alive)
         float sum = 0.0f;
@@ -1357,293 +1259,20 @@ __global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const Pai
 #endif
 }
 
-
-// knn2_hamming2_fp4_kernel plus the reverse best of every train row (knn2_i8_mutual_kernel's scheme, see there).  Along a column the
-// train tile index and off_k are constant, so the accumulator orders the queries directly: (value + row in the wave) is compared as a
-// float (exact: |value| < 2^16) beside each top-2 update.  Pad query rows (and the rows of waves that only repeat the block's first
-// rows) are the rows r >= nq - q0, a suffix of every lane's registers: a compare and a select per value put H4_QPAD in their place
-// (four VALU ops per distance for the column, beside the top-2's two).  A tile's column minimum is complete at K-step 11 of the NEXT tile (where the top-2 update
-// of the finished tile ends): one lane swap across the halves, one LDS store per lane of the lower half; the stage's minima meet
-// after the following barrier (three buffers: a stage's second tile lands one stage late), where the last wave decodes (distance,
-// row), takes the minimum over the waves and folds (distance << 32 | query) into rev[] with a 64-bit atomicMin.
-// The kept copy (not a template flag) leaves the plain kernel's instructions exactly as they were; tests/test_match_mutual_cpu.py
-// checks that every code line of the plain kernel is still in this one, in order.
-#define H4_QPAD 4.0e6f
-template <int NW>        // waves per workgroup (4 or 8), 64 query rows each
+// Wrappers, as for the int8 pair (see the note there).  knn2_hamming2_fp4_mutual_kernel<8> keeps the kept copy's 255 registers, 20
+// bytes of scratch and 4 spilled registers and is five instructions longer (inlining the body alone does that, with no if constexpr in
+// it): the MFMA stream is the same, the staging block at the top of the stage loop reloads four SGPRs from VGPR lanes, the column
+// flush is arranged differently (profiles/r10_knn_one_body_asm.log; timed against the copy in profiles/README.md, round 10).
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_kernel(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs)
+{
+    knn2_hamming2_fp4_body<NW, false>(pairs, part, n_pairs, nullptr, nullptr);
+}
+template <int NW>
 __global__ __launch_bounds__(64 * NW, 2) void knn2_hamming2_fp4_mutual_kernel(const PairDesc* __restrict__ pairs, long long* __restrict__ part, int n_pairs,
                                                                               unsigned long long* __restrict__ rev, const long long* __restrict__ rev_off)
 {
-#ifdef __HIP_DEVICE_COMPILE__      // the host pass only needs the launch stub: instantiating a TEMPLATE body with gfx950 builtins there drops the stub
-#ifndef H4_TROWS
-#define H4_TROWS 64
-#endif
-    constexpr int RB = H4_ROW_BYTES, TROWS = H4_TROWS, BUF_BYTES = TROWS * RB, BUF_STRIDE = TROWS * 512, TILE_BYTES = 32 * RB, QB = 64 * NW;
-    constexpr int NG = 12 * (TROWS / 32);                    // K-steps per stage
-
-    constexpr int PASSES = BUF_BYTES / (1024 * NW);          // LDS-DMA instructions per wave and stage: 6 (4 waves) / 3 (8 waves)
-    constexpr int MERGE_BYTES = NW * 32 * 33 * 8, STAGE_BYTES = BUF_STRIDE + BUF_BYTES;
-    static_assert(BUF_BYTES % (1024 * NW) == 0 && BUF_BYTES <= BUF_STRIDE, "whole 1 KB pieces per wave");
-    constexpr int MAIN_BYTES = STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[MAIN_BYTES + 3 * NW * TROWS * 4];      // + column minima [stage % 3][wave][train row]
-    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int per_pair = gridDim.x * gridDim.y, slot = lin >> 3;
-    const int pair = (slot / per_pair) * 8 + (lin & 7), rest = slot % per_pair;       // pair -> XCD, as knn2_i8_kernel
-    if (pair >= n_pairs) return;
-    const PairDesc pd = pairs[pair];
-    const int qb = rest % gridDim.x, chunk = rest / gridDim.x;
-    if (qb * QB >= pd.nq_pad || chunk >= pd.nchunks) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, half = lane >> 5;
-    typedef const char __attribute__((address_space(1)))* gbytes;
-    typedef char __attribute__((address_space(3)))* lbytes;
-    typedef const v4i __attribute__((address_space(1)))* gv4;
-    const gbytes Q = (gbytes)(uintptr_t)pd.q;
-    const gbytes T = (gbytes)(uintptr_t)pd.t;
-    const int t_begin = chunk * pd.chunk_rows;
-    int t_end = t_begin + pd.chunk_rows; if (t_end > pd.nt_pad) t_end = pd.nt_pad;
-    const int nblocks = (t_end - t_begin) / TROWS;
-    const int q0 = qb * QB + wave * 64;
-    // sets are padded to 256 rows: with 512-row query blocks the upper waves of the last block may have no rows; they still stage and
-    // meet the barriers, on the block's first rows, and write nothing
-    const bool has_rows = q0 < pd.nq_pad;
-    const int q0r = has_rows ? q0 : qb * QB;
-
-    // stationary operand
-    v4i afrag[2][12];
-#pragma unroll
-    for (int at = 0; at < 2; ++at)
-#pragma unroll
-        for (int s = 0; s < 12; ++s) {
-            v4i a = *(gv4)(Q + (size_t)(q0r + 32 * at + l31) * RB + 16 * (2 * s + half));
-            a ^= (v4i){ (int)0x88888888, (int)0x88888888, (int)0x88888888, (int)0x88888888 };
-            if (s == 11) {
-                if (half == 0) a[3] = (a[3] & 0x0000ffff) | 0x77770000;                                  // values 732..735: 6.0
-                else a = (v4i){ 0x66664211, 0x77777776, 0x77777777, 0x77777777 };                        // tile-bit weights (9 values), then 6.0
-            }
-            asm volatile("" : "+v"(a));
-            afrag[at][s] = a;
-        }
-    // block scales, one register each: query side 2^6 on the even blocks (lanes 0..31) and 2^2 on the odd ones (lanes 32..63), train
-    // side 2^0 / 2^4 -- so every data block is scaled by 2^6 -- except in the last K-step, where the train side is 2^0 on both (block 23
-    // = 2^2) or 2^8 on a pad row
-    const int sa = half ? 129 : 133;
-    const int sb = half ? 131 : 127;
-    float neg_inf = -__builtin_inff();
-    asm volatile("" : "+s"(neg_inf));                      // an SGPR operand, not a literal per instruction
-
-    float best1[2][16], best2[2][16];
-#pragma unroll
-    for (int at = 0; at < 2; ++at)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { best1[at][i] = 1.0e9f; best2[at][i] = 1.0e9f; }
-    // rows r = 32 at + (i & 3) + 8 (i >> 2) + 4 half of the wave are real iff r < pd.nq - q0 (q0, not q0r: a wave without rows has none)
-    const float lim = (float)(pd.nq - q0 - 4 * half), hoff = half ? 4.0f : 0.0f;
-    float cm = 1.0e9f;                         // running column minimum of the pending tile
-    float* colbuf = (float*)(lds + MAIN_BYTES);
-
-    // staging: the buffer is the stage's 64 rows back to back (24 KB); piece NW p + w (1 KB, one LDS-DMA instruction of wave w) covers
-    // LDS bytes [1024 (NW p + w), +1024): the lane's 16 bytes are slot (pos % 384) / 16 of row pos / 384, which holds chunk
-    // slot ^ ((row >> 1) & 7) (inside its group of 8) of that row.
-    // Per-lane source offsets: three registers at most (4 waves: pieces 12 apart are 32 rows apart and repeat the pattern).  The
-    // kernel sits close to the 256-register limit, and ONE spilled fragment once made the loop wait for its reload with
-    // s_waitcnt vmcnt(0) -- i.e. for the LDS-DMA pieces just issued, every stage: 22 % of the kernel.
-    unsigned g_off[PASSES < 3 ? PASSES : 3];
-#pragma unroll
-    for (int p = 0; p < (PASSES < 3 ? PASSES : 3); ++p) {
-        const int pos = (NW * p + wave) * 1024 + lane * 16, r = pos / RB, sl = (pos % RB) / 16;
-        g_off[p] = (unsigned)(r * RB + 16 * ((sl & ~7) | ((sl ^ (r >> 1)) & 7)));
-    }
-    auto g_stage = [&](int buf, int blk) {                 // buf: 0 / 1, wave-uniform
-        const gbytes blk_base = (gbytes)(T + (size_t)(t_begin + blk * TROWS) * RB);       // wave-uniform
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            unsigned long long pb = (unsigned long long)(uintptr_t)(blk_base + (p / 3) * (8 * NW * RB));      // three pieces per wave = 8 NW rows
-            asm volatile("" : "+s"(pb));
-            __builtin_amdgcn_global_load_lds((gbytes)pb + g_off[p % 3], (lbytes)(lds + buf * BUF_STRIDE + (NW * p + wave) * 1024), 16, 0, 0);
-        }
-    };
-    // operand reads: lane (row l31 of the tile, K half): chunk 2s + half of its row, swizzled
-    int rd_off[4];
-    {
-        const int base_lane = l31 * RB, k16 = 16 * ((l31 >> 1) & 7);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rd_off[j] = base_lane + ((32 * j + 16 * half) ^ k16);
-    }
-    // One stage = two tiles of 32 trains = 24 K-steps out of the buffer rd_off[] points into, as ONE software-pipelined stream:
-    //   * train fragments are read H4_AHEAD K-steps ahead of their MFMAs, across the tile boundary;
-    //   * the top-2 update of a finished tile (64 VALU ops per wave) is spread over K-steps 1..11 of the NEXT tile, six ops behind
-    //     each MFMA pair -- an MFMA holds the SIMD's issue port for 8 of its 32 cycles, so they cost nothing -- which needs two
-    //     accumulator sets: tile 0 of a stage fills set A while set B (tile 1 of the stage before) is consumed, and vice versa;
-    //   * two VALU ops per distance, in place: runner-up = med3(best, runner-up, key), best = med3(best, key, -inf) = min
-    //     (v_min_f32 through fminf() would canonicalise both inputs first).  asm, so that the results stay in their inputs'
-    //     registers (hipcc renamed them into a second generation of best[] and spilled the stationary operand).  hipcc pads
-    //     nothing for asm: a set is first read five MFMAs (>= 40 cycles) after its last write -- 11 wait states are required
-    //     after an 8-pass MFMA -- and the flush after the loop pads explicitly.
-    // The scheduling barriers pin this order (hipcc otherwise hoists all twelve reads of a tile, 48 registers, above the first MFMA).
-    v16f accA0, accA1, accB0, accB1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { accB0[i] = 1.0e9f; accB1[i] = 1.0e9f; }
-#define H4_TOP2(B1v, B2v, KEY) asm volatile("v_med3_f32 %1, %0, %1, %2\n\tv_med3_f32 %0, %0, %2, %3" : "+v"(B1v), "+v"(B2v) : "v"(KEY), "s"(neg_inf))
-#define H4_COLMIN(CM, X) asm volatile("v_min_f32 %0, %0, %1" : "+v"(CM) : "v"(X))
-    // column update of one value: its row r in the wave (less 4 half) as the tie-break, pad query rows (r >= lim) out of the race
-    auto col_of = [&](float p, int r) {
-        float x = p + (float)r;
-        x = (float)r < lim ? x : H4_QPAD;
-        H4_COLMIN(cm, x);
-    };
-    auto top2_of = [&](v16f& p0, v16f& p1, int v) {          // value v = 0..31 of a finished tile's two accumulators
-        if (v < 16) { H4_TOP2(best1[0][v], best2[0][v], p0[v]); col_of(p0[v], (v & 3) + 8 * (v >> 2)); }
-        else if (v < 32) { const int i = v - 16; H4_TOP2(best1[1][i], best2[1][i], p1[i]); col_of(p1[i], 32 + (i & 3) + 8 * (i >> 2)); }
-    };
-    // the finished tile's column minima (stage sb, tile position tp) into LDS
-    auto col_emit = [&](int sb, int tp) {
-        float c2 = cm + hoff;
-        const float o = __shfl_xor(c2, 32);
-        c2 = c2 < o ? c2 : o;
-        if (half == 0) colbuf[((sb % 3) * NW + wave) * TROWS + tp * 32 + l31] = c2;
-        cm = 1.0e9f;
-    };
-    const int off_k = 768 * pd.dim;
-    // after the barrier that follows the stage after sb (where sb's second tile was stored): fold the waves' minima into rev[]
-    auto col_flush = [&](int sb) {
-        if (tid >= 64 * NW - TROWS) {
-            const int c = tid - (64 * NW - TROWS), j = t_begin + sb * TROWS + c;
-            if (j < pd.nt) {
-                const int tix = (j >> 5) & 255;
-                int best = INT_MAX;
-                for (int w = 0; w < NW; ++w) {
-                    const int x = (int)colbuf[((sb % 3) * NW + w) * TROWS + c] + off_k - tix;      // 256 distance + row
-                    const int d = x >> 8, r = x & 255;
-                    const int key = (d >= 0 && d <= 4 * pd.dim && r < 64) ? (d << 9) | (w * 64 + r) : INT_MAX;
-                    best = key < best ? key : best;
-                }
-                if (best != INT_MAX)
-                    atomicMin(rev + rev_off[pair] + j, ((unsigned long long)(unsigned)(best >> 9) << 32) | (unsigned)(qb * QB + (best & 511)));
-            }
-        }
-    };
-    auto compute = [&](int blk) {
-        auto rd = [&](int g) { return *(const v4i*)(lds + rd_off[(g % 12) & 3] + ((g / 12) * TILE_BYTES + 128 * ((g % 12) >> 2))); };
-#ifndef H4_AHEAD
-#define H4_AHEAD 1             // K-steps a train fragment is read ahead of its MFMAs: 1, 2 and 3 measured the same (1.36-1.37 ms), 1 leaves 8 registers of margin
-#endif
-        v4i bq[H4_AHEAD + 1];
-#pragma unroll
-        for (int g = 0; g < H4_AHEAD; ++g) bq[g] = rd(g);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int tile = (g / 12) & 1, s = g % 12;     // accumulator set by tile parity
-            if (g + H4_AHEAD < NG) bq[(g + H4_AHEAD) % (H4_AHEAD + 1)] = rd(g + H4_AHEAD);
-            const v4i b4 = bq[g % (H4_AHEAD + 1)];
-            const v8i b8 = { b4[0], b4[1], b4[2], b4[3], 0, 0, 0, 0 };
-            const v8i a0 = { afrag[0][s][0], afrag[0][s][1], afrag[0][s][2], afrag[0][s][3], 0, 0, 0, 0 };
-            const v8i a1 = { afrag[1][s][0], afrag[1][s][1], afrag[1][s][2], afrag[1][s][3], 0, 0, 0, 0 };
-            v16f& c0 = tile == 0 ? accA0 : accB0;
-            v16f& c1 = tile == 0 ? accA1 : accB1;
-            v16f& p0 = tile == 0 ? accB0 : accA0;
-            v16f& p1 = tile == 0 ? accB1 : accA1;
-            int sbv = sb;
-            if (s == 11) sbv = 127 + ((b4[3] >> 27) & 8);       // rows past the end: the top value of the fragment is 6.0 (bit 30 set) -> 2^8
-            if (s == 0) {
-                v16f z;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) z[i] = 0.0f;
-                // the pending set is still being read: the first MFMA pair of a tile writes the OTHER set
-                c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a0, b8, z, 4, 4, 0, sa, 0, sb);
-                c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a1, b8, z, 4, 4, 0, sa, 0, sb);
-            } else {
-                c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a0, b8, c0, 4, 4, 0, sa, 0, sbv);
-                c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a1, b8, c1, 4, 4, 0, sa, 0, sbv);
-                top2_of(p0, p1, 3 * (s - 1)); top2_of(p0, p1, 3 * (s - 1) + 1); top2_of(p0, p1, 3 * (s - 1) + 2);
-                // the pending tile is done: tile 1 of the previous stage (nothing before stage 0) or tile 0 of this one
-                if (s == 11) { if (tile == 1) col_emit(blk, 0); else if (blk > 0) col_emit(blk - 1, 1); }
-            }
-            // pin the pair here: set B's second chain has no reader before the next trip of the loop, and LLVM sank all twelve of
-            // its MFMAs (and their twelve train fragments: 48 registers) below the stage's last step
-            asm volatile("" : "+v"(c0), "+v"(c1));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    // one loop body for both buffers (the buffer is a run-time offset: an XOR on the four read addresses per stage) -- with the two
-    // buffers as separate code paths hipcc moved best[] between register sets at the joins and spilled the stationary operand
-    g_stage(0, 0);
-    __syncthreads();
-    for (int blk = 0; blk < nblocks; ++blk) {
-        if (blk + 1 < nblocks) g_stage((blk + 1) & 1, blk + 1);
-        compute(blk);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rd_off[j] ^= BUF_STRIDE;
-        __syncthreads();
-        if (blk > 0) col_flush(blk - 1);
-    }
-    // flush: the last tile's accumulators (set B)
-    asm volatile("s_nop 11");
-#pragma unroll
-    for (int v = 0; v < 32; ++v) top2_of(accB0, accB1, v);
-#undef H4_TOP2
-#undef H4_COLMIN
-    if (nblocks > 0) {
-        col_emit(nblocks - 1, 1);
-        __syncthreads();
-        col_flush(nblocks - 1);
-    }
-
-    // merge across the 32 lanes that share a query row (as knn2_i8_kernel), one query tile at a time, on integer keys
-    // K = key + 192 cells = 256 distance + tile for a real train (< 2^16); a pad row or the initial value is above 2^20
-    // The margin between the two, spelled out (advisor, round 3): the largest real key is 256 * (4 * H4_MAX_NBYTES) + 255 = 62,719;
-    // a pad row's spare values (6.0 on both sides, the train side's last K-step under a 2^8 block scale) put its key above 3e6 (see the
-    // kernel's header); block 23's 23 + 4 products alone give 27 * 36 * 2^10 = 995,328.  Change H4_ROW_BYTES, the number of spare values
-    // or the 2^8 scale and the k_pad = 2^20 test below no longer separates the two: the asserts pin the ingredients, and
-    // tests/test_match_gpu.py::test_knn2_hamming2_matrix_core_kernel_pad_rows_never_beat_the_worst_real_row the outcome.
-    static_assert(256 * (4 * H4_MAX_NBYTES) + 255 < (1 << 16), "real Hamming2 keys must stay below 2^16");
-    static_assert(27 * 36 * 1024 + 768 >= (1 << 20) - (1 << 16), "pad-row keys must clear every real key by the tested margin");
-    const int k_pad = 1 << 20;
-    const int win_base = t_begin & ~8191;
-    int2* wk = (int2*)lds + wave * (32 * 33);
-#pragma unroll
-    for (int at = 0; at < 2; ++at) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
-            wk[row * 33 + l31] = make_int2((int)best1[at][i] + off_k, (int)best2[at][i] + off_k);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int row = lane >> 1, side = lane & 1;
-        int m1 = INT_MAX, m2 = INT_MAX, i1 = 0, i2 = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int l = side * 16 + j;
-            const int2 v = wk[row * 33 + l];
-            const bool c1 = v.x < m1, c2 = v.x < m2;
-            m2 = c1 ? m1 : (c2 ? v.x : m2); i2 = c1 ? i1 : (c2 ? l : i2);
-            m1 = c1 ? v.x : m1;             i1 = c1 ? l : i1;
-            const bool c3 = v.y < m2;
-            m2 = c3 ? v.y : m2;             i2 = c3 ? l : i2;
-        }
-        const int o1 = __shfl_xor(m1, 1), oi1 = __shfl_xor(i1, 1), o2 = __shfl_xor(m2, 1), oi2 = __shfl_xor(i2, 1);
-        {
-            const bool c1 = o1 < m1, c2 = o1 < m2;
-            m2 = c1 ? m1 : (c2 ? o1 : m2); i2 = c1 ? i1 : (c2 ? oi1 : i2);
-            m1 = c1 ? o1 : m1;             i1 = c1 ? oi1 : i1;
-            const bool c3 = o2 < m2;
-            m2 = c3 ? o2 : m2;             i2 = c3 ? oi2 : i2;
-        }
-        if (side == 0 && has_rows) {
-            const int qrow = q0 + 32 * at + row;
-            long long k1 = KEY_INVALID, k2 = KEY_INVALID;
-            if (m1 < k_pad) k1 = ((long long)(m1 >> 8) << 32) | (unsigned int)(win_base + (m1 & 255) * 32 + i1);
-            if (m2 < k_pad) k2 = ((long long)(m2 >> 8) << 32) | (unsigned int)(win_base + (m2 & 255) * 32 + i2);
-            long long* o = part + 2 * (pd.part_off + (long long)qrow * pd.nchunks + chunk);
-            o[0] = k1; o[1] = k2;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-#endif
+    knn2_hamming2_fp4_body<NW, true>(pairs, part, n_pairs, rev, rev_off);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2410,6 +2039,14 @@ static void rev_finalize(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& W, in
     hipLaunchKernelGGL(rev_rescore_l2_kernel, dim3(64), dim3(256), 0, ctx->stream, W.d_pd, R.d_off, (const int2*)R.list, (const int*)R.count, R.rev_idx, R.rev_dist);
 }
 
+// the int8 kNN kernel of one KS: the mutual form with rev, the plain one without
+template <int KS>
+static void launch_knn2_i8(sfmhip_ctx* ctx, const dim3& grid, const KnnWork& W, int n_pairs, const RevArgs* rev)
+{
+    if (rev) hipLaunchKernelGGL(knn2_i8_mutual_kernel<KS>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs, rev->keys, rev->d_off);
+    else hipLaunchKernelGGL(knn2_i8_kernel<KS>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs);
+}
+
 // enqueue the kNN-2 of all pairs; results in d_idx2 / d_dist2 (rows concatenated in pair order).  rev != nullptr (int8 path only):
 // the mutual kernel also leaves the nearest query of every train row in rev->rev_idx / rev_dist (int8 and FP4 paths).
 static int knn2_pairs_enqueue(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& W, int n_pairs, int32_t* d_idx2, float* d_dist2,
@@ -2424,17 +2061,10 @@ static int knn2_pairs_enqueue(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& 
     if (tev) (void)hipEventRecord(tev[0], ctx->stream);
     if (P.path == 2) {
         const dim3 grid(P.max_qpad / 128, P.max_chunks, round_up(n_pairs, 8));       // z padded: see the kernel's XCD mapping
-        if (rev) {
-            switch (P.ks) {
-                case 1: hipLaunchKernelGGL(knn2_i8_mutual_kernel<1>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs, rev->keys, rev->d_off); break;
-                case 2: hipLaunchKernelGGL(knn2_i8_mutual_kernel<2>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs, rev->keys, rev->d_off); break;
-                case 4: hipLaunchKernelGGL(knn2_i8_mutual_kernel<4>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs, rev->keys, rev->d_off); break;
-                default: ctx->last_error = "int8 path: dim > 128"; return SFMHIP_E_ARG;
-            }
-        } else switch (P.ks) {
-            case 1: hipLaunchKernelGGL(knn2_i8_kernel<1>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs); break;
-            case 2: hipLaunchKernelGGL(knn2_i8_kernel<2>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs); break;
-            case 4: hipLaunchKernelGGL(knn2_i8_kernel<4>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs); break;
+        switch (P.ks) {
+            case 1: launch_knn2_i8<1>(ctx, grid, W, n_pairs, rev); break;
+            case 2: launch_knn2_i8<2>(ctx, grid, W, n_pairs, rev); break;
+            case 4: launch_knn2_i8<4>(ctx, grid, W, n_pairs, rev); break;
             default: ctx->last_error = "int8 path: dim > 128"; return SFMHIP_E_ARG;
         }
         SFM_HIP_TRY(ctx, hipGetLastError());

@@ -46,36 +46,39 @@ def test_drivers_list_cross_check_in_their_usage(prog):
     assert out.returncode == 0 and "[--cross-check]" in out.stdout, out.stdout
 
 
-# The mutual kernels are kept copies of the plain ones (a template flag changed the plain kernels' register allocation): every code line
-# of the plain kernel must still be in its mutual copy, in order, apart from the lines listed here (the LDS size, the timing-experiment
-# knobs the copies leave out, the places where the column pass is threaded in).  Tuning one kernel without the other fails here.
-_COPY_EXCEPTIONS = {'knn2_i8_kernel': ['__shared__ __attribute__((aligned(16))) unsigned char lds[STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES];'], 'knn2_hamming2_fp4_kernel': ['#if !defined(H4_EXP) || !defined(SFMHIP_EXPERIMENTS)', '#undef H4_EXP', '#define H4_EXP 0', '__shared__ __attribute__((aligned(16))) unsigned char lds[STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES];', 'const int nblocks = (H4_EXP & 32) ? 1 : (t_end - t_begin) / TROWS;', 'v4i a = (H4_EXP & 128) ? (v4i){ lane, s, at, 7 } : *(gv4)(Q + (size_t)(q0r + 32 * at + l31) * RB + 16 * (2 * s + half));', 'if (v < 16) H4_TOP2(best1[0][v], best2[0][v], p0[v]);', 'else if (v < 32) H4_TOP2(best1[1][v - 16], best2[1][v - 16], p1[v - 16]);', 'auto compute = [&]() {', 'if (g + H4_AHEAD < NG && !((H4_EXP & 8) && g >= 1)) bq[(g + H4_AHEAD) % (H4_AHEAD + 1)] = rd(g + H4_AHEAD);', 'if (!(H4_EXP & 4)) { top2_of(p0, p1, 3 * (s - 1)); top2_of(p0, p1, 3 * (s - 1) + 1); top2_of(p0, p1, 3 * (s - 1) + 2); }', 'if (blk + 1 < nblocks && !(H4_EXP & 1)) g_stage((blk + 1) & 1, blk + 1);', 'compute();', 'if (!(H4_EXP & 2)) __syncthreads();', 'if (H4_EXP & 2) __syncthreads();', 'const int off_k = 768 * pd.dim, k_pad = 1 << 20;', 'if (H4_EXP & 64) {', 'float sum = 0.0f;', 'for (int i = 0; i < 16; ++i) sum += best1[at][i] + best2[at][i];', 'if (sum == 12345.0f) part[2 * pd.part_off + tid] = 1;', 'return;']}
+# Each plain / mutual kernel pair is one body: the four __global__ kernels only call it, so neither can be tuned without the other.
+_KNN_MFMA = {"knn2_i8": "__builtin_amdgcn_mfma_i32_32x32x32_i8", "knn2_hamming2_fp4": "__builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4"}
 
 
-def _code_lines(src, name):
-    i = src.index(name + "(")
-    j = src.index("{", i)
-    depth = 0
-    for k in range(j, len(src)):
-        depth += {"{": 1, "}": -1}.get(src[k], 0)
-        if depth == 0:
-            break
-    lines = (re.sub(r"//.*", "", l).strip() for l in src[j:k + 1].split("\n"))
-    return [l for l in lines if l]
+def _void_functions(src):
+    """{name: text} of the void functions of match.hip, comments stripped: definitions start and close at column 0"""
+    src = re.sub(r"//.*", "", src)
+    return {m.group(1): m.group(0) for m in re.finditer(r"^(?:\w[^\n;{]*\s)?void\s+(\w+)\s*\([^{;]*\)\s*\{.*?^\}", src, re.M | re.S)}
 
 
-@pytest.mark.parametrize("plain,mutual", [("knn2_i8_kernel", "knn2_i8_mutual_kernel"),
-                                          ("knn2_hamming2_fp4_kernel", "knn2_hamming2_fp4_mutual_kernel")])
-def test_mutual_kernels_still_contain_their_plain_kernel(plain, mutual):
-    src = open(os.path.join(ROOT, "sfm_opencv_amd", "csrc", "match.hip")).read()
-    p, m = _code_lines(src, "void " + plain), _code_lines(src, "void " + mutual)
-    missing, k = [], 0
-    for line in p:
-        while k < len(m) and m[k] != line:
-            k += 1
-        if k == len(m):
-            missing.append(line)
-            k = 0
-        else:
-            k += 1
-    assert missing == _COPY_EXCEPTIONS[plain], [l for l in missing if l not in _COPY_EXCEPTIONS[plain]]
+@pytest.mark.parametrize("stem", sorted(_KNN_MFMA))
+def test_each_kernel_pair_is_one_body(stem):
+    f = _void_functions(open(os.path.join(ROOT, "sfm_opencv_amd", "csrc", "match.hip")).read())
+    for kernel in (stem + "_kernel", stem + "_mutual_kernel"):
+        head, body = f[kernel].split("{", 1)
+        assert "__global__" in head, kernel
+        assert re.search(r"\b%s_body\s*<" % stem, body) and body.count(";") == 1, (kernel, body)
+        assert "__builtin_amdgcn_mfma" not in body and "__builtin_amdgcn_global_load_lds" not in body, kernel
+    assert [n for n, text in f.items() if n.startswith("knn2_") and _KNN_MFMA[stem] in text] == [stem + "_body"]
+
+
+# vgpr + agpr, LDS bytes, scratch bytes, spilled registers of every instantiation, as the commit before the shared bodies compiled them
+# (its kept copies, read off its libsfmhip.so with _kernel_table): sharing the source must not move the register allocation.
+_PARENT_RESOURCES = {"knn2_i8_kernelILi1E": (110, 33792, 0, 0), "knn2_i8_kernelILi2E": (118, 33792, 0, 0), "knn2_i8_kernelILi4E": (128, 33792, 0, 0),
+                     "knn2_i8_mutual_kernelILi1E": (134, 37888, 0, 0), "knn2_i8_mutual_kernelILi2E": (139, 37888, 0, 0),
+                     "knn2_i8_mutual_kernelILi4E": (150, 37888, 0, 0),
+                     "knn2_hamming2_fp4_kernelILi8E": (248, 67584, 0, 0), "knn2_hamming2_fp4_mutual_kernelILi8E": (255, 73728, 20, 4)}
+
+
+@pytest.mark.skipif(not os.path.exists(READELF), reason="llvm-readelf not found")
+def test_shared_bodies_keep_the_kept_copies_resources(tmp_path):
+    t = _kernel_table(tmp_path)
+    got = {sub: [(k["vgpr"] + k["agpr"], k["lds"], k["scratch"], k["spill"] or 0) for name, k in sorted(t.items()) if sub in name]
+           for sub in _PARENT_RESOURCES}
+    assert got == {sub: [r] for sub, r in _PARENT_RESOURCES.items()}
+    assert sum("knn2_i8_" in n or "knn2_hamming2_fp4_" in n for n in t) == len(_PARENT_RESOURCES), sorted(t)
