@@ -422,8 +422,41 @@ int sfmhip_estimate_normals_ex(sfmhip_ctx*, const double* pts, int n, int K, int
  * No finite value: stats NaN, keep all 0.  The sums are fixed-order trees on the device: a rerun gives the same bits. */
 int sfmhip_statistical_outliers(sfmhip_ctx*, const double* pts, int n, int K, double std_ratio, int method,
                                 uint8_t* keep, double* mean_dist /* may be NULL */, double stats[3] /* may be NULL */);
-/* diagnostic: how many queries the context's last SFMHIP_POINTS_GRID search handed to its brute-force pass.  Synchronises. */
+/* diagnostic: how many queries the context's last SFMHIP_POINTS_GRID search handed to its brute-force pass (K nearest: what it could
+ * not certify; fixed radius: always 0, that grid decides every query itself).  Synchronises. */
 int sfmhip_points_fallback_count(sfmhip_ctx*, int* count);
+
+/* Fixed-radius queries on the same cloud conventions.  count[i] = #{ j != i : d(i,j) <= r } with d as above and the comparison made on
+ * the COMPUTED d, inclusive: i is excluded by index (a duplicate at distance 0 counts; r = 0 counts coincident points), a point with a
+ * non-finite coordinate has count 0 and is counted by nobody.  r finite and >= 0.  count: n int32.  n == 0: OK, no pointer touched.
+ * Every method gives the same counts (the grid takes its cell size from r, so the 27 cells around a query suffice). */
+int sfmhip_radius_count    (sfmhip_ctx*, const double* pts,   int n, double r, int method, int32_t* count);
+/* the same on device arrays: enqueues on the context's stream, never synchronises */
+int sfmhip_radius_count_dev(sfmhip_ctx*, const double* d_pts, int n, double r, int method, int32_t* d_count);
+/* Radius outlier removal: keep[i] = 1 iff count[i] >= min_neighbors (min_neighbors >= 1), count as above, decided on the device; a
+ * point with a non-finite coordinate is never kept.  Modelled on PCL's RadiusOutlierRemoval and Open3D's remove_radius_outlier; the
+ * rule stated here is the definition (whether those libraries count the point itself, or compare with < or <=, is not claimed). */
+int sfmhip_radius_outliers(sfmhip_ctx*, const double* pts, int n, double r, int min_neighbors, int method,
+                           uint8_t* keep, int32_t* count /* may be NULL */);
+/* Voxel-grid down-sampling: one centroid per occupied voxel.  Over the points with three finite coordinates m_a = min x_a,
+ * origin_a = m_a - voxel * 0.5 and c_a = floor((x_a - origin_a) / voxel) (IEEE subtraction, true division, floor); a voxel is a
+ * distinct (c_x, c_y, c_z); voxels are numbered in ascending lexicographic (c_x, c_y, c_z); the centroid of a voxel is, per axis,
+ * ((x_j0 + x_j1) + x_j2 ...) / count over its points in ascending original index j.  voxel_of[i] = the number of point i's voxel, -1
+ * for a non-finite point.  A rerun gives the same bits.  voxel finite and > 0.  centroids: capacity n x 3, the first n_voxels rows are
+ * written; counts: capacity n.  No finite point: n_voxels = 0, origin +inf.  At most 2^21 voxels along an axis: beyond that the call
+ * fails with SFMHIP_E_ARG (the voxel is too small for the cloud's extent) -- one far outlier stretches the extent, so a cloud with far
+ * outliers wants a filter first (sfmhip_statistical_outliers, sfmhip_radius_outliers).  A voxel's points are summed by one thread. */
+int sfmhip_voxel_downsample    (sfmhip_ctx*, const double* pts, int n, double voxel,
+                                double* centroids /* capacity n x 3 */, int32_t* counts /* capacity n, may be NULL */,
+                                int32_t* voxel_of /* n, may be NULL */, int* n_voxels, double origin[3] /* may be NULL */);
+/* the same on device arrays: enqueues on the context's stream, never synchronises; d_n_voxels: one int32, -1 where the voxel is too
+ * small for the cloud's extent (the call still returns SFMHIP_OK and the other outputs are then unspecified) */
+int sfmhip_voxel_downsample_dev(sfmhip_ctx*, const double* d_pts, int n, double voxel,
+                                double* d_centroids, int32_t* d_counts /* may be NULL */, int32_t* d_voxel_of /* may be NULL */,
+                                int32_t* d_n_voxels, double* d_origin /* may be NULL */);
+/* Radius-limited ("hybrid") normals: the K nearest neighbours of sfmhip_knn_points, but none farther than r (finite, >= 0), then the
+ * plane fit of sfmhip_estimate_normals on those that remain; NaN for a point without any. */
+int sfmhip_estimate_normals_hybrid(sfmhip_ctx*, const double* pts, int n, int K, double r, int method, double* normals);
 
 #ifdef __cplusplus
 }

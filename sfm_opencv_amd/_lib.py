@@ -64,6 +64,8 @@ SYMBOLS = [
     "sfmhip_ba_create_ex", "sfmhip_ba_solve_ex", "sfmhip_ba_solve_multi_ex",
     "sfmhip_knn_points", "sfmhip_knn_points_dev", "sfmhip_estimate_normals_ex", "sfmhip_statistical_outliers",
     "sfmhip_points_fallback_count",
+    "sfmhip_radius_count", "sfmhip_radius_count_dev", "sfmhip_radius_outliers", "sfmhip_voxel_downsample", "sfmhip_voxel_downsample_dev",
+    "sfmhip_estimate_normals_hybrid",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -157,6 +159,12 @@ def load():
         "sfmhip_estimate_normals_ex": (i32, [vp, vp, i32, i32, i32, vp]),
         "sfmhip_statistical_outliers": (i32, [vp, vp, i32, i32, f64, i32, vp, vp, vp]),
         "sfmhip_points_fallback_count": (i32, [vp, C.POINTER(i32)]),
+        "sfmhip_radius_count": (i32, [vp, vp, i32, f64, i32, vp]),
+        "sfmhip_radius_count_dev": (i32, [vp, vp, i32, f64, i32, vp]),
+        "sfmhip_radius_outliers": (i32, [vp, vp, i32, f64, i32, i32, vp, vp]),
+        "sfmhip_voxel_downsample": (i32, [vp, vp, i32, f64, vp, vp, vp, C.POINTER(i32), vp]),
+        "sfmhip_voxel_downsample_dev": (i32, [vp, vp, i32, f64, vp, vp, vp, vp, vp]),
+        "sfmhip_estimate_normals_hybrid": (i32, [vp, vp, i32, i32, f64, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

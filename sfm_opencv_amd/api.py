@@ -346,10 +346,16 @@ class Context:
         self._check(self.lib.sfmhip_knn_points_dev(self.h, C.c_void_p(int(d_pts)), int(n), int(K), self._points_method(method),
                                                    C.c_void_p(int(d_idx)) if d_idx else None, C.c_void_p(int(d_dist)) if d_dist else None))
 
-    def estimate_normals(self, pts, K=10, method="auto"):
+    def estimate_normals(self, pts, K=10, method="auto", radius=None):
+        """normals from the K nearest neighbours; with a radius, from those of them within it (sfmhip_estimate_normals_hybrid:
+        NaN for a point that has none)"""
         pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
         out = np.empty_like(pts)
-        self._check(self.lib.sfmhip_estimate_normals_ex(self.h, pts.ctypes.data, pts.shape[0], int(K), self._points_method(method), out.ctypes.data))
+        if radius is None:
+            self._check(self.lib.sfmhip_estimate_normals_ex(self.h, pts.ctypes.data, pts.shape[0], int(K), self._points_method(method), out.ctypes.data))
+        else:
+            self._check(self.lib.sfmhip_estimate_normals_hybrid(self.h, pts.ctypes.data, pts.shape[0], int(K), float(radius),
+                                                                self._points_method(method), out.ctypes.data))
         return out
 
     def statistical_outliers(self, pts, K=10, std_ratio=2.0, method="auto"):
@@ -361,6 +367,46 @@ class Context:
         self._check(self.lib.sfmhip_statistical_outliers(self.h, pts.ctypes.data, n, int(K), float(std_ratio), self._points_method(method),
                                                          keep.ctypes.data, mean_dist.ctypes.data, stats.ctypes.data))
         return keep.astype(bool), mean_dist, stats
+
+    def radius_count(self, pts, r, method="auto"):
+        """count int32 n: the number of OTHER points within distance r (inclusive, on the computed fp64 distance) of every point
+        (sfmhip_radius_count); r = 0 counts exact duplicates.  The same counts for every method."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        count = np.zeros(pts.shape[0], np.int32)
+        self._check(self.lib.sfmhip_radius_count(self.h, pts.ctypes.data, pts.shape[0], float(r), self._points_method(method), count.ctypes.data))
+        return count
+
+    def radius_count_dev(self, d_pts, n, r, d_count, method="auto"):
+        """the same on device pointers (integers): enqueues on the context's stream, never synchronises"""
+        self._check(self.lib.sfmhip_radius_count_dev(self.h, C.c_void_p(int(d_pts)), int(n), float(r), self._points_method(method),
+                                                     C.c_void_p(int(d_count)) if d_count else None))
+
+    def radius_outliers(self, pts, r, min_neighbors, method="auto"):
+        """(keep bool n, count int32 n): radius outlier removal (sfmhip_radius_outliers); keep == (count >= min_neighbors)"""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        keep = np.zeros(n, np.uint8); count = np.zeros(n, np.int32)
+        self._check(self.lib.sfmhip_radius_outliers(self.h, pts.ctypes.data, n, float(r), int(min_neighbors), self._points_method(method),
+                                                    keep.ctypes.data, count.ctypes.data))
+        return keep.astype(bool), count
+
+    def voxel_downsample(self, pts, voxel):
+        """(centroids m x 3 float64, counts int32 m, voxel_of int32 n, origin float64 3): one centroid per occupied voxel of edge
+        `voxel`, voxels in ascending (c_x, c_y, c_z) (sfmhip_voxel_downsample); voxel_of is -1 for a non-finite point"""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        cen = np.empty((n, 3), np.float64); counts = np.empty(n, np.int32); voxel_of = np.full(n, -1, np.int32)
+        origin = np.full(3, np.inf); m = C.c_int(0)
+        self._check(self.lib.sfmhip_voxel_downsample(self.h, pts.ctypes.data, n, float(voxel), cen.ctypes.data, counts.ctypes.data,
+                                                     voxel_of.ctypes.data, C.byref(m), origin.ctypes.data))
+        return cen[:m.value].copy(), counts[:m.value].copy(), voxel_of, origin
+
+    def voxel_downsample_dev(self, d_pts, n, voxel, d_centroids, d_counts, d_voxel_of, d_n_voxels, d_origin=0):
+        """the same on device pointers (integers; 0 for d_counts / d_voxel_of / d_origin: not wanted): enqueues on the context's
+        stream, never synchronises; the int32 at d_n_voxels becomes -1 where the voxel is too small for the cloud's extent"""
+        p = lambda a: C.c_void_p(int(a)) if a else None      # noqa: E731
+        self._check(self.lib.sfmhip_voxel_downsample_dev(self.h, p(d_pts), int(n), float(voxel), p(d_centroids), p(d_counts), p(d_voxel_of),
+                                                         p(d_n_voxels), p(d_origin)))
 
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""

@@ -1970,3 +1970,6 @@ int sfm_enqueue_radix_sort(hipStream_t st, unsigned long long* k0, unsigned long
     B.k[0] = k0; B.k[1] = k1; B.v[0] = v0; B.v[1] = v1; B.hist = hist; B.bsum = bsum;
     return setup_radix_sort(st, B, n, bits, identity_vals);
 }
+// ... and its exclusive prefix sum of 32-bit counters, in place (points.hip numbers the voxels of a cloud with it)
+size_t sfm_scan_bsum_words(size_t n) { return setup_scan_tiles(n); }
+void sfm_enqueue_scan_u32(hipStream_t st, unsigned* data, size_t n, unsigned* bsum) { setup_enqueue_scan(st, data, n, bsum, nullptr); }

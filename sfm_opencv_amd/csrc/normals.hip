@@ -129,6 +129,13 @@ __global__ __launch_bounds__(NTILE) void normals_from_knn_kernel(const double* _
     plane_fit(pts, bi, K, i, normals);
 }
 
+// radius-limited ("hybrid") neighbourhoods: an entry of the table farther than r is no neighbour (plane_fit skips -1)
+__global__ __launch_bounds__(256) void normals_radius_mask_kernel(int32_t* __restrict__ idx, const double* __restrict__ dist, size_t total, double r)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < total && dist[t] > r) idx[t] = -1;
+}
+
 int sfm_normals_from_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, const int32_t* d_idx, int n, int K, double* d_normals)
 {
     hipLaunchKernelGGL(normals_from_knn_kernel, dim3(ceil_div(n, NTILE)), dim3(NTILE), 0, ctx->stream, d_pts, d_idx, n, K, d_normals);
@@ -170,4 +177,34 @@ extern "C" int sfmhip_estimate_normals_ex(sfmhip_ctx* ctx, const double* pts, in
 extern "C" int sfmhip_estimate_normals(sfmhip_ctx* ctx, const double* pts, int n, int K, double* normals)
 {
     return sfmhip_estimate_normals_ex(ctx, pts, n, K, SFMHIP_POINTS_AUTO, normals);
+}
+
+extern "C" int sfmhip_estimate_normals_hybrid(sfmhip_ctx* ctx, const double* pts, int n, int K, double r, int method, double* normals)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_estimate_normals_hybrid");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && std::isfinite(r) && r >= 0.0);
+    SFM_ARG_CHECK(ctx, method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID);
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, pts && normals);
+    SfmPoolHold hold(ctx);
+    double *d_p = nullptr, *d_n = nullptr, *d_dist = nullptr; int32_t* d_idx = nullptr;
+    const size_t total = (size_t)n * K;
+    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_n);
+    if (rc == SFMHIP_OK) rc = hold.get(total * sizeof(int32_t), (void**)&d_idx);
+    if (rc == SFMHIP_OK) rc = hold.get(total * sizeof(double), (void**)&d_dist);
+    if (rc != SFMHIP_OK) return rc;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+    rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_idx, d_dist);
+    if (rc == SFMHIP_OK) {
+        hipLaunchKernelGGL(normals_radius_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_idx, (const double*)d_dist, total, r);
+        rc = sfm_normals_from_knn_enqueue(ctx, d_p, d_idx, n, K, d_n);
+    }
+    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    hipError_t e = hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
+    return SFMHIP_OK;
 }

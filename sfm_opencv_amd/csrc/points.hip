@@ -1,5 +1,6 @@
 // points.hip -- neighbour search over a 3-D point cloud: the K nearest OTHER points of every point, exact, and what is built on
-// it (statistical outlier removal; normals.hip fits its planes on the same table).
+// it (statistical outlier removal; normals.hip fits its planes on the same table); the fixed-radius neighbour COUNT on the same grid
+// (radius outlier removal) and voxel-grid down-sampling on the same sort (second half of the file).
 //
 // Semantics, the same for every method (they are what normals_kernel has always done):
 //   d(i, j) = sqrt((dx*dx + dy*dy) + dz*dz) in fp64 without contraction; neighbours ordered by (d, j) ascending; i itself excluded by
@@ -106,7 +107,8 @@ __global__ __launch_bounds__(NTILE) void points_knn_brute_kernel(const double* _
 // cloud, the distance r_m to a sample point's m-th nearest sample point holds about m f points of the cloud, and between m = 2 and
 // m = 8 the growth of r_m tells the local dimension D of the cloud (a surface: 2, a volume: 3), so the radius that holds T = 2K points
 // is r_8 (T / (8 f))^(1/D).  Medians over the sample points throughout.  The cell size only steers speed: whatever comes out, the
-// certificate and the fallback keep the result exact.  params: [0..2] origin, [3] 1/h, [4] h_lo (a lower bound of h, see the certificate)
+// certificate and the fallback keep the result exact.  rmin > 0 (the fixed-radius search): h is at least rmin (1 + 2^-20), whatever the
+// sample says.  params: [0..2] origin, [3] 1/h, [4] h_lo (a lower bound of h, see the certificate)
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void lds_bitonic_sort(double* a, int len)       // len: power of two, NTILE threads
 {
@@ -125,7 +127,7 @@ __device__ __forceinline__ void lds_bitonic_sort(double* a, int len)       // le
     __syncthreads();
 }
 
-__global__ __launch_bounds__(NTILE) void points_cell_stats_kernel(const double* __restrict__ pts, int n, int K, double* __restrict__ params)
+__global__ __launch_bounds__(NTILE) void points_cell_stats_kernel(const double* __restrict__ pts, int n, int K, double rmin, double* __restrict__ params)
 {
     __shared__ double sx[NSAMPLE], sy[NSAMPLE], sz[NSAMPLE], srt[NSAMPLE];
     __shared__ double med[3];
@@ -190,6 +192,7 @@ __global__ __launch_bounds__(NTILE) void points_cell_stats_kernel(const double* 
             if (r8 > 0.0) h = r8 * pow(T / (8.0 * f), 1.0 / D);
         }
         if (!(h >= 1e-100 && h <= 1e100)) h = 1.0;
+        if (rmin > 0.0) { const double hr = rmin * (1.0 + 0x1p-20); h = h < hr ? hr : h; }      // rmin <= 1e100 (the caller's business)
         const double inv_h = 1.0 / h;
         params[0] = med[0] - 0x1p20 * h; params[1] = med[1] - 0x1p20 * h; params[2] = med[2] - 0x1p20 * h;
         params[3] = inv_h;
@@ -324,16 +327,12 @@ int sfm_points_auto_method(int n) { return n >= POINTS_AUTO_GRID_FROM ? SFMHIP_P
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-int sfm_points_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist)
+// the binning shared by the two grid searches: cell statistics, keys, stable sort, the cloud gathered into cell order, an empty fallback
+// list.  Everything lives in one block of the cache that `hold` gives back.
+struct PointsGrid { const double* params; const pu64* keys; const pu32* order; const double* spts; pu32* list; };
+static int points_grid_enqueue(sfmhip_ctx* ctx, SfmPoolHold& hold, const double* d_pts, int n, int K, double rmin, PointsGrid* G)
 {
-    if (method == SFMHIP_POINTS_AUTO) method = sfm_points_auto_method(n);
     hipStream_t st = ctx->stream;
-    const int nb = ceil_div(n, NTILE);
-    if (method == SFMHIP_POINTS_BRUTE) {
-        hipLaunchKernelGGL(points_knn_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, K, (const pu32*)nullptr, (const pu32*)nullptr, d_idx, d_dist);
-        SFM_HIP_TRY(ctx, hipGetLastError());
-        return SFMHIP_OK;
-    }
     if (!ctx->d_points_fallback) {
         void* q = nullptr;
         const int rc = sfm_pool_get(ctx, 256, &q);            // kept for the life of the context
@@ -346,7 +345,6 @@ int sfm_points_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, int K, i
     auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
     const size_t o_par = carve(8 * sizeof(double)), o_k0 = carve(N * 8), o_k1 = carve(N * 8), o_v0 = carve(N * 4), o_v1 = carve(N * 4),
                  o_hist = carve(hist_w * 4), o_bsum = carve(bsum_w * 4), o_spts = carve(N * 24), o_list = carve(N * 4);
-    SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(off, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
@@ -354,15 +352,31 @@ int sfm_points_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, int K, i
     pu64* k[2] = { (pu64*)(w + o_k0), (pu64*)(w + o_k1) };
     pu32* v[2] = { (pu32*)(w + o_v0), (pu32*)(w + o_v1) };
     double* spts = (double*)(w + o_spts);
-    pu32* list = (pu32*)(w + o_list);
     SFM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_points_fallback, 0, sizeof(unsigned), st));
-    hipLaunchKernelGGL(points_cell_stats_kernel, dim3(1), dim3(NTILE), 0, st, d_pts, n, K, params);
+    hipLaunchKernelGGL(points_cell_stats_kernel, dim3(1), dim3(NTILE), 0, st, d_pts, n, K, rmin, params);
     hipLaunchKernelGGL(points_cell_key_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, n, (const double*)params, k[0]);
     const int cur = sfm_enqueue_radix_sort(st, k[0], k[1], v[0], v[1], (pu32*)(w + o_hist), (pu32*)(w + o_bsum), N, 64, true);
     hipLaunchKernelGGL(points_gather_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, (const pu32*)v[cur], n, spts);
-    hipLaunchKernelGGL(points_knn_grid_kernel, dim3(nb), dim3(NTILE), 0, st, (const pu64*)k[cur], (const pu32*)v[cur], (const double*)spts, n, K,
-                       (const double*)params, d_idx, d_dist, list, ctx->d_points_fallback);
-    hipLaunchKernelGGL(points_knn_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, K, (const pu32*)list, (const pu32*)ctx->d_points_fallback, d_idx, d_dist);
+    G->params = params; G->keys = k[cur]; G->order = v[cur]; G->spts = spts; G->list = (pu32*)(w + o_list);
+    return SFMHIP_OK;
+}
+
+int sfm_points_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist)
+{
+    if (method == SFMHIP_POINTS_AUTO) method = sfm_points_auto_method(n);
+    hipStream_t st = ctx->stream;
+    const int nb = ceil_div(n, NTILE);
+    if (method == SFMHIP_POINTS_BRUTE) {
+        hipLaunchKernelGGL(points_knn_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, K, (const pu32*)nullptr, (const pu32*)nullptr, d_idx, d_dist);
+        SFM_HIP_TRY(ctx, hipGetLastError());
+        return SFMHIP_OK;
+    }
+    SfmPoolHold hold(ctx);
+    PointsGrid G;
+    const int rc = points_grid_enqueue(ctx, hold, d_pts, n, K, 0.0, &G);
+    if (rc != SFMHIP_OK) return rc;
+    hipLaunchKernelGGL(points_knn_grid_kernel, dim3(nb), dim3(NTILE), 0, st, G.keys, G.order, G.spts, n, K, G.params, d_idx, d_dist, G.list, ctx->d_points_fallback);
+    hipLaunchKernelGGL(points_knn_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, K, (const pu32*)G.list, (const pu32*)ctx->d_points_fallback, d_idx, d_dist);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;
 }
@@ -426,6 +440,273 @@ __global__ __launch_bounds__(256) void points_keep_kernel(const double* __restri
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) keep[i] = m[i] <= stats[2] ? 1 : 0;               // false for an infinite mean and for a NaN threshold
+}
+
+// ------------------------------------------------------------------------------------------------
+// fixed radius: count[i] = #{ j != i : d(i, j) <= r }, d the distance above, the comparison on the computed d, inclusive.
+//
+// The gate.  The decision `sqrt(d2) <= r` is made without the square root on both sides of a thin band: with q = fl(r * r) normal and
+// finite, lo2 = q (1 - 2^-50) <= r^2 <= q (1 + 2^-50) = hi2 whatever the three roundings did (each is off by a relative 2^-53).
+// d2 <= lo2: the real root is <= r, and rounding is monotone, so the computed d is <= r.  d2 > hi2: the real root exceeds
+// r sqrt(1 + 3/4 2^-50) > r (1 + 2^-52), which is at least the double after r, so the computed d is > r.  In between the root is
+// taken.  r = 0: lo2 = -1, hi2 = 0 (d2 = 0 takes the root: 0 <= 0).  q subnormal, zero or infinite: lo2 = -1, hi2 = inf, every
+// candidate takes the root.  A NaN d2 (a non-finite coordinate on either side) fails `d2 <= hi2`; an infinite one has an infinite root.
+// ------------------------------------------------------------------------------------------------
+struct RadiusGate { double r, lo2, hi2; };
+static inline RadiusGate radius_gate(double r)
+{
+    RadiusGate g = { r, -1.0, INFINITY };
+    const double q = r * r;
+    if (r == 0.0) g.hi2 = 0.0;
+    else if (q >= 0x1p-960 && q <= 0x1p960) { g.lo2 = q * (1.0 - 0x1p-50); g.hi2 = q * (1.0 + 0x1p-50); }
+    return g;
+}
+__device__ __forceinline__ int radius_hit(double d2, const RadiusGate& g) { return d2 <= g.hi2 && (d2 <= g.lo2 || sqrt(d2) <= g.r) ? 1 : 0; }
+
+// all pairs: the sweep of points_knn_brute_kernel
+__global__ __launch_bounds__(NTILE) void points_radius_brute_kernel(const double* __restrict__ pts, int n, RadiusGate g, int32_t* __restrict__ count)
+{
+    __shared__ double tx[NTILE], ty[NTILE], tz[NTILE];
+    const int i = blockIdx.x * NTILE + threadIdx.x;
+    const bool active = i < n;
+    const double px = active ? pts[3 * (size_t)i] : 0.0, py = active ? pts[3 * (size_t)i + 1] : 0.0, pz = active ? pts[3 * (size_t)i + 2] : 0.0;
+    int c = 0;
+    for (int base = 0; base < n; base += NTILE) {
+        const int j0 = base + threadIdx.x;
+        __syncthreads();
+        if (j0 < n) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; }
+        __syncthreads();
+        const int cnt = n - base < NTILE ? n - base : NTILE;
+        for (int s = 0; s < cnt; ++s) {
+            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            c += base + s != i ? radius_hit(d2, g) : 0;
+        }
+    }
+    if (active) count[i] = c;
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid count.  Thread p is the p-th point in cell order; it visits the 3 x 3 columns (x, y) of its cell's neighbourhood, each with
+// z in [cz - 1, cz + 1] as ONE run of the sorted keys, everything clipped to [0, CELL_MAX].  No rings, no test at run time, no fallback
+// list: the cell size is chosen so that the 27 cells suffice, h >= r (1 + 2^-20) (points_cell_stats_kernel, rmin = r).
+//
+// Why they suffice.  For a finite x let delta = x - o (real) and t = cell_pos(x) = fl(fl(delta) inv_h) = delta inv_h (1 + e), |e| < 2^-51,
+// wherever fl(delta) is finite; cell_pos is monotone in x.  For 1 <= m <= 2^21 therefore
+//     t >= m  =>  delta >= m (1 - 2^-51) / inv_h,            t < m  =>  delta < m (1 + 2^-51) / inv_h
+// (m / inv_h >= 1e-100 is far from subnormal; an overflowed fl(delta) or t only lies farther out on its side).  Let c = cell_of(t_q) on
+// some axis.  By the definition of cell_of, t_q < c + 1 unless c = CELL_MAX, and t_q >= c unless c = 0: clamping from above only yields
+// CELL_MAX, from below only 0.  A finite point p outside the 27 cells has, on some axis, cell_of(t_p) >= c + 2 -- then c < CELL_MAX,
+// t_p >= c + 2 and t_q < c + 1 -- or cell_of(t_p) <= c - 2 -- then c > 0, t_p < c - 1 and t_q >= c.  Either way, with 2c + 3 < 2^23,
+//     |p_a - q_a| = |delta_p - delta_q| > (1 - 2^-28) / inv_h.
+// The cell size IS 1 / inv_h, and inv_h = fl(1 / h) with h >= fl(r (1 + 2^-20)), so 1 / inv_h >= r (1 + 2^-20) (1 - 2^-52): the true
+// distance from q to p exceeds r (1 + 2^-21).  The distance the kernels COMPUTE is below the true one by at most a relative 2^-50 (the
+// slack the certificate above names), so it exceeds r: no point outside the 27 cells can be counted.  What IS visited is decided by
+// the computed distance itself, so a cell size larger than needed (a small r against the point spacing; r = 0) changes the work, never
+// the result.
+//
+// Border cells.  The argument is EXTENDED to them rather than handing their queries to a brute-force pass: nothing above needs t_q to be
+// bounded outward.  A query in or next to a clamped border cell visits that cell whole, with whatever was clamped into it, and the
+// unvisited side only needs the definition of cell_of.  (Far outliers are what lands in border cells -- 16,000 of the 20,000 far points
+// of the 2M-point outlier cloud at a radius of 0.02 -- and an all-pairs pass for them would cost 60 times the search itself.)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NTILE) void points_radius_grid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ spts,
+                                                                   int n, RadiusGate g, int32_t* __restrict__ count)
+{
+    const int p = blockIdx.x * NTILE + threadIdx.x;
+    if (p >= n) return;
+    const pu64 key = keys[p];
+    const int i = (int)order[p];
+    if (key >> 63) { count[i] = 0; return; }                               // non-finite: counts nobody
+    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
+    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
+    const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < CELL_MAX ? cz + 1 : CELL_MAX;
+    int c = 0;
+    for (int dx = -1; dx <= 1; ++dx) {
+        const int X = cx + dx;
+        if (X < 0 || X > CELL_MAX) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int Y = cy + dy;
+            if (Y < 0 || Y > CELL_MAX) continue;
+            const pu64 k0 = cell_key(X, Y, z0), k1 = cell_key(X, Y, z1);
+            const int a = keys_lower_bound(keys, 0, n, k0);
+            if (a >= n || keys[a] > k1) continue;                          // an empty run
+            const int b = keys_lower_bound(keys, a, n, k1 + 1ull);
+            for (int s = a; s < b; ++s) {
+                const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
+                const double d2 = ex * ex + ey * ey + ez * ez;
+                c += s != p ? radius_hit(d2, g) : 0;
+            }
+        }
+    }
+    count[i] = c;
+}
+
+// SFMHIP_POINTS_AUTO of the radius count.  Measured (profiles/r10_time_radius.log: median count 10 and 100, noisy sphere / that sphere
+// with 1 % far outliers / a volume cloud, 20k .. 2M points): the grid is faster by at least 10 % on all three clouds at every measured
+// size, three times at 20,000 points, the smallest one measured, so that is the crossover.
+#define RADIUS_AUTO_GRID_FROM 20000
+// beyond this radius the binning has nothing to offer (and h = r would leave the range the cell statistics are written for)
+#define RADIUS_GRID_MAX 1e100
+// the cell size where r is small against the point spacing: what the kNN grid derives from its sample for this K
+#define RADIUS_GRID_K 4
+
+// count[i] of a device cloud, on the context's stream; method: SFMHIP_POINTS_*
+static int points_radius_count_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double r, int method, int32_t* d_count)
+{
+    if (method == SFMHIP_POINTS_AUTO) method = n >= RADIUS_AUTO_GRID_FROM ? SFMHIP_POINTS_GRID : SFMHIP_POINTS_BRUTE;
+    if (r > RADIUS_GRID_MAX) method = SFMHIP_POINTS_BRUTE;
+    hipStream_t st = ctx->stream;
+    const int nb = ceil_div(n, NTILE);
+    const RadiusGate g = radius_gate(r);
+    if (method == SFMHIP_POINTS_BRUTE) {
+        hipLaunchKernelGGL(points_radius_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, g, d_count);
+        SFM_HIP_TRY(ctx, hipGetLastError());
+        return SFMHIP_OK;
+    }
+    SfmPoolHold hold(ctx);
+    PointsGrid G;
+    const int rc = points_grid_enqueue(ctx, hold, d_pts, n, RADIUS_GRID_K, r, &G);       // leaves the context's fallback count at 0: this search has no list
+    if (rc != SFMHIP_OK) return rc;
+    hipLaunchKernelGGL(points_radius_grid_kernel, dim3(nb), dim3(NTILE), 0, st, G.keys, G.order, G.spts, n, g, d_count);
+    SFM_HIP_TRY(ctx, hipGetLastError());
+    return SFMHIP_OK;
+}
+
+__global__ __launch_bounds__(256) void points_count_keep_kernel(const int32_t* __restrict__ count, int n, int min_neighbors, uint8_t* __restrict__ keep)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) keep[i] = count[i] >= min_neighbors ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// voxel-grid down-sampling.  origin_a = (min over the finite points of x_a) - voxel * 0.5, c_a = floor((x_a - origin_a) / voxel) -- a
+// subtraction, a true division, a floor --, a voxel is a distinct (c_x, c_y, c_z), voxels are numbered in ascending (c_x, c_y, c_z), and a
+// centroid is ((x_j0 + x_j1) + x_j2 ...) / count over the voxel's points in ascending original index: the order in which the STABLE sort
+// of the packed key (identity values) delivers them.  The minimum is exact, so its reduction order does not matter; a rerun gives the
+// same bits.  c_a >= 0 always (origin <= min <= x, and rounding is monotone); c_a > CELL_MAX raises the overflow flag.
+// One thread sums a whole voxel: a voxel that holds the entire cloud is one sequential chain (accepted: the point of the operation is
+// many small voxels).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void block_min3(double (&v)[3], double* sm)          // 256 threads, result in every thread
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        sm[threadIdx.x] = v[a];
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if ((int)threadIdx.x < off) { const double y = sm[threadIdx.x + off]; if (y < sm[threadIdx.x]) sm[threadIdx.x] = y; }
+            __syncthreads();
+        }
+        v[a] = sm[0];
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(256) void voxel_min_tile_kernel(const double* __restrict__ pts, int n, double* __restrict__ partial)
+{
+    __shared__ double sm[256];
+    double v[3] = { INFINITY, INFINITY, INFINITY };
+    for (int r = 0; r < RED_TILE / 256; ++r) {
+        const size_t i = (size_t)blockIdx.x * RED_TILE + (size_t)r * 256 + threadIdx.x;
+        if (i < (size_t)n) {
+            const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+            if (isfinite(x) && isfinite(y) && isfinite(z)) { v[0] = x < v[0] ? x : v[0]; v[1] = y < v[1] ? y : v[1]; v[2] = z < v[2] ? z : v[2]; }
+        }
+    }
+    block_min3(v, sm);
+    if (threadIdx.x < 3) partial[3 * (size_t)blockIdx.x + threadIdx.x] = v[threadIdx.x];
+}
+// one workgroup over the tiles: origin[a] (+inf where the cloud has no finite point); the overflow flag starts at 0
+__global__ __launch_bounds__(256) void voxel_min_top_kernel(const double* __restrict__ partial, int nt, double voxel, double* __restrict__ origin, pu32* __restrict__ overflow)
+{
+    __shared__ double sm[256];
+    double v[3] = { INFINITY, INFINITY, INFINITY };
+    for (int t = threadIdx.x; t < nt; t += 256)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { const double y = partial[3 * (size_t)t + a]; v[a] = y < v[a] ? y : v[a]; }
+    block_min3(v, sm);
+    if (threadIdx.x < 3) origin[threadIdx.x] = v[threadIdx.x] - voxel * 0.5;
+    if (threadIdx.x == 0) *overflow = 0u;
+}
+__global__ __launch_bounds__(256) void voxel_key_kernel(const double* __restrict__ pts, int n, double voxel, const double* __restrict__ origin,
+                                                        pu64* __restrict__ keys, pu32* __restrict__ overflow)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    pu64 key = ~0ull;
+    if (isfinite(x) && isfinite(y) && isfinite(z)) {
+        const double cx = floor((x - origin[0]) / voxel), cy = floor((y - origin[1]) / voxel), cz = floor((z - origin[2]) / voxel);
+        const double cmax = (double)CELL_MAX;
+        if (cx >= 0.0 && cx <= cmax && cy >= 0.0 && cy <= cmax && cz >= 0.0 && cz <= cmax) key = cell_key((int)cx, (int)cy, (int)cz);
+        else *overflow = 1u;                                               // every writer writes the same value
+    }
+    keys[i] = key;
+}
+// run heads of the sorted keys, n + 1 entries: the exclusive scan leaves the number of voxels in flag[n]
+__global__ __launch_bounds__(256) void voxel_head_kernel(const pu64* __restrict__ keys, int n, pu32* __restrict__ flag)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t > n) return;
+    flag[t] = (t < n && !(keys[t] >> 63) && (t == 0 || keys[t] != keys[t - 1])) ? 1u : 0u;
+}
+// thread t: the t-th point in key order writes its voxel number; the head of a run also sums the run
+__global__ __launch_bounds__(256) void voxel_centroid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ pts, int n,
+                                                             const pu32* __restrict__ excl, const pu32* __restrict__ overflow, double* __restrict__ centroids,
+                                                             int32_t* __restrict__ counts, int32_t* __restrict__ voxel_of, int32_t* __restrict__ n_voxels)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t == 0) *n_voxels = *overflow ? -1 : (int32_t)excl[n];
+    if (t >= n) return;
+    const pu64 key = keys[t];
+    const size_t i = order[t];
+    if (key >> 63) { if (voxel_of) voxel_of[i] = -1; return; }
+    const bool head = t == 0 || keys[t - 1] != key;
+    const int v = (int)excl[t] + (head ? 1 : 0) - 1;                       // heads at or before t, minus one
+    if (voxel_of) voxel_of[i] = v;
+    if (!head) return;
+    double sx = pts[3 * i], sy = pts[3 * i + 1], sz = pts[3 * i + 2];
+    int c = 1;
+    for (int s = t + 1; s < n && keys[s] == key; ++s, ++c) {
+        const size_t j = order[s];
+        sx += pts[3 * j]; sy += pts[3 * j + 1]; sz += pts[3 * j + 2];
+    }
+    centroids[3 * (size_t)v] = sx / (double)c; centroids[3 * (size_t)v + 1] = sy / (double)c; centroids[3 * (size_t)v + 2] = sz / (double)c;
+    if (counts) counts[v] = c;
+}
+
+// everything on the context's stream; d_counts / d_voxel_of / d_origin may be null
+static int voxel_downsample_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double voxel, double* d_centroids, int32_t* d_counts,
+                                    int32_t* d_voxel_of, int32_t* d_n_voxels, double* d_origin)
+{
+    hipStream_t st = ctx->stream;
+    const size_t N = (size_t)n, hist_w = sfm_radix_sort_hist_words(N), bsum_w = sfm_radix_sort_bsum_words(N), scan_w = sfm_scan_bsum_words(N + 1);
+    const int nt = ceil_div(n, RED_TILE), nb = ceil_div(n, 256);
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_org = carve(4 * sizeof(double)), o_ovf = carve(sizeof(pu32)), o_part = carve((size_t)3 * nt * sizeof(double)), o_k0 = carve(N * 8),
+                 o_k1 = carve(N * 8), o_v0 = carve(N * 4), o_v1 = carve(N * 4), o_hist = carve(hist_w * 4), o_bsum = carve(bsum_w * 4),
+                 o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4);
+    SfmPoolHold hold(ctx);
+    char* w = nullptr;
+    const int rc = hold.get(off, (void**)&w);
+    if (rc != SFMHIP_OK) return rc;
+    double* origin = (double*)(w + o_org);
+    pu32* overflow = (pu32*)(w + o_ovf);
+    pu64* k[2] = { (pu64*)(w + o_k0), (pu64*)(w + o_k1) };
+    pu32* v[2] = { (pu32*)(w + o_v0), (pu32*)(w + o_v1) };
+    pu32* flag = (pu32*)(w + o_flag);
+    hipLaunchKernelGGL(voxel_min_tile_kernel, dim3(nt), dim3(256), 0, st, d_pts, n, (double*)(w + o_part));
+    hipLaunchKernelGGL(voxel_min_top_kernel, dim3(1), dim3(256), 0, st, (const double*)(w + o_part), nt, voxel, origin, overflow);
+    hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(256), 0, st, d_pts, n, voxel, (const double*)origin, k[0], overflow);
+    const int cur = sfm_enqueue_radix_sort(st, k[0], k[1], v[0], v[1], (pu32*)(w + o_hist), (pu32*)(w + o_bsum), N, 64, true);
+    hipLaunchKernelGGL(voxel_head_kernel, dim3(ceil_div(n + 1, 256)), dim3(256), 0, st, (const pu64*)k[cur], n, flag);
+    sfm_enqueue_scan_u32(st, flag, N + 1, (pu32*)(w + o_scan));
+    hipLaunchKernelGGL(voxel_centroid_kernel, dim3(nb), dim3(256), 0, st, (const pu64*)k[cur], (const pu32*)v[cur], d_pts, n, (const pu32*)flag,
+                       (const pu32*)overflow, d_centroids, d_counts, d_voxel_of, d_n_voxels);
+    SFM_HIP_TRY(ctx, hipGetLastError());
+    if (d_origin) SFM_HIP_TRY(ctx, hipMemcpyAsync(d_origin, origin, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return SFMHIP_OK;
 }
 
 static inline bool points_method_ok(int method) { return method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID; }
@@ -508,6 +789,109 @@ int sfmhip_statistical_outliers(sfmhip_ctx* ctx, const double* pts, int n, int K
     if (e == hipSuccess && mean_dist) e = hipMemcpyAsync(mean_dist, d_m, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, 3 * sizeof(double), hipMemcpyDeviceToHost, st);
     return points_finish(ctx, e);
+}
+
+int sfmhip_radius_count_dev(sfmhip_ctx* ctx, const double* d_pts, int n, double r, int method, int32_t* d_count)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_radius_count_dev");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && points_method_ok(method));
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, d_pts && d_count);
+    return points_radius_count_enqueue(ctx, d_pts, n, r, method, d_count);
+}
+
+// count (and keep, where min_neighbors >= 1) of a host cloud: the body of the two host entry points
+static int radius_count_host(sfmhip_ctx* ctx, const double* pts, int n, double r, int min_neighbors, int method, uint8_t* keep, int32_t* count)
+{
+    SfmPoolHold hold(ctx);
+    double* d_p = nullptr; int32_t* d_c = nullptr; uint8_t* d_keep = nullptr;
+    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_c);
+    if (rc == SFMHIP_OK && keep) rc = hold.get((size_t)n, (void**)&d_keep);
+    if (rc != SFMHIP_OK) return rc;
+    hipStream_t st = ctx->stream;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    rc = points_radius_count_enqueue(ctx, d_p, n, r, method, d_c);
+    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    hipError_t e = hipSuccess;
+    if (keep) {
+        hipLaunchKernelGGL(points_count_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const int32_t*)d_c, n, min_neighbors, d_keep);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess && count) e = hipMemcpyAsync(count, d_c, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    return points_finish(ctx, e);
+}
+
+int sfmhip_radius_count(sfmhip_ctx* ctx, const double* pts, int n, double r, int method, int32_t* count)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_radius_count");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && points_method_ok(method));
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, pts && count);
+    return radius_count_host(ctx, pts, n, r, 0, method, nullptr, count);
+}
+
+int sfmhip_radius_outliers(sfmhip_ctx* ctx, const double* pts, int n, double r, int min_neighbors, int method, uint8_t* keep, int32_t* count)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_radius_outliers");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_neighbors >= 1 && points_method_ok(method));
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, pts && keep);
+    return radius_count_host(ctx, pts, n, r, min_neighbors, method, keep, count);
+}
+
+int sfmhip_voxel_downsample_dev(sfmhip_ctx* ctx, const double* d_pts, int n, double voxel, double* d_centroids, int32_t* d_counts, int32_t* d_voxel_of,
+                                int32_t* d_n_voxels, double* d_origin)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_voxel_downsample_dev");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(voxel) && voxel > 0.0);
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, d_pts && d_centroids && d_n_voxels);
+    return voxel_downsample_enqueue(ctx, d_pts, n, voxel, d_centroids, d_counts, d_voxel_of, d_n_voxels, d_origin);
+}
+
+int sfmhip_voxel_downsample(sfmhip_ctx* ctx, const double* pts, int n, double voxel, double* centroids, int32_t* counts, int32_t* voxel_of, int* n_voxels,
+                            double origin[3])
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_voxel_downsample");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(voxel) && voxel > 0.0);
+    if (n == 0) { if (n_voxels) *n_voxels = 0; return SFMHIP_OK; }
+    SFM_ARG_CHECK(ctx, pts && centroids && n_voxels);
+    *n_voxels = 0;
+    SfmPoolHold hold(ctx);
+    double *d_p = nullptr, *d_c = nullptr, *d_org = nullptr; int32_t *d_cnt = nullptr, *d_vof = nullptr, *d_nv = nullptr;
+    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_c);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_cnt);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_vof);
+    if (rc == SFMHIP_OK) rc = hold.get(256, (void**)&d_org);               // origin[3], then n_voxels
+    if (rc != SFMHIP_OK) return rc;
+    d_nv = (int32_t*)(d_org + 4);
+    hipStream_t st = ctx->stream;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    rc = voxel_downsample_enqueue(ctx, d_p, n, voxel, d_c, d_cnt, d_vof, d_nv, d_org);
+    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    int32_t nv = 0;
+    rc = points_finish(ctx, hipMemcpyAsync(&nv, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (rc != SFMHIP_OK) return rc;
+    if (nv < 0) {
+        ctx->last_error = "bad argument: the voxel is too small for the cloud's extent (more than 2^21 voxels along an axis; filter far outliers first)";
+        return SFMHIP_E_ARG;
+    }
+    hipError_t e = hipSuccess;
+    if (nv > 0) e = hipMemcpyAsync(centroids, d_c, (size_t)nv * 24, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && counts && nv > 0) e = hipMemcpyAsync(counts, d_cnt, (size_t)nv * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && voxel_of) e = hipMemcpyAsync(voxel_of, d_vof, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && origin) e = hipMemcpyAsync(origin, d_org, 3 * sizeof(double), hipMemcpyDeviceToHost, st);
+    rc = points_finish(ctx, e);
+    if (rc == SFMHIP_OK) *n_voxels = nv;
+    return rc;
 }
 
 int sfmhip_points_fallback_count(sfmhip_ctx* ctx, int* count)

@@ -421,6 +421,54 @@ inline int filter_outliers(const std::vector<Point3d>& pts3d, const int K, const
     return kept;
 }
 
+// ---- radius outlier removal (extension; modelled on pcl::RadiusOutlierRemoval / Open3D's remove_radius_outlier) -- keep[i] = 1 where
+// point i has at least min_neighbors OTHER points within distance r (sfmhip_radius_outliers).  Returns the number kept, -1 on error.
+inline int filter_radius_outliers(const std::vector<Point3d>& pts3d, const double r, const int min_neighbors, std::vector<unsigned char>& keep)
+{
+    sfmhip_ctx* ctx = context();
+    keep.assign(pts3d.size(), 0);
+    if (!ctx) return -1;
+    if (pts3d.empty()) return 0;
+    if (sfmhip_radius_outliers(ctx, &pts3d[0].x, (int)pts3d.size(), r, min_neighbors, SFMHIP_POINTS_AUTO, keep.data(), nullptr) != SFMHIP_OK) {
+        printf("[Err]: filter_radius_outliers: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    int kept = 0;
+    for (unsigned char k : keep) kept += k ? 1 : 0;
+    return kept;
+}
+
+// ---- voxel-grid down-sampling (extension; sfmhip_voxel_downsample) -- one centroid per occupied voxel of edge `voxel`, in ascending
+// voxel order; a voxel's colour is, per channel, the rounded mean (2 * sum + count) / (2 * count) in integers over its points (colors
+// may be shorter than pts3d: out_colors is then left empty).  Returns the number of voxels, -1 on error.
+inline int voxel_downsample(const std::vector<Point3d>& pts3d, const std::vector<Vec3b>& colors, const double voxel,
+                            std::vector<Point3d>& out_pts, std::vector<Vec3b>& out_colors)
+{
+    sfmhip_ctx* ctx = context();
+    out_pts.clear(); out_colors.clear();
+    if (!ctx) return -1;
+    if (pts3d.empty()) return 0;
+    const int n = (int)pts3d.size();
+    std::vector<Point3d> cen(pts3d.size());
+    std::vector<int32_t> counts(pts3d.size()), voxel_of(pts3d.size());
+    int nv = 0;
+    if (sfmhip_voxel_downsample(ctx, &pts3d[0].x, n, voxel, &cen[0].x, counts.data(), voxel_of.data(), &nv, nullptr) != SFMHIP_OK) {
+        printf("[Err]: voxel_downsample: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    out_pts.assign(cen.begin(), cen.begin() + nv);
+    if (colors.size() >= pts3d.size()) {
+        std::vector<long long> sum((size_t)nv * 3, 0);
+        for (int i = 0; i < n; ++i)
+            if (voxel_of[i] >= 0)
+                for (int ch = 0; ch < 3; ++ch) sum[(size_t)voxel_of[i] * 3 + ch] += colors[i][ch];
+        out_colors.resize(nv);
+        for (int v = 0; v < nv; ++v)
+            for (int ch = 0; ch < 3; ++ch) out_colors[v][ch] = (unsigned char)((2 * sum[(size_t)v * 3 + ch] + counts[v]) / (2 * (long long)counts[v]));
+    }
+    return nv;
+}
+
 // ---- outputs (NView:186-338) ------------------------------------------------------------------------------------
 namespace detail {
 // fs::doubleToString [3P] + the "%.16e" of the Windows CRT the reference's files were written with (exact decimal ties

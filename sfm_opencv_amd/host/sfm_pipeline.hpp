@@ -231,6 +231,9 @@ struct PipelineOptions {
     double refine_px = 0.0;                // > 0: after BA, refine_structure(max_px) + a second BA (extension, not reference behaviour)
     bool cross_check = false;              // mutual nearest neighbours only, after the ratio test (extension, not reference behaviour)
     double filter_outliers_ratio = 0.0;    // > 0: structure_ba.ply holds only the points that pass filter_outliers(K = 10, ratio) (extension, not reference behaviour)
+    double radius_outliers_r = -1.0;       // >= 0: ... and, of those, only the points with at least radius_outliers_min others within this distance (filter_radius_outliers; extension)
+    int    radius_outliers_min = 2;
+    double voxel_size = 0.0;               // > 0: ... and what is left replaced by one centroid per voxel of this edge (voxel_downsample; extension)
 };
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
@@ -312,7 +315,8 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         for (size_t i = 0; i < pts3d.size(); ++i)
             printf("Point3d %zu offset: [%.17g, %.17g, %.17g]\n", i, pts3d[i].x - pts3d_old[i].x, pts3d[i].y - pts3d_old[i].y, pts3d[i].z - pts3d_old[i].z);
 
-    // the cloud of the .ply: every point, or (--filter-outliers) what the statistical filter keeps, with normals of THAT cloud
+    // the cloud of the .ply: every point, or what is left after the statistical filter (--filter-outliers), the radius filter
+    // (--radius-outliers) and the voxel grid (--voxel-size), in that order, with normals of THAT cloud
     std::vector<Point3d> ply_pts = pts3d;
     std::vector<Vec3b> ply_colors = colors;
     if (opt.filter_outliers_ratio > 0.0) {
@@ -322,6 +326,21 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         for (size_t i = 0; i < pts3d.size(); ++i)
             if (keep[i]) { ply_pts.push_back(pts3d[i]); if (i < colors.size()) ply_colors.push_back(colors[i]); }
         printf("outlier filter: kept %zu of %zu points\n", ply_pts.size(), pts3d.size());
+    }
+    if (opt.radius_outliers_r >= 0.0) {
+        std::vector<unsigned char> keep;
+        if (filter_radius_outliers(ply_pts, opt.radius_outliers_r, opt.radius_outliers_min, keep) < 0) return -1;
+        std::vector<Point3d> in_pts; std::vector<Vec3b> in_colors;
+        in_pts.swap(ply_pts); in_colors.swap(ply_colors);
+        for (size_t i = 0; i < in_pts.size(); ++i)
+            if (keep[i]) { ply_pts.push_back(in_pts[i]); if (i < in_colors.size()) ply_colors.push_back(in_colors[i]); }
+        printf("radius filter: kept %zu of %zu points\n", ply_pts.size(), in_pts.size());
+    }
+    if (opt.voxel_size > 0.0) {
+        std::vector<Point3d> in_pts; std::vector<Vec3b> in_colors;
+        in_pts.swap(ply_pts); in_colors.swap(ply_colors);
+        if (voxel_downsample(in_pts, in_colors, opt.voxel_size, ply_pts, ply_colors) < 0) return -1;
+        printf("voxel grid: %zu points -> %zu voxels\n", in_pts.size(), ply_pts.size());
     }
     std::vector<Point3d> normals(ply_pts.size());
     estimate_normals(ply_pts, 10, normals);
@@ -376,7 +395,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--voxel-size=H]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -403,6 +422,12 @@ inline int driver_main(int argc, char** argv, bool nview)
         else if (a.rfind("--refine=", 0) == 0) opt.refine_px = std::atof(a.c_str() + 9);
         else if (a == "--filter-outliers") opt.filter_outliers_ratio = 2.0;
         else if (a.rfind("--filter-outliers=", 0) == 0) opt.filter_outliers_ratio = std::atof(a.c_str() + 18);
+        else if (a.rfind("--radius-outliers=", 0) == 0) {        // R[,MIN]: keep a point of the .ply only with at least MIN (2) others within R
+            opt.radius_outliers_r = std::atof(a.c_str() + 18);
+            const size_t comma = a.find(',', 18);
+            if (comma != std::string::npos) opt.radius_outliers_min = std::atoi(a.c_str() + comma + 1);
+        }
+        else if (a.rfind("--voxel-size=", 0) == 0) opt.voxel_size = std::atof(a.c_str() + 13);
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
         else if (positional++ == 0) opt.out_dir = a;
     }
