@@ -190,12 +190,18 @@ int sfmhip_selftest_exact_sqrt(sfmhip_ctx*, int* mismatches);
 /* xyzw: 4 x n float32 exactly like pts4d (row-major, may be NULL); xyz: n x 3 double holding   */
 /* float32-exact values (Point3f -> Point3d, NView:1155; may be NULL).                          */
 /* ------------------------------------------------------------------------------------------ */
+/* Degenerate input (pinned by tests/test_triangulate_edges_gpu.py; every entry point below does the oracle's arithmetic bit for bit):
+ * sfmhip_triangulate2_f32: a NaN pixel coordinate gives NaN in all four xyzw and all three xyz components of that correspondence and
+ * of no other; w == 0 (a point at infinity) gives +-inf in xyz, NaN where the component is 0 too; a system without a one-dimensional
+ * null space (identical cameras, an all-zero P) gives a finite unit xyzw picked by the fixed rotation order (xyz: inf where its w is 0). */
 int sfmhip_triangulate2_f32(sfmhip_ctx*, const float P1[12], const float P2[12],
                             const float* xy1, const float* xy2, int n, float* xyzw, double* xyz);
+/* sfmhip_triangulate2_f32_dev: the same values, correspondence by correspondence; only xyzw[0 .. 4n) and xyz[0 .. 3n) are written. */
 int sfmhip_triangulate2_f32_dev(sfmhip_ctx*, const float P1[12], const float P2[12],
                                 const float* d_xy1, const float* d_xy2, int n, float* d_xyzw, double* d_xyz);
 /* fused get_matched_points (NView:989-1003) + triangulation: points are gathered on the device
  * from keypoint arrays through the match list. kp1/kp2: sfm_keypoint arrays (device). */
+/* sfmhip_triangulate2_matches_dev: the values of sfmhip_triangulate2_f32 on the gathered pixels, NaN and inf included. */
 int sfmhip_triangulate2_matches_dev(sfmhip_ctx*, const float P1[12], const float P2[12],
                                     const sfm_keypoint* d_kp1, const sfm_keypoint* d_kp2,
                                     const sfm_dmatch* d_matches, int n, float* d_xyzw, double* d_xyz);
@@ -205,9 +211,14 @@ int sfmhip_triangulate2_matches_dev(sfmhip_ctx*, const float P1[12], const float
  * coordinates ((u-cx)/fx, (v-cy)/fy) with [R|t] from the angle-axis extrinsics of the BA parameterisation (NView:151-183,
  * 1464-1487); points with fewer than two observations come back as NaN.  n_views_out (may be NULL) = observations used.
  * sfmhip_reprojection_errors: pixel error |K (R X + t)/z - uv| of every observation, e.g. to filter tracks after BA. */
+/* sfmhip_triangulate_tracks: a point with fewer than two observations (n_obs == 0 with NULL arrays included) is NaN, a NaN pixel or
+ * extrinsic makes its points NaN, a null vector with v[3] == 0 gives +-inf (NaN where the component is 0 too); a track whose rays all
+ * leave one camera centre has no unique point and returns whatever the fixed rotation order leaves (finite or inf, never an error). */
 int  sfmhip_triangulate_tracks(sfmhip_ctx* ctx, const double K4[4], const double* ext6, int n_cam,
                                const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs, int n_pt,
                                double* pts_out, int32_t* n_views_out);
+/* sfmhip_reprojection_errors: a NaN point (what sfmhip_triangulate_tracks returns for a short track) or parameter gives NaN; a point
+ * with z == 0 in its camera gives +inf (NaN if x or y is 0 too); a point behind its camera gives an ordinary finite error. */
 int  sfmhip_reprojection_errors(sfmhip_ctx* ctx, const double K4[4], const double* ext6, int n_cam, const double* pts, int n_pt,
                                 const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, int n_obs, double* err_out);
 
@@ -397,6 +408,8 @@ int  sfmhip_ba_phase_ms(sfmhip_ba*, double out_ms[8]);
 /* 601-690): brute-force kNN-K (self excluded) + 3x3 PCA, smallest-eigenvalue vector, flipped   */
 /* so that n.mean <= 0, normalised.  pts: n x 3 double; normals: n x 3 double.                  */
 /* ------------------------------------------------------------------------------------------ */
+/* Degenerate input: a point without a neighbour (n == 1, or a non-finite coordinate in its row) gets NaN in all three components,   */
+/* and every other point a finite unit normal; neighbours that coincide (zero covariance) give (-+1, 0, 0) by the sign rule.           */
 int sfmhip_estimate_normals(sfmhip_ctx*, const double* pts, int n, int K, double* normals);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -414,7 +427,7 @@ int sfmhip_estimate_normals(sfmhip_ctx*, const double* pts, int n, int K, double
 int sfmhip_knn_points    (sfmhip_ctx*, const double* pts,   int n, int K, int method, int32_t* idx,   double* dist);
 /* the same on device arrays: enqueues on the context's stream, never synchronises */
 int sfmhip_knn_points_dev(sfmhip_ctx*, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist);
-/* sfmhip_estimate_normals on the neighbours of the chosen method (same bits for every method) */
+/* sfmhip_estimate_normals on the neighbours of the chosen method (same bits for every method, NaN rows included; no inf occurs) */
 int sfmhip_estimate_normals_ex(sfmhip_ctx*, const double* pts, int n, int K, int method, double* normals);
 /* Statistical outlier removal (PCL StatisticalOutlierRemoval, Open3D remove_statistical_outlier): mean_dist[i] = ((d_0 + d_1) + ... +
  * d_{K-1}) / K over the K neighbours in order (+inf for a point with fewer than K); mu, sigma = mean and population standard deviation
@@ -455,7 +468,8 @@ int sfmhip_voxel_downsample_dev(sfmhip_ctx*, const double* d_pts, int n, double 
                                 double* d_centroids, int32_t* d_counts /* may be NULL */, int32_t* d_voxel_of /* may be NULL */,
                                 int32_t* d_n_voxels, double* d_origin /* may be NULL */);
 /* Radius-limited ("hybrid") normals: the K nearest neighbours of sfmhip_knn_points, but none farther than r (finite, >= 0), then the
- * plane fit of sfmhip_estimate_normals on those that remain; NaN for a point without any. */
+ * plane fit of sfmhip_estimate_normals on those that remain; NaN in all three components for a point without any (a radius below its
+ * nearest neighbour, n == 1, a non-finite row), a finite unit normal for every other point. */
 int sfmhip_estimate_normals_hybrid(sfmhip_ctx*, const double* pts, int n, int K, double r, int method, double* normals);
 
 #ifdef __cplusplus

@@ -7,6 +7,8 @@
 // reference).  Then the plane fit of PCAFitPlane: mean of the K neighbours, covariance / K, eigenvector of the
 // smallest eigenvalue (cyclic Jacobi instead of Eigen::EigenSolver), flipped when n . mean > 0 (NView:672),
 // normalised.  fp64 throughout, no FMA contraction so distances compare exactly like the host's.
+// The contract with oracle/orc_normals.c (tests/test_normals_fit_gpu.py: equal in every bit): both sides are compiled with
+// -ffp-contract=off, fp64 sqrt and division are the correctly rounded ones on both, and plane_fit / eig3_min keep the oracle's order.
 #include "common.hpp"
 #pragma clang fp contract(off)
 

@@ -11,6 +11,8 @@
 #include "common.hpp"
 // float32 results must be bit-exact with the CPU restatement: no FMA contraction, correctly rounded sqrt
 // (HIP's __fsqrt_rn/__fmul_rn are NOT the rounded forms on this toolchain: native sqrt / contractible mul).
+// The contract with oracle/orc_triangulate.c (tests/test_triangulate_edges_gpu.py: equal in every bit, on every row): both sides are
+// compiled with -ffp-contract=off, fp64 sqrt and division are the correctly rounded ones on both, and the operation order is the same.
 #pragma clang fp contract(off)
 #include <cmath>
 #include <vector>

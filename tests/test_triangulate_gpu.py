@@ -1,4 +1,4 @@
-"""GPU parity of two-view triangulation vs the oracle (float tolerance stated per test)."""
+"""GPU parity of two-view triangulation vs the oracle (bit for bit, or the float tolerance stated per test)."""
 import numpy as np
 import pytest
 
@@ -14,10 +14,10 @@ def test_triangulate_matches_oracle(ctx):
     assert np.array_equal(P1, api.projection_matrix(s["K"], s["R1"], s["T1"]))
     gw, gx = ctx.triangulate2(P1, P2, s["xy1"], s["xy2"])
     ow, ox = orc.triangulate2(P1, P2, s["xy1"], s["xy2"])
-    # float32 outputs of an fp64 solve: tolerance 1e-5 relative; observed agreement is ~1 ulp of float32
-    rel = np.linalg.norm(gx - ox, axis=1) / np.linalg.norm(ox, axis=1)
-    assert rel.max() <= 1e-5
-    assert np.median(rel) <= 2e-7
+    # float32 outputs of an fp64 solve done in the oracle's operation order without FMA contraction: equal in every bit
+    # (tests/test_triangulate_edges_gpu.py holds the edge shapes and the independent reference)
+    assert np.array_equal(gw.view(np.uint32), ow.view(np.uint32))
+    assert np.array_equal(gx.view(np.uint64), ox.view(np.uint64))
     # values are float32-exact (Point3f -> Point3d, NViewReconstuct.cpp:1155)
     assert np.array_equal(gx, gx.astype(np.float32).astype(np.float64))
     # homogeneous output agrees up to sign
