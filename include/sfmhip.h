@@ -472,6 +472,30 @@ int sfmhip_voxel_downsample_dev(sfmhip_ctx*, const double* d_pts, int n, double 
  * nearest neighbour, n == 1, a non-finite row), a finite unit normal for every other point. */
 int sfmhip_estimate_normals_hybrid(sfmhip_ctx*, const double* pts, int n, int K, double r, int method, double* normals);
 
+/* DBSCAN / Euclidean clustering (modelled on PCL's EuclideanClusterExtraction and Open3D's cluster_dbscan; not in the reference).
+ * r finite and >= 0, min_points >= 1.  With count[i] exactly what sfmhip_radius_count returns:
+ *   - point i is CORE iff its three coordinates are finite and count[i] + 1 >= min_points (the point counts itself, as in
+ *     scikit-learn and Open3D); min_points = 1 makes every finite point core: plain Euclidean cluster extraction;
+ *   - two core points are linked iff the computed d(i,j) <= r; a CLUSTER is a connected component of the core points;
+ *   - clusters are numbered 0 .. C-1 in ascending order of their smallest core member's index; a core point gets its cluster's number;
+ *   - a finite non-core point with a core point within r is a BORDER point and gets the smallest cluster number among the clusters
+ *     of its core neighbours (what sequential DBSCAN in index order produces);
+ *   - everything else is noise, label -1: non-finite points and non-core points without a core neighbour;
+ *   - sizes[c] = the number of points labelled c, core and border together: sum(sizes) + #noise == n.
+ * The labels are a function of the input alone: the same for every method, run and launch geometry (integer work only).
+ * labels: n int32; sizes: capacity n, the first *n_clusters entries are written; count: n.  n == 0: OK, *n_clusters = 0. */
+int sfmhip_cluster_dbscan    (sfmhip_ctx*, const double* pts,   int n, double r, int min_points, int method,
+                              int32_t* labels,   int* n_clusters,       int32_t* sizes /* n entries, first C valid; may be NULL */,
+                              int32_t* count /* may be NULL */);
+/* the same on device arrays: enqueues on the context's stream, never synchronises; all n entries of d_sizes are written (zero from
+ * C on); d_n_clusters: one int32, -1 should the union-find's retry cap ever be hit (the host forms return SFMHIP_E_NUMERIC then) */
+int sfmhip_cluster_dbscan_dev(sfmhip_ctx*, const double* d_pts, int n, double r, int min_points, int method,
+                              int32_t* d_labels, int32_t* d_n_clusters, int32_t* d_sizes /* may be NULL */, int32_t* d_count /* may be NULL */);
+/* Largest-cluster filter (not in the reference): the clustering above, then keep[i] = 1 iff labels[i] == c, c the cluster with the
+ * most points, the smallest number among equals; no cluster: keep all 0, *largest_size = 0.  Decided on the device. */
+int sfmhip_largest_cluster   (sfmhip_ctx*, const double* pts,   int n, double r, int min_points, int method,
+                              uint8_t* keep, int32_t* labels /* may be NULL */, int* n_clusters /* may be NULL */, int* largest_size /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

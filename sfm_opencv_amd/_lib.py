@@ -66,6 +66,7 @@ SYMBOLS = [
     "sfmhip_points_fallback_count",
     "sfmhip_radius_count", "sfmhip_radius_count_dev", "sfmhip_radius_outliers", "sfmhip_voxel_downsample", "sfmhip_voxel_downsample_dev",
     "sfmhip_estimate_normals_hybrid",
+    "sfmhip_cluster_dbscan", "sfmhip_cluster_dbscan_dev", "sfmhip_largest_cluster",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -165,6 +166,9 @@ def load():
         "sfmhip_voxel_downsample": (i32, [vp, vp, i32, f64, vp, vp, vp, C.POINTER(i32), vp]),
         "sfmhip_voxel_downsample_dev": (i32, [vp, vp, i32, f64, vp, vp, vp, vp, vp]),
         "sfmhip_estimate_normals_hybrid": (i32, [vp, vp, i32, i32, f64, i32, vp]),
+        "sfmhip_cluster_dbscan": (i32, [vp, vp, i32, f64, i32, i32, vp, C.POINTER(i32), vp, vp]),
+        "sfmhip_cluster_dbscan_dev": (i32, [vp, vp, i32, f64, i32, i32, vp, vp, vp, vp]),
+        "sfmhip_largest_cluster": (i32, [vp, vp, i32, f64, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -408,6 +408,36 @@ class Context:
         self._check(self.lib.sfmhip_voxel_downsample_dev(self.h, p(d_pts), int(n), float(voxel), p(d_centroids), p(d_counts), p(d_voxel_of),
                                                          p(d_n_voxels), p(d_origin)))
 
+    def cluster_dbscan(self, pts, eps, min_points=1, method="auto"):
+        """(labels int32 n, sizes int32 C): DBSCAN as in scikit-learn / Open3D's cluster_dbscan (sfmhip_cluster_dbscan): a point with
+        at least min_points points within eps of it, itself included, is core; clusters are the connected components of the core
+        points, numbered by their smallest core index; a border point takes the smallest number among its core neighbours; noise and
+        non-finite points are -1.  min_points = 1: Euclidean cluster extraction.  The same labels for every method."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        labels = np.full(n, -1, np.int32); sizes = np.zeros(n, np.int32); m = C.c_int(0)
+        self._check(self.lib.sfmhip_cluster_dbscan(self.h, pts.ctypes.data, n, float(eps), int(min_points), self._points_method(method),
+                                                   labels.ctypes.data, C.byref(m), sizes.ctypes.data, None))
+        return labels, sizes[:m.value].copy()
+
+    def cluster_dbscan_dev(self, d_pts, n, eps, min_points, d_labels, d_n_clusters, d_sizes=0, d_count=0, method="auto"):
+        """the same on device pointers (integers; 0 for d_sizes / d_count: not wanted): enqueues on the context's stream, never
+        synchronises; d_sizes holds n entries, zero from the number of clusters on"""
+        p = lambda a: C.c_void_p(int(a)) if a else None      # noqa: E731
+        self._check(self.lib.sfmhip_cluster_dbscan_dev(self.h, p(d_pts), int(n), float(eps), int(min_points), self._points_method(method),
+                                                       p(d_labels), p(d_n_clusters), p(d_sizes), p(d_count)))
+
+    def largest_cluster(self, pts, eps, min_points=1, method="auto"):
+        """(keep bool n, labels int32 n, sizes int32 C): keep marks the cluster with the most points, the smallest number among equals
+        (sfmhip_largest_cluster); all False where there is no cluster"""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        keep = np.zeros(n, np.uint8); labels = np.full(n, -1, np.int32); m = C.c_int(0); big = C.c_int(0)
+        self._check(self.lib.sfmhip_largest_cluster(self.h, pts.ctypes.data, n, float(eps), int(min_points), self._points_method(method),
+                                                    keep.ctypes.data, labels.ctypes.data, C.byref(m), C.byref(big)))
+        sizes = np.bincount(labels[labels >= 0], minlength=m.value).astype(np.int32)
+        return keep.astype(bool), labels, sizes
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)

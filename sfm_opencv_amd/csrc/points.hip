@@ -551,24 +551,36 @@ __global__ __launch_bounds__(NTILE) void points_radius_grid_kernel(const pu64* _
 // the cell size where r is small against the point spacing: what the kNN grid derives from its sample for this K
 #define RADIUS_GRID_K 4
 
+// the method a fixed-radius sweep runs with: AUTO by the caller's measured crossover, brute force beyond RADIUS_GRID_MAX
+static inline int radius_method(int method, int n, double r, int auto_grid_from)
+{
+    if (method == SFMHIP_POINTS_AUTO) method = n >= auto_grid_from ? SFMHIP_POINTS_GRID : SFMHIP_POINTS_BRUTE;
+    return r > RADIUS_GRID_MAX ? SFMHIP_POINTS_BRUTE : method;
+}
+// the binning of a fixed-radius sweep at radius r (leaves the context's fallback count at 0: these sweeps have no list)
+static inline int radius_grid_enqueue(sfmhip_ctx* ctx, SfmPoolHold& hold, const double* d_pts, int n, double r, PointsGrid* G)
+{
+    return points_grid_enqueue(ctx, hold, d_pts, n, RADIUS_GRID_K, r, G);
+}
+// count[i] by all pairs, or (G given) on a binning of radius_grid_enqueue at g.r that the caller holds
+static void radius_count_launch(hipStream_t st, const double* d_pts, const PointsGrid* G, int n, const RadiusGate& g, int32_t* d_count)
+{
+    const int nb = ceil_div(n, NTILE);
+    if (!G) hipLaunchKernelGGL(points_radius_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, g, d_count);
+    else hipLaunchKernelGGL(points_radius_grid_kernel, dim3(nb), dim3(NTILE), 0, st, G->keys, G->order, G->spts, n, g, d_count);
+}
+
 // count[i] of a device cloud, on the context's stream; method: SFMHIP_POINTS_*
 static int points_radius_count_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double r, int method, int32_t* d_count)
 {
-    if (method == SFMHIP_POINTS_AUTO) method = n >= RADIUS_AUTO_GRID_FROM ? SFMHIP_POINTS_GRID : SFMHIP_POINTS_BRUTE;
-    if (r > RADIUS_GRID_MAX) method = SFMHIP_POINTS_BRUTE;
-    hipStream_t st = ctx->stream;
-    const int nb = ceil_div(n, NTILE);
-    const RadiusGate g = radius_gate(r);
-    if (method == SFMHIP_POINTS_BRUTE) {
-        hipLaunchKernelGGL(points_radius_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, g, d_count);
-        SFM_HIP_TRY(ctx, hipGetLastError());
-        return SFMHIP_OK;
-    }
+    method = radius_method(method, n, r, RADIUS_AUTO_GRID_FROM);
     SfmPoolHold hold(ctx);
     PointsGrid G;
-    const int rc = points_grid_enqueue(ctx, hold, d_pts, n, RADIUS_GRID_K, r, &G);       // leaves the context's fallback count at 0: this search has no list
-    if (rc != SFMHIP_OK) return rc;
-    hipLaunchKernelGGL(points_radius_grid_kernel, dim3(nb), dim3(NTILE), 0, st, G.keys, G.order, G.spts, n, g, d_count);
+    if (method != SFMHIP_POINTS_BRUTE) {
+        const int rc = radius_grid_enqueue(ctx, hold, d_pts, n, r, &G);
+        if (rc != SFMHIP_OK) return rc;
+    }
+    radius_count_launch(ctx->stream, d_pts, method == SFMHIP_POINTS_BRUTE ? nullptr : &G, n, radius_gate(r), d_count);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;
 }
@@ -706,6 +718,318 @@ static int voxel_downsample_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n,
                        (const pu32*)overflow, d_centroids, d_counts, d_voxel_of, d_n_voxels);
     SFM_HIP_TRY(ctx, hipGetLastError());
     if (d_origin) SFM_HIP_TRY(ctx, hipMemcpyAsync(d_origin, origin, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return SFMHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// DBSCAN / Euclidean clustering (PCL EuclideanClusterExtraction, Open3D cluster_dbscan; the definition is in sfmhip.h).  count[] is
+// the radius count above; core[i] = finite and count[i] + 1 >= min_points; two core points within r (radius_hit) are linked; a cluster
+// is a connected component of the core points, numbered by its smallest core index; a non-core point takes the smallest number among
+// its core neighbours (border), else -1.  Everything is integer work on decisions radius_hit makes, so the labels do not depend on the
+// method, the launch geometry or the order in which the atomics land.
+//
+// The components: a union-find over ORIGINAL indices, parent[x] <= x for every core x at all times (parent[x] == x: a root; a non-core
+// entry is never read).  A union hooks the LARGER root under the smaller with atomicCAS(parent + hi, hi, lo), so a root is hooked once
+// and the root of a finished component is its smallest member: the numbering needs nothing more than the roots in index order.
+// Every access to parent[] while unions run (cluster_link_*, cluster_flatten_kernel) is an agent-scope atomic -- a plain load may be
+// served from a line another XCD's L2 has since changed; the kernels after them read it with plain loads behind the kernel boundary.
+//
+// Termination, independent of any other workgroup's progress:
+//   cluster_find: the loop runs while parent[x] < x and moves x to that parent: x strictly decreases, at most n trips, and a value that
+//     breaks parent[x] <= x ends the loop instead of extending it.  The atomicMin on the way (path halving: a node is pointed at its
+//     grandparent) only lowers a parent to one of the node's ancestors: a root is never changed, nobody leaves its tree, and
+//     parent[x] <= x stays.  Without it the trees of a chain-shaped cloud visited in chain order reach a depth of n.
+//   cluster_unite: a trip ends the loop (same root, or the CAS hooked hi) or has OBSERVED parent[hi] < hi in the value the CAS returned
+//     and goes on from the root found below that value, so max(a, b) strictly decreases from trip to trip: at most n trips, in fact
+//     one per root that another thread hooked between this thread's find and its CAS.  Hooking under a lo that has meanwhile stopped
+//     being a root is still a correct link (lo < hi, same component).  The loop is capped at CLUSTER_RETRY_CAP all the same; a thread
+//     that hits the cap raises *err, the call then reports n_clusters = -1 and the host forms return SFMHIP_E_NUMERIC.  Nothing waits:
+//     no thread reads a word in order to see another thread's write arrive.
+// ------------------------------------------------------------------------------------------------
+#define CLUSTER_RETRY_CAP (1 << 16)
+
+__device__ __forceinline__ pu32 cluster_parent(pu32* parent, pu32 x) { return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ pu32 cluster_find(pu32* parent, pu32 x)
+{
+    pu32 p = cluster_parent(parent, x);
+    while (p < x) {
+        const pu32 gp = cluster_parent(parent, p);
+        if (gp < p) atomicMin(parent + x, gp);
+        x = p; p = gp;
+    }
+    return x;
+}
+
+// unites the components of a and b; returns a member of that component no larger than the root found for a (the caller's next start)
+__device__ __forceinline__ pu32 cluster_unite(pu32* parent, pu32 a, pu32 b, pu32* err)
+{
+    a = cluster_find(parent, a); b = cluster_find(parent, b);
+    for (int trip = 0; trip < CLUSTER_RETRY_CAP; ++trip) {
+        if (a == b) return a;
+        const pu32 hi = a > b ? a : b, lo = a > b ? b : a;
+        const pu32 old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) return lo;
+        a = cluster_find(parent, old); b = lo;             // old < hi: somebody else hooked hi first
+    }
+    __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return a;
+}
+
+// core flags, and every core point a root
+__global__ __launch_bounds__(256) void cluster_init_kernel(const double* __restrict__ pts, const int32_t* __restrict__ count, int n, int min_points,
+                                                           uint8_t* __restrict__ core, pu32* __restrict__ parent)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    core[i] = isfinite(x) && isfinite(y) && isfinite(z) && count[i] >= min_points - 1 ? 1 : 0;
+    parent[i] = (pu32)i;
+}
+
+// link sweep, all pairs: core point i unites itself with every core j < i within r (each pair from its larger index only, so a
+// workgroup needs the tiles below its own last point and no others).  The tile sweep of points_radius_brute_kernel.
+__global__ __launch_bounds__(NTILE) void cluster_link_brute_kernel(const double* __restrict__ pts, int n, RadiusGate g, const uint8_t* __restrict__ core,
+                                                                   pu32* parent, pu32* err)
+{
+    __shared__ double tx[NTILE], ty[NTILE], tz[NTILE];
+    __shared__ int tc[NTILE];
+    const int i = blockIdx.x * NTILE + threadIdx.x;
+    const bool mine = i < n && core[i];
+    if (!__syncthreads_or(mine ? 1 : 0)) return;                           // uniform: no core point in this workgroup
+    const double px = mine ? pts[3 * (size_t)i] : 0.0, py = mine ? pts[3 * (size_t)i + 1] : 0.0, pz = mine ? pts[3 * (size_t)i + 2] : 0.0;
+    const int jend = n < (blockIdx.x + 1) * NTILE ? n : (blockIdx.x + 1) * NTILE;
+    pu32 me = (pu32)i;
+    for (int base = 0; base < jend; base += NTILE) {
+        const int j0 = base + threadIdx.x;
+        __syncthreads();
+        if (j0 < jend) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; tc[threadIdx.x] = core[j0]; }
+        __syncthreads();
+        const int cnt = jend - base < NTILE ? jend - base : NTILE;
+        for (int s = 0; s < cnt; ++s) {
+            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            if (mine && base + s < i && tc[s] && radius_hit(d2, g)) me = cluster_unite(parent, me, (pu32)(base + s), err);
+        }
+    }
+}
+
+// link sweep on the grid: the 27-cell visit of points_radius_grid_kernel (its comment says why those cells suffice, border cells included)
+__global__ __launch_bounds__(NTILE) void cluster_link_grid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ spts,
+                                                                  int n, RadiusGate g, const uint8_t* __restrict__ core, pu32* parent, pu32* err)
+{
+    const int p = blockIdx.x * NTILE + threadIdx.x;
+    if (p >= n) return;
+    const pu64 key = keys[p];
+    const pu32 i = order[p];
+    if ((key >> 63) || !core[i]) return;
+    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
+    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
+    const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < CELL_MAX ? cz + 1 : CELL_MAX;
+    pu32 me = i;
+    for (int dx = -1; dx <= 1; ++dx) {
+        const int X = cx + dx;
+        if (X < 0 || X > CELL_MAX) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int Y = cy + dy;
+            if (Y < 0 || Y > CELL_MAX) continue;
+            const pu64 k0 = cell_key(X, Y, z0), k1 = cell_key(X, Y, z1);
+            const int a = keys_lower_bound(keys, 0, n, k0);
+            if (a >= n || keys[a] > k1) continue;                          // an empty run
+            const int b = keys_lower_bound(keys, a, n, k1 + 1ull);
+            for (int s = a; s < b; ++s) {
+                const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
+                const double d2 = ex * ex + ey * ey + ez * ez;
+                if (!radius_hit(d2, g)) continue;
+                const pu32 j = order[s];
+                if (j < i && core[j]) me = cluster_unite(parent, me, j, err);
+            }
+        }
+    }
+}
+
+// after the sweep: every core point is pointed at its root; flag[i] = 1 where i is a root, n + 1 entries for the exclusive scan.  A root
+// stays one from here on (nothing hooks any more), so the flags can be written in the same pass.
+__global__ __launch_bounds__(256) void cluster_flatten_kernel(const uint8_t* __restrict__ core, int n, pu32* parent, pu32* __restrict__ flag)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > n) return;
+    pu32 f = 0u;
+    if (i < n && core[i]) {
+        const pu32 r = cluster_find(parent, (pu32)i);
+        if (r == (pu32)i) f = 1u; else atomicMin(parent + i, r);
+    }
+    flag[i] = f;
+}
+
+// excl[x] = roots below x = the number of the cluster whose root is x (roots are the smallest core members: ascending order of them)
+__global__ __launch_bounds__(256) void cluster_label_kernel(const uint8_t* __restrict__ core, const pu32* __restrict__ parent, const pu32* __restrict__ excl,
+                                                            const pu32* __restrict__ err, int n, int32_t* __restrict__ labels, int32_t* __restrict__ n_clusters)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *n_clusters = *err ? -1 : (int32_t)excl[n];
+    if (i < n) labels[i] = core[i] ? (int32_t)excl[parent[i]] : -1;
+}
+
+// border sweep, all pairs: a non-core point takes the smallest label among the core points within r.  labels[] is read at core points
+// and written at non-core points only.
+__global__ __launch_bounds__(NTILE) void cluster_border_brute_kernel(const double* __restrict__ pts, int n, RadiusGate g, const uint8_t* __restrict__ core,
+                                                                     int32_t* labels)
+{
+    __shared__ double tx[NTILE], ty[NTILE], tz[NTILE];
+    __shared__ int tl[NTILE];
+    const int i = blockIdx.x * NTILE + threadIdx.x;
+    const bool mine = i < n && !core[i];
+    if (!__syncthreads_or(mine ? 1 : 0)) return;                           // uniform: core points only
+    const double px = mine ? pts[3 * (size_t)i] : 0.0, py = mine ? pts[3 * (size_t)i + 1] : 0.0, pz = mine ? pts[3 * (size_t)i + 2] : 0.0;
+    int lab = INT32_MAX;
+    for (int base = 0; base < n; base += NTILE) {
+        const int j0 = base + threadIdx.x;
+        __syncthreads();
+        if (j0 < n) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; tl[threadIdx.x] = core[j0] ? labels[j0] : -1; }
+        __syncthreads();
+        const int cnt = n - base < NTILE ? n - base : NTILE;
+        for (int s = 0; s < cnt; ++s) {
+            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            if (tl[s] >= 0 && tl[s] < lab && radius_hit(d2, g)) lab = tl[s];      // a non-finite point of either side: d2 fails the gate
+        }
+    }
+    if (mine) labels[i] = lab == INT32_MAX ? -1 : lab;
+}
+
+__global__ __launch_bounds__(NTILE) void cluster_border_grid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ spts,
+                                                                    int n, RadiusGate g, const uint8_t* __restrict__ core, int32_t* labels)
+{
+    const int p = blockIdx.x * NTILE + threadIdx.x;
+    if (p >= n) return;
+    const pu64 key = keys[p];
+    const pu32 i = order[p];
+    if ((key >> 63) || core[i]) return;                                    // non-finite: -1 already
+    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
+    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
+    const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < CELL_MAX ? cz + 1 : CELL_MAX;
+    int lab = INT32_MAX;
+    for (int dx = -1; dx <= 1; ++dx) {
+        const int X = cx + dx;
+        if (X < 0 || X > CELL_MAX) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int Y = cy + dy;
+            if (Y < 0 || Y > CELL_MAX) continue;
+            const pu64 k0 = cell_key(X, Y, z0), k1 = cell_key(X, Y, z1);
+            const int a = keys_lower_bound(keys, 0, n, k0);
+            if (a >= n || keys[a] > k1) continue;                          // an empty run
+            const int b = keys_lower_bound(keys, a, n, k1 + 1ull);
+            for (int s = a; s < b; ++s) {
+                const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
+                const double d2 = ex * ex + ey * ey + ez * ez;
+                if (!radius_hit(d2, g)) continue;
+                const pu32 j = order[s];
+                if (core[j]) { const int l = labels[j]; lab = l < lab ? l : lab; }
+            }
+        }
+    }
+    labels[i] = lab == INT32_MAX ? -1 : lab;
+}
+
+// sizes[c] += 1 per point labelled c (sizes zeroed by the caller).  A wave first settles up to four of its labels with one add each
+// -- the lanes that share the first open lane's label count themselves by ballot --, which is the whole wave wherever a cluster fills
+// it; lanes still open after that add for themselves.
+__global__ __launch_bounds__(256) void cluster_sizes_kernel(const int32_t* __restrict__ labels, int n, int32_t* __restrict__ sizes)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int lab = i < n ? labels[i] : -1;
+    const int lane = threadIdx.x & 63;
+    bool open = lab >= 0;
+    for (int round = 0; round < 4; ++round) {
+        const pu64 m = __ballot(open);
+        if (!m) break;                                                     // uniform over the wave
+        const int leader = __ffsll((long long)m) - 1;
+        const int lab0 = __shfl(lab, leader);
+        const bool same = open && lab == lab0;
+        const pu64 ms = __ballot(same);
+        if (same) { if (lane == leader) atomicAdd(sizes + lab0, (int32_t)__popcll(ms)); open = false; }
+    }
+    if (open) atomicAdd(sizes + lab, 1);
+}
+
+// one workgroup: best[0] = the cluster with the most points (the smallest number among equals), -1 without a cluster; best[1] = its size
+__global__ __launch_bounds__(256) void cluster_largest_kernel(const int32_t* __restrict__ sizes, const int32_t* __restrict__ n_clusters, int32_t* __restrict__ best)
+{
+    __shared__ pu64 sb[256];
+    const int C = *n_clusters;
+    pu64 b = 0ull;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const pu64 v = ((pu64)(pu32)sizes[c] << 32) | (pu64)(0xffffffffu - (pu32)c);       // a cluster has at least one point: v > 0
+        b = v > b ? v : b;
+    }
+    sb[threadIdx.x] = b;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off && sb[threadIdx.x + off] > sb[threadIdx.x]) sb[threadIdx.x] = sb[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { best[0] = sb[0] ? (int32_t)(0xffffffffu - (pu32)sb[0]) : -1; best[1] = (int32_t)(sb[0] >> 32); }
+}
+__global__ __launch_bounds__(256) void cluster_keep_kernel(const int32_t* __restrict__ labels, int n, const int32_t* __restrict__ best, uint8_t* __restrict__ keep)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) keep[i] = best[0] >= 0 && labels[i] == best[0] ? 1 : 0;
+}
+
+// SFMHIP_POINTS_AUTO of the clustering.  Measured (profiles/r11_time_cluster.log: radius for a median count of 10, min_points 1 and 10,
+// noisy sphere / that sphere with 1 % far outliers / a volume cloud, 20k .. 2M points): the grid is faster by at least 10 % on all
+// three clouds at every measured size, five to seven times at 20,000 points, the smallest one measured, so that is the crossover.
+#define CLUSTER_AUTO_GRID_FROM 20000
+
+// labels / n_clusters / sizes (n entries, may be null) / count (may be null) of a device cloud, on the context's stream.  One binning
+// serves the three neighbourhood sweeps (count, link, border) of SFMHIP_POINTS_GRID.
+static int cluster_dbscan_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double r, int min_points, int method, int32_t* d_labels,
+                                  int32_t* d_n_clusters, int32_t* d_sizes, int32_t* d_count)
+{
+    method = radius_method(method, n, r, CLUSTER_AUTO_GRID_FROM);
+    hipStream_t st = ctx->stream;
+    const size_t N = (size_t)n, scan_w = sfm_scan_bsum_words(N + 1);
+    const int nb = ceil_div(n, NTILE), nb256 = ceil_div(n, 256);
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_err = carve(sizeof(pu32)), o_core = carve(N), o_par = carve(N * 4), o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4),
+                 o_cnt = carve(d_count ? 0 : N * 4);
+    SfmPoolHold hold(ctx);
+    char* w = nullptr;
+    int rc = hold.get(off, (void**)&w);
+    if (rc != SFMHIP_OK) return rc;
+    pu32* err = (pu32*)(w + o_err);
+    uint8_t* core = (uint8_t*)(w + o_core);
+    pu32* parent = (pu32*)(w + o_par);
+    pu32* flag = (pu32*)(w + o_flag);
+    int32_t* count = d_count ? d_count : (int32_t*)(w + o_cnt);
+    const RadiusGate g = radius_gate(r);
+    PointsGrid G;
+    const bool grid = method != SFMHIP_POINTS_BRUTE;
+    if (grid) {
+        rc = radius_grid_enqueue(ctx, hold, d_pts, n, r, &G);
+        if (rc != SFMHIP_OK) return rc;
+    }
+    SFM_HIP_TRY(ctx, hipMemsetAsync(err, 0, sizeof(pu32), st));
+    radius_count_launch(st, d_pts, grid ? &G : nullptr, n, g, count);
+    hipLaunchKernelGGL(cluster_init_kernel, dim3(nb256), dim3(256), 0, st, d_pts, (const int32_t*)count, n, min_points, core, parent);
+    if (grid) hipLaunchKernelGGL(cluster_link_grid_kernel, dim3(nb), dim3(NTILE), 0, st, G.keys, G.order, G.spts, n, g, (const uint8_t*)core, parent, err);
+    else hipLaunchKernelGGL(cluster_link_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, g, (const uint8_t*)core, parent, err);
+    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(ceil_div(n + 1, 256)), dim3(256), 0, st, (const uint8_t*)core, n, parent, flag);
+    sfm_enqueue_scan_u32(st, flag, N + 1, (pu32*)(w + o_scan));
+    hipLaunchKernelGGL(cluster_label_kernel, dim3(nb256), dim3(256), 0, st, (const uint8_t*)core, (const pu32*)parent, (const pu32*)flag, (const pu32*)err, n,
+                       d_labels, d_n_clusters);
+    if (min_points > 1) {                                                  // min_points = 1: every finite point is core, nothing to adopt
+        if (grid) hipLaunchKernelGGL(cluster_border_grid_kernel, dim3(nb), dim3(NTILE), 0, st, G.keys, G.order, G.spts, n, g, (const uint8_t*)core, d_labels);
+        else hipLaunchKernelGGL(cluster_border_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, g, (const uint8_t*)core, d_labels);
+    }
+    SFM_HIP_TRY(ctx, hipGetLastError());
+    if (d_sizes) {
+        SFM_HIP_TRY(ctx, hipMemsetAsync(d_sizes, 0, N * sizeof(int32_t), st));
+        hipLaunchKernelGGL(cluster_sizes_kernel, dim3(nb256), dim3(256), 0, st, (const int32_t*)d_labels, n, d_sizes);
+        SFM_HIP_TRY(ctx, hipGetLastError());
+    }
     return SFMHIP_OK;
 }
 
@@ -892,6 +1216,81 @@ int sfmhip_voxel_downsample(sfmhip_ctx* ctx, const double* pts, int n, double vo
     rc = points_finish(ctx, e);
     if (rc == SFMHIP_OK) *n_voxels = nv;
     return rc;
+}
+
+int sfmhip_cluster_dbscan_dev(sfmhip_ctx* ctx, const double* d_pts, int n, double r, int min_points, int method, int32_t* d_labels, int32_t* d_n_clusters,
+                              int32_t* d_sizes, int32_t* d_count)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_cluster_dbscan_dev");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_points >= 1 && points_method_ok(method));
+    if (n == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, d_pts && d_labels && d_n_clusters);
+    return cluster_dbscan_enqueue(ctx, d_pts, n, r, min_points, method, d_labels, d_n_clusters, d_sizes, d_count);
+}
+
+// the clustering of a host cloud and, where keep is given, its largest cluster: the body of the two host entry points
+static int cluster_host(sfmhip_ctx* ctx, const double* pts, int n, double r, int min_points, int method, int32_t* labels, int* n_clusters, int32_t* sizes,
+                        int32_t* count, uint8_t* keep, int* largest_size)
+{
+    SfmPoolHold hold(ctx);
+    double* d_p = nullptr; int32_t *d_lab = nullptr, *d_sz = nullptr, *d_cnt = nullptr, *d_head = nullptr; uint8_t* d_keep = nullptr;
+    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_lab);
+    if (rc == SFMHIP_OK && (sizes || keep)) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_sz);
+    if (rc == SFMHIP_OK && count) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_cnt);
+    if (rc == SFMHIP_OK && keep) rc = hold.get((size_t)n, (void**)&d_keep);
+    if (rc == SFMHIP_OK) rc = hold.get(256, (void**)&d_head);              // n_clusters, then the largest cluster's number and size
+    if (rc != SFMHIP_OK) return rc;
+    hipStream_t st = ctx->stream;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    rc = cluster_dbscan_enqueue(ctx, d_p, n, r, min_points, method, d_lab, d_head, d_sz, d_cnt);
+    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    if (keep) {
+        hipLaunchKernelGGL(cluster_largest_kernel, dim3(1), dim3(256), 0, st, (const int32_t*)d_sz, (const int32_t*)d_head, d_head + 1);
+        hipLaunchKernelGGL(cluster_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const int32_t*)d_lab, n, (const int32_t*)(d_head + 1), d_keep);
+    }
+    int32_t head[3] = { 0, -1, 0 };
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(head, d_head, (keep ? 3 : 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    rc = points_finish(ctx, e);
+    if (rc != SFMHIP_OK) return rc;
+    if (head[0] < 0) {
+        ctx->last_error = "clustering: a union exceeded its retry cap (the parent array broke its invariant); no result";
+        return SFMHIP_E_NUMERIC;
+    }
+    e = hipSuccess;
+    if (labels) e = hipMemcpyAsync(labels, d_lab, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && sizes && head[0] > 0) e = hipMemcpyAsync(sizes, d_sz, (size_t)head[0] * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && count) e = hipMemcpyAsync(count, d_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && keep) e = hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, st);
+    rc = points_finish(ctx, e);
+    if (rc != SFMHIP_OK) return rc;
+    if (n_clusters) *n_clusters = head[0];
+    if (largest_size) *largest_size = head[2];
+    return SFMHIP_OK;
+}
+
+int sfmhip_cluster_dbscan(sfmhip_ctx* ctx, const double* pts, int n, double r, int min_points, int method, int32_t* labels, int* n_clusters, int32_t* sizes,
+                          int32_t* count)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_cluster_dbscan");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_points >= 1 && points_method_ok(method));
+    if (n == 0) { if (n_clusters) *n_clusters = 0; return SFMHIP_OK; }
+    SFM_ARG_CHECK(ctx, pts && labels && n_clusters);
+    return cluster_host(ctx, pts, n, r, min_points, method, labels, n_clusters, sizes, count, nullptr, nullptr);
+}
+
+int sfmhip_largest_cluster(sfmhip_ctx* ctx, const double* pts, int n, double r, int min_points, int method, uint8_t* keep, int32_t* labels, int* n_clusters,
+                           int* largest_size)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_largest_cluster");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_points >= 1 && points_method_ok(method));
+    if (n == 0) { if (n_clusters) *n_clusters = 0; if (largest_size) *largest_size = 0; return SFMHIP_OK; }
+    SFM_ARG_CHECK(ctx, pts && keep);
+    return cluster_host(ctx, pts, n, r, min_points, method, labels, n_clusters, nullptr, nullptr, keep, largest_size);
 }
 
 int sfmhip_points_fallback_count(sfmhip_ctx* ctx, int* count)

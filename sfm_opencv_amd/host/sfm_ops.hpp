@@ -438,6 +438,26 @@ inline int filter_radius_outliers(const std::vector<Point3d>& pts3d, const doubl
     return kept;
 }
 
+// ---- largest-cluster filter (extension; modelled on pcl::EuclideanClusterExtraction / Open3D's cluster_dbscan followed by "keep the
+// largest") -- keep[i] = 1 where point i belongs to the cluster with the most points (sfmhip_largest_cluster: clusters are the connected
+// components, at distance r, of the points with at least min_points points within r of them, themselves included, plus the border
+// points they adopt).  Returns the number kept, -1 on error; n_clusters: the number of clusters found.
+inline int filter_largest_cluster(const std::vector<Point3d>& pts3d, const double r, const int min_points, std::vector<unsigned char>& keep,
+                                  int* n_clusters = nullptr)
+{
+    sfmhip_ctx* ctx = context();
+    keep.assign(pts3d.size(), 0);
+    if (n_clusters) *n_clusters = 0;
+    if (!ctx) return -1;
+    if (pts3d.empty()) return 0;
+    int kept = 0;
+    if (sfmhip_largest_cluster(ctx, &pts3d[0].x, (int)pts3d.size(), r, min_points, SFMHIP_POINTS_AUTO, keep.data(), nullptr, n_clusters, &kept) != SFMHIP_OK) {
+        printf("[Err]: filter_largest_cluster: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    return kept;
+}
+
 // ---- voxel-grid down-sampling (extension; sfmhip_voxel_downsample) -- one centroid per occupied voxel of edge `voxel`, in ascending
 // voxel order; a voxel's colour is, per channel, the rounded mean (2 * sum + count) / (2 * count) in integers over its points (colors
 // may be shorter than pts3d: out_colors is then left empty).  Returns the number of voxels, -1 on error.

@@ -233,6 +233,8 @@ struct PipelineOptions {
     double filter_outliers_ratio = 0.0;    // > 0: structure_ba.ply holds only the points that pass filter_outliers(K = 10, ratio) (extension, not reference behaviour)
     double radius_outliers_r = -1.0;       // >= 0: ... and, of those, only the points with at least radius_outliers_min others within this distance (filter_radius_outliers; extension)
     int    radius_outliers_min = 2;
+    double largest_cluster_r = -1.0;       // >= 0: ... and, of those, only the largest cluster at this distance with largest_cluster_min points for a core point (filter_largest_cluster; extension)
+    int    largest_cluster_min = 1;
     double voxel_size = 0.0;               // > 0: ... and what is left replaced by one centroid per voxel of this edge (voxel_downsample; extension)
 };
 
@@ -316,7 +318,8 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
             printf("Point3d %zu offset: [%.17g, %.17g, %.17g]\n", i, pts3d[i].x - pts3d_old[i].x, pts3d[i].y - pts3d_old[i].y, pts3d[i].z - pts3d_old[i].z);
 
     // the cloud of the .ply: every point, or what is left after the statistical filter (--filter-outliers), the radius filter
-    // (--radius-outliers) and the voxel grid (--voxel-size), in that order, with normals of THAT cloud
+    // (--radius-outliers), the largest-cluster filter (--largest-cluster) and the voxel grid (--voxel-size), in that order, with normals
+    // of THAT cloud
     std::vector<Point3d> ply_pts = pts3d;
     std::vector<Vec3b> ply_colors = colors;
     if (opt.filter_outliers_ratio > 0.0) {
@@ -335,6 +338,16 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         for (size_t i = 0; i < in_pts.size(); ++i)
             if (keep[i]) { ply_pts.push_back(in_pts[i]); if (i < in_colors.size()) ply_colors.push_back(in_colors[i]); }
         printf("radius filter: kept %zu of %zu points\n", ply_pts.size(), in_pts.size());
+    }
+    if (opt.largest_cluster_r >= 0.0) {
+        std::vector<unsigned char> keep;
+        int n_clusters = 0;
+        if (filter_largest_cluster(ply_pts, opt.largest_cluster_r, opt.largest_cluster_min, keep, &n_clusters) < 0) return -1;
+        std::vector<Point3d> in_pts; std::vector<Vec3b> in_colors;
+        in_pts.swap(ply_pts); in_colors.swap(ply_colors);
+        for (size_t i = 0; i < in_pts.size(); ++i)
+            if (keep[i]) { ply_pts.push_back(in_pts[i]); if (i < in_colors.size()) ply_colors.push_back(in_colors[i]); }
+        printf("cluster filter: kept %zu of %zu points (%d clusters)\n", ply_pts.size(), in_pts.size(), n_clusters);
     }
     if (opt.voxel_size > 0.0) {
         std::vector<Point3d> in_pts; std::vector<Vec3b> in_colors;
@@ -395,7 +408,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--voxel-size=H]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -426,6 +439,11 @@ inline int driver_main(int argc, char** argv, bool nview)
             opt.radius_outliers_r = std::atof(a.c_str() + 18);
             const size_t comma = a.find(',', 18);
             if (comma != std::string::npos) opt.radius_outliers_min = std::atoi(a.c_str() + comma + 1);
+        }
+        else if (a.rfind("--largest-cluster=", 0) == 0) {        // R[,MIN_POINTS]: keep only the largest cluster at distance R, a core point having MIN_POINTS (1) points within R, itself included
+            opt.largest_cluster_r = std::atof(a.c_str() + 18);
+            const size_t comma = a.find(',');
+            if (comma != std::string::npos) opt.largest_cluster_min = std::atoi(a.c_str() + comma + 1);
         }
         else if (a.rfind("--voxel-size=", 0) == 0) opt.voxel_size = std::atof(a.c_str() + 13);
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
