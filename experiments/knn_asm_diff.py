@@ -1,13 +1,32 @@
-"""Compare the kNN kernels of two gfx950 device assemblies of csrc/match.hip (hipcc <the match.o flags> --cuda-device-only -S):
-resource numbers, instruction count and opcode histogram per kernel; for kernels whose opcode sequence differs, the differing runs
-and where each lies relative to the kernel's stage loop (head label .. last back-branch) and the MFMA stream inside it.
-python3 experiments/knn_asm_diff.py parent.s branch.s"""
+"""Compare kernels of two gfx950 device assemblies of one source file (hipcc <the object's flags> --cuda-device-only -S): resource
+numbers, instruction count and opcode histogram per kernel; for kernels whose opcode sequence differs, the differing runs and where
+each lies: in which loop of the branch's kernel (loops are found by their back-branches and described by what they hold: barriers,
+LDS reads, global loads, MFMAs), or outside every loop.  For a kernel with MFMAs the place is given relative to its stage loop (head
+label .. last back-branch) and the MFMA stream inside it.
+
+    python3 experiments/knn_asm_diff.py parent.s branch.s [kernel ...]
+
+A kernel is named by its mangled symbol or by a fragment of it that fits exactly one kernel; `all` stands for every kernel of the
+parent's file.  Without names: the kNN kernels of csrc/match.hip."""
 import collections, difflib, re, sys
 
-KERNELS = ["_Z14knn2_i8_kernelILi%dEEvPK8PairDescPxi" % k for k in (1, 2, 4)] + \
-          ["_Z21knn2_i8_mutual_kernelILi%dEEvPK8PairDescPxiPyPKx" % k for k in (1, 2, 4)] + \
-          ["_Z24knn2_hamming2_fp4_kernelILi8EEvPK8PairDescPxi", "_Z31knn2_hamming2_fp4_mutual_kernelILi8EEvPK8PairDescPxiPyPKx"]
+KNN_KERNELS = ["_Z14knn2_i8_kernelILi%dEEvPK8PairDescPxi" % k for k in (1, 2, 4)] + \
+              ["_Z21knn2_i8_mutual_kernelILi%dEEvPK8PairDescPxiPyPKx" % k for k in (1, 2, 4)] + \
+              ["_Z24knn2_hamming2_fp4_kernelILi8EEvPK8PairDescPxi", "_Z31knn2_hamming2_fp4_mutual_kernelILi8EEvPK8PairDescPxiPyPKx"]
 RES = ("NumVgprs", "NumAgprs", "TotalNumSgprs", "ScratchSize", "LDSByteSize", "Occupancy")
+
+
+def kernel_names(path):
+    return re.findall(r"^\s*\.amdhsa_kernel (\S+)", open(path).read(), re.M)
+
+
+def resolve(arg, names):
+    if arg in names:
+        return arg
+    hits = [k for k in names if arg in k]
+    if len(hits) != 1:
+        raise SystemExit("%r names %d kernels: %s" % (arg, len(hits), hits))
+    return hits[0]
 
 
 def kernel(path, name):
@@ -28,28 +47,39 @@ def kernel(path, name):
     return lines, res
 
 
-def stage_loop(lines):
-    """instruction indices (head, first MFMA, last MFMA, back-branch) and the head label of the outermost loop that holds MFMAs"""
+def loops(lines):
+    """the loops of a kernel, outermost first: (head, back-branch, head label), instruction indices; one entry per head label"""
     ops, labels = [], {}
     for l in lines:
         if l[0] == "label":
             labels[l[1]] = len(ops)
         else:
             ops.append(l)
-    best = None
+    found = {}
     for i, o in enumerate(ops):
         m = re.match(r"s_c?branch\w* (\.LBB\d+_\d+)", o[2])
         if m and labels[m.group(1)] <= i:
-            h = labels[m.group(1)]
-            mf = [k for k in range(h, i) if ops[k][1].startswith("v_mfma")]
-            if mf and (best is None or h <= best[0]):
-                best = (h, mf[0], mf[-1], i, m.group(1))
-    if best is None:
-        raise SystemExit("no loop around the MFMAs")
-    return best
+            found[m.group(1)] = (labels[m.group(1)], i, m.group(1))          # the last back-branch to a head wins
+    return ops, sorted(found.values(), key=lambda q: (q[0], -q[1]))
 
 
-def where(i1, i2, loop):
+def holds(ops, q):
+    body = [o[1] for o in ops[q[0]:q[1] + 1]]
+    what = [w for w, pre in (("barrier", "s_barrier"), ("LDS reads", "ds_read"), ("global loads", "global_load"), ("sqrt", "v_sqrt"),
+                             ("atomics", "global_atomic"), ("MFMAs", "v_mfma")) if any(b.startswith(pre) for b in body)]
+    return ", ".join(what) or "no memory access"
+
+
+def stage_loop(ops, ls):
+    """instruction indices (head, first MFMA, last MFMA, back-branch) and the head label of the outermost loop that holds MFMAs"""
+    for h, i, label in ls:
+        mf = [k for k in range(h, i) if ops[k][1].startswith("v_mfma")]
+        if mf:
+            return (h, mf[0], mf[-1], i, label)
+    raise SystemExit("no loop around the MFMAs")
+
+
+def where_mfma(i1, i2, loop):
     lo, hi = i1, max(i2, i1 + 1) - 1
     if hi < loop[0]:
         return "before the loop"
@@ -62,10 +92,21 @@ def where(i1, i2, loop):
     return "loop: MFMA STREAM"
 
 
-a_path, b_path = sys.argv[1:3]
-for name in KERNELS:
+def where_loop(i1, i2, ls):
+    """the innermost loop that holds the whole run, else the innermost one it touches"""
+    lo, hi = i1, max(i2, i1 + 1) - 1
+    inside = [q for q in ls if q[0] <= lo and hi <= q[1]]
+    if inside:
+        return "in loop %s" % min(inside, key=lambda q: q[1] - q[0])[2]
+    touched = [q for q in ls if lo <= q[1] and q[0] <= hi]
+    if touched:
+        return "across the edge of loop %s" % min(touched, key=lambda q: q[1] - q[0])[2]
+    return "outside every loop"
+
+
+def compare(a_path, b_path, name):
     (la, ra), (lb, rb) = kernel(a_path, name), kernel(b_path, name)
-    oa, ob = [l for l in la if l[0] == "op"], [l for l in lb if l[0] == "op"]
+    (oa, lsa), (ob, lsb) = loops(la), loops(lb)
     ha, hb = collections.Counter(o[1] for o in oa), collections.Counter(o[1] for o in ob)
     print(name)
     print("  resources  parent %s\n             branch %s  %s" % (ra, rb, "identical" if ra == rb else "DIFFERENT"))
@@ -75,16 +116,23 @@ for name in KERNELS:
     sa, sb = [o[1] for o in oa], [o[1] for o in ob]
     if sa == sb:
         print("  opcode sequence identical")
-        continue
-    pa, pb = stage_loop(la), stage_loop(lb)
-    for tag, q in (("parent", pa), ("branch", pb)):
-        print("  %s loop: head %s = instruction %d, MFMAs %d .. %d, last back-branch %d" % (tag, q[4], q[0], q[1], q[2], q[3]))
-    print("  MFMA stream (opcode sequence first .. last MFMA):", "identical" if sa[pa[1]:pa[2] + 1] == sb[pb[1]:pb[2] + 1] else "DIFFERENT")
+        return
+    mfma = any(s.startswith("v_mfma") for s in sb)
+    if mfma:
+        pa, pb = stage_loop(oa, lsa), stage_loop(ob, lsb)
+        for tag, q in (("parent", pa), ("branch", pb)):
+            print("  %s loop: head %s = instruction %d, MFMAs %d .. %d, last back-branch %d" % (tag, q[4], q[0], q[1], q[2], q[3]))
+        print("  MFMA stream (opcode sequence first .. last MFMA):", "identical" if sa[pa[1]:pa[2] + 1] == sb[pb[1]:pb[2] + 1] else "DIFFERENT")
+    else:
+        for tag, ops, ls in (("parent", oa, lsa), ("branch", ob, lsb)):
+            for q in ls:
+                depth = sum(1 for o in ls if o[0] <= q[0] and q[1] <= o[1]) - 1
+                print("  %s loop %s%s: instructions %d .. %d (%d), holds %s" % (tag, "  " * depth, q[2], q[0], q[1], q[1] - q[0] + 1, holds(ops, q)))
     count = collections.Counter()
     for tag, i1, i2, j1, j2 in difflib.SequenceMatcher(None, sa, sb, autojunk=False).get_opcodes():
         if tag == "equal":
             continue
-        w = where(j1, j2, pb)
+        w = where_mfma(j1, j2, pb) if mfma else where_loop(j1, j2, lsb)
         count[w] += 1
         print("  %s parent[%d:%d] branch[%d:%d]  %s" % (tag, i1, i2, j1, j2, w))
         for o in oa[i1:i2]:
@@ -92,3 +140,15 @@ for name in KERNELS:
         for o in ob[j1:j2]:
             print("    + " + o[2])
     print("  differing runs by place:", dict(count))
+
+
+def main():
+    a_path, b_path = sys.argv[1:3]
+    names = kernel_names(a_path)
+    want = sys.argv[3:] or KNN_KERNELS
+    for name in (names if want == ["all"] else [resolve(w, names) for w in want]):
+        compare(a_path, b_path, name)
+
+
+if __name__ == "__main__":
+    main()

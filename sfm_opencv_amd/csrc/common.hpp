@@ -201,6 +201,28 @@ struct SfmPoolHold {
     SfmPoolHold& operator=(const SfmPoolHold&) = delete;
 };
 
+// the call shape of the host entry points of points.hip and normals.hip: upload the cloud, enqueue, download, finish
+static inline bool points_method_ok(int method) { return method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID; }
+// the cloud's device block (n x 3 double) from `hold`, filled from the caller's array on the context's stream
+static inline int points_upload(sfmhip_ctx* ctx, SfmPoolHold& hold, const double* pts, int n, double*& d_p)
+{
+    const int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    if (rc != SFMHIP_OK) return rc;
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+    return SFMHIP_OK;
+}
+// a step failed with rc while work may be in flight: drain the stream (the blocks go back to the cache behind this call), return rc
+static inline int points_drain(sfmhip_ctx* ctx, int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+// the end of a call, also after an error with work possibly in flight: drain the stream (the caller's host buffers may be targets of
+// copies), keep the first error
+static inline int points_finish(sfmhip_ctx* ctx, hipError_t e)
+{
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
+    return SFMHIP_OK;
+}
+
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline int ceil_div(int x, int m) { return (x + m - 1) / m; }
 

@@ -150,30 +150,25 @@ extern "C" int sfmhip_estimate_normals_ex(sfmhip_ctx* ctx, const double* pts, in
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_estimate_normals");
     SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX);
-    SFM_ARG_CHECK(ctx, method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID);
+    SFM_ARG_CHECK(ctx, points_method_ok(method));
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, pts && normals);
     if (method == SFMHIP_POINTS_AUTO) method = sfm_points_auto_method(n);
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_n = nullptr; int32_t* d_idx = nullptr;
-    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    int rc = points_upload(ctx, hold, pts, n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_n);
     if (rc == SFMHIP_OK && method == SFMHIP_POINTS_GRID) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_idx);
-    if (rc != SFMHIP_OK) return rc;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
     if (method == SFMHIP_POINTS_GRID) {
         rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_idx, nullptr);
         if (rc == SFMHIP_OK) rc = sfm_normals_from_knn_enqueue(ctx, d_p, d_idx, n, K, d_n);
-        if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        if (rc != SFMHIP_OK) return points_drain(ctx, rc);
     } else {
         hipLaunchKernelGGL(normals_kernel, dim3(ceil_div(n, NTILE)), dim3(NTILE), 0, ctx->stream, d_p, n, K, d_n);
         SFM_HIP_TRY(ctx, hipGetLastError());
     }
-    hipError_t e = hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);        // also on an error: the blocks go back to the cache behind this call
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    return SFMHIP_OK;
+    return points_finish(ctx, hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
 }
 
 extern "C" int sfmhip_estimate_normals(sfmhip_ctx* ctx, const double* pts, int n, int K, double* normals)
@@ -186,27 +181,21 @@ extern "C" int sfmhip_estimate_normals_hybrid(sfmhip_ctx* ctx, const double* pts
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_estimate_normals_hybrid");
     SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && std::isfinite(r) && r >= 0.0);
-    SFM_ARG_CHECK(ctx, method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID);
+    SFM_ARG_CHECK(ctx, points_method_ok(method));
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, pts && normals);
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_n = nullptr, *d_dist = nullptr; int32_t* d_idx = nullptr;
     const size_t total = (size_t)n * K;
-    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    int rc = points_upload(ctx, hold, pts, n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_n);
     if (rc == SFMHIP_OK) rc = hold.get(total * sizeof(int32_t), (void**)&d_idx);
     if (rc == SFMHIP_OK) rc = hold.get(total * sizeof(double), (void**)&d_dist);
-    if (rc != SFMHIP_OK) return rc;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-    rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_idx, d_dist);
+    if (rc == SFMHIP_OK) rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_idx, d_dist);
     if (rc == SFMHIP_OK) {
         hipLaunchKernelGGL(normals_radius_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_idx, (const double*)d_dist, total, r);
         rc = sfm_normals_from_knn_enqueue(ctx, d_p, d_idx, n, K, d_n);
     }
-    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    hipError_t e = hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    return SFMHIP_OK;
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    return points_finish(ctx, hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
 }

@@ -69,9 +69,35 @@ struct TopK {
 };
 
 // ------------------------------------------------------------------------------------------------
-// brute force: query t of the list (or point t where there is no list) against every point, LDS tiles of NTILE points.  Scanning j
-// ascending with a strict (d, j) test is the order of normals_kernel.  The grid's fallback pass is this kernel on its list: the
-// launch covers n queries and the workgroups beyond the list's length (read from the device) leave at once.
+// the all-pairs sweep, the first of the file's two traversals: the query (px, py, pz) of every thread of the workgroup against the
+// points [0, jend), LDS tiles of NTILE points, j ascending.  Every thread of the workgroup has to come here (the barriers), with or
+// without a query.  stage(j0) runs between the barriers beside the staging of point j0 (a fourth LDS column of the caller's);
+// visit(j, s, d2) gets point j = base + s of the tile and the squared distance defined at the top of the file.
+// ------------------------------------------------------------------------------------------------
+template <class Stage, class Visit>
+__device__ __forceinline__ void tile_sweep(const double* __restrict__ pts, int jend, double px, double py, double pz, double* tx, double* ty, double* tz,
+                                           Stage stage, Visit visit)
+{
+    for (int base = 0; base < jend; base += NTILE) {
+        const int j0 = base + threadIdx.x;
+        __syncthreads();
+        if (j0 < jend) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; stage(j0); }
+        __syncthreads();
+        const int cnt = jend - base < NTILE ? jend - base : NTILE;
+        for (int s = 0; s < cnt; ++s) {
+            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
+            const double d2 = dx * dx + dy * dy + dz * dz;
+            visit(base + s, s, d2);
+        }
+    }
+}
+// the staging functor of a sweep with three columns
+struct NoStage { __device__ __forceinline__ void operator()(int) const {} };
+
+// ------------------------------------------------------------------------------------------------
+// brute force: query t of the list (or point t where there is no list) against every point.  Scanning j ascending with a strict
+// (d, j) test is the order of normals_kernel.  The grid's fallback pass is this kernel on its list: the launch covers n queries and
+// the workgroups beyond the list's length (read from the device) leave at once.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NTILE) void points_knn_brute_kernel(const double* __restrict__ pts, int n, int K, const pu32* __restrict__ list,
                                                                  const pu32* __restrict__ list_len, int32_t* __restrict__ idx, double* __restrict__ dist)
@@ -84,19 +110,7 @@ __global__ __launch_bounds__(NTILE) void points_knn_brute_kernel(const double* _
     const int i = active ? (list ? (int)list[t] : t) : -1;
     const double px = active ? pts[3 * (size_t)i] : 0.0, py = active ? pts[3 * (size_t)i + 1] : 0.0, pz = active ? pts[3 * (size_t)i + 2] : 0.0;
     TopK top; top.init();
-    for (int base = 0; base < n; base += NTILE) {
-        const int j0 = base + threadIdx.x;
-        __syncthreads();
-        if (j0 < n) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; }
-        __syncthreads();
-        const int cnt = n - base < NTILE ? n - base : NTILE;
-        for (int s = 0; s < cnt; ++s) {
-            const int j = base + s;
-            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            if (j != i) top.offer(d2, j, K);
-        }
-    }
+    tile_sweep(pts, n, px, py, pz, tx, ty, tz, NoStage(), [&](int j, int, double d2) { if (j != i) top.offer(d2, j, K); });
     if (active) top.store(K, (size_t)i, idx, dist);
 }
 
@@ -241,10 +255,30 @@ __device__ __forceinline__ int keys_lower_bound(const pu64* __restrict__ keys, i
 }
 
 // ------------------------------------------------------------------------------------------------
+// the cell-run visit, the second traversal: cells with the same (x, y) and consecutive z are consecutive keys, so the column
+// (X, Y, z0 .. z1), 0 <= z0 <= z1 <= CELL_MAX, is ONE run of the sorted keys, found by two binary searches.  visit(s, d2) gets every
+// record s of the run (a position in cell order, the query's own included) and its squared distance from (qx, qy, qz).
+// ------------------------------------------------------------------------------------------------
+template <class Visit>
+__device__ __forceinline__ void cell_run_visit(const pu64* __restrict__ keys, const double* __restrict__ spts, int n, int X, int Y, int z0, int z1,
+                                               double qx, double qy, double qz, Visit visit)
+{
+    const pu64 k0 = cell_key(X, Y, z0), k1 = cell_key(X, Y, z1);
+    const int a = keys_lower_bound(keys, 0, n, k0);
+    if (a >= n || keys[a] > k1) return;                                // an empty run
+    const int b = keys_lower_bound(keys, a, n, k1 + 1ull);
+    for (int s = a; s < b; ++s) {
+        const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
+        const double d2 = ex * ex + ey * ey + ez * ez;
+        visit(s, d2);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // grid search.  Thread p handles the p-th point in cell order (a wave walks the same cells) and writes to the row of its point.
 //
-// Ring r visits the cells of the cube [c - r, c + r]^3 (clipped to [0, CELL_MAX]) that ring r - 1 has not visited; cells with the same
-// (x, y) and consecutive z are consecutive keys, so a column of the cube is ONE run of the sorted keys, found by two binary searches.
+// Ring r visits the cells of the cube [c - r, c + r]^3 (clipped to [0, CELL_MAX]) that ring r - 1 has not visited, column by column
+// (cell_run_visit).
 //
 // The certificate.  Let t_q = cell_pos(q_a) on axis a, c = cell_of(t_q) with 0 < c < CELL_MAX on every axis (a query in a border cell is
 // not searched at all: border cells are unbounded outward and hold whatever was clamped into them).  A point p that the cube has NOT
@@ -293,14 +327,7 @@ __global__ __launch_bounds__(NTILE) void points_knn_grid_kernel(const pu64* __re
                         int z1 = shell ? cz + r : z0;
                         if (z1 < 0 || z0 > CELL_MAX) continue;
                         z0 = z0 < 0 ? 0 : z0; z1 = z1 > CELL_MAX ? CELL_MAX : z1;
-                        const int a = keys_lower_bound(keys, 0, n, cell_key(X, Y, z0));
-                        if (a >= n || keys[a] > cell_key(X, Y, z1)) continue;             // an empty run
-                        const int b = keys_lower_bound(keys, a, n, cell_key(X, Y, z1) + 1ull);
-                        for (int s = a; s < b; ++s) {
-                            const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
-                            const double d2 = ex * ex + ey * ey + ez * ez;
-                            if (s != p) top.offer(d2, (int)order[s], K);
-                        }
+                        cell_run_visit(keys, spts, n, X, Y, z0, z1, qx, qy, qz, [&](int s, double d2) { if (s != p) top.offer(d2, (int)order[s], K); });
                     }
                 }
             }
@@ -463,7 +490,7 @@ static inline RadiusGate radius_gate(double r)
 }
 __device__ __forceinline__ int radius_hit(double d2, const RadiusGate& g) { return d2 <= g.hi2 && (d2 <= g.lo2 || sqrt(d2) <= g.r) ? 1 : 0; }
 
-// all pairs: the sweep of points_knn_brute_kernel
+// all pairs
 __global__ __launch_bounds__(NTILE) void points_radius_brute_kernel(const double* __restrict__ pts, int n, RadiusGate g, int32_t* __restrict__ count)
 {
     __shared__ double tx[NTILE], ty[NTILE], tz[NTILE];
@@ -471,24 +498,14 @@ __global__ __launch_bounds__(NTILE) void points_radius_brute_kernel(const double
     const bool active = i < n;
     const double px = active ? pts[3 * (size_t)i] : 0.0, py = active ? pts[3 * (size_t)i + 1] : 0.0, pz = active ? pts[3 * (size_t)i + 2] : 0.0;
     int c = 0;
-    for (int base = 0; base < n; base += NTILE) {
-        const int j0 = base + threadIdx.x;
-        __syncthreads();
-        if (j0 < n) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; }
-        __syncthreads();
-        const int cnt = n - base < NTILE ? n - base : NTILE;
-        for (int s = 0; s < cnt; ++s) {
-            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            c += base + s != i ? radius_hit(d2, g) : 0;
-        }
-    }
+    tile_sweep(pts, n, px, py, pz, tx, ty, tz, NoStage(), [&](int j, int, double d2) { c += j != i ? radius_hit(d2, g) : 0; });
     if (active) count[i] = c;
 }
 
 // ------------------------------------------------------------------------------------------------
-// grid count.  Thread p is the p-th point in cell order; it visits the 3 x 3 columns (x, y) of its cell's neighbourhood, each with
-// z in [cz - 1, cz + 1] as ONE run of the sorted keys, everything clipped to [0, CELL_MAX].  No rings, no test at run time, no fallback
+// the 27-cell visit of every fixed-radius sweep on the grid.  The p-th point in cell order, with key `key` (finite: bit 63 clear),
+// visits the 3 x 3 columns (x, y) of its cell's neighbourhood, each with z in [cz - 1, cz + 1] as ONE run of the sorted keys
+// (cell_run_visit, whose visit(s, d2) this passes on), everything clipped to [0, CELL_MAX].  No rings, no test at run time, no fallback
 // list: the cell size is chosen so that the 27 cells suffice, h >= r (1 + 2^-20) (points_cell_stats_kernel, rmin = r).
 //
 // Why they suffice.  For a finite x let delta = x - o (real) and t = cell_pos(x) = fl(fl(delta) inv_h) = delta inv_h (1 + e), |e| < 2^-51,
@@ -510,6 +527,24 @@ __global__ __launch_bounds__(NTILE) void points_radius_brute_kernel(const double
 // unvisited side only needs the definition of cell_of.  (Far outliers are what lands in border cells -- 16,000 of the 20,000 far points
 // of the 2M-point outlier cloud at a radius of 0.02 -- and an all-pairs pass for them would cost 60 times the search itself.)
 // ------------------------------------------------------------------------------------------------
+template <class Visit>
+__device__ __forceinline__ void cells27_visit(const pu64* __restrict__ keys, const double* __restrict__ spts, int n, int p, pu64 key, Visit visit)
+{
+    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
+    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
+    const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < CELL_MAX ? cz + 1 : CELL_MAX;
+    for (int dx = -1; dx <= 1; ++dx) {
+        const int X = cx + dx;
+        if (X < 0 || X > CELL_MAX) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int Y = cy + dy;
+            if (Y < 0 || Y > CELL_MAX) continue;
+            cell_run_visit(keys, spts, n, X, Y, z0, z1, qx, qy, qz, visit);
+        }
+    }
+}
+
+// grid count: thread p is the p-th point in cell order
 __global__ __launch_bounds__(NTILE) void points_radius_grid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ spts,
                                                                    int n, RadiusGate g, int32_t* __restrict__ count)
 {
@@ -518,27 +553,8 @@ __global__ __launch_bounds__(NTILE) void points_radius_grid_kernel(const pu64* _
     const pu64 key = keys[p];
     const int i = (int)order[p];
     if (key >> 63) { count[i] = 0; return; }                               // non-finite: counts nobody
-    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
-    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
-    const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < CELL_MAX ? cz + 1 : CELL_MAX;
     int c = 0;
-    for (int dx = -1; dx <= 1; ++dx) {
-        const int X = cx + dx;
-        if (X < 0 || X > CELL_MAX) continue;
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int Y = cy + dy;
-            if (Y < 0 || Y > CELL_MAX) continue;
-            const pu64 k0 = cell_key(X, Y, z0), k1 = cell_key(X, Y, z1);
-            const int a = keys_lower_bound(keys, 0, n, k0);
-            if (a >= n || keys[a] > k1) continue;                          // an empty run
-            const int b = keys_lower_bound(keys, a, n, k1 + 1ull);
-            for (int s = a; s < b; ++s) {
-                const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
-                const double d2 = ex * ex + ey * ey + ez * ez;
-                c += s != p ? radius_hit(d2, g) : 0;
-            }
-        }
-    }
+    cells27_visit(keys, spts, n, p, key, [&](int s, double d2) { c += s != p ? radius_hit(d2, g) : 0; });
     count[i] = c;
 }
 
@@ -788,7 +804,7 @@ __global__ __launch_bounds__(256) void cluster_init_kernel(const double* __restr
 }
 
 // link sweep, all pairs: core point i unites itself with every core j < i within r (each pair from its larger index only, so a
-// workgroup needs the tiles below its own last point and no others).  The tile sweep of points_radius_brute_kernel.
+// workgroup needs the tiles below its own last point and no others).
 __global__ __launch_bounds__(NTILE) void cluster_link_brute_kernel(const double* __restrict__ pts, int n, RadiusGate g, const uint8_t* __restrict__ core,
                                                                    pu32* parent, pu32* err)
 {
@@ -800,21 +816,12 @@ __global__ __launch_bounds__(NTILE) void cluster_link_brute_kernel(const double*
     const double px = mine ? pts[3 * (size_t)i] : 0.0, py = mine ? pts[3 * (size_t)i + 1] : 0.0, pz = mine ? pts[3 * (size_t)i + 2] : 0.0;
     const int jend = n < (blockIdx.x + 1) * NTILE ? n : (blockIdx.x + 1) * NTILE;
     pu32 me = (pu32)i;
-    for (int base = 0; base < jend; base += NTILE) {
-        const int j0 = base + threadIdx.x;
-        __syncthreads();
-        if (j0 < jend) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; tc[threadIdx.x] = core[j0]; }
-        __syncthreads();
-        const int cnt = jend - base < NTILE ? jend - base : NTILE;
-        for (int s = 0; s < cnt; ++s) {
-            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            if (mine && base + s < i && tc[s] && radius_hit(d2, g)) me = cluster_unite(parent, me, (pu32)(base + s), err);
-        }
-    }
+    tile_sweep(pts, jend, px, py, pz, tx, ty, tz, [&](int j0) { tc[threadIdx.x] = core[j0]; }, [&](int j, int s, double d2) {
+        if (mine && j < i && tc[s] && radius_hit(d2, g)) me = cluster_unite(parent, me, (pu32)j, err);
+    });
 }
 
-// link sweep on the grid: the 27-cell visit of points_radius_grid_kernel (its comment says why those cells suffice, border cells included)
+// link sweep on the grid
 __global__ __launch_bounds__(NTILE) void cluster_link_grid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ spts,
                                                                   int n, RadiusGate g, const uint8_t* __restrict__ core, pu32* parent, pu32* err)
 {
@@ -823,29 +830,12 @@ __global__ __launch_bounds__(NTILE) void cluster_link_grid_kernel(const pu64* __
     const pu64 key = keys[p];
     const pu32 i = order[p];
     if ((key >> 63) || !core[i]) return;
-    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
-    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
-    const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < CELL_MAX ? cz + 1 : CELL_MAX;
     pu32 me = i;
-    for (int dx = -1; dx <= 1; ++dx) {
-        const int X = cx + dx;
-        if (X < 0 || X > CELL_MAX) continue;
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int Y = cy + dy;
-            if (Y < 0 || Y > CELL_MAX) continue;
-            const pu64 k0 = cell_key(X, Y, z0), k1 = cell_key(X, Y, z1);
-            const int a = keys_lower_bound(keys, 0, n, k0);
-            if (a >= n || keys[a] > k1) continue;                          // an empty run
-            const int b = keys_lower_bound(keys, a, n, k1 + 1ull);
-            for (int s = a; s < b; ++s) {
-                const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
-                const double d2 = ex * ex + ey * ey + ez * ez;
-                if (!radius_hit(d2, g)) continue;
-                const pu32 j = order[s];
-                if (j < i && core[j]) me = cluster_unite(parent, me, j, err);
-            }
-        }
-    }
+    cells27_visit(keys, spts, n, p, key, [&](int s, double d2) {
+        if (!radius_hit(d2, g)) return;
+        const pu32 j = order[s];
+        if (j < i && core[j]) me = cluster_unite(parent, me, j, err);
+    });
 }
 
 // after the sweep: every core point is pointed at its root; flag[i] = 1 where i is a root, n + 1 entries for the exclusive scan.  A root
@@ -883,18 +873,9 @@ __global__ __launch_bounds__(NTILE) void cluster_border_brute_kernel(const doubl
     if (!__syncthreads_or(mine ? 1 : 0)) return;                           // uniform: core points only
     const double px = mine ? pts[3 * (size_t)i] : 0.0, py = mine ? pts[3 * (size_t)i + 1] : 0.0, pz = mine ? pts[3 * (size_t)i + 2] : 0.0;
     int lab = INT32_MAX;
-    for (int base = 0; base < n; base += NTILE) {
-        const int j0 = base + threadIdx.x;
-        __syncthreads();
-        if (j0 < n) { tx[threadIdx.x] = pts[3 * (size_t)j0]; ty[threadIdx.x] = pts[3 * (size_t)j0 + 1]; tz[threadIdx.x] = pts[3 * (size_t)j0 + 2]; tl[threadIdx.x] = core[j0] ? labels[j0] : -1; }
-        __syncthreads();
-        const int cnt = n - base < NTILE ? n - base : NTILE;
-        for (int s = 0; s < cnt; ++s) {
-            const double dx = px - tx[s], dy = py - ty[s], dz = pz - tz[s];
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            if (tl[s] >= 0 && tl[s] < lab && radius_hit(d2, g)) lab = tl[s];      // a non-finite point of either side: d2 fails the gate
-        }
-    }
+    tile_sweep(pts, n, px, py, pz, tx, ty, tz, [&](int j0) { tl[threadIdx.x] = core[j0] ? labels[j0] : -1; }, [&](int, int s, double d2) {
+        if (tl[s] >= 0 && tl[s] < lab && radius_hit(d2, g)) lab = tl[s];          // a non-finite point of either side: d2 fails the gate
+    });
     if (mine) labels[i] = lab == INT32_MAX ? -1 : lab;
 }
 
@@ -906,29 +887,12 @@ __global__ __launch_bounds__(NTILE) void cluster_border_grid_kernel(const pu64* 
     const pu64 key = keys[p];
     const pu32 i = order[p];
     if ((key >> 63) || core[i]) return;                                    // non-finite: -1 already
-    const int cx = (int)(key >> (2 * CELL_BITS)), cy = (int)(key >> CELL_BITS) & CELL_MAX, cz = (int)key & CELL_MAX;
-    const double qx = spts[3 * (size_t)p], qy = spts[3 * (size_t)p + 1], qz = spts[3 * (size_t)p + 2];
-    const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < CELL_MAX ? cz + 1 : CELL_MAX;
     int lab = INT32_MAX;
-    for (int dx = -1; dx <= 1; ++dx) {
-        const int X = cx + dx;
-        if (X < 0 || X > CELL_MAX) continue;
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int Y = cy + dy;
-            if (Y < 0 || Y > CELL_MAX) continue;
-            const pu64 k0 = cell_key(X, Y, z0), k1 = cell_key(X, Y, z1);
-            const int a = keys_lower_bound(keys, 0, n, k0);
-            if (a >= n || keys[a] > k1) continue;                          // an empty run
-            const int b = keys_lower_bound(keys, a, n, k1 + 1ull);
-            for (int s = a; s < b; ++s) {
-                const double ex = qx - spts[3 * (size_t)s], ey = qy - spts[3 * (size_t)s + 1], ez = qz - spts[3 * (size_t)s + 2];
-                const double d2 = ex * ex + ey * ey + ez * ez;
-                if (!radius_hit(d2, g)) continue;
-                const pu32 j = order[s];
-                if (core[j]) { const int l = labels[j]; lab = l < lab ? l : lab; }
-            }
-        }
-    }
+    cells27_visit(keys, spts, n, p, key, [&](int s, double d2) {
+        if (!radius_hit(d2, g)) return;
+        const pu32 j = order[s];
+        if (core[j]) { const int l = labels[j]; lab = l < lab ? l : lab; }
+    });
     labels[i] = lab == INT32_MAX ? -1 : lab;
 }
 
@@ -1033,16 +997,9 @@ static int cluster_dbscan_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, d
     return SFMHIP_OK;
 }
 
-static inline bool points_method_ok(int method) { return method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID; }
-
-// after an error with work possibly in flight: drain the stream (the caller's host buffers may be targets of copies), keep the first error
-static int points_finish(sfmhip_ctx* ctx, hipError_t e)
-{
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    return SFMHIP_OK;
-}
+// the argument conditions shared by the entry points: of a kNN query, of a fixed-radius query
+static inline bool knn_args_ok(const sfmhip_ctx* ctx, int n, int K, int method) { return ctx && n >= 0 && K >= 1 && K <= KMAX && points_method_ok(method); }
+static inline bool radius_args_ok(const sfmhip_ctx* ctx, int n, double r, int method) { return ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && points_method_ok(method); }
 
 extern "C" {
 
@@ -1050,7 +1007,7 @@ int sfmhip_knn_points_dev(sfmhip_ctx* ctx, const double* d_pts, int n, int K, in
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_knn_points_dev");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, knn_args_ok(ctx, n, K, method));
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, d_pts);
     if (!d_idx && !d_dist) return SFMHIP_OK;
@@ -1061,19 +1018,17 @@ int sfmhip_knn_points(sfmhip_ctx* ctx, const double* pts, int n, int K, int meth
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_knn_points");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, knn_args_ok(ctx, n, K, method));
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, pts);
     if (!idx && !dist) return SFMHIP_OK;
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_d = nullptr; int32_t* d_i = nullptr;
-    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    int rc = points_upload(ctx, hold, pts, n, d_p);
     if (rc == SFMHIP_OK && idx) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_i);
     if (rc == SFMHIP_OK && dist) rc = hold.get((size_t)n * K * sizeof(double), (void**)&d_d);
-    if (rc != SFMHIP_OK) return rc;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-    rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
-    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc == SFMHIP_OK) rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
     hipError_t e = hipSuccess;
     if (idx) e = hipMemcpyAsync(idx, d_i, (size_t)n * K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, d_d, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
@@ -1084,24 +1039,22 @@ int sfmhip_statistical_outliers(sfmhip_ctx* ctx, const double* pts, int n, int K
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_statistical_outliers");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && K >= 1 && K <= KMAX && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, knn_args_ok(ctx, n, K, method));
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, pts && keep);
     const int nt = ceil_div(n, RED_TILE);
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_d = nullptr, *d_m = nullptr, *d_part = nullptr; int32_t* d_i = nullptr; uint8_t* d_keep = nullptr;
-    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    int rc = points_upload(ctx, hold, pts, n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_i);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * K * sizeof(double), (void**)&d_d);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(double), (void**)&d_m);
     if (rc == SFMHIP_OK) rc = hold.get(((size_t)2 * nt + 4) * sizeof(double), (void**)&d_part);       // tile sums, then stats[3]
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n, (void**)&d_keep);
-    if (rc != SFMHIP_OK) return rc;
+    if (rc == SFMHIP_OK) rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
     double* d_stats = d_part + 2 * (size_t)nt;
     hipStream_t st = ctx->stream;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
-    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
     hipLaunchKernelGGL(points_mean_dist_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const int32_t*)d_i, (const double*)d_d, n, K, d_m);
     for (int pass = 0; pass < 2; ++pass) {
         hipLaunchKernelGGL(points_stat_tile_kernel, dim3(nt), dim3(256), 0, st, (const double*)d_m, n, pass, (const double*)d_stats, d_part);
@@ -1119,7 +1072,7 @@ int sfmhip_radius_count_dev(sfmhip_ctx* ctx, const double* d_pts, int n, double 
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_radius_count_dev");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, radius_args_ok(ctx, n, r, method));
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, d_pts && d_count);
     return points_radius_count_enqueue(ctx, d_pts, n, r, method, d_count);
@@ -1130,14 +1083,12 @@ static int radius_count_host(sfmhip_ctx* ctx, const double* pts, int n, double r
 {
     SfmPoolHold hold(ctx);
     double* d_p = nullptr; int32_t* d_c = nullptr; uint8_t* d_keep = nullptr;
-    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    int rc = points_upload(ctx, hold, pts, n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_c);
     if (rc == SFMHIP_OK && keep) rc = hold.get((size_t)n, (void**)&d_keep);
-    if (rc != SFMHIP_OK) return rc;
+    if (rc == SFMHIP_OK) rc = points_radius_count_enqueue(ctx, d_p, n, r, method, d_c);
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
     hipStream_t st = ctx->stream;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    rc = points_radius_count_enqueue(ctx, d_p, n, r, method, d_c);
-    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
     hipError_t e = hipSuccess;
     if (keep) {
         hipLaunchKernelGGL(points_count_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const int32_t*)d_c, n, min_neighbors, d_keep);
@@ -1152,7 +1103,7 @@ int sfmhip_radius_count(sfmhip_ctx* ctx, const double* pts, int n, double r, int
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_radius_count");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, radius_args_ok(ctx, n, r, method));
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, pts && count);
     return radius_count_host(ctx, pts, n, r, 0, method, nullptr, count);
@@ -1162,7 +1113,7 @@ int sfmhip_radius_outliers(sfmhip_ctx* ctx, const double* pts, int n, double r, 
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_radius_outliers");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_neighbors >= 1 && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, radius_args_ok(ctx, n, r, method) && min_neighbors >= 1);
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, pts && keep);
     return radius_count_host(ctx, pts, n, r, min_neighbors, method, keep, count);
@@ -1190,17 +1141,16 @@ int sfmhip_voxel_downsample(sfmhip_ctx* ctx, const double* pts, int n, double vo
     *n_voxels = 0;
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_c = nullptr, *d_org = nullptr; int32_t *d_cnt = nullptr, *d_vof = nullptr, *d_nv = nullptr;
-    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    int rc = points_upload(ctx, hold, pts, n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_c);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_cnt);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_vof);
     if (rc == SFMHIP_OK) rc = hold.get(256, (void**)&d_org);               // origin[3], then n_voxels
-    if (rc != SFMHIP_OK) return rc;
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
     d_nv = (int32_t*)(d_org + 4);
-    hipStream_t st = ctx->stream;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
     rc = voxel_downsample_enqueue(ctx, d_p, n, voxel, d_c, d_cnt, d_vof, d_nv, d_org);
-    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    hipStream_t st = ctx->stream;
     int32_t nv = 0;
     rc = points_finish(ctx, hipMemcpyAsync(&nv, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (rc != SFMHIP_OK) return rc;
@@ -1223,7 +1173,7 @@ int sfmhip_cluster_dbscan_dev(sfmhip_ctx* ctx, const double* d_pts, int n, doubl
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_cluster_dbscan_dev");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_points >= 1 && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, radius_args_ok(ctx, n, r, method) && min_points >= 1);
     if (n == 0) return SFMHIP_OK;
     SFM_ARG_CHECK(ctx, d_pts && d_labels && d_n_clusters);
     return cluster_dbscan_enqueue(ctx, d_pts, n, r, min_points, method, d_labels, d_n_clusters, d_sizes, d_count);
@@ -1235,17 +1185,15 @@ static int cluster_host(sfmhip_ctx* ctx, const double* pts, int n, double r, int
 {
     SfmPoolHold hold(ctx);
     double* d_p = nullptr; int32_t *d_lab = nullptr, *d_sz = nullptr, *d_cnt = nullptr, *d_head = nullptr; uint8_t* d_keep = nullptr;
-    int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    int rc = points_upload(ctx, hold, pts, n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_lab);
     if (rc == SFMHIP_OK && (sizes || keep)) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_sz);
     if (rc == SFMHIP_OK && count) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_cnt);
     if (rc == SFMHIP_OK && keep) rc = hold.get((size_t)n, (void**)&d_keep);
     if (rc == SFMHIP_OK) rc = hold.get(256, (void**)&d_head);              // n_clusters, then the largest cluster's number and size
-    if (rc != SFMHIP_OK) return rc;
+    if (rc == SFMHIP_OK) rc = cluster_dbscan_enqueue(ctx, d_p, n, r, min_points, method, d_lab, d_head, d_sz, d_cnt);
+    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
     hipStream_t st = ctx->stream;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    rc = cluster_dbscan_enqueue(ctx, d_p, n, r, min_points, method, d_lab, d_head, d_sz, d_cnt);
-    if (rc != SFMHIP_OK) { (void)hipStreamSynchronize(st); return rc; }
     if (keep) {
         hipLaunchKernelGGL(cluster_largest_kernel, dim3(1), dim3(256), 0, st, (const int32_t*)d_sz, (const int32_t*)d_head, d_head + 1);
         hipLaunchKernelGGL(cluster_keep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const int32_t*)d_lab, n, (const int32_t*)(d_head + 1), d_keep);
@@ -1276,7 +1224,7 @@ int sfmhip_cluster_dbscan(sfmhip_ctx* ctx, const double* pts, int n, double r, i
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_cluster_dbscan");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_points >= 1 && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, radius_args_ok(ctx, n, r, method) && min_points >= 1);
     if (n == 0) { if (n_clusters) *n_clusters = 0; return SFMHIP_OK; }
     SFM_ARG_CHECK(ctx, pts && labels && n_clusters);
     return cluster_host(ctx, pts, n, r, min_points, method, labels, n_clusters, sizes, count, nullptr, nullptr);
@@ -1287,7 +1235,7 @@ int sfmhip_largest_cluster(sfmhip_ctx* ctx, const double* pts, int n, double r, 
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_largest_cluster");
-    SFM_ARG_CHECK(ctx, ctx && n >= 0 && std::isfinite(r) && r >= 0.0 && min_points >= 1 && points_method_ok(method));
+    SFM_ARG_CHECK(ctx, radius_args_ok(ctx, n, r, method) && min_points >= 1);
     if (n == 0) { if (n_clusters) *n_clusters = 0; if (largest_size) *largest_size = 0; return SFMHIP_OK; }
     SFM_ARG_CHECK(ctx, pts && keep);
     return cluster_host(ctx, pts, n, r, min_points, method, labels, n_clusters, nullptr, nullptr, keep, largest_size);

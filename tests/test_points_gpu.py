@@ -40,7 +40,7 @@ def _with_bad_rows():
 
 
 CLOUDS = {
-    **{f"cube_{n}": (lambda n=n: _cube(n)) for n in (0, 1, 2, 5, 11, 17, 1000, 20000)},
+    **{f"cube_{n}": (lambda n=n: _cube(n)) for n in (0, 1, 2, 5, 11, 17, 255, 256, 257, 513, 1000, 20000)},
     "sphere_1000": lambda: pr.sphere_cloud(1000),
     "sphere_20000": lambda: pr.sphere_cloud(20000),
     "lattice_32": lambda: pr.lattice(32),
