@@ -191,12 +191,18 @@ int sfm_normals_from_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, const int
 // the method SFMHIP_POINTS_AUTO stands for at n points
 int sfm_points_auto_method(int n);
 
-// device blocks of the context's cache that go back to it when the holder leaves scope
+// device blocks of the context's cache that go back to it when the holder leaves scope (the first few are kept in the holder
+// itself: a call that takes a block or two per pass allocates nothing on the heap for it)
 struct SfmPoolHold {
-    sfmhip_ctx* ctx; std::vector<void*> blocks;
+    sfmhip_ctx* ctx; void* few[4]; int n_few = 0; std::vector<void*> more;
     explicit SfmPoolHold(sfmhip_ctx* c) : ctx(c) {}
-    ~SfmPoolHold() { for (void* p : blocks) sfm_pool_put(ctx, p); }
-    int get(size_t bytes, void** out) { const int rc = sfm_pool_get(ctx, bytes, out); if (rc == SFMHIP_OK) blocks.push_back(*out); return rc; }
+    ~SfmPoolHold() { for (int i = 0; i < n_few; ++i) sfm_pool_put(ctx, few[i]); for (void* p : more) sfm_pool_put(ctx, p); }
+    int get(size_t bytes, void** out)
+    {
+        const int rc = sfm_pool_get(ctx, bytes, out);
+        if (rc == SFMHIP_OK) { if (n_few < 4) few[n_few++] = *out; else more.push_back(*out); }
+        return rc;
+    }
     SfmPoolHold(const SfmPoolHold&) = delete;
     SfmPoolHold& operator=(const SfmPoolHold&) = delete;
 };

@@ -1495,13 +1495,20 @@ __global__ void rev_from_knn_kernel(const int32_t* __restrict__ idx2, const floa
 // ================================================================================================
 // host side
 // ================================================================================================
-static int descset_alloc_common(sfmhip_ctx* ctx, int kind, int rows, int dim, sfmhip_descset** out)
+// a HIP status as a return code; the text of a failure goes to last_error
+static inline int hip_rc(sfmhip_ctx* ctx, hipError_t e)
+{
+    if (e == hipSuccess) return SFMHIP_OK;
+    ctx->last_error = hipGetErrorString(e);
+    return SFMHIP_E_HIP;
+}
+
+static sfmhip_descset* descset_new(sfmhip_ctx* ctx, int kind, int rows, int dim)
 {
     sfmhip_descset* s = new sfmhip_descset();
     s->ctx = ctx; s->kind = kind; s->rows = rows; s->dim = dim;
     s->rows_pad = round_up(rows > 0 ? rows : 1, KNN_BLOCK_ROWS);
-    *out = s;
-    return SFMHIP_OK;
+    return s;
 }
 
 static int descset_flag_slot(sfmhip_ctx* ctx, sfmhip_descset* s)
@@ -1514,6 +1521,38 @@ static int descset_flag_slot(sfmhip_ctx* ctx, sfmhip_descset* s)
     int rc = sfm_pool_get(ctx, 256, &q); if (rc) return rc;
     s->d_flag = (int*)q;
     return SFMHIP_OK;
+}
+
+// The device blocks of the encodings a set of its kind keeps (released by sfmhip_descset_destroy, also after an error here).
+// L2: the int8 copy, its norms and the flag -- none of them for rows of more than 128 values, which only the exact kernels take.
+// Hamming2: the 64-byte rows, and the FP4 copy of rows that fit its 768 values.
+static int descset_buffers(sfmhip_ctx* ctx, sfmhip_descset* s)
+{
+    void* q = nullptr; int rc;
+    if (s->kind == SFMHIP_DESC_HAMMING2_U8) {
+        rc = sfm_pool_get(ctx, (size_t)s->rows_pad * 64, &q); if (rc) return rc; s->d_u32 = (uint32_t*)q;
+        if (s->dim > H4_MAX_NBYTES) return SFMHIP_OK;
+        rc = sfm_pool_get(ctx, (size_t)s->rows_pad * H4_ROW_BYTES, &q); if (rc) return rc; s->d_f4 = (uint32_t*)q;
+        return SFMHIP_OK;
+    }
+    s->dim_pad = s->dim <= 32 ? 32 : (s->dim <= 64 ? 64 : round_up(s->dim, 128));   // int8 row bytes: 32, 64 or 128
+    if (s->dim_pad > 128) { s->exact_u8 = 0; return SFMHIP_OK; }    // d^2 <= 128*255^2 < 2^23 keeps the packed keys exact
+    rc = sfm_pool_get(ctx, (size_t)s->rows_pad * s->dim_pad, &q); if (rc) return rc; s->d_i8 = (int8_t*)q;
+    rc = sfm_pool_get(ctx, 2 * (size_t)s->rows_pad * sizeof(int32_t), &q); if (rc) return rc; s->d_norm = (int32_t*)q;
+    return descset_flag_slot(ctx, s);
+}
+
+// the end of a per-image constructor: the set, or nothing after an error
+static int descset_done(sfmhip_descset* s, int rc, sfmhip_descset** out)
+{
+    if (rc != SFMHIP_OK) { sfmhip_descset_destroy(s); return rc; }
+    *out = s;
+    return SFMHIP_OK;
+}
+
+static void descsets_destroy_all(sfmhip_descset** out, int n)
+{
+    for (int i = 0; i < n; ++i) if (out[i]) { sfmhip_descset_destroy(out[i]); out[i] = nullptr; }
 }
 
 // The preparation kernels leave "not every value is an integer in [0, 255]" in the sets' flags; whoever needs the verdict
@@ -1546,22 +1585,25 @@ static int descsets_resolve(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n)
     return SFMHIP_OK;
 }
 
-static int descset_prepare_l2(sfmhip_ctx* ctx, sfmhip_descset* s)
+// rows of the int8 copy that one 4-wave block of the L2 preparation kernels writes: 16 values per lane on the fast path, else 4
+static inline int prep_l2_rows_per_block(bool fast, int dim, int dim_pad) { return 4 * (fast ? 1024 / dim : 256 / dim_pad); }
+
+// (re-)derive the int8 copy, the norms and the flag of a set from its float rows
+static int enqueue_prep_l2(sfmhip_ctx* ctx, sfmhip_descset* s)
 {
-    s->dim_pad = s->dim <= 32 ? 32 : (s->dim <= 64 ? 64 : round_up(s->dim, 128));   // int8 row bytes: 32, 64 or 128
-    const bool mfma_ok = s->dim_pad <= 128;    // d^2 <= 128*255^2 < 2^23 keeps the packed keys exact
-    if (!mfma_ok) { s->exact_u8 = 0; return SFMHIP_OK; }
-    void* q = nullptr;
-    int rc = sfm_pool_get(ctx, (size_t)s->rows_pad * s->dim_pad, &q); if (rc) return rc; s->d_i8 = (int8_t*)q;
-    rc = sfm_pool_get(ctx, 2 * (size_t)s->rows_pad * sizeof(int32_t), &q); if (rc) return rc; s->d_norm = (int32_t*)q;
-    rc = descset_flag_slot(ctx, s); if (rc) return rc;
     SFM_HIP_TRY(ctx, hipMemsetAsync(s->d_flag, 0, sizeof(int), ctx->stream));
-    const int waves_per_block = 4;
     const bool fast = prep_l2_fast(s->d_f32, s->ld, s->dim, s->dim_pad);
-    const int rows_per_wave = fast ? 1024 / s->dim : 256 / s->dim_pad;
-    hipLaunchKernelGGL(prep_l2_kernel, dim3(ceil_div(s->rows_pad, waves_per_block * rows_per_wave)), dim3(64 * waves_per_block), 0, ctx->stream,
+    hipLaunchKernelGGL(prep_l2_kernel, dim3(ceil_div(s->rows_pad, prep_l2_rows_per_block(fast, s->dim, s->dim_pad))), dim3(256), 0, ctx->stream,
                        s->d_f32, s->ld, s->rows, s->dim, s->dim_pad, s->d_i8, s->d_norm, s->d_flag, s->rows_pad, fast ? 1 : 0);
     SFM_HIP_TRY(ctx, hipGetLastError());
+    return SFMHIP_OK;
+}
+
+static int descset_prepare_l2(sfmhip_ctx* ctx, sfmhip_descset* s)
+{
+    int rc = descset_buffers(ctx, s); if (rc) return rc;
+    if (!s->d_i8) return SFMHIP_OK;
+    rc = enqueue_prep_l2(ctx, s); if (rc) return rc;
     s->exact_pending = true;
     return SFMHIP_OK;
 }
@@ -1590,18 +1632,71 @@ static inline bool l2_row_to_u8(const float* __restrict__ src, uint8_t* __restri
     return ok;
 }
 
-static int descset_create_l2_host_f32(sfmhip_ctx* ctx, const float* desc, int rows, int dim, size_t ld, sfmhip_descset** out);
-static void descsets_destroy_all(sfmhip_descset** out, int n)
+// The rows of n host images (w elements each, image i with row stride ld[i], or w without ld) as rows of w bytes, concatenated in
+// one block of `hold`: image i starts at row first[i].  The copy threads of the staging ring produce the bytes on their way into
+// it: visit(image, source rows, their stride, row count, destination) sees every run of rows of one image in a thread's share once.
+template <class T, class Visit>
+static int stage_host_images(sfmhip_ctx* ctx, SfmPoolHold& hold, const T* const* desc, const int32_t* rows, const size_t* ld, int n, int w,
+                             std::vector<long long>& first, uint8_t** d_rows, const Visit& visit)
 {
-    for (int i = 0; i < n; ++i) if (out[i]) { sfmhip_descset_destroy(out[i]); out[i] = nullptr; }
+    first.assign((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) first[i + 1] = first[i] + rows[i];
+    const long long total = first[n];
+    const int rc = hold.get((size_t)std::max<long long>(total, 1) * w, (void**)d_rows); if (rc) return rc;
+    return sfm_upload_produced(ctx, *d_rows, (size_t)total * w, (size_t)w, [&](char* piece, size_t off, size_t nb, int t, int nt) {
+        const long long g0 = (long long)(off / w), cnt = (long long)(nb / w);
+        long long r = g0 + cnt * t / nt;
+        const long long re = g0 + cnt * (t + 1) / nt;
+        int img = (int)(std::upper_bound(first.begin(), first.end(), r) - first.begin()) - 1;
+        while (r < re) {
+            while (r >= first[img + 1]) ++img;
+            const long long run = std::min(re, first[img + 1]) - r;          // rows of this image in the share
+            const size_t l = ld ? ld[img] : (size_t)w;
+            visit(img, desc[img] + (size_t)(r - first[img]) * l, l, run, (uint8_t*)piece + (size_t)(r - g0) * w);
+            r += run;
+        }
+    });
+}
+
+// a table of per-image descriptors to the device (scratch2: consumed by the launches that follow), then launch(table)
+template <class Launch>
+static int launch_with_table(sfmhip_ctx* ctx, const void* table, size_t bytes, const Launch& launch)
+{
+    void* d_tbl = nullptr;
+    const int rc = sfm_scratch2(ctx, bytes, &d_tbl); if (rc) return rc;
+    if (sfm_upload(ctx, d_tbl, table, bytes) != SFMHIP_OK) return SFMHIP_E_HIP;     // (the table is consumed on return)
+    launch(d_tbl);
+    return hip_rc(ctx, hipGetLastError());
+}
+
+// The float way of one image: the rows as they are (dense ones through the pinned staging ring, strided ones with a 2-D copy),
+// verdict and int8 copy from the preparation kernel.  For images with a value that is not an integer in [0, 255] and for dim not in
+// {32, 64, 128}.
+static int descset_create_l2_host_f32(sfmhip_ctx* ctx, const float* desc, int rows, int dim, size_t ld, sfmhip_descset** out)
+{
+    sfmhip_descset* s = descset_new(ctx, SFMHIP_DESC_L2_F32, rows, dim);
+    s->ld = dim; s->owns_f32 = true;
+    void* d = nullptr;
+    int rc = sfm_pool_get(ctx, (size_t)std::max(rows, 1) * dim * sizeof(float), &d);
+    if (rc == SFMHIP_OK) s->d_f32 = (const float*)d;
+    if (rc == SFMHIP_OK && rows > 0 && ld == (size_t)dim)          // a dense cv::Mat (the reference's descriptors)
+        rc = sfm_upload(ctx, d, desc, (size_t)rows * dim * sizeof(float));
+    else if (rc == SFMHIP_OK && rows > 0) {
+        hipError_t e = hipMemcpy2DAsync(d, dim * sizeof(float), desc, ld * sizeof(float), dim * sizeof(float), rows, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // the caller's rows must have been read when this returns
+        rc = hip_rc(ctx, e);
+    }
+    if (rc == SFMHIP_OK) rc = descset_prepare_l2(ctx, s);
+    return descset_done(s, rc, out);
 }
 
 extern "C" {
 
 // Many images from host matrices in one call (the chain of match_features_for_all, NViewReconstuct.cpp:850-871 / :1369):
 // one pass of the staging threads over all rows, one transfer stream, one preparation launch.  Integer-valued rows in [0, 255]
-// (what cv::SIFT emits) cross PCIe as bytes: a quarter of the float rows' size; an image with any other value goes the
-// float way of sfmhip_descset_create_l2_host (and takes the exact kernels later), image by image.
+// (what cv::SIFT emits) cross PCIe as bytes: a quarter of the float rows' size; an image with any other value, and every image
+// whose rows are not 32, 64 or 128 values (the int8 copy then has padding columns), goes the float way (and takes the exact
+// kernels later), image by image.
 int sfmhip_descsets_create_l2_host(sfmhip_ctx* ctx, const float* const* desc, const int32_t* rows, int dim, const size_t* ld, int n, sfmhip_descset** out)
 {
     SFM_DEVICE_GUARD(ctx);
@@ -1610,62 +1705,32 @@ int sfmhip_descsets_create_l2_host(sfmhip_ctx* ctx, const float* const* desc, co
     for (int i = 0; i < n; ++i) { out[i] = nullptr; SFM_ARG_CHECK(ctx, rows[i] >= 0 && (desc[i] || rows[i] == 0) && (!ld || ld[i] >= (size_t)dim)); }
     if (n == 0) return SFMHIP_OK;
     const bool bytes_ok = dim == 32 || dim == 64 || dim == 128;        // the int8 copy has no padding columns and a lane takes 16 values
-    if (!bytes_ok) {
-        for (int i = 0; i < n; ++i) {
-            const int rc = descset_create_l2_host_f32(ctx, desc[i], rows[i], dim, ld ? ld[i] : (size_t)dim, &out[i]);
-            if (rc) { descsets_destroy_all(out, n); return rc; }
-        }
-        return SFMHIP_OK;
-    }
-    std::vector<long long> first((size_t)n + 1, 0);                   // first row of image i in the concatenation of all images
-    for (int i = 0; i < n; ++i) first[i + 1] = first[i] + rows[i];
-    const long long total = first[n];
-    uint8_t* d_u8 = nullptr;
-    { void* q = nullptr; int rc = sfm_pool_get(ctx, (size_t)std::max<long long>(total, 1) * dim, &q); if (rc) return rc; d_u8 = (uint8_t*)q; }
-    std::vector<int> bad((size_t)n, 0);
-    int rc = sfm_upload_produced(ctx, d_u8, (size_t)total * dim, (size_t)dim, [&](char* piece, size_t off, size_t nb, int t, int nt) {
-        const long long g0 = (long long)(off / dim), cnt = (long long)(nb / dim);
-        long long r = g0 + cnt * t / nt;
-        const long long re = g0 + cnt * (t + 1) / nt;
-        int img = (int)(std::upper_bound(first.begin(), first.end(), r) - first.begin()) - 1;
-        for (; r < re; ++r) {
-            while (r >= first[img + 1]) ++img;
-            const float* src = desc[img] + (size_t)(r - first[img]) * (ld ? ld[img] : (size_t)dim);
-            if (!l2_row_to_u8(src, (uint8_t*)piece + (size_t)(r - g0) * dim, dim)) __atomic_store_n(&bad[img], 1, __ATOMIC_RELAXED);
-        }
+    std::vector<int> bad((size_t)n, bytes_ok ? 0 : 1);
+    SfmPoolHold hold(ctx);          // the byte rows: read only by the launch enqueued below (stream-ordered reuse)
+    std::vector<long long> first; uint8_t* d_u8 = nullptr;
+    int rc = SFMHIP_OK;
+    if (bytes_ok) rc = stage_host_images(ctx, hold, desc, rows, ld, n, dim, first, &d_u8, [&](int img, const float* src, size_t l, long long run, uint8_t* dst) {
+        for (long long k = 0; k < run; ++k)
+            if (!l2_row_to_u8(src + (size_t)k * l, dst + (size_t)k * dim, dim)) __atomic_store_n(&bad[img], 1, __ATOMIC_RELAXED);
     });
-    if (rc) { sfm_pool_put(ctx, d_u8); return rc; }
+    if (rc) return rc;
     std::vector<PrepU8Desc> tbl;
     int max_pad = 0;
     for (int i = 0; i < n && rc == SFMHIP_OK; ++i) {
         if (bad[i]) { rc = descset_create_l2_host_f32(ctx, desc[i], rows[i], dim, ld ? ld[i] : (size_t)dim, &out[i]); continue; }
-        sfmhip_descset* s = nullptr;
-        descset_alloc_common(ctx, SFMHIP_DESC_L2_F32, rows[i], dim, &s);
-        out[i] = s;
-        s->dim_pad = dim; s->ld = dim; s->owns_f32 = true; s->exact_u8 = 1; s->exact_pending = false;
+        sfmhip_descset* s = out[i] = descset_new(ctx, SFMHIP_DESC_L2_F32, rows[i], dim);
+        s->ld = dim; s->owns_f32 = true; s->exact_u8 = 1;          // (sfmhip_descset_refresh re-derives the verdict in the set's flag)
         void* q = nullptr;
         rc = sfm_pool_get(ctx, (size_t)std::max(rows[i], 1) * dim * sizeof(float), &q); if (rc) break; s->d_f32 = (float*)q;
-        rc = sfm_pool_get(ctx, (size_t)s->rows_pad * dim, &q); if (rc) break; s->d_i8 = (int8_t*)q;
-        rc = sfm_pool_get(ctx, 2 * (size_t)s->rows_pad * sizeof(int32_t), &q); if (rc) break; s->d_norm = (int32_t*)q;
-        rc = descset_flag_slot(ctx, s); if (rc) break;          // (sfmhip_descset_refresh re-derives the verdict there)
+        rc = descset_buffers(ctx, s); if (rc) break;
         PrepU8Desc d; d.src = d_u8 + (size_t)first[i] * dim; d.rows = rows[i]; d.dim = dim; d.rows_pad = s->rows_pad; d.dst = s->d_i8; d.norm = s->d_norm; d.f32 = (float*)s->d_f32;
         tbl.push_back(d);
         max_pad = std::max(max_pad, s->rows_pad);
     }
-    if (rc == SFMHIP_OK && !tbl.empty()) {
-        void* d_tbl = nullptr;
-        rc = sfm_scratch2(ctx, tbl.size() * sizeof(PrepU8Desc), &d_tbl);
-        if (rc == SFMHIP_OK) {
-            hipError_t e = sfm_upload(ctx, d_tbl, tbl.data(), tbl.size() * sizeof(PrepU8Desc)) == SFMHIP_OK ? hipSuccess : hipErrorUnknown;     // (consumed on return)
-            if (e == hipSuccess) {
-                const int rows_per_block = 4 * (1024 / dim);
-                hipLaunchKernelGGL(prep_l2_u8_batched_kernel, dim3(ceil_div(max_pad, rows_per_block), (unsigned)tbl.size()), dim3(256), 0, ctx->stream, (const PrepU8Desc*)d_tbl);
-                e = hipGetLastError();
-            }
-            if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = SFMHIP_E_HIP; }
-        }
-    }
-    sfm_pool_put(ctx, d_u8);          // read only by the launch just enqueued (stream-ordered reuse)
+    if (rc == SFMHIP_OK && !tbl.empty())
+        rc = launch_with_table(ctx, tbl.data(), tbl.size() * sizeof(PrepU8Desc), [&](const void* d_tbl) {
+            hipLaunchKernelGGL(prep_l2_u8_batched_kernel, dim3(ceil_div(max_pad, prep_l2_rows_per_block(true, dim, dim)), (unsigned)tbl.size()), dim3(256), 0, ctx->stream, (const PrepU8Desc*)d_tbl);
+        });
     if (rc) descsets_destroy_all(out, n);
     return rc;
 }
@@ -1678,56 +1743,28 @@ int sfmhip_descsets_create_hamming2_host(sfmhip_ctx* ctx, const uint8_t* const* 
     SFM_ARG_CHECK(ctx, ctx && out && (n == 0 || (desc && rows)) && n >= 0 && nbytes > 0 && nbytes <= 64);
     for (int i = 0; i < n; ++i) { out[i] = nullptr; SFM_ARG_CHECK(ctx, rows[i] >= 0 && (desc[i] || rows[i] == 0) && (!ld || ld[i] >= (size_t)nbytes)); }
     if (n == 0) return SFMHIP_OK;
-    std::vector<long long> first((size_t)n + 1, 0);
-    for (int i = 0; i < n; ++i) first[i + 1] = first[i] + rows[i];
-    const long long total = first[n];
-    uint8_t* d_u8 = nullptr;
-    { void* q = nullptr; int rc = sfm_pool_get(ctx, (size_t)std::max<long long>(total, 1) * nbytes, &q); if (rc) return rc; d_u8 = (uint8_t*)q; }
-    int rc = sfm_upload_produced(ctx, d_u8, (size_t)total * nbytes, (size_t)nbytes, [&](char* piece, size_t off, size_t nb, int t, int nt) {
-        const long long g0 = (long long)(off / nbytes), cnt = (long long)(nb / nbytes);
-        long long r = g0 + cnt * t / nt;
-        const long long re = g0 + cnt * (t + 1) / nt;
-        int img = (int)(std::upper_bound(first.begin(), first.end(), r) - first.begin()) - 1;
-        while (r < re) {
-            while (r >= first[img + 1]) ++img;
-            const long long run = std::min(re, first[img + 1]) - r;          // rows of this image in the share
-            const size_t l = ld ? ld[img] : (size_t)nbytes;
-            const uint8_t* src = desc[img] + (size_t)(r - first[img]) * l;
-            uint8_t* dst = (uint8_t*)piece + (size_t)(r - g0) * nbytes;
-            if (l == (size_t)nbytes) memcpy(dst, src, (size_t)run * nbytes);
-            else for (long long k = 0; k < run; ++k) memcpy(dst + (size_t)k * nbytes, src + (size_t)k * l, (size_t)nbytes);
-            r += run;
-        }
+    SfmPoolHold hold(ctx);          // the byte rows: read only by the launches enqueued below (stream-ordered reuse)
+    std::vector<long long> first; uint8_t* d_u8 = nullptr;
+    int rc = stage_host_images(ctx, hold, desc, rows, ld, n, nbytes, first, &d_u8, [&](int, const uint8_t* src, size_t l, long long run, uint8_t* dst) {
+        if (l == (size_t)nbytes) memcpy(dst, src, (size_t)run * nbytes);          // a dense image: its run in one piece
+        else for (long long k = 0; k < run; ++k) memcpy(dst + (size_t)k * nbytes, src + (size_t)k * l, (size_t)nbytes);
     });
-    if (rc) { sfm_pool_put(ctx, d_u8); return rc; }
+    if (rc) return rc;
     std::vector<PrepHamDesc> tbl((size_t)n);
-    int max_pad = 0; bool any_f4 = false;
+    int max_pad = 0;
     for (int i = 0; i < n && rc == SFMHIP_OK; ++i) {
-        sfmhip_descset* s = nullptr;
-        descset_alloc_common(ctx, SFMHIP_DESC_HAMMING2_U8, rows[i], nbytes, &s);
-        out[i] = s;
-        void* q = nullptr;
-        rc = sfm_pool_get(ctx, (size_t)s->rows_pad * 64, &q); if (rc) break; s->d_u32 = (uint32_t*)q;
-        if (nbytes <= H4_MAX_NBYTES) { rc = sfm_pool_get(ctx, (size_t)s->rows_pad * H4_ROW_BYTES, &q); if (rc) break; s->d_f4 = (uint32_t*)q; any_f4 = true; }
+        sfmhip_descset* s = out[i] = descset_new(ctx, SFMHIP_DESC_HAMMING2_U8, rows[i], nbytes);
+        rc = descset_buffers(ctx, s); if (rc) break;
         PrepHamDesc& d = tbl[i];
         d.src = d_u8 + (size_t)first[i] * nbytes; d.ld = (size_t)nbytes; d.rows = rows[i]; d.nbytes = nbytes; d.rows_pad = s->rows_pad; d.u32 = s->d_u32; d.f4 = s->d_f4;
         max_pad = std::max(max_pad, s->rows_pad);
     }
-    if (rc == SFMHIP_OK) {
-        void* d_tbl = nullptr;
-        rc = sfm_scratch2(ctx, tbl.size() * sizeof(PrepHamDesc), &d_tbl);
-        if (rc == SFMHIP_OK) {
-            hipError_t e = sfm_upload(ctx, d_tbl, tbl.data(), tbl.size() * sizeof(PrepHamDesc)) == SFMHIP_OK ? hipSuccess : hipErrorUnknown;
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(prep_hamming_batched_kernel, dim3((unsigned)(((size_t)max_pad * 8 + 255) / 256), (unsigned)n), dim3(256), 0, ctx->stream, (const PrepHamDesc*)d_tbl);
-                if (any_f4)
-                    hipLaunchKernelGGL(prep_hamming_fp4_batched_kernel, dim3((unsigned)(((size_t)max_pad * 96 + 255) / 256), (unsigned)n), dim3(256), 0, ctx->stream, (const PrepHamDesc*)d_tbl);
-                e = hipGetLastError();
-            }
-            if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = SFMHIP_E_HIP; }
-        }
-    }
-    sfm_pool_put(ctx, d_u8);
+    if (rc == SFMHIP_OK)
+        rc = launch_with_table(ctx, tbl.data(), tbl.size() * sizeof(PrepHamDesc), [&](const void* d_tbl) {
+            hipLaunchKernelGGL(prep_hamming_batched_kernel, dim3((unsigned)(((size_t)max_pad * 8 + 255) / 256), (unsigned)n), dim3(256), 0, ctx->stream, (const PrepHamDesc*)d_tbl);
+            if (nbytes <= H4_MAX_NBYTES)
+                hipLaunchKernelGGL(prep_hamming_fp4_batched_kernel, dim3((unsigned)(((size_t)max_pad * 96 + 255) / 256), (unsigned)n), dim3(256), 0, ctx->stream, (const PrepHamDesc*)d_tbl);
+        });
     if (rc) descsets_destroy_all(out, n);
     return rc;
 }
@@ -1737,67 +1774,15 @@ int sfmhip_descset_create_l2_dev(sfmhip_ctx* ctx, const float* d_desc, int rows,
     SFM_DEVICE_GUARD(ctx);
     SFM_ARG_CHECK(ctx, ctx && out);
     SFM_ARG_CHECK(ctx, d_desc && rows >= 0 && dim > 0 && ld >= (size_t)dim);
-    sfmhip_descset* s = nullptr;
-    descset_alloc_common(ctx, SFMHIP_DESC_L2_F32, rows, dim, &s);
+    sfmhip_descset* s = descset_new(ctx, SFMHIP_DESC_L2_F32, rows, dim);
     s->d_f32 = d_desc; s->ld = ld; s->owns_f32 = false;
-    const int rc = descset_prepare_l2(ctx, s);
-    if (rc != SFMHIP_OK) { sfmhip_descset_destroy(s); return rc; }
-    *out = s;
-    return SFMHIP_OK;
+    return descset_done(s, descset_prepare_l2(ctx, s), out);
 }
 
+// one image from host rows: the batch of one (which checks the arguments)
 int sfmhip_descset_create_l2_host(sfmhip_ctx* ctx, const float* desc, int rows, int dim, size_t ld, sfmhip_descset** out)
 {
-    SFM_DEVICE_GUARD(ctx);
-    SFM_ARG_CHECK(ctx, ctx && out);
-    SFM_ARG_CHECK(ctx, (desc || rows == 0) && rows >= 0 && dim > 0 && ld >= (size_t)dim);
-    // integer-valued rows cross PCIe as bytes (sfmhip_descsets_create_l2_host); anything else as floats (below)
-    if (dim == 32 || dim == 64 || dim == 128) return sfmhip_descsets_create_l2_host(ctx, &desc, &rows, dim, &ld, 1, out);
-    return descset_create_l2_host_f32(ctx, desc, rows, dim, ld, out);
-}
-
-}  // extern "C"
-
-static int descset_create_l2_host_f32(sfmhip_ctx* ctx, const float* desc, int rows, int dim, size_t ld, sfmhip_descset** out)
-{
-    float* d = nullptr;
-    const size_t nrow = rows > 0 ? rows : 1;
-    { void* q = nullptr; int rc = sfm_pool_get(ctx, nrow * dim * sizeof(float), &q); if (rc) return rc; d = (float*)q; }
-    if (rows > 0 && ld == (size_t)dim) {          // a dense cv::Mat (the reference's descriptors): through the pinned staging ring
-        const int rc = sfm_upload(ctx, d, desc, (size_t)rows * dim * sizeof(float));
-        if (rc) { sfm_pool_put(ctx, d); return rc; }
-    } else if (rows > 0) {
-        hipError_t e = hipMemcpy2DAsync(d, dim * sizeof(float), desc, ld * sizeof(float), dim * sizeof(float), rows,
-                                        hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // the caller's rows must have been read when this returns
-        if (e != hipSuccess) { sfm_pool_put(ctx, d); ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    }
-    sfmhip_descset* s = nullptr;
-    descset_alloc_common(ctx, SFMHIP_DESC_L2_F32, rows, dim, &s);
-    s->d_f32 = d; s->ld = dim; s->owns_f32 = true;
-    const int rc = descset_prepare_l2(ctx, s);
-    if (rc != SFMHIP_OK) { sfmhip_descset_destroy(s); return rc; }
-    *out = s;
-    return SFMHIP_OK;
-}
-
-extern "C" {
-
-static int descset_prepare_hamming(sfmhip_ctx* ctx, sfmhip_descset* s, const uint8_t* d_src, size_t ld)
-{
-    { void* q = nullptr; int rc = sfm_pool_get(ctx, (size_t)s->rows_pad * 64, &q); if (rc) return rc; s->d_u32 = (uint32_t*)q; }
-    const size_t n = (size_t)s->rows_pad * 64;
-    hipLaunchKernelGGL(prep_hamming_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, ctx->stream,
-                       d_src, ld, s->rows, s->dim, (uint32_t*)s->d_u32, s->rows_pad);
-    SFM_HIP_TRY(ctx, hipGetLastError());
-    if (s->dim <= H4_MAX_NBYTES) {
-        { void* q = nullptr; int rc = sfm_pool_get(ctx, (size_t)s->rows_pad * H4_ROW_BYTES, &q); if (rc) return rc; s->d_f4 = (uint32_t*)q; }
-        const size_t nw = (size_t)s->rows_pad * (H4_ROW_BYTES / 4);
-        hipLaunchKernelGGL(prep_hamming_fp4_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, ctx->stream,
-                           d_src, ld, s->rows, s->dim, s->d_f4, s->rows_pad);
-        SFM_HIP_TRY(ctx, hipGetLastError());
-    }
-    return SFMHIP_OK;
+    return sfmhip_descsets_create_l2_host(ctx, &desc, &rows, dim, &ld, 1, out);
 }
 
 int sfmhip_descset_create_hamming2_dev(sfmhip_ctx* ctx, const uint8_t* d_desc, int rows, int nbytes, size_t ld, sfmhip_descset** out)
@@ -1805,37 +1790,26 @@ int sfmhip_descset_create_hamming2_dev(sfmhip_ctx* ctx, const uint8_t* d_desc, i
     SFM_DEVICE_GUARD(ctx);
     SFM_ARG_CHECK(ctx, ctx && out);
     SFM_ARG_CHECK(ctx, d_desc && rows >= 0 && nbytes > 0 && nbytes <= 64 && ld >= (size_t)nbytes);
-    sfmhip_descset* s = nullptr;
-    descset_alloc_common(ctx, SFMHIP_DESC_HAMMING2_U8, rows, nbytes, &s);
-    const int rc = descset_prepare_hamming(ctx, s, d_desc, ld);
-    if (rc != SFMHIP_OK) { sfmhip_descset_destroy(s); return rc; }
-    *out = s;
-    return SFMHIP_OK;
+    sfmhip_descset* s = descset_new(ctx, SFMHIP_DESC_HAMMING2_U8, rows, nbytes);
+    int rc = descset_buffers(ctx, s);
+    if (rc == SFMHIP_OK) {
+        const size_t n = (size_t)s->rows_pad * 64;
+        hipLaunchKernelGGL(prep_hamming_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, ctx->stream,
+                           d_desc, ld, s->rows, s->dim, (uint32_t*)s->d_u32, s->rows_pad);
+        rc = hip_rc(ctx, hipGetLastError());
+    }
+    if (rc == SFMHIP_OK && s->d_f4) {
+        const size_t nw = (size_t)s->rows_pad * (H4_ROW_BYTES / 4);
+        hipLaunchKernelGGL(prep_hamming_fp4_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, ctx->stream,
+                           d_desc, ld, s->rows, s->dim, s->d_f4, s->rows_pad);
+        rc = hip_rc(ctx, hipGetLastError());
+    }
+    return descset_done(s, rc, out);
 }
 
 int sfmhip_descset_create_hamming2_host(sfmhip_ctx* ctx, const uint8_t* desc, int rows, int nbytes, size_t ld, sfmhip_descset** out)
 {
-    SFM_DEVICE_GUARD(ctx);
-    SFM_ARG_CHECK(ctx, ctx && out);
-    SFM_ARG_CHECK(ctx, (desc || rows == 0) && rows >= 0 && nbytes > 0 && nbytes <= 64 && ld >= (size_t)nbytes);
-    uint8_t* d = nullptr;
-    const size_t nrow = rows > 0 ? rows : 1;
-    { void* q = nullptr; int rc = sfm_pool_get(ctx, nrow * nbytes, &q); if (rc) return rc; d = (uint8_t*)q; }
-    if (rows > 0 && ld == (size_t)nbytes) {
-        const int rc = sfm_upload(ctx, d, desc, (size_t)rows * nbytes);
-        if (rc) { sfm_pool_put(ctx, d); return rc; }
-    } else if (rows > 0) {
-        hipError_t e = hipMemcpy2DAsync(d, nbytes, desc, ld, nbytes, rows, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { sfm_pool_put(ctx, d); ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    }
-    sfmhip_descset* s = nullptr;
-    descset_alloc_common(ctx, SFMHIP_DESC_HAMMING2_U8, rows, nbytes, &s);
-    int rc = descset_prepare_hamming(ctx, s, d, nbytes);
-    sfm_pool_put(ctx, d);          // the byte rows are only read by the re-encoding kernel just enqueued (stream-ordered reuse)
-    if (rc != SFMHIP_OK) { sfmhip_descset_destroy(s); return rc; }
-    *out = s;
-    return SFMHIP_OK;
+    return sfmhip_descsets_create_hamming2_host(ctx, &desc, &rows, nbytes, &ld, 1, out);
 }
 
 void sfmhip_descset_destroy(sfmhip_descset* s)
@@ -1859,14 +1833,8 @@ int sfmhip_descset_refresh(sfmhip_descset* s)
 {
     SFM_DEVICE_GUARD(s ? s->ctx : nullptr);
     if (!s || !s->ctx) return SFMHIP_E_ARG;
-    sfmhip_ctx* ctx = s->ctx;
     if (s->kind != SFMHIP_DESC_L2_F32 || !s->d_i8) return SFMHIP_OK;
-    SFM_HIP_TRY(ctx, hipMemsetAsync(s->d_flag, 0, sizeof(int), ctx->stream));
-    const bool fast = prep_l2_fast(s->d_f32, s->ld, s->dim, s->dim_pad);
-    hipLaunchKernelGGL(prep_l2_kernel, dim3(ceil_div(s->rows_pad, 4 * (fast ? 1024 / s->dim : 256 / s->dim_pad))), dim3(256), 0, ctx->stream,
-                       s->d_f32, s->ld, s->rows, s->dim, s->dim_pad, s->d_i8, s->d_norm, s->d_flag, s->rows_pad, fast ? 1 : 0);
-    SFM_HIP_TRY(ctx, hipGetLastError());
-    return SFMHIP_OK;
+    return enqueue_prep_l2(s->ctx, s);
 }
 
 // one launch for many images: what a per-frame "descriptors arrived" step costs when the float rows were rewritten
@@ -1892,8 +1860,8 @@ int sfmhip_descsets_refresh(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n)
     void* d_tbl = nullptr;
     int rc = sfm_scratch2(ctx, tbl.size() * sizeof(PrepDesc), &d_tbl); if (rc) return rc;
     SFM_HIP_TRY(ctx, hipMemcpyAsync(d_tbl, tbl.data(), tbl.size() * sizeof(PrepDesc), hipMemcpyHostToDevice, ctx->stream));
-    // rows per 4-wave block: the smallest over the batch (16 values per lane when every image qualifies, else 4: >= 2 rows per wave)
-    for (const PrepDesc& d : tbl) { const int r = 4 * (fast ? 1024 / d.dim : 256 / d.dim_pad); if (r < rows_per_block) rows_per_block = r; }
+    // rows per block: the smallest over the batch (16 values per lane when every image qualifies, else 4: >= 2 rows per wave)
+    for (const PrepDesc& d : tbl) rows_per_block = std::min(rows_per_block, prep_l2_rows_per_block(fast, d.dim, d.dim_pad));
     hipLaunchKernelGGL(prep_l2_batched_kernel, dim3(ceil_div(max_pad, rows_per_block), (unsigned)tbl.size()), dim3(256), 0, ctx->stream, (const PrepDesc*)d_tbl, fast ? 1 : 0);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;
@@ -1915,13 +1883,39 @@ int sfmhip_descset_info(sfmhip_descset* s, int* kind, int* rows, int* dim, int* 
 // ------------------------------------------------------------------------------------------------
 // batched kNN-2 driver
 // ------------------------------------------------------------------------------------------------
+// The four kernels a launch sequence can run on; the values are the force_path arguments of sfmhip.h (0: chosen here).
+enum KnnPathId { KNN_AUTO = 0, KNN_EXACT_F32 = 1, KNN_I8 = 2, KNN_HAMMING_VALU = 3, KNN_HAMMING_FP4 = 4 };
+// what the planner and the launch sequence need to know about a path's kernel
+struct KnnPath {
+    int qgran;               // query rows per workgroup
+    int block_rows;          // train rows per staged block: chunks are whole blocks
+    int max_chunk_rows;      // train rows a chunk may hold (the tile index in the packed keys: 7 bits, 8 on the FP4 path)
+    bool pow2_chunks;        // chunks are aligned power-of-two windows (the FP4 kernel's tile index is (row >> 5) & 255)
+    bool fused_reverse;      // a mutual form of the kernel also finds the nearest query of every train row (else: a second, swapped kNN-2)
+    int merge_mode;          // what its keys hold: MODE of merge_kernel and rev_finalize_kernel
+};
+static const KnnPath KNN_PATHS[5] = {
+    { 0, 0, 0, false, false, 0 },
+    { 4, 128, 4096, false, false, 1 },                          // KNN_EXACT_F32
+    { 128, KNN_STAGE_ROWS, 4096, false, true, 0 },              // KNN_I8
+    { 256, 128, 4096, false, false, 2 },                        // KNN_HAMMING_VALU
+    { 64 * H4_WAVES, 128, 8192, true, true, 2 },                // KNN_HAMMING_FP4
+};
+
 struct KnnPlan {
     std::vector<PairDesc> pd;
     long long part_entries = 0, list_entries = 0, out_rows = 0;
     int max_qpad = 0, max_chunks = 0, max_nq = 0;
-    int path = 0;    // 1 exact f32, 2 int8 mfma, 3 hamming (VALU), 4 hamming (FP4 MFMA)
+    KnnPathId path = KNN_AUTO;
     int ks = 0, dim = 0;
     bool aligned = true;
+};
+
+// the sets and the pair list of a call on one (query, train) pair
+struct OnePair {
+    sfmhip_descset* sets[2];
+    int32_t pairs[2] = { 0, 1 };
+    OnePair(const sfmhip_descset* q, const sfmhip_descset* t) : sets{ const_cast<sfmhip_descset*>(q), const_cast<sfmhip_descset*>(t) } {}
 };
 
 static int plan_pairs(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, const int32_t* pairs, int n_pairs,
@@ -1941,19 +1935,19 @@ static int plan_pairs(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, 
     P.dim = dim;
     if (kind == SFMHIP_DESC_HAMMING2_U8) {
         // the matrix-core kernel whenever the rows fit its 768-value encoding (nbytes <= 61: AKAZE's 61-byte rows do)
-        SFM_ARG_CHECK(ctx, force_path == 0 || force_path == 3 || (force_path == 4 && dim <= H4_MAX_NBYTES));
-        P.path = (force_path == 3 || dim > H4_MAX_NBYTES) ? 3 : 4;
+        SFM_ARG_CHECK(ctx, force_path == KNN_AUTO || force_path == KNN_HAMMING_VALU || (force_path == KNN_HAMMING_FP4 && dim <= H4_MAX_NBYTES));
+        P.path = (force_path == KNN_HAMMING_VALU || dim > H4_MAX_NBYTES) ? KNN_HAMMING_VALU : KNN_HAMMING_FP4;
     } else {
-        SFM_ARG_CHECK(ctx, force_path >= 0 && force_path <= 2);
-        if (force_path == 2) { SFM_ARG_CHECK(ctx, all_exact); P.path = 2; }
-        else if (force_path == 1) P.path = 1;
-        else P.path = all_exact ? 2 : 1;
+        SFM_ARG_CHECK(ctx, force_path == KNN_AUTO || force_path == KNN_EXACT_F32 || force_path == KNN_I8);
+        if (force_path == KNN_I8) { SFM_ARG_CHECK(ctx, all_exact); P.path = KNN_I8; }
+        else if (force_path == KNN_EXACT_F32) P.path = KNN_EXACT_F32;
+        else P.path = all_exact ? KNN_I8 : KNN_EXACT_F32;
         P.ks = sets[pairs[0]]->dim_pad / 32;
     }
-    // chunking: enough workgroups to fill the chip, chunks of whole 128-row blocks, <= 4096 rows (7-bit tile index)
+    const KnnPath& K = KNN_PATHS[P.path];
+    // chunking: enough workgroups to fill the chip, chunks of whole staged blocks, at most max_chunk_rows rows
     long long qblocks_total = 0;
-    const int qgran = (P.path == 4) ? 64 * H4_WAVES : (P.path == 3 ? 256 : (P.path == 1 ? 4 : 128));
-    for (int p = 0; p < n_pairs; ++p) qblocks_total += ceil_div(sets[pairs[2 * p]]->rows_pad, qgran);
+    for (int p = 0; p < n_pairs; ++p) qblocks_total += ceil_div(sets[pairs[2 * p]]->rows_pad, K.qgran);
     const long long target_wgs = 4LL * ctx->num_cus;
     P.pd.resize(n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
@@ -1961,19 +1955,19 @@ static int plan_pairs(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, 
         PairDesc& d = P.pd[p];
         memset(&d, 0, sizeof d);
         d.nq = q->rows; d.nt = t->rows; d.nq_pad = q->rows_pad; d.nt_pad = t->rows_pad; d.dim = dim;
-        if (P.path == 3) { d.q = q->d_u32; d.t = t->d_u32; }
-        else if (P.path == 4) { d.q = q->d_f4; d.t = t->d_f4; }
+        if (P.path == KNN_HAMMING_VALU) { d.q = q->d_u32; d.t = t->d_u32; }
+        else if (P.path == KNN_HAMMING_FP4) { d.q = q->d_f4; d.t = t->d_f4; }
         else { d.q = q->d_i8; d.t = t->d_i8; d.qn = q->d_norm; d.tn = t->d_norm + t->rows_pad; d.qf = q->d_f32; d.tf = t->d_f32; d.ldq = q->ld; d.ldt = t->ld; }
-        const int brows = (P.path == 2) ? KNN_STAGE_ROWS : 128;               // rows per staged block of the kernel that runs
-        const int tblocks = d.nt_pad / brows, max_cb = (P.path == 4 ? 8192 : 4096) / brows;   // <= 4096 train rows per chunk (7-bit tile index; 8 bits on path 4)
+        const int brows = K.block_rows;
+        const int tblocks = d.nt_pad / brows, max_cb = K.max_chunk_rows / brows;
         int nch = (int)((target_wgs + qblocks_total - 1) / (qblocks_total > 0 ? qblocks_total : 1));
-        if (P.path == 1) nch = 1 > nch ? 1 : (nch > 8 ? 8 : nch);
+        if (P.path == KNN_EXACT_F32) nch = 1 > nch ? 1 : (nch > 8 ? 8 : nch);
         if (nch < 1) nch = 1;
         if (nch > tblocks) nch = tblocks;
         if (nch < ceil_div(tblocks, max_cb)) nch = ceil_div(tblocks, max_cb);
         int cb = ceil_div(tblocks, nch);      // balanced chunks
-        if (P.path == 4) {          // power-of-two chunks (aligned windows of <= 8192 rows: the tile index in the rows is (row >> 5) & 255)
-            int c2 = 2; while (c2 < cb && c2 * 2 * brows <= 8192) c2 *= 2;
+        if (K.pow2_chunks) {
+            int c2 = 2; while (c2 < cb && c2 * 2 * brows <= K.max_chunk_rows) c2 *= 2;
             cb = c2;
         }
         nch = ceil_div(tblocks, cb);
@@ -1984,7 +1978,7 @@ static int plan_pairs(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, 
         if (d.nq_pad > P.max_qpad) P.max_qpad = d.nq_pad;
         if (d.nq > P.max_nq) P.max_nq = d.nq;
         if (nch > P.max_chunks) P.max_chunks = nch;
-        if (P.path != 3) {
+        if (P.path != KNN_HAMMING_VALU) {
             if ((d.ldq % 4) || (d.ldt % 4) || ((uintptr_t)d.qf % 16) || ((uintptr_t)d.tf % 16)) P.aligned = false;
         }
     }
@@ -2012,16 +2006,17 @@ static int knn_workspace(sfmhip_ctx* ctx, const KnnPlan& P, int n_pairs, KnnWork
     return SFMHIP_OK;
 }
 
-template <bool ALIGNED>
-static void launch_exact(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& W, int n_pairs, bool use_list)
+// the exact fp32 kernel on the plan's pairs: every query row, or (use_list) the rows listed for a re-score; STORE_ALL: every distance to d_dist
+template <bool ALIGNED, bool STORE_ALL>
+static void launch_exact(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& W, int n_pairs, bool use_list, float* d_dist = nullptr, size_t ld = 0)
 {
     constexpr int QR = 4;
     int gx = ceil_div(P.max_nq > 0 ? P.max_nq : 1, QR);
     if (use_list && gx > 8) gx = 8;          // the re-score list is normally empty: a few blocks per (chunk, pair) loop over it
     const dim3 grid(gx, P.max_chunks, n_pairs);
     const size_t shm = (size_t)QR * P.dim * sizeof(float);
-    hipLaunchKernelGGL((knn2_exact_f32_kernel<QR, ALIGNED, false>), grid, dim3(256), shm, ctx->stream,
-                       W.d_pd, W.d_part, use_list ? W.d_list : (const int*)nullptr, W.d_count, (float*)nullptr, (size_t)0);
+    hipLaunchKernelGGL((knn2_exact_f32_kernel<QR, ALIGNED, STORE_ALL>), grid, dim3(256), shm, ctx->stream,
+                       W.d_pd, W.d_part, use_list ? W.d_list : (const int*)nullptr, W.d_count, d_dist, ld);
 }
 
 // the fused reverse pass of the int8 and FP4 paths: rev keys (one per train row of every pair), their per-pair offsets, re-score list
@@ -2030,7 +2025,7 @@ struct RevArgs { unsigned long long* keys; const long long* d_off; int2* list; i
 static void rev_finalize(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& W, int n_pairs, const RevArgs& R)
 {
     const dim3 grid(ceil_div(R.max_nt > 0 ? R.max_nt : 1, 256), n_pairs);
-    if (P.path == 4) {
+    if (KNN_PATHS[P.path].merge_mode == 2) {
         hipLaunchKernelGGL(rev_finalize_kernel<2>, grid, dim3(256), 0, ctx->stream, W.d_pd, R.d_off, R.keys, R.rev_idx, R.rev_dist, R.list, R.count);
         return;
     }
@@ -2047,8 +2042,8 @@ static void launch_knn2_i8(sfmhip_ctx* ctx, const dim3& grid, const KnnWork& W, 
     else hipLaunchKernelGGL(knn2_i8_kernel<KS>, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, n_pairs);
 }
 
-// enqueue the kNN-2 of all pairs; results in d_idx2 / d_dist2 (rows concatenated in pair order).  rev != nullptr (int8 path only):
-// the mutual kernel also leaves the nearest query of every train row in rev->rev_idx / rev_dist (int8 and FP4 paths).
+// enqueue the kNN-2 of all pairs; results in d_idx2 / d_dist2 (rows concatenated in pair order).  rev != nullptr (paths with a
+// fused reverse only): the mutual kernel also leaves the nearest query of every train row in rev->rev_idx / rev_dist.
 static int knn2_pairs_enqueue(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& W, int n_pairs, int32_t* d_idx2, float* d_dist2,
                               const RevArgs* rev = nullptr)
 {
@@ -2056,41 +2051,44 @@ static int knn2_pairs_enqueue(sfmhip_ctx* ctx, const KnnPlan& P, const KnnWork& 
         if (rev) { rev_finalize(ctx, P, W, n_pairs, *rev); SFM_HIP_TRY(ctx, hipGetLastError()); }
         return SFMHIP_OK;
     }
-    const dim3 mgrid(ceil_div(P.max_nq, 256), n_pairs);
+    const KnnPath& K = KNN_PATHS[P.path];
     hipEvent_t* tev = (ctx->timing && ctx->timing_used < sfmhip_ctx::TIMING_SLOTS) ? ctx->tev[ctx->timing_used++] : nullptr;
     if (tev) (void)hipEventRecord(tev[0], ctx->stream);
-    if (P.path == 2) {
-        const dim3 grid(P.max_qpad / 128, P.max_chunks, round_up(n_pairs, 8));       // z padded: see the kernel's XCD mapping
-        switch (P.ks) {
-            case 1: launch_knn2_i8<1>(ctx, grid, W, n_pairs, rev); break;
-            case 2: launch_knn2_i8<2>(ctx, grid, W, n_pairs, rev); break;
-            case 4: launch_knn2_i8<4>(ctx, grid, W, n_pairs, rev); break;
-            default: ctx->last_error = "int8 path: dim > 128"; return SFMHIP_E_ARG;
-        }
-        SFM_HIP_TRY(ctx, hipGetLastError());
-        if (tev) (void)hipEventRecord(tev[1], ctx->stream);
+    // the path's kernel: partial top-2 of every (query block, chunk); z padded on the matrix-core kernels: see their XCD mapping
+    const dim3 grid(ceil_div(P.max_qpad, K.qgran), P.max_chunks, K.fused_reverse ? round_up(n_pairs, 8) : n_pairs);
+    switch (P.path) {
+        case KNN_I8:
+            switch (P.ks) {
+                case 1: launch_knn2_i8<1>(ctx, grid, W, n_pairs, rev); break;
+                case 2: launch_knn2_i8<2>(ctx, grid, W, n_pairs, rev); break;
+                case 4: launch_knn2_i8<4>(ctx, grid, W, n_pairs, rev); break;
+                default: ctx->last_error = "int8 path: dim > 128"; return SFMHIP_E_ARG;
+            }
+            SFM_HIP_TRY(ctx, hipGetLastError());
+            break;
+        case KNN_EXACT_F32:
+            if (P.aligned) launch_exact<true, false>(ctx, P, W, n_pairs, false); else launch_exact<false, false>(ctx, P, W, n_pairs, false);
+            break;
+        case KNN_HAMMING_FP4:
+            if (rev) hipLaunchKernelGGL(knn2_hamming2_fp4_mutual_kernel<H4_WAVES>, grid, dim3(64 * H4_WAVES), 0, ctx->stream, W.d_pd, W.d_part, n_pairs, rev->keys, rev->d_off);
+            else hipLaunchKernelGGL(knn2_hamming2_fp4_kernel<H4_WAVES>, grid, dim3(64 * H4_WAVES), 0, ctx->stream, W.d_pd, W.d_part, n_pairs);
+            break;
+        default:
+            hipLaunchKernelGGL(knn2_hamming2_kernel, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part);
+    }
+    if (tev) (void)hipEventRecord(tev[1], ctx->stream);
+    // the chunks' partial results into idx2 / dist2
+    const dim3 mgrid(ceil_div(P.max_nq, 256), n_pairs);
+    if (K.merge_mode == 0) {
         hipLaunchKernelGGL(merge_kernel<0>, mgrid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, d_idx2, d_dist2, W.d_list, W.d_count, 0);
         // rows whose float distances may tie although the integers differ: exact re-score (normally none)
-        if (P.aligned) launch_exact<true>(ctx, P, W, n_pairs, true); else launch_exact<false>(ctx, P, W, n_pairs, true);
+        if (P.aligned) launch_exact<true, false>(ctx, P, W, n_pairs, true); else launch_exact<false, false>(ctx, P, W, n_pairs, true);
         hipLaunchKernelGGL(merge_kernel<1>, mgrid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, d_idx2, d_dist2, W.d_list, W.d_count, 1);
-        if (rev) rev_finalize(ctx, P, W, n_pairs, *rev);
-    } else if (P.path == 1) {
-        if (P.aligned) launch_exact<true>(ctx, P, W, n_pairs, false); else launch_exact<false>(ctx, P, W, n_pairs, false);
-        if (tev) (void)hipEventRecord(tev[1], ctx->stream);
+    } else if (K.merge_mode == 1)
         hipLaunchKernelGGL(merge_kernel<1>, mgrid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, d_idx2, d_dist2, (int*)nullptr, W.d_count, 0);
-    } else if (P.path == 4) {
-        const dim3 grid(ceil_div(P.max_qpad, 64 * H4_WAVES), P.max_chunks, round_up(n_pairs, 8));
-        if (rev) hipLaunchKernelGGL(knn2_hamming2_fp4_mutual_kernel<H4_WAVES>, grid, dim3(64 * H4_WAVES), 0, ctx->stream, W.d_pd, W.d_part, n_pairs, rev->keys, rev->d_off);
-        else hipLaunchKernelGGL(knn2_hamming2_fp4_kernel<H4_WAVES>, grid, dim3(64 * H4_WAVES), 0, ctx->stream, W.d_pd, W.d_part, n_pairs);
-        if (tev) (void)hipEventRecord(tev[1], ctx->stream);
+    else
         hipLaunchKernelGGL(merge_kernel<2>, mgrid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, d_idx2, d_dist2, (int*)nullptr, W.d_count, 0);
-        if (rev) rev_finalize(ctx, P, W, n_pairs, *rev);
-    } else {
-        const dim3 grid(ceil_div(P.max_qpad, 256), P.max_chunks, n_pairs);
-        hipLaunchKernelGGL(knn2_hamming2_kernel, grid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part);
-        if (tev) (void)hipEventRecord(tev[1], ctx->stream);
-        hipLaunchKernelGGL(merge_kernel<2>, mgrid, dim3(256), 0, ctx->stream, W.d_pd, W.d_part, d_idx2, d_dist2, (int*)nullptr, W.d_count, 0);
-    }
+    if (rev) rev_finalize(ctx, P, W, n_pairs, *rev);
     if (tev) (void)hipEventRecord(tev[2], ctx->stream);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;
@@ -2104,10 +2102,9 @@ int sfmhip_knn2_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const sfmhip_d
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_knn2_dev");
     SFM_ARG_CHECK(ctx, ctx && query && train && d_idx2 && d_dist2);
-    sfmhip_descset* sets[2] = { (sfmhip_descset*)query, (sfmhip_descset*)train };
-    const int32_t pr[2] = { 0, 1 };
+    const OnePair one(query, train);
     KnnPlan P; KnnWork W;
-    int rc = plan_pairs(ctx, sets, 2, pr, 1, force_path, P); if (rc) return rc;
+    int rc = plan_pairs(ctx, one.sets, 2, one.pairs, 1, force_path, P); if (rc) return rc;
     rc = knn_workspace(ctx, P, 1, W); if (rc) return rc;
     return knn2_pairs_enqueue(ctx, P, W, 1, d_idx2, d_dist2);
 }
@@ -2115,7 +2112,7 @@ int sfmhip_knn2_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const sfmhip_d
 }  // extern "C"
 
 // Forward kNN-2 (d_idx2 / d_dist2) and the reverse best of every train row (d_rev_idx / d_rev_dist at rev_off[p] + train row) of all
-// pairs.  The int8 and FP4 Hamming2 paths find the reverse best inside their kNN kernels (knn2_i8_mutual_kernel,
+// pairs.  The paths with a fused reverse (int8, FP4 Hamming2) find the reverse best inside their kNN kernels (knn2_i8_mutual_kernel,
 // knn2_hamming2_fp4_mutual_kernel); the exact fp32 and VALU Hamming2 paths run one more kNN-2 launch sequence with query and train
 // swapped -- every distance they compute is symmetric in its operands bit for bit -- and take its column 0.  On return the forward plan and workspace are in P / W (the ratio tail reads W.d_pd).
 static int knn2_mutual_enqueue(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, const int32_t* pairs, int n_pairs, int force_path,
@@ -2125,45 +2122,40 @@ static int knn2_mutual_enqueue(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int
     int rc = plan_pairs(ctx, sets, n_sets, pairs, n_pairs, force_path, P); if (rc) return rc;
     int max_nt = 0;
     for (int p = 0; p < n_pairs; ++p) max_nt = std::max(max_nt, sets[pairs[2 * p + 1]]->rows);
-    if (P.path != 2 && P.path != 4) {
+    if (!KNN_PATHS[P.path].fused_reverse) {
         if (rev_total > 0) {
             std::vector<int32_t> sw((size_t)2 * n_pairs);
             for (int p = 0; p < n_pairs; ++p) { sw[2 * p] = pairs[2 * p + 1]; sw[2 * p + 1] = pairs[2 * p]; }
             KnnPlan P2; KnnWork W2;
             rc = plan_pairs(ctx, sets, n_sets, sw.data(), n_pairs, force_path, P2); if (rc) return rc;
             rc = knn_workspace(ctx, P2, n_pairs, W2); if (rc) return rc;
+            SfmPoolHold hold(ctx);          // the swapped pass's kNN-2: read only by the launch below (stream-ordered reuse)
             void* tmp = nullptr;
-            rc = sfm_pool_get(ctx, (size_t)rev_total * 16, &tmp); if (rc) return rc;
+            rc = hold.get((size_t)rev_total * 16, &tmp); if (rc) return rc;
             int32_t* t_idx = (int32_t*)tmp; float* t_dist = (float*)((char*)tmp + (size_t)rev_total * 8);
-            rc = knn2_pairs_enqueue(ctx, P2, W2, n_pairs, t_idx, t_dist);     // rows of pair p at P2.pd[p].out_off = rev_off[p]
-            if (rc == SFMHIP_OK) {
-                hipLaunchKernelGGL(rev_from_knn_kernel, dim3((unsigned)((rev_total + 255) / 256)), dim3(256), 0, ctx->stream, t_idx, t_dist, rev_total, d_rev_idx, d_rev_dist);
-                const hipError_t e = hipGetLastError();
-                if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = SFMHIP_E_HIP; }
-            }
-            sfm_pool_put(ctx, tmp);          // stream-ordered reuse
-            if (rc) return rc;
+            rc = knn2_pairs_enqueue(ctx, P2, W2, n_pairs, t_idx, t_dist); if (rc) return rc;     // rows of pair p at P2.pd[p].out_off = rev_off[p]
+            hipLaunchKernelGGL(rev_from_knn_kernel, dim3((unsigned)((rev_total + 255) / 256)), dim3(256), 0, ctx->stream, t_idx, t_dist, rev_total, d_rev_idx, d_rev_dist);
+            rc = hip_rc(ctx, hipGetLastError()); if (rc) return rc;
         }
         rc = knn_workspace(ctx, P, n_pairs, W); if (rc) return rc;
         return knn2_pairs_enqueue(ctx, P, W, n_pairs, d_idx2, d_dist2);
     }
     rc = knn_workspace(ctx, P, n_pairs, W); if (rc) return rc;
+    SfmPoolHold hold(ctx);          // the reverse keys and the re-score list
     void* tmp = nullptr;
     const size_t nk = (size_t)std::max<long long>(rev_total, 1);
-    rc = sfm_pool_get(ctx, nk * 8 + nk * 8 + 256, &tmp); if (rc) return rc;
+    rc = hold.get(nk * 8 + nk * 8 + 256, &tmp); if (rc) return rc;
     RevArgs R;
     R.keys = (unsigned long long*)tmp; R.list = (int2*)((char*)tmp + nk * 8); R.count = (int*)((char*)tmp + nk * 16);
     R.d_off = d_rev_off; R.rev_idx = d_rev_idx; R.rev_dist = d_rev_dist; R.max_nt = max_nt;
     hipError_t e = hipMemsetAsync(R.keys, 0xff, nk * 8, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(R.count, 0, sizeof(int), ctx->stream);
-    if (e != hipSuccess) { sfm_pool_put(ctx, tmp); ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    rc = knn2_pairs_enqueue(ctx, P, W, n_pairs, d_idx2, d_dist2, &R);
-    sfm_pool_put(ctx, tmp);
-    return rc;
+    rc = hip_rc(ctx, e); if (rc) return rc;
+    return knn2_pairs_enqueue(ctx, P, W, n_pairs, d_idx2, d_dist2, &R);
 }
 
-// rev_off[p] = train rows of the pairs before p; the table also goes to the device (pool block, released by the caller)
-static int rev_offsets(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, const int32_t* pairs, int n_pairs,
+// rev_off[p] = train rows of the pairs before p; the table also goes to the device (a block of `hold`)
+static int rev_offsets(sfmhip_ctx* ctx, SfmPoolHold& hold, sfmhip_descset* const* sets, int n_sets, const int32_t* pairs, int n_pairs,
                        std::vector<long long>& off, long long& total, long long** d_off)
 {
     off.assign((size_t)n_pairs, 0); total = 0;
@@ -2172,12 +2164,8 @@ static int rev_offsets(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets,
         SFM_ARG_CHECK(ctx, b >= 0 && b < n_sets && sets[b]);
         off[p] = total; total += sets[b]->rows;
     }
-    void* q = nullptr;
-    int rc = sfm_pool_get(ctx, (size_t)std::max(n_pairs, 1) * sizeof(long long), &q); if (rc) return rc;
-    *d_off = (long long*)q;
-    const hipError_t e = hipMemcpyAsync(*d_off, off.data(), (size_t)n_pairs * sizeof(long long), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { sfm_pool_put(ctx, q); ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    return SFMHIP_OK;
+    const int rc = hold.get((size_t)std::max(n_pairs, 1) * sizeof(long long), (void**)d_off); if (rc) return rc;
+    return hip_rc(ctx, hipMemcpyAsync(*d_off, off.data(), (size_t)n_pairs * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
 }
 
 extern "C" {
@@ -2188,14 +2176,12 @@ int sfmhip_knn2_mutual_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const s
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_knn2_mutual_dev");
     SFM_ARG_CHECK(ctx, ctx && query && train && d_idx2 && d_dist2 && d_rev_idx && d_rev_dist);
-    sfmhip_descset* sets[2] = { (sfmhip_descset*)query, (sfmhip_descset*)train };
-    const int32_t pr[2] = { 0, 1 };
+    const OnePair one(query, train);
+    SfmPoolHold hold(ctx);
     std::vector<long long> off; long long total = 0, *d_off = nullptr;
-    int rc = rev_offsets(ctx, sets, 2, pr, 1, off, total, &d_off); if (rc) return rc;
+    const int rc = rev_offsets(ctx, hold, one.sets, 2, one.pairs, 1, off, total, &d_off); if (rc) return rc;
     KnnPlan P; KnnWork W;
-    rc = knn2_mutual_enqueue(ctx, sets, 2, pr, 1, force_path, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total);
-    sfm_pool_put(ctx, d_off);
-    return rc;
+    return knn2_mutual_enqueue(ctx, one.sets, 2, one.pairs, 1, force_path, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total);
 }
 
 int sfmhip_match_pairs_ex_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets,
@@ -2212,13 +2198,13 @@ int sfmhip_match_pairs_ex_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int 
     int max_nq = 0;
     for (int p = 0; p < n_pairs; ++p) { const int a = pairs[2 * p]; SFM_ARG_CHECK(ctx, a >= 0 && a < n_sets && sets[a]); max_nq = std::max(max_nq, sets[a]->rows); }
     SFM_ARG_CHECK(ctx, max_per_pair >= max_nq);
+    SfmPoolHold hold(ctx);          // both blocks are read only by what this call enqueues (stream-ordered reuse)
     std::vector<long long> off; long long total = 0, *d_off = nullptr;
-    int rc = rev_offsets(ctx, sets, n_sets, pairs, n_pairs, off, total, &d_off); if (rc) return rc;
+    int rc = rev_offsets(ctx, hold, sets, n_sets, pairs, n_pairs, off, total, &d_off); if (rc) return rc;
     // reverse results, then the plain tail's lists and counts (filtered into the caller's buffers)
     void* rv = nullptr;
     const size_t nrev = (size_t)std::max<long long>(total, 1), b_list = (size_t)n_pairs * max_per_pair * sizeof(sfm_dmatch);
-    rc = sfm_pool_get(ctx, nrev * 8 + b_list + (size_t)n_pairs * 4, &rv);
-    if (rc) { sfm_pool_put(ctx, d_off); return rc; }
+    rc = hold.get(nrev * 8 + b_list + (size_t)n_pairs * 4, &rv); if (rc) return rc;
     int32_t* d_rev_idx = (int32_t*)rv; float* d_rev_dist = (float*)((char*)rv + nrev * 4);
     sfm_dmatch* d_plain = (sfm_dmatch*)((char*)rv + nrev * 8); int32_t* d_plain_counts = (int32_t*)((char*)rv + nrev * 8 + b_list);
     KnnPlan P; KnnWork W;
@@ -2226,21 +2212,14 @@ int sfmhip_match_pairs_ex_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int 
     long long rows_total = 0;
     for (int p = 0; p < n_pairs; ++p) rows_total += sets[pairs[2 * p]]->rows;
     const size_t rows = (size_t)(rows_total > 0 ? rows_total : 1);
-    rc = sfm_scratch2(ctx, rows * 16, &tmp);
-    if (rc == SFMHIP_OK) {
-        int32_t* d_idx2 = (int32_t*)tmp; float* d_dist2 = (float*)((char*)tmp + rows * 8);
-        rc = knn2_mutual_enqueue(ctx, sets, n_sets, pairs, n_pairs, 0, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total);
-        if (rc == SFMHIP_OK) {
-            hipLaunchKernelGGL(ratio_tail_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, W.d_pd, d_idx2, d_dist2,
-                               ratio, floor_, mult, d_plain, max_per_pair, d_plain_counts);
-            hipLaunchKernelGGL(mutual_filter_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, (const sfm_dmatch*)d_plain, (const int32_t*)d_plain_counts,
-                               d_matches, max_per_pair, d_counts, (const int32_t*)d_rev_idx, (const long long*)d_off);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = SFMHIP_E_HIP; }
-        }
-    }
-    sfm_pool_put(ctx, rv); sfm_pool_put(ctx, d_off);       // stream-ordered reuse
-    return rc;
+    rc = sfm_scratch2(ctx, rows * 16, &tmp); if (rc) return rc;
+    int32_t* d_idx2 = (int32_t*)tmp; float* d_dist2 = (float*)((char*)tmp + rows * 8);
+    rc = knn2_mutual_enqueue(ctx, sets, n_sets, pairs, n_pairs, 0, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total); if (rc) return rc;
+    hipLaunchKernelGGL(ratio_tail_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, W.d_pd, d_idx2, d_dist2,
+                       ratio, floor_, mult, d_plain, max_per_pair, d_plain_counts);
+    hipLaunchKernelGGL(mutual_filter_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, (const sfm_dmatch*)d_plain, (const int32_t*)d_plain_counts,
+                       d_matches, max_per_pair, d_counts, (const int32_t*)d_rev_idx, (const long long*)d_off);
+    return hip_rc(ctx, hipGetLastError());
 }
 
 int sfmhip_match_pairs_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets,
@@ -2298,23 +2277,50 @@ int sfmhip_match_pairs_ex(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_se
     return SFMHIP_OK;
 }
 
-static int knn2_host_common(sfmhip_ctx* ctx, sfmhip_descset* qs, sfmhip_descset* ts, int nq, int32_t* idx2, float* dist2)
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// the calls on two host matrices
+// ------------------------------------------------------------------------------------------------
+// both sets from one call of the batch constructor `create`, act(query set, train set), both sets destroyed
+template <class T, class Create, class Action>
+static int with_host_pair(sfmhip_ctx* ctx, Create create, const T* q, int nq, const T* t, int nt, int dim, size_t ldq, size_t ldt, const Action& act)
 {
-    int32_t* d_idx = nullptr; float* d_dist = nullptr;
-    const size_t n = nq > 0 ? nq : 1;
-    SFM_HIP_TRY(ctx, hipMalloc((void**)&d_idx, n * 8));
-    hipError_t e = hipMalloc((void**)&d_dist, n * 8);
-    if (e != hipSuccess) { (void)hipFree(d_idx); ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    int rc = sfmhip_knn2_dev(ctx, qs, ts, d_idx, d_dist, 0);
-    if (rc == SFMHIP_OK && nq > 0) {
-        e = hipMemcpyAsync(idx2, d_idx, (size_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dist2, d_dist, (size_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = SFMHIP_E_HIP; }
-    }
-    (void)hipFree(d_idx); (void)hipFree(d_dist);
+    const T* desc[2] = { q, t }; const int32_t rows[2] = { nq, nt }; const size_t ld[2] = { ldq, ldt };
+    sfmhip_descset* sets[2] = { nullptr, nullptr };
+    int rc = create(ctx, desc, rows, dim, ld, 2, sets);
+    if (rc == SFMHIP_OK) rc = act(sets[0], sets[1]);
+    descsets_destroy_all(sets, 2);
     return rc;
 }
+
+static int knn2_host_common(sfmhip_ctx* ctx, sfmhip_descset* qs, sfmhip_descset* ts, int nq, int32_t* idx2, float* dist2)
+{
+    SfmPoolHold hold(ctx);
+    const size_t n = nq > 0 ? nq : 1;
+    void* d = nullptr;
+    int rc = hold.get(n * 16, &d); if (rc) return rc;
+    int32_t* d_idx = (int32_t*)d; float* d_dist = (float*)((char*)d + n * 8);
+    rc = sfmhip_knn2_dev(ctx, qs, ts, d_idx, d_dist, 0);
+    if (rc != SFMHIP_OK || nq == 0) return rc;
+    hipError_t e = hipMemcpyAsync(idx2, d_idx, (size_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dist2, d_dist, (size_t)nq * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return hip_rc(ctx, e);
+}
+
+static int match_features_common(sfmhip_ctx* ctx, sfmhip_descset* qs, sfmhip_descset* ts, int nq, sfm_dmatch* out, int* n_out)
+{
+    const OnePair one(qs, ts);
+    int32_t cnt = 0;
+    if (nq == 0) { *n_out = 0; return SFMHIP_OK; }
+    // NViewReconstuct.cpp:884,900-901: ratio 0.6 (double), gate 5 * max(min_dist, 10.0f)
+    const int rc = sfmhip_match_pairs(ctx, one.sets, 2, one.pairs, 1, 0.6, 10.0f, 5.0f, out, nq, &cnt);
+    *n_out = cnt;
+    return rc;
+}
+
+extern "C" {
 
 int sfmhip_knn2_l2_f32(sfmhip_ctx* ctx, const float* q, int nq, const float* t, int nt, int dim,
                        size_t ldq, size_t ldt, int32_t* idx2, float* dist2)
@@ -2322,12 +2328,8 @@ int sfmhip_knn2_l2_f32(sfmhip_ctx* ctx, const float* q, int nq, const float* t, 
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_knn2_l2_f32");
     SFM_ARG_CHECK(ctx, ctx && idx2 && dist2 && nq >= 0 && nt >= 0);
-    sfmhip_descset *qs = nullptr, *ts = nullptr;
-    int rc = sfmhip_descset_create_l2_host(ctx, q, nq, dim, ldq, &qs); if (rc) return rc;
-    rc = sfmhip_descset_create_l2_host(ctx, t, nt, dim, ldt, &ts);
-    if (rc == SFMHIP_OK) rc = knn2_host_common(ctx, qs, ts, nq, idx2, dist2);
-    sfmhip_descset_destroy(qs); sfmhip_descset_destroy(ts);
-    return rc;
+    return with_host_pair(ctx, sfmhip_descsets_create_l2_host, q, nq, t, nt, dim, ldq, ldt,
+                          [&](sfmhip_descset* qs, sfmhip_descset* ts) { return knn2_host_common(ctx, qs, ts, nq, idx2, dist2); });
 }
 
 int sfmhip_knn2_hamming2_u8(sfmhip_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int nbytes,
@@ -2336,24 +2338,8 @@ int sfmhip_knn2_hamming2_u8(sfmhip_ctx* ctx, const uint8_t* q, int nq, const uin
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_knn2_hamming2_u8");
     SFM_ARG_CHECK(ctx, ctx && idx2 && dist2 && nq >= 0 && nt >= 0);
-    sfmhip_descset *qs = nullptr, *ts = nullptr;
-    int rc = sfmhip_descset_create_hamming2_host(ctx, q, nq, nbytes, ldq, &qs); if (rc) return rc;
-    rc = sfmhip_descset_create_hamming2_host(ctx, t, nt, nbytes, ldt, &ts);
-    if (rc == SFMHIP_OK) rc = knn2_host_common(ctx, qs, ts, nq, idx2, dist2);
-    sfmhip_descset_destroy(qs); sfmhip_descset_destroy(ts);
-    return rc;
-}
-
-static int match_features_common(sfmhip_ctx* ctx, sfmhip_descset* qs, sfmhip_descset* ts, int nq, sfm_dmatch* out, int* n_out)
-{
-    sfmhip_descset* sets[2] = { qs, ts };
-    const int32_t pr[2] = { 0, 1 };
-    int32_t cnt = 0;
-    if (nq == 0) { *n_out = 0; return SFMHIP_OK; }
-    // NViewReconstuct.cpp:884,900-901: ratio 0.6 (double), gate 5 * max(min_dist, 10.0f)
-    const int rc = sfmhip_match_pairs(ctx, sets, 2, pr, 1, 0.6, 10.0f, 5.0f, out, nq, &cnt);
-    *n_out = cnt;
-    return rc;
+    return with_host_pair(ctx, sfmhip_descsets_create_hamming2_host, q, nq, t, nt, nbytes, ldq, ldt,
+                          [&](sfmhip_descset* qs, sfmhip_descset* ts) { return knn2_host_common(ctx, qs, ts, nq, idx2, dist2); });
 }
 
 int sfmhip_match_features_l2(sfmhip_ctx* ctx, const float* q, int nq, const float* t, int nt, int dim,
@@ -2362,12 +2348,8 @@ int sfmhip_match_features_l2(sfmhip_ctx* ctx, const float* q, int nq, const floa
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_match_features_l2");
     SFM_ARG_CHECK(ctx, ctx && out && n_out && nq >= 0 && nt >= 0);
-    sfmhip_descset *qs = nullptr, *ts = nullptr;
-    int rc = sfmhip_descset_create_l2_host(ctx, q, nq, dim, ldq, &qs); if (rc) return rc;
-    rc = sfmhip_descset_create_l2_host(ctx, t, nt, dim, ldt, &ts);
-    if (rc == SFMHIP_OK) rc = match_features_common(ctx, qs, ts, nq, out, n_out);
-    sfmhip_descset_destroy(qs); sfmhip_descset_destroy(ts);
-    return rc;
+    return with_host_pair(ctx, sfmhip_descsets_create_l2_host, q, nq, t, nt, dim, ldq, ldt,
+                          [&](sfmhip_descset* qs, sfmhip_descset* ts) { return match_features_common(ctx, qs, ts, nq, out, n_out); });
 }
 
 int sfmhip_match_features_hamming2(sfmhip_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int nbytes,
@@ -2376,12 +2358,8 @@ int sfmhip_match_features_hamming2(sfmhip_ctx* ctx, const uint8_t* q, int nq, co
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_match_features_hamming2");
     SFM_ARG_CHECK(ctx, ctx && out && n_out && nq >= 0 && nt >= 0);
-    sfmhip_descset *qs = nullptr, *ts = nullptr;
-    int rc = sfmhip_descset_create_hamming2_host(ctx, q, nq, nbytes, ldq, &qs); if (rc) return rc;
-    rc = sfmhip_descset_create_hamming2_host(ctx, t, nt, nbytes, ldt, &ts);
-    if (rc == SFMHIP_OK) rc = match_features_common(ctx, qs, ts, nq, out, n_out);
-    sfmhip_descset_destroy(qs); sfmhip_descset_destroy(ts);
-    return rc;
+    return with_host_pair(ctx, sfmhip_descsets_create_hamming2_host, q, nq, t, nt, nbytes, ldq, ldt,
+                          [&](sfmhip_descset* qs, sfmhip_descset* ts) { return match_features_common(ctx, qs, ts, nq, out, n_out); });
 }
 
 // self-test (sfmhip.h): number of integers in [0, 2^24) whose sqrt_exact_int differs from sqrtf
@@ -2396,8 +2374,7 @@ int sfmhip_selftest_exact_sqrt(sfmhip_ctx* ctx, int* mismatches)
     hipError_t e = hipMemcpyAsync(mismatches, d, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(d);
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return SFMHIP_E_HIP; }
-    return SFMHIP_OK;
+    return hip_rc(ctx, e);
 }
 
 int sfmhip_l2_distance_matrix_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const sfmhip_descset* train,
@@ -2446,20 +2423,11 @@ int sfmhip_l2_distance_matrix_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, 
         return SFMHIP_OK;
     }
     // exact fp32 path, all distances stored
-    sfmhip_descset* sets[2] = { (sfmhip_descset*)query, (sfmhip_descset*)train };
-    const int32_t pr[2] = { 0, 1 };
+    const OnePair one(query, train);
     KnnPlan P; KnnWork W;
-    int rc = plan_pairs(ctx, sets, 2, pr, 1, 1, P); if (rc) return rc;
+    int rc = plan_pairs(ctx, one.sets, 2, one.pairs, 1, KNN_EXACT_F32, P); if (rc) return rc;
     rc = knn_workspace(ctx, P, 1, W); if (rc) return rc;
-    constexpr int QR = 4;
-    const dim3 grid(ceil_div(P.max_nq, QR), P.max_chunks, 1);
-    const size_t shm = (size_t)QR * P.dim * sizeof(float);
-    if (P.aligned)
-        hipLaunchKernelGGL((knn2_exact_f32_kernel<QR, true, true>), grid, dim3(256), shm, ctx->stream, W.d_pd, W.d_part,
-                           (const int*)nullptr, W.d_count, d_dist, ld);
-    else
-        hipLaunchKernelGGL((knn2_exact_f32_kernel<QR, false, true>), grid, dim3(256), shm, ctx->stream, W.d_pd, W.d_part,
-                           (const int*)nullptr, W.d_count, d_dist, ld);
+    if (P.aligned) launch_exact<true, true>(ctx, P, W, 1, false, d_dist, ld); else launch_exact<false, true>(ctx, P, W, 1, false, d_dist, ld);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;
 }
