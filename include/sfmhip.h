@@ -242,9 +242,7 @@ typedef struct {
     int    fix_first_camera;            /* 1    (NView:1178) */
     int    fix_intrinsics;              /* 0    (NView:1181: free, shared) */
     int    verbose;                     /* 0    (NView:1216-1217) */
-    int    linearizer;                  /* 0    how the reduced system is built (same result up to rounding): 0 / 1 = per-observation
-                                         *      kernels; 2 = run tiles (points sharing a camera list linearised once, reduced on the
-                                         *      matrix pipe) when every point has 1..7 observations, else the per-observation kernels */
+    int    linearizer;                  /* 0    kept for the struct layout and ignored: the reduced system is built one way */
     int    solver;                      /* 0    reduced camera solve (same result up to rounding): 0 = the chain solver (csrc/ba_chain.hpp: fronts
                                          *      in LDS, a camera at a time, two launches) where the cameras form a chain of band width <= 3
                                          *      cameras and at most 640 of them are free, else 1; 1 = nested dissection, one launch per tree
@@ -283,7 +281,7 @@ int sfmhip_ba_solve(sfmhip_ctx*, double* intrinsic4, double* ext6, int n_cam, do
  * Environment, read by every sfmhip_ba_create (per problem, not per process): SFMHIP_BA_SEAM = bit mask of the pieces of an LM
  * iteration that ride inside its big kernels; unset = all of them.  Bit 2 (value 4): the back-substitution also runs the point
  * pass of the next linearisation at the candidate (ba_back_kernel_lin), so an accepted step whose radius grows as guessed starts
- * without ba_point_kernel; single rank, linearizer 0 and up to 699,050 points only (both sets of per-point arrays, 2 x 192 B per point, within the
+ * without ba_point_kernel; single rank and up to 699,050 points only (both sets of per-point arrays, 2 x 192 B per point, within the
  * 256 MB last-level cache: beyond that the separate launch measured faster).  0: every
  * piece is a launch of its own.  The results are the same bits either way. */
 int  sfmhip_ba_create(sfmhip_ctx*, const double* intrinsic4, const double* ext6, int n_cam,
@@ -307,7 +305,6 @@ int  sfmhip_ba_create(sfmhip_ctx*, const double* intrinsic4, const double* ext6,
  *   - Any block may be constant, all of them included: all cameras constant with fixed intrinsics (n = 0, structure-only), all points
  *     constant (no Schur pairs, motion-only).  A problem with no free parameter returns SFMHIP_BA_CONVERGENCE after 0 iterations with
  *     initial_cost == final_cost == the fixed cost.
- *   - linearizer = 2 with a constant point runs the per-observation kernels (which store V^-1 = 0 for it), not the run tiles.
  *   - Under an all-reduce hook a problem with constant blocks beyond camera 0 never selects the chain solver (solver 0 then means 1).
  *     The ranks agree on it among themselves (a rank whose shard holds none of the constant points follows the others), so each
  *     process of a multi-process run passes its own shard's pt_const.
@@ -399,7 +396,7 @@ int  sfmhip_ba_debug_table(sfmhip_ba*, const char* name, void* out, size_t cap_b
  * (with SFMHIP_BA_SEAM bit 2 the point pass of an iteration's linearisation ran inside the PREVIOUS iteration's back-substitution: its
  * time is part of [2], not of [0], except in the iterations that fall back to ba_point_kernel),
  * single kernels: [4]=ba_camera_kernel, [5]=ba_schur_kernel -- or, where the two share one launch, [4]=ba_camschur_kernel and [5]=0
- * ([4]=ba_tile_kernel with linearizer = 2) --, [6]=chol_node_forward_kernel of the leaf level (0 if unused);
+ * --, [6]=chol_node_forward_kernel of the leaf level (0 if unused);
  * [7] = number of non-zero 32x32 blocks of the Cholesky factor (not a time) */
 int  sfmhip_ba_phase_ms(sfmhip_ba*, double out_ms[8]);
 

@@ -12,7 +12,6 @@
 #include "ba_kernels.hpp"
 #include "ba_solver.hpp"
 #include "ba_chain.hpp"
-#include "ba_tiles.hpp"
 #include "ba_setup.hpp"
 #include <algorithm>
 #include <chrono>
@@ -233,7 +232,7 @@ struct sfmhip_ba {
     bool cleared = false;               // S (the npad x npad part of d_msg) is already zero for the next build -- ONLY S: the tail [rhs | diagU | graw | scalars]
                                         // and d_err are not refilled, they rely on the finalisation storing every real entry (padding entries stay zero
                                         // through the solve) and on ba_back_reduce_kernel re-arming the error flag; tests/test_ba_gpu.py::
-                                        // test_reused_message_tail_with_an_unobserved_camera holds both linearisers to that
+                                        // test_reused_message_tail_with_an_unobserved_camera holds the build to that
     bool top_cleared = false;      // d_topbuf was zero-filled ahead of time (behind the publish kernel, while the host decides)
     int n_diag_blk = 0;            // camera pairs (a, a): a point seen twice by one camera
     bool solver_damps = false; double damp_radius = 0.0;    // the next enqueue_solve applies the LM damping inside its kernels
@@ -246,14 +245,7 @@ struct sfmhip_ba {
     long long ar_calls = 0;         // all-reduce hook invocations since sfmhip_ba_set_allreduce (tests assert one per LM iteration)
     bool force_dense = false;      // SFMHIP_EXPERIMENTS builds: SFMHIP_DENSE_SOLVER routes every problem to the dense fallback
     long long* d_stamps = nullptr; int stamp_calls = 0;      // SFMHIP_EXPERIMENTS builds only: per-panel cycle stamps of the solver
-    // run-tile linearisation (ba_tiles.hpp): segments of point runs, their tiles, and the fold table of ba_tile_reduce_kernel
     int fuse_max_blocks = 4096;        // camera + pair workgroups up to which they share one launch
-    bool use_tiles = false; int n_tseg = 0; long long n_ttiles = 0;
-    std::vector<TileSeg> tsegs; std::vector<int> tcams;
-    TileSeg* d_tsegs = nullptr; int* d_tcams = nullptr; double *d_tpart = nullptr, *d_tpart_seg = nullptr;
-    int *d_rd_start = nullptr, *d_rd_dst = nullptr, *d_rd_dst2 = nullptr; unsigned* d_rd_src = nullptr; int rd_nd = 0, rd_n_long = 0;
-    size_t rd_dst_cap = 0, rd_src_cap = 0;
-    std::vector<int> tile_tab_cam_pos; int tile_tab_npad = -1;      // the layout the fold table was built for
     // chain solver (ba_chain.hpp): plan, factor records, the sub-trees' exported fronts
     bool use_chain = false; ChainArgs chain; double *d_chain_rec = nullptr, *d_chain_img = nullptr; size_t chain_rec_cap = 0, chain_img_cap = 0;
     size_t chain_lds1 = 0, chain_lds2 = 0;
@@ -378,15 +370,6 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
     if (!at_candidate && !h->campre_valid) {
         hipLaunchKernelGGL(ba_campre_kernel, dim3(ceil_div(h->nc, 64)), dim3(64), 0, st, h->d_ext, h->nc, h->d_campre);
         h->campre_valid = true;
-    }
-    if (h->use_tiles) {
-        if (tv) { (void)hipEventRecord(tv[3], st); (void)hipEventRecord(tv[4], st); (void)hipEventRecord(tv[1], st); }
-        hipLaunchKernelGGL(ba_tile_kernel, dim3(h->n_tseg), dim3(256), TILE_LDS_BYTES, st, P, h->d_tsegs, h->d_tcams, h->d_tpart, h->d_tpart_seg, h->d_err);
-        if (tv) (void)hipEventRecord(tv[2], st);
-        hipLaunchKernelGGL(ba_tile_reduce_kernel, dim3(h->rd_n_long + ceil_div(h->rd_nd - h->rd_n_long, 256) + 1), dim3(256), 0, st, P, h->d_rd_start, h->d_rd_dst, h->d_rd_dst2, h->d_rd_src,
-                           h->rd_n_long, h->rd_nd, h->d_tpart, h->d_tpart_seg, h->n_tseg);
-        SFM_HIP_TRY(ctx, hipGetLastError());
-        return enqueue_build_exchange(h, carry);
     }
     // the point pass: already there if the last back-substitution computed it at what is now the current point (ba_loop)
     if (h->pt_ready && !at_candidate) { h->pt_ready = false; h->pt_fold_err = true; }
@@ -974,113 +957,12 @@ static int build_solver_plan(sfmhip_ba* h)
     return SFMHIP_E_ARG;
 }
 
-// Fold table of the run tiles for the current solver layout: for every entry of [S | rhs | diagU | graw] that the tiles
-// touch, the list of (+/-) tile elements that sum to it, segments in storage order.  With D_k the direct tile of
-// observation slot k (rows [E_ck (6) | E_K (4) | r]) and Z the (6M + 5)^2 product (rows [E_c0 .. E_cM-1 | E_K | r]):
-//   S[ck,ck] = sum D_k[c,c] - Z[ck,ck]     S[ck,cl] = -Z[ck,cl]     S[ck,K] = D_k[c,K] - Z[ck,K]     S[K,K] = sum_k D_k[K,K] - Z[K,K]
-//   rhs_ck = D_k[c,r] - Z[ck,r]     rhs_K = sum_k D_k[K,r] - Z[K,r]     diagU = diag D     graw = D[.,r]
-static int build_tile_tables(sfmhip_ba* h)
-{
-    if (!h->use_tiles) return SFMHIP_OK;
-    if (h->tile_tab_npad == h->npad && h->tile_tab_cam_pos == h->cam_pos) return SFMHIP_OK;
-    sfmhip_ctx* ctx = h->ctx;
-    const int ld = h->npad, koff = h->koff;
-    const long long np2 = (long long)ld * ld;
-    if (np2 + 3ll * ld >= (1ll << 31)) { ctx->last_error = "reduced system too large for the tile fold table"; return SFMHIP_E_ARG; }
-    std::vector<std::pair<int, unsigned>> ents;
-    ents.reserve((size_t)h->n_tseg * 600);
-    const unsigned NEG = 0x80000000u;
-    for (const TileSeg& sg : h->tsegs) {
-        const int M = sg.M;
-        int co[TILE_MMAX];
-        for (int k = 0; k < M; ++k) co[k] = h->cam_pos[h->tcams[sg.cams_off + k]];
-        auto D = [&](int k, int row, int col) -> unsigned { return (unsigned)((sg.tile_off + k) * 256 + tile_elem(row, col)); };
-        auto Z = [&](int a, int b) -> unsigned {
-            if (a < b) std::swap(a, b);
-            const int tr = a / 16, tc = b / 16;
-            return (unsigned)((sg.tile_off + M + tr * (tr + 1) / 2 + tc) * 256 + tile_elem(a % 16, b % 16));
-        };
-        auto sdst = [&](int r, int c) -> int { if (r < c) std::swap(r, c); return r * ld + c; };
-        for (int k = 0; k < M; ++k) {
-            if (co[k] < 0) continue;
-            for (int i = 0; i < 6; ++i) {
-                for (int j = 0; j <= i; ++j) { ents.push_back({ sdst(co[k] + i, co[k] + j), D(k, i, j) }); ents.push_back({ sdst(co[k] + i, co[k] + j), Z(6 * k + i, 6 * k + j) | NEG }); }
-                if (!h->fixK)
-                    for (int j = 0; j < 4; ++j) { ents.push_back({ sdst(co[k] + i, koff + j), D(k, i, 6 + j) }); ents.push_back({ sdst(co[k] + i, koff + j), Z(6 * k + i, 6 * M + j) | NEG }); }
-                ents.push_back({ (int)np2 + co[k] + i, D(k, i, 10) }); ents.push_back({ (int)np2 + co[k] + i, Z(6 * k + i, 6 * M + 4) | NEG });
-                ents.push_back({ (int)np2 + ld + co[k] + i, D(k, i, i) });
-                ents.push_back({ (int)np2 + 2 * ld + co[k] + i, D(k, i, 10) });
-            }
-            for (int l = 0; l < k; ++l) {
-                if (co[l] < 0) continue;
-                for (int i = 0; i < 6; ++i)
-                    for (int j = 0; j < 6; ++j) {
-                        ents.push_back({ sdst(co[k] + i, co[l] + j), Z(6 * k + i, 6 * l + j) | NEG });
-                        if (co[k] == co[l] && i == j) ents.push_back({ sdst(co[k] + i, co[l] + j), Z(6 * k + i, 6 * l + j) | NEG });     // one camera twice: block + its transpose
-                    }
-            }
-        }
-        if (!h->fixK) {
-            for (int i = 0; i < 4; ++i) {
-                for (int j = 0; j <= i; ++j) {
-                    for (int k = 0; k < M; ++k) ents.push_back({ sdst(koff + i, koff + j), D(k, 6 + i, 6 + j) });
-                    ents.push_back({ sdst(koff + i, koff + j), Z(6 * M + i, 6 * M + j) | NEG });
-                }
-                for (int k = 0; k < M; ++k) {
-                    ents.push_back({ (int)np2 + koff + i, D(k, 6 + i, 10) });
-                    ents.push_back({ (int)np2 + ld + koff + i, D(k, 6 + i, 6 + i) });
-                    ents.push_back({ (int)np2 + 2 * ld + koff + i, D(k, 6 + i, 10) });
-                }
-                ents.push_back({ (int)np2 + koff + i, Z(6 * M + i, 6 * M + 4) | NEG });
-            }
-        }
-    }
-    std::stable_sort(ents.begin(), ents.end(), [](const std::pair<int, unsigned>& a, const std::pair<int, unsigned>& b) { return a.first < b.first; });
-    // destinations with long source lists first (a workgroup each in ba_tile_reduce_kernel), then the rest in ascending order
-    std::vector<int> start, dst, dst2; std::vector<unsigned> src; src.reserve(ents.size());
-    h->rd_n_long = 0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (size_t e = 0; e < ents.size();) {
-            size_t f = e;
-            while (f < ents.size() && ents[f].first == ents[e].first) ++f;
-            if ((f - e > 192) == (pass == 0)) {
-                start.push_back((int)src.size()); dst.push_back(ents[e].first);
-                int m = -1;
-                if (ents[e].first < np2) { const int r = ents[e].first / ld, c = ents[e].first % ld; if (r != c) m = c * ld + r; }
-                dst2.push_back(m);
-                for (size_t g = e; g < f; ++g) src.push_back(ents[g].second);
-                if (pass == 0) ++h->rd_n_long;
-            }
-            e = f;
-        }
-    start.push_back((int)src.size());
-    h->rd_nd = (int)dst.size();
-    int rc = SFMHIP_OK;
-    if (dst.size() + 1 > h->rd_dst_cap) {
-        rc = dalloc(h, &h->d_rd_start, dst.size() + 1); if (rc) return rc;
-        rc = dalloc(h, &h->d_rd_dst, dst.size() + 1); if (rc) return rc;
-        rc = dalloc(h, &h->d_rd_dst2, dst.size() + 1); if (rc) return rc;
-        h->rd_dst_cap = dst.size() + 1;
-    }
-    if (src.size() + 1 > h->rd_src_cap) { rc = dalloc(h, &h->d_rd_src, src.size() + 1); if (rc) return rc; h->rd_src_cap = src.size() + 1; }
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_rd_start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (!dst.empty()) {
-        SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_rd_dst, dst.data(), dst.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_rd_dst2, dst2.data(), dst2.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (!src.empty()) SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_rd_src, src.data(), src.size() * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    h->tile_tab_npad = h->npad; h->tile_tab_cam_pos = h->cam_pos;
-    return SFMHIP_OK;
-}
-
 // iteration 0 work: jacobi scaling from the column norms at x0, |x0|
 static int ba_start(sfmhip_ba* h)
 {
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
     { int rc = build_solver_plan(h); if (rc) return rc; }
-    { int rc = build_tile_tables(h); if (rc) return rc; }
     const size_t np3 = 3 * (size_t)h->np;
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((h->npad_max + 255) / 256)), dim3(256), 0, st, h->d_scale_c, (size_t)h->npad_max, 1.0);
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((np3 + 255) / 256 + 1)), dim3(256), 0, st, h->d_scale_p, np3, 1.0);
@@ -1130,7 +1012,7 @@ static void read_pending_timing(sfmhip_ba* h)
     float a = 0, b = 0, c = 0, k1 = 0, k2 = 0, k3 = 0;
     (void)hipEventElapsedTime(&a, tb[0], ti[0]); (void)hipEventElapsedTime(&b, ti[0], ti[1]); (void)hipEventElapsedTime(&c, ti[1], ti[2]);
     (void)hipEventElapsedTime(&k1, tb[1], tb[2]); (void)hipEventElapsedTime(&k2, tb[3], tb[4]);
-    if (h->build_fused[h->pending_build] || h->use_tiles) k2 = 0.0f;
+    if (h->build_fused[h->pending_build]) k2 = 0.0f;
     if (h->use_sparse && h->nseg > 1) (void)hipEventElapsedTime(&k3, ti[3], ti[4]);
     h->phase_acc[0] += a; h->phase_acc[1] += b; h->phase_acc[2] += c; h->phase_acc[3] += a + b + c;
     h->phase_acc[4] += k1; h->phase_acc[5] += k2; h->phase_acc[6] += k3; h->phase_cnt++;
@@ -1186,8 +1068,8 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
         // the point blocks are damped inside the build, so a speculation must also guess the next radius: a step with
         // rho >= 0.937 (the normal case while LM is making progress) grows it by exactly 1 / (1/3)
         const double spec_radius = std::min(o.max_trust_region_radius, h->radius / (1.0 / 3.0));
-        // single rank, per-observation lineariser: the back-substitution carries the next point pass (SFMHIP_BA_SEAM bit 2)
-        const bool lin_in_back = (h->seam & SEAM_LIN_IN_BACK) && !h->ar_fn && !h->use_tiles && !speculate && h->d_Vinv2;
+        // single rank: the back-substitution carries the next point pass (SFMHIP_BA_SEAM bit 2)
+        const bool lin_in_back = (h->seam & SEAM_LIN_IN_BACK) && !h->ar_fn && !speculate && h->d_Vinv2;
         h->publish_in_back = true; h->fold_step_scalars = folded;
         rc = enqueue_back(h, h->radius, lin_in_back ? spec_radius : 0.0); h->publish_in_back = false; h->fold_step_scalars = false; if (rc) return rc;
         if (timing) SFM_HIP_TRY(ctx, hipEventRecord(ti[2], st));
@@ -1306,8 +1188,8 @@ struct SetupTemps {
 // them (lexicographic on the ascending camera list; internal only, sfmhip_ba_get_params hands them back in the caller's
 // order) -- every per-camera and per-camera-pair walk then gathers from runs of neighbouring point records instead of
 // from all over HBM (C4 on MI355X: linearisation 0.41 -> 0.31 ms, back-substitution 0.13 -> 0.08 ms) --, a point's
-// observations in ascending camera order (the k-th observation of every point of a run then belongs to the same camera,
-// which the run tiles rely on), the camera-ordered copy, and the camera-pair lists for the off-diagonal Schur blocks.
+// observations in ascending camera order (the k-th observation of every point of a run then belongs to the same camera),
+// the camera-ordered copy, and the camera-pair lists for the off-diagonal Schur blocks.
 static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_uv, const uint8_t* pt_const)
 {
     sfmhip_ctx* ctx = h->ctx;
@@ -1487,45 +1369,6 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     if (const char* e = getenv("SFMHIP_CAM_WG_OBS")) cam_wg_obs = std::max(256, atoi(e));
 #endif
     h->cam_split = std::min(32, std::max(1, ceil_div(max_cam, cam_wg_obs)));
-
-    // ---- run tiles (opt-in linearizer = 2): runs of points with one camera list, cut into segments of <= seg_max points (one
-    // workgroup each).  Host pass over the finished tables.
-    h->tsegs.clear(); h->tcams.clear(); h->n_tseg = 0; h->n_ttiles = 0; h->use_tiles = false;
-    // (not with constant points: those problems run the per-observation kernels, which store V^-1 = 0 for them)
-    if (h->o.linearizer == 2 && np > 0 && !h->d_ptfix) {
-        std::vector<int> pt_start((size_t)np + 1), ocam((size_t)nobs);
-        SFM_HIP_TRY(ctx, hipMemcpy(pt_start.data(), h->d_pt_start, pt_start.size() * sizeof(int), hipMemcpyDeviceToHost));
-        if (nobs) SFM_HIP_TRY(ctx, hipMemcpy(ocam.data(), h->d_ocam, ocam.size() * sizeof(int), hipMemcpyDeviceToHost));
-        int seg_max = 320;
-#ifdef SFMHIP_EXPERIMENTS
-        if (const char* e = getenv("SFMHIP_TILE_SEG")) seg_max = std::max(16, atoi(e));
-#endif
-        bool fits = true;
-        long long tiles = 0;
-        for (int p = 0; p < np && fits;) {
-            const int M = pt_start[p + 1] - pt_start[p];
-            if (M < 1 || M > TILE_MMAX) { fits = false; break; }
-            int q = p + 1;
-            while (q < np && pt_start[q + 1] - pt_start[q] == M && std::equal(ocam.begin() + pt_start[p], ocam.begin() + pt_start[p + 1], ocam.begin() + pt_start[q])) ++q;
-            const int len = q - p, nseg = ceil_div(len, seg_max), per = round_up(ceil_div(len, nseg), 16);
-            const int cams_off = (int)h->tcams.size();
-            for (int k = 0; k < M; ++k) h->tcams.push_back(ocam[pt_start[p] + k]);
-            const int R = 6 * M + 5, Tn = (R + 15) / 16, NT = M + Tn * (Tn + 1) / 2;
-            for (int a = p; a < q; a += per) {
-                TileSeg sg; sg.p0 = a; sg.npts = std::min(per, q - a); sg.obs0 = pt_start[a]; sg.M = M; sg.cams_off = cams_off; sg.tile_off = (int)tiles; sg.pad0 = sg.pad1 = 0;
-                h->tsegs.push_back(sg); tiles += NT;
-            }
-            p = q;
-        }
-        // heaviest segments first (work per point grows with M: more tiles, and two observations per lane from M = 5): the
-        // dispatcher hands workgroups out in index order, so the short ones fill the tail
-        std::stable_sort(h->tsegs.begin(), h->tsegs.end(), [](const TileSeg& a, const TileSeg& b) { return a.M > b.M; });
-        if (tiles * 256 >= (1ll << 31)) fits = false;                // the fold table addresses the tile buffer with 31 bits
-        // opt-in only: measured on MI355X the tile kernel + fold take 0.125 + 0.04 ms at C4 against 0.13 ms for the whole
-        // per-observation pipeline (profiles/README.md, round 2), so 0 = "choose" resolves to the per-observation kernels
-        h->use_tiles = fits;
-        if (fits) { h->n_tseg = (int)h->tsegs.size(); h->n_ttiles = tiles; } else { h->tsegs.clear(); h->tcams.clear(); }
-    }
 #undef TRY_RC
     return SFMHIP_OK;
 }
@@ -1687,13 +1530,6 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     TRY_RC(dupload(h, &h->d_K, K4, 4)); TRY_RC(dupload(h, &h->d_ext, ext6, 6 * (size_t)n_cam));
     TRY_RC(dupload(h, &h->d_K0, K4, 4)); TRY_RC(dupload(h, &h->d_ext0, ext6, 6 * (size_t)n_cam));
     TRY_RC(dupload(h, &h->d_Kc, K4, 4)); TRY_RC(dupload(h, &h->d_extc, ext6, 6 * (size_t)n_cam));
-    if (h->use_tiles) {
-        TRY_RC(dupload(h, &h->d_tsegs, h->tsegs.data(), h->tsegs.size())); TRY_RC(dupload(h, &h->d_tcams, h->tcams.data(), h->tcams.size()));
-        TRY_RC(dalloc(h, &h->d_tpart, (size_t)h->n_ttiles * 256)); TRY_RC(dalloc(h, &h->d_tpart_seg, 2 * (size_t)h->n_tseg));
-        if (hipFuncSetAttribute((const void*)ba_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_LDS_BYTES) != hipSuccess) {
-            sfmhip_ba_destroy(h); ctx->last_error = "hipFuncSetAttribute(ba_tile_kernel)"; return SFMHIP_E_HIP;
-        }
-    }
     TRY_RC(dalloc(h, &h->d_scale_c, (size_t)h->npad_max)); TRY_RC(dalloc(h, &h->d_scale_p, 3 * (size_t)n_pt));
     TRY_RC(dalloc(h, &h->d_campre, CAMPRE * (size_t)n_cam)); TRY_RC(dalloc(h, &h->d_campre_c, CAMPRE * (size_t)n_cam));
     TRY_RC(dalloc(h, &h->d_cam_pos, (size_t)n_cam)); TRY_RC(dalloc(h, &h->d_posmask, (size_t)h->npad_max));
@@ -1704,7 +1540,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     // Second point-side set: the point pass the back-substitution computes ahead.  Only while both sets (2 x 192 B per point) fit the
     // 256 MB last-level cache: measured faster at 80k and 300k points (C3 0.164 -> 0.161, C4 0.299 -> 0.290 ms per iteration), slower
     // at 2M (C5 1.16 -> 1.29 ms), where neither set stays on chip and the separate, purely streaming ba_point_kernel is ahead.
-    if ((h->seam & SEAM_LIN_IN_BACK) && !h->use_tiles && 2 * 192 * (size_t)n_pt <= ((size_t)256 << 20)) {
+    if ((h->seam & SEAM_LIN_IN_BACK) && 2 * 192 * (size_t)n_pt <= ((size_t)256 << 20)) {
         TRY_RC(dalloc(h, &h->d_Vinv2, 6 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_bp2, 3 * (size_t)n_pt));
         TRY_RC(dalloc(h, &h->d_WK2, 12 * (size_t)n_pt)); TRY_RC(dalloc(h, &h->d_colsq_p2, 3 * (size_t)n_pt));
         TRY_RC(dalloc(h, &h->d_part_pt2, 32 * (size_t)h->n_pt_blocks)); TRY_RC(dalloc(h, &h->d_err_pt, 2));
@@ -1731,7 +1567,7 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     if (h->o.verbose)
         printf("[sfmhip_ba] seam %d: the next point pass %s; intrinsic block + scalars %s; gradient maximum %s; backward sweep below the top %s; ba_back_reduce_kernel's loads %s\n", h->seam,
                h->d_Vinv2 ? "rides in the back-substitution (ba_back_kernel_lin)" : "is a launch of its own (ba_point_kernel)",
-               (h->seam & SEAM_INTR_FRONT) && !h->use_tiles ? "in ba_camschur_kernel's front group (where camera items and pair chunks share that launch)" : "in ba_fold_kernel",
+               (h->seam & SEAM_INTR_FRONT) ? "in ba_camschur_kernel's front group (where camera items and pair chunks share that launch)" : "in ba_fold_kernel",
                (h->seam & SEAM_CAMSTEP_ROLES) ? "in a workgroup of its own" : "behind the step in block 0",
                (h->seam & SEAM_TREE_BACKWARD) ? "in one launch (if the plan has parallel separator levels)" : "a launch per level",
                (h->seam & SEAM_BACK_REDUCE) ? "in flight together" : "trip by trip");

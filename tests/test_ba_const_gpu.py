@@ -158,6 +158,11 @@ def _mixed_cases():
         ("motion-only", (8, 400), [], 1.0, dict()),
         ("pnp", (1, 300), [], 1.0, dict(fix_first_camera=0, fix_intrinsics=1)),
         ("structure-only", (8, 400), list(range(8)), 0.0, dict(fix_intrinsics=1)),
+        # constant cameras in the middle of the index range (renumbered internally), no constant point: 16 cameras for the indices,
+        # 400 points like the cases above (what the dense reference costs grows with the cube of the point count)
+        ("cams 4 9 10", (16, 400), [4, 9, 10], 0.0, dict()),
+        ("cams 3 8 fixed K", (16, 400), [3, 8], 0.0, dict(fix_intrinsics=1)),
+        ("cams 2 7 12 free first camera", (16, 400), [2, 7, 12], 0.0, dict(fix_first_camera=0)),
     ]
 
 
@@ -270,29 +275,14 @@ def test_masked_reruns_are_bitwise_identical_and_seam_on_off_agree(ctx):
     _same_bits(outs[0], outs[1])
 
 
-def test_linearizers_and_solvers_agree_with_masks(ctx):
+def test_solvers_agree_with_masks(ctx):
     sc = synth.ba_scene(16, 1500)
     cm = _cam_mask(16, [3, 9]); pm = _pt_mask(1500)
-    outs = []
-    for lin, sol in ((0, 0), (1, 0), (2, 0), (0, 1), (2, 1)):
-        outs.append(_forced(ctx, sc, ctx.ba_options(linearizer=lin, solver=sol), cm, pm))
+    outs = [_forced(ctx, sc, ctx.ba_options(solver=sol), cm, pm) for sol in (0, 1)]
     for K, e, p, s in outs[1:]:
         assert np.abs(K - outs[0][0]).max() <= 1e-10 * np.abs(outs[0][0]).max()
         assert np.abs(e - outs[0][1]).max() <= 1e-10 and np.abs(p - outs[0][2]).max() <= 1e-10
         _constants_kept(sc, (K, e, p), cm | (np.arange(16) == 0), pm, False)
-
-
-def test_tile_linearizer_agrees_with_camera_masks(ctx):
-    """linearizer 2 (run tiles) is live with constant cameras and no constant point: constant cameras in the middle of the index range
-    (renumbered internally) must leave it where the per-observation kernels are"""
-    sc = synth.ba_scene(16, 1500)
-    for cams, kw in (([4, 9, 10], {}), ([3, 8], dict(fix_intrinsics=1)), ([2, 7, 12], dict(fix_first_camera=0))):
-        cm = _cam_mask(16, cams)
-        outs = [_forced(ctx, sc, ctx.ba_options(linearizer=lin, **kw), cm) for lin in (0, 1, 2)]
-        for K, e, p, s in outs[1:]:
-            assert np.abs(K - outs[0][0]).max() <= 1e-10 * np.abs(outs[0][0]).max()
-            assert np.abs(e - outs[0][1]).max() <= 1e-10 and np.abs(p - outs[0][2]).max() <= 1e-10
-            _constants_kept(sc, (K, e, p), cm | (np.arange(16) == 0) if kw.get("fix_first_camera", 1) else cm, None, kw.get("fix_intrinsics", 0))
 
 
 def test_chain_solver_with_constant_cameras_inside_the_chain(ctx, capfd):
