@@ -1170,20 +1170,6 @@ static void fill_summary(const sfmhip_ba* h, sfm_ba_summary* s, double t_s)
     s->preprocessor_time_s = h->start_ms * 1e-3; s->minimizer_time_s = t_s - h->start_ms * 1e-3; s->postprocessor_time_s = 0.0;
 }
 
-// Device temporaries of sfmhip_ba_create, out of the context's block cache.
-struct SetupTemps {
-    sfmhip_ctx* ctx; std::vector<void*> blocks;
-    explicit SetupTemps(sfmhip_ctx* c) : ctx(c) {}
-    ~SetupTemps() { for (void* p : blocks) sfm_pool_put(ctx, p); }       // stream-ordered reuse: back to the context's cache
-    template <typename T> int get(T** p, size_t count)
-    {
-        void* q = nullptr;
-        int rc = sfm_pool_get(ctx, (count > 0 ? count : 1) * sizeof(T), &q); if (rc) return rc;
-        blocks.push_back(q); *p = (T*)q;
-        return SFMHIP_OK;
-    }
-};
-
 // Orderings of the observation list, built on the device (ba_setup.hpp): points sorted by the set of cameras that see
 // them (lexicographic on the ascending camera list; internal only, sfmhip_ba_get_params hands them back in the caller's
 // order) -- every per-camera and per-camera-pair walk then gathers from runs of neighbouring point records instead of
@@ -1195,7 +1181,7 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
     const int nc = h->nc, np = h->np, nobs = h->nobs;
-    SetupTemps T(ctx);
+    SfmPoolHold T(ctx);          // the construction temporaries: back to the context's cache on every way out
     int rc = SFMHIP_OK;
 #define TRY_RC(x) do { rc = (x); if (rc) return rc; } while (0)
     const auto t0 = std::chrono::steady_clock::now();
@@ -1667,14 +1653,14 @@ int sfmhip_ba_get_params(sfmhip_ba* h, double* K4, double* ext6, double* pts)
         }
     }
     if (pts && h->np) {           // back into the caller's point order on the device, then one copy into the caller's array
-        void* tmp = nullptr;
-        int rc = sfm_scratch(ctx, 3 * (size_t)h->np * sizeof(double), &tmp); if (rc) return rc;
-        hipLaunchKernelGGL(setup_permute_pts_kernel, dim3(ceil_div(h->np, 256)), dim3(256), 0, ctx->stream, (const double*)h->d_pts, (const int*)h->d_slot, h->np, (double*)tmp, 0);
+        SfmPoolHold hold(ctx);
+        double* tmp = nullptr;
+        const int rc = hold.get(&tmp, 3 * (size_t)h->np); if (rc) return rc;
+        hipLaunchKernelGGL(setup_permute_pts_kernel, dim3(ceil_div(h->np, 256)), dim3(256), 0, ctx->stream, (const double*)h->d_pts, (const int*)h->d_slot, h->np, tmp, 0);
         if (h->d_ptfix)
             hipLaunchKernelGGL(setup_restore_fixed_pts_kernel, dim3(ceil_div(h->np, 256)), dim3(256), 0, ctx->stream, (const double*)h->d_pts0, (const int*)h->d_slot,
-                               (const unsigned char*)h->d_ptfix, h->np, (double*)tmp);
-        SFM_HIP_TRY(ctx, hipMemcpyAsync(pts, tmp, 3 * (size_t)h->np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                               (const unsigned char*)h->d_ptfix, h->np, tmp);
+        return sfm_finish(ctx, hipMemcpyAsync(pts, tmp, 3 * (size_t)h->np * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }
     return SFMHIP_OK;
 }

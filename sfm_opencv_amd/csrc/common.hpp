@@ -16,11 +16,6 @@ struct sfmhip_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;       // the stream every launch goes to (own_stream or an external one)
     std::string last_error;
-    // grow-only device scratch (kNN partial results, pair descriptors, rescore lists)
-    void*  scratch = nullptr;
-    size_t scratch_bytes = 0;
-    void*  scratch2 = nullptr;
-    size_t scratch2_bytes = 0;
     // grow-only pinned host staging (results the kernels write straight into host memory: sfmhip_match_pairs)
     void*  pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -31,9 +26,19 @@ struct sfmhip_ctx {
     bool   stage_busy[2] = { false, false };
     int    stage_next = 0;
     struct CopyPool* copy_pool = nullptr;      // three helper threads that fill the staging buffers beside the caller (context.hip)
-    // Cache of device blocks (sfm_pool_get / sfm_pool_put): the arrays and the construction temporaries of bundle-adjustment
-    // problems.  Giving gigabytes back to the driver costs ~0.1 s that surfaces in whatever HIP call comes next (measured: the
-    // second sfmhip_ba_create at C5 took 127 ms against 13 ms for the first), so freed blocks are kept and handed out again;
+    // Cache of device blocks (sfm_pool_get / sfm_pool_put), the one source of device memory of this library: the arrays of
+    // descriptor sets and bundle-adjustment problems, and every temporary of every call (through an SfmPoolHold, below).
+    //  * Who may take blocks: code that works on ctx->stream, and only on it (a BA problem also runs on a second stream:
+    //    sfmhip_ba_destroy drains both before its blocks can be handed out again).
+    //  * Reuse is stream-ordered: a block that is put back may be handed out at once, while work that reads or writes it is
+    //    still queued.  Its next user is enqueued behind that work on the same stream, so it sees the block only afterwards;
+    //    nobody waits on the host.  A block comes back with whatever its last user left in it.
+    //  * An enqueue-only (_dev) call may therefore hold its temporaries in an SfmPoolHold of its own scope and return with its
+    //    launches still queued.  It may not assume anything about a block's contents, nor keep a pointer to one past its return.
+    //    A call whose HOST buffers are sources or targets of queued copies drains the stream before it returns (sfm_finish /
+    //    sfm_drain); sfmhip_set_stream drains the old stream before work moves to another.
+    // Giving gigabytes back to the driver costs ~0.1 s that surfaces in whatever HIP call comes next (measured: the second
+    // sfmhip_ba_create at C5 took 127 ms against 13 ms for the first), so freed blocks are kept and handed out again;
     // sfmhip_trim / sfmhip_destroy release them.
     struct PoolBlock { void* p; size_t bytes; bool used; };
     std::vector<PoolBlock> pool;
@@ -109,34 +114,6 @@ struct SfmRange {
         }                                                                                        \
     } while (0)
 
-static inline int sfm_scratch(sfmhip_ctx* ctx, size_t bytes, void** out)
-{
-    if (bytes > ctx->scratch_bytes) {
-        // the stream may still be using the old block: drain it before freeing
-        SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) SFM_HIP_TRY(ctx, hipFree(ctx->scratch));
-        ctx->scratch = nullptr; ctx->scratch_bytes = 0;
-        size_t want = bytes + bytes / 4 + 4096;
-        SFM_HIP_TRY(ctx, hipMalloc(&ctx->scratch, want));
-        ctx->scratch_bytes = want;
-    }
-    *out = ctx->scratch;
-    return SFMHIP_OK;
-}
-static inline int sfm_scratch2(sfmhip_ctx* ctx, size_t bytes, void** out)
-{
-    if (bytes > ctx->scratch2_bytes) {
-        SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch2) SFM_HIP_TRY(ctx, hipFree(ctx->scratch2));
-        ctx->scratch2 = nullptr; ctx->scratch2_bytes = 0;
-        size_t want = bytes + bytes / 4 + 4096;
-        SFM_HIP_TRY(ctx, hipMalloc(&ctx->scratch2, want));
-        ctx->scratch2_bytes = want;
-    }
-    *out = ctx->scratch2;
-    return SFMHIP_OK;
-}
-
 static inline int sfm_pinned(sfmhip_ctx* ctx, size_t bytes, void** out)
 {
     if (bytes > ctx->pinned_bytes) {
@@ -162,8 +139,8 @@ int sfm_upload_produced(sfmhip_ctx* ctx, void* dst, size_t bytes, size_t granule
 // f(t, nt) on every copy thread of the context, the caller included
 void sfm_parallel(sfmhip_ctx* ctx, const std::function<void(int, int)>& f);
 
-// device block of at least `bytes` from the context's cache (an idle block of up to 4x the size, else a new hipMalloc); stream-ordered
-// reuse: every user of these blocks works on the context's stream
+// device block of at least `bytes` from the context's cache (an idle block of up to 4x the size, else a new hipMalloc); the rule of
+// use is stated at sfmhip_ctx::pool
 int  sfm_pool_get(sfmhip_ctx* ctx, size_t bytes, void** out);
 void sfm_pool_put(sfmhip_ctx* ctx, void* p);
 void sfm_pool_trim(sfmhip_ctx* ctx);
@@ -203,25 +180,27 @@ struct SfmPoolHold {
         if (rc == SFMHIP_OK) { if (n_few < 4) few[n_few++] = *out; else more.push_back(*out); }
         return rc;
     }
+    template <typename T> int get(T** out, size_t count) { return get((count > 0 ? count : 1) * sizeof(T), (void**)out); }
     SfmPoolHold(const SfmPoolHold&) = delete;
     SfmPoolHold& operator=(const SfmPoolHold&) = delete;
 };
 
-// the call shape of the host entry points of points.hip and normals.hip: upload the cloud, enqueue, download, finish
+// the call shape of the host entry points of points.hip, normals.hip and triangulate.hip: hold, upload, enqueue, download, finish
 static inline bool points_method_ok(int method) { return method == SFMHIP_POINTS_AUTO || method == SFMHIP_POINTS_BRUTE || method == SFMHIP_POINTS_GRID; }
-// the cloud's device block (n x 3 double) from `hold`, filled from the caller's array on the context's stream
-static inline int points_upload(sfmhip_ctx* ctx, SfmPoolHold& hold, const double* pts, int n, double*& d_p)
+// a device block of `count` elements from `hold`, filled from the caller's array on the context's stream
+template <typename T>
+static inline int sfm_upload_async(sfmhip_ctx* ctx, SfmPoolHold& hold, const T* src, size_t count, T*& d)
 {
-    const int rc = hold.get((size_t)n * 24, (void**)&d_p);
+    const int rc = hold.get(&d, count);
     if (rc != SFMHIP_OK) return rc;
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_p, pts, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return SFMHIP_OK;
 }
 // a step failed with rc while work may be in flight: drain the stream (the blocks go back to the cache behind this call), return rc
-static inline int points_drain(sfmhip_ctx* ctx, int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-// the end of a call, also after an error with work possibly in flight: drain the stream (the caller's host buffers may be targets of
-// copies), keep the first error
-static inline int points_finish(sfmhip_ctx* ctx, hipError_t e)
+static inline int sfm_drain(sfmhip_ctx* ctx, int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+// the end of a call, also after an error with work possibly in flight: drain the stream (the caller's host buffers may be sources or
+// targets of copies), keep the first error
+static inline int sfm_finish(sfmhip_ctx* ctx, hipError_t e)
 {
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = e2;

@@ -196,8 +196,6 @@ void sfmhip_destroy(sfmhip_ctx* ctx)
     sfm_rccl_forget_ctx(ctx);
     for (auto& b : ctx->pool) (void)hipFree(b.p);
     if (ctx->d_flagpool) (void)hipFree(ctx->d_flagpool);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->scratch2) (void)hipFree(ctx->scratch2);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     free(ctx->host_scratch);
     delete ctx->copy_pool;

@@ -1658,12 +1658,12 @@ static int stage_host_images(sfmhip_ctx* ctx, SfmPoolHold& hold, const T* const*
     });
 }
 
-// a table of per-image descriptors to the device (scratch2: consumed by the launches that follow), then launch(table)
+// a table of per-image descriptors to the device (a block of `hold`: consumed by the launches that follow), then launch(table)
 template <class Launch>
-static int launch_with_table(sfmhip_ctx* ctx, const void* table, size_t bytes, const Launch& launch)
+static int launch_with_table(sfmhip_ctx* ctx, SfmPoolHold& hold, const void* table, size_t bytes, const Launch& launch)
 {
     void* d_tbl = nullptr;
-    const int rc = sfm_scratch2(ctx, bytes, &d_tbl); if (rc) return rc;
+    const int rc = hold.get(bytes, &d_tbl); if (rc) return rc;
     if (sfm_upload(ctx, d_tbl, table, bytes) != SFMHIP_OK) return SFMHIP_E_HIP;     // (the table is consumed on return)
     launch(d_tbl);
     return hip_rc(ctx, hipGetLastError());
@@ -1706,7 +1706,7 @@ int sfmhip_descsets_create_l2_host(sfmhip_ctx* ctx, const float* const* desc, co
     if (n == 0) return SFMHIP_OK;
     const bool bytes_ok = dim == 32 || dim == 64 || dim == 128;        // the int8 copy has no padding columns and a lane takes 16 values
     std::vector<int> bad((size_t)n, bytes_ok ? 0 : 1);
-    SfmPoolHold hold(ctx);          // the byte rows: read only by the launch enqueued below (stream-ordered reuse)
+    SfmPoolHold hold(ctx);          // the byte rows and the table: read only by the launch enqueued below (stream-ordered reuse)
     std::vector<long long> first; uint8_t* d_u8 = nullptr;
     int rc = SFMHIP_OK;
     if (bytes_ok) rc = stage_host_images(ctx, hold, desc, rows, ld, n, dim, first, &d_u8, [&](int img, const float* src, size_t l, long long run, uint8_t* dst) {
@@ -1728,7 +1728,7 @@ int sfmhip_descsets_create_l2_host(sfmhip_ctx* ctx, const float* const* desc, co
         max_pad = std::max(max_pad, s->rows_pad);
     }
     if (rc == SFMHIP_OK && !tbl.empty())
-        rc = launch_with_table(ctx, tbl.data(), tbl.size() * sizeof(PrepU8Desc), [&](const void* d_tbl) {
+        rc = launch_with_table(ctx, hold, tbl.data(), tbl.size() * sizeof(PrepU8Desc), [&](const void* d_tbl) {
             hipLaunchKernelGGL(prep_l2_u8_batched_kernel, dim3(ceil_div(max_pad, prep_l2_rows_per_block(true, dim, dim)), (unsigned)tbl.size()), dim3(256), 0, ctx->stream, (const PrepU8Desc*)d_tbl);
         });
     if (rc) descsets_destroy_all(out, n);
@@ -1743,7 +1743,7 @@ int sfmhip_descsets_create_hamming2_host(sfmhip_ctx* ctx, const uint8_t* const* 
     SFM_ARG_CHECK(ctx, ctx && out && (n == 0 || (desc && rows)) && n >= 0 && nbytes > 0 && nbytes <= 64);
     for (int i = 0; i < n; ++i) { out[i] = nullptr; SFM_ARG_CHECK(ctx, rows[i] >= 0 && (desc[i] || rows[i] == 0) && (!ld || ld[i] >= (size_t)nbytes)); }
     if (n == 0) return SFMHIP_OK;
-    SfmPoolHold hold(ctx);          // the byte rows: read only by the launches enqueued below (stream-ordered reuse)
+    SfmPoolHold hold(ctx);          // the byte rows and the table: read only by the launches enqueued below (stream-ordered reuse)
     std::vector<long long> first; uint8_t* d_u8 = nullptr;
     int rc = stage_host_images(ctx, hold, desc, rows, ld, n, nbytes, first, &d_u8, [&](int, const uint8_t* src, size_t l, long long run, uint8_t* dst) {
         if (l == (size_t)nbytes) memcpy(dst, src, (size_t)run * nbytes);          // a dense image: its run in one piece
@@ -1760,7 +1760,7 @@ int sfmhip_descsets_create_hamming2_host(sfmhip_ctx* ctx, const uint8_t* const* 
         max_pad = std::max(max_pad, s->rows_pad);
     }
     if (rc == SFMHIP_OK)
-        rc = launch_with_table(ctx, tbl.data(), tbl.size() * sizeof(PrepHamDesc), [&](const void* d_tbl) {
+        rc = launch_with_table(ctx, hold, tbl.data(), tbl.size() * sizeof(PrepHamDesc), [&](const void* d_tbl) {
             hipLaunchKernelGGL(prep_hamming_batched_kernel, dim3((unsigned)(((size_t)max_pad * 8 + 255) / 256), (unsigned)n), dim3(256), 0, ctx->stream, (const PrepHamDesc*)d_tbl);
             if (nbytes <= H4_MAX_NBYTES)
                 hipLaunchKernelGGL(prep_hamming_fp4_batched_kernel, dim3((unsigned)(((size_t)max_pad * 96 + 255) / 256), (unsigned)n), dim3(256), 0, ctx->stream, (const PrepHamDesc*)d_tbl);
@@ -1857,8 +1857,9 @@ int sfmhip_descsets_refresh(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n)
         if (s->rows_pad > max_pad) max_pad = s->rows_pad;
     }
     if (tbl.empty()) return SFMHIP_OK;
-    void* d_tbl = nullptr;
-    int rc = sfm_scratch2(ctx, tbl.size() * sizeof(PrepDesc), &d_tbl); if (rc) return rc;
+    SfmPoolHold hold(ctx);          // the table: read only by the launch below (stream-ordered reuse)
+    PrepDesc* d_tbl = nullptr;
+    const int rc = hold.get(&d_tbl, tbl.size()); if (rc) return rc;
     SFM_HIP_TRY(ctx, hipMemcpyAsync(d_tbl, tbl.data(), tbl.size() * sizeof(PrepDesc), hipMemcpyHostToDevice, ctx->stream));
     // rows per block: the smallest over the batch (16 values per lane when every image qualifies, else 4: >= 2 rows per wave)
     for (const PrepDesc& d : tbl) rows_per_block = std::min(rows_per_block, prep_l2_rows_per_block(fast, d.dim, d.dim_pad));
@@ -1987,14 +1988,15 @@ static int plan_pairs(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, 
 
 struct KnnWork { PairDesc* d_pd; long long* d_part; int* d_list; int* d_count; };
 
-static int knn_workspace(sfmhip_ctx* ctx, const KnnPlan& P, int n_pairs, KnnWork& W)
+// the workspace of a plan: one block of `hold`, carved up
+static int knn_workspace(sfmhip_ctx* ctx, SfmPoolHold& hold, const KnnPlan& P, int n_pairs, KnnWork& W)
 {
     const size_t b_pd = (sizeof(PairDesc) * n_pairs + 255) / 256 * 256;
     const size_t b_part = ((size_t)P.part_entries * 16 + 255) / 256 * 256;
     const size_t b_list = ((size_t)P.list_entries * 4 + 255) / 256 * 256;
     const size_t b_cnt = ((size_t)n_pairs * 4 + 255) / 256 * 256;
     void* base = nullptr;
-    int rc = sfm_scratch(ctx, b_pd + b_part + b_list + b_cnt, &base);
+    int rc = hold.get(b_pd + b_part + b_list + b_cnt, &base);
     if (rc != SFMHIP_OK) return rc;
     char* p = (char*)base;
     W.d_pd = (PairDesc*)p; p += b_pd;
@@ -2105,7 +2107,8 @@ int sfmhip_knn2_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const sfmhip_d
     const OnePair one(query, train);
     KnnPlan P; KnnWork W;
     int rc = plan_pairs(ctx, one.sets, 2, one.pairs, 1, force_path, P); if (rc) return rc;
-    rc = knn_workspace(ctx, P, 1, W); if (rc) return rc;
+    SfmPoolHold hold(ctx);          // the workspace: read only by what this call enqueues (stream-ordered reuse)
+    rc = knn_workspace(ctx, hold, P, 1, W); if (rc) return rc;
     return knn2_pairs_enqueue(ctx, P, W, 1, d_idx2, d_dist2);
 }
 
@@ -2114,8 +2117,9 @@ int sfmhip_knn2_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const sfmhip_d
 // Forward kNN-2 (d_idx2 / d_dist2) and the reverse best of every train row (d_rev_idx / d_rev_dist at rev_off[p] + train row) of all
 // pairs.  The paths with a fused reverse (int8, FP4 Hamming2) find the reverse best inside their kNN kernels (knn2_i8_mutual_kernel,
 // knn2_hamming2_fp4_mutual_kernel); the exact fp32 and VALU Hamming2 paths run one more kNN-2 launch sequence with query and train
-// swapped -- every distance they compute is symmetric in its operands bit for bit -- and take its column 0.  On return the forward plan and workspace are in P / W (the ratio tail reads W.d_pd).
-static int knn2_mutual_enqueue(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets, const int32_t* pairs, int n_pairs, int force_path,
+// swapped -- every distance they compute is symmetric in its operands bit for bit -- and take its column 0.  On return the forward plan and
+// workspace are in P / W (the ratio tail reads W.d_pd); W and the reverse keys are blocks of `hold`.
+static int knn2_mutual_enqueue(sfmhip_ctx* ctx, SfmPoolHold& hold, sfmhip_descset* const* sets, int n_sets, const int32_t* pairs, int n_pairs, int force_path,
                                KnnPlan& P, KnnWork& W, int32_t* d_idx2, float* d_dist2, int32_t* d_rev_idx, float* d_rev_dist,
                                const long long* d_rev_off, long long rev_total)
 {
@@ -2128,21 +2132,22 @@ static int knn2_mutual_enqueue(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int
             for (int p = 0; p < n_pairs; ++p) { sw[2 * p] = pairs[2 * p + 1]; sw[2 * p + 1] = pairs[2 * p]; }
             KnnPlan P2; KnnWork W2;
             rc = plan_pairs(ctx, sets, n_sets, sw.data(), n_pairs, force_path, P2); if (rc) return rc;
-            rc = knn_workspace(ctx, P2, n_pairs, W2); if (rc) return rc;
-            SfmPoolHold hold(ctx);          // the swapped pass's kNN-2: read only by the launch below (stream-ordered reuse)
+            // the swapped pass's workspace and kNN-2: read only by what this scope enqueues, and back in the cache before the forward
+            // pass asks for its workspace, which may be the same block behind them on the stream (stream-ordered reuse)
+            SfmPoolHold swapped(ctx);
+            rc = knn_workspace(ctx, swapped, P2, n_pairs, W2); if (rc) return rc;
             void* tmp = nullptr;
-            rc = hold.get((size_t)rev_total * 16, &tmp); if (rc) return rc;
+            rc = swapped.get((size_t)rev_total * 16, &tmp); if (rc) return rc;
             int32_t* t_idx = (int32_t*)tmp; float* t_dist = (float*)((char*)tmp + (size_t)rev_total * 8);
             rc = knn2_pairs_enqueue(ctx, P2, W2, n_pairs, t_idx, t_dist); if (rc) return rc;     // rows of pair p at P2.pd[p].out_off = rev_off[p]
             hipLaunchKernelGGL(rev_from_knn_kernel, dim3((unsigned)((rev_total + 255) / 256)), dim3(256), 0, ctx->stream, t_idx, t_dist, rev_total, d_rev_idx, d_rev_dist);
             rc = hip_rc(ctx, hipGetLastError()); if (rc) return rc;
         }
-        rc = knn_workspace(ctx, P, n_pairs, W); if (rc) return rc;
+        rc = knn_workspace(ctx, hold, P, n_pairs, W); if (rc) return rc;
         return knn2_pairs_enqueue(ctx, P, W, n_pairs, d_idx2, d_dist2);
     }
-    rc = knn_workspace(ctx, P, n_pairs, W); if (rc) return rc;
-    SfmPoolHold hold(ctx);          // the reverse keys and the re-score list
-    void* tmp = nullptr;
+    rc = knn_workspace(ctx, hold, P, n_pairs, W); if (rc) return rc;
+    void* tmp = nullptr;          // the reverse keys and the re-score list
     const size_t nk = (size_t)std::max<long long>(rev_total, 1);
     rc = hold.get(nk * 8 + nk * 8 + 256, &tmp); if (rc) return rc;
     RevArgs R;
@@ -2181,7 +2186,7 @@ int sfmhip_knn2_mutual_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const s
     std::vector<long long> off; long long total = 0, *d_off = nullptr;
     const int rc = rev_offsets(ctx, hold, one.sets, 2, one.pairs, 1, off, total, &d_off); if (rc) return rc;
     KnnPlan P; KnnWork W;
-    return knn2_mutual_enqueue(ctx, one.sets, 2, one.pairs, 1, force_path, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total);
+    return knn2_mutual_enqueue(ctx, hold, one.sets, 2, one.pairs, 1, force_path, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total);
 }
 
 int sfmhip_match_pairs_ex_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_sets,
@@ -2198,7 +2203,7 @@ int sfmhip_match_pairs_ex_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int 
     int max_nq = 0;
     for (int p = 0; p < n_pairs; ++p) { const int a = pairs[2 * p]; SFM_ARG_CHECK(ctx, a >= 0 && a < n_sets && sets[a]); max_nq = std::max(max_nq, sets[a]->rows); }
     SFM_ARG_CHECK(ctx, max_per_pair >= max_nq);
-    SfmPoolHold hold(ctx);          // both blocks are read only by what this call enqueues (stream-ordered reuse)
+    SfmPoolHold hold(ctx);          // every block is read only by what this call enqueues (stream-ordered reuse)
     std::vector<long long> off; long long total = 0, *d_off = nullptr;
     int rc = rev_offsets(ctx, hold, sets, n_sets, pairs, n_pairs, off, total, &d_off); if (rc) return rc;
     // reverse results, then the plain tail's lists and counts (filtered into the caller's buffers)
@@ -2212,9 +2217,9 @@ int sfmhip_match_pairs_ex_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int 
     long long rows_total = 0;
     for (int p = 0; p < n_pairs; ++p) rows_total += sets[pairs[2 * p]]->rows;
     const size_t rows = (size_t)(rows_total > 0 ? rows_total : 1);
-    rc = sfm_scratch2(ctx, rows * 16, &tmp); if (rc) return rc;
+    rc = hold.get(rows * 16, &tmp); if (rc) return rc;
     int32_t* d_idx2 = (int32_t*)tmp; float* d_dist2 = (float*)((char*)tmp + rows * 8);
-    rc = knn2_mutual_enqueue(ctx, sets, n_sets, pairs, n_pairs, 0, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total); if (rc) return rc;
+    rc = knn2_mutual_enqueue(ctx, hold, sets, n_sets, pairs, n_pairs, 0, P, W, d_idx2, d_dist2, d_rev_idx, d_rev_dist, d_off, total); if (rc) return rc;
     hipLaunchKernelGGL(ratio_tail_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, W.d_pd, d_idx2, d_dist2,
                        ratio, floor_, mult, d_plain, max_per_pair, d_plain_counts);
     hipLaunchKernelGGL(mutual_filter_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, (const sfm_dmatch*)d_plain, (const int32_t*)d_plain_counts,
@@ -2233,10 +2238,11 @@ int sfmhip_match_pairs_dev(sfmhip_ctx* ctx, sfmhip_descset* const* sets, int n_s
     KnnPlan P; KnnWork W;
     int rc = plan_pairs(ctx, sets, n_sets, pairs, n_pairs, 0, P); if (rc) return rc;
     SFM_ARG_CHECK(ctx, max_per_pair >= P.max_nq);
-    rc = knn_workspace(ctx, P, n_pairs, W); if (rc) return rc;
+    SfmPoolHold hold(ctx);          // workspace and kNN-2 rows: read only by what this call enqueues (stream-ordered reuse)
+    rc = knn_workspace(ctx, hold, P, n_pairs, W); if (rc) return rc;
     void* tmp = nullptr;
     const size_t rows = (size_t)(P.out_rows > 0 ? P.out_rows : 1);
-    rc = sfm_scratch2(ctx, rows * 16, &tmp); if (rc) return rc;
+    rc = hold.get(rows * 16, &tmp); if (rc) return rc;
     int32_t* d_idx2 = (int32_t*)tmp; float* d_dist2 = (float*)((char*)tmp + rows * 8);
     rc = knn2_pairs_enqueue(ctx, P, W, n_pairs, d_idx2, d_dist2); if (rc) return rc;
     hipLaunchKernelGGL(ratio_tail_kernel, dim3(n_pairs), dim3(1024), 0, ctx->stream, W.d_pd, d_idx2, d_dist2,
@@ -2367,14 +2373,15 @@ int sfmhip_selftest_exact_sqrt(sfmhip_ctx* ctx, int* mismatches)
 {
     SFM_DEVICE_GUARD(ctx);
     SFM_ARG_CHECK(ctx, ctx && mismatches);
+    SfmPoolHold hold(ctx);
     int* d = nullptr;
-    SFM_HIP_TRY(ctx, hipMalloc((void**)&d, sizeof(int)));
-    SFM_HIP_TRY(ctx, hipMemsetAsync(d, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(sqrt_check_kernel, dim3((1 << 24) / 256), dim3(256), 0, ctx->stream, d);
-    hipError_t e = hipMemcpyAsync(mismatches, d, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    return hip_rc(ctx, e);
+    const int rc = hold.get(&d, 1); if (rc) return rc;
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(int), ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(sqrt_check_kernel, dim3((1 << 24) / 256), dim3(256), 0, ctx->stream, d);
+        e = hipMemcpyAsync(mismatches, d, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    return sfm_finish(ctx, e);
 }
 
 int sfmhip_l2_distance_matrix_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, const sfmhip_descset* train,
@@ -2426,7 +2433,8 @@ int sfmhip_l2_distance_matrix_dev(sfmhip_ctx* ctx, const sfmhip_descset* query, 
     const OnePair one(query, train);
     KnnPlan P; KnnWork W;
     int rc = plan_pairs(ctx, one.sets, 2, one.pairs, 1, KNN_EXACT_F32, P); if (rc) return rc;
-    rc = knn_workspace(ctx, P, 1, W); if (rc) return rc;
+    SfmPoolHold hold(ctx);          // the workspace: read only by the launch below (stream-ordered reuse)
+    rc = knn_workspace(ctx, hold, P, 1, W); if (rc) return rc;
     if (P.aligned) launch_exact<true, true>(ctx, P, W, 1, false, d_dist, ld); else launch_exact<false, true>(ctx, P, W, 1, false, d_dist, ld);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;

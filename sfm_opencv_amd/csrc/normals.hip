@@ -156,19 +156,19 @@ extern "C" int sfmhip_estimate_normals_ex(sfmhip_ctx* ctx, const double* pts, in
     if (method == SFMHIP_POINTS_AUTO) method = sfm_points_auto_method(n);
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_n = nullptr; int32_t* d_idx = nullptr;
-    int rc = points_upload(ctx, hold, pts, n, d_p);
+    int rc = sfm_upload_async(ctx, hold, pts, 3 * (size_t)n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_n);
     if (rc == SFMHIP_OK && method == SFMHIP_POINTS_GRID) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_idx);
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     if (method == SFMHIP_POINTS_GRID) {
         rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_idx, nullptr);
         if (rc == SFMHIP_OK) rc = sfm_normals_from_knn_enqueue(ctx, d_p, d_idx, n, K, d_n);
-        if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+        if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     } else {
         hipLaunchKernelGGL(normals_kernel, dim3(ceil_div(n, NTILE)), dim3(NTILE), 0, ctx->stream, d_p, n, K, d_n);
         SFM_HIP_TRY(ctx, hipGetLastError());
     }
-    return points_finish(ctx, hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
+    return sfm_finish(ctx, hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
 }
 
 extern "C" int sfmhip_estimate_normals(sfmhip_ctx* ctx, const double* pts, int n, int K, double* normals)
@@ -187,7 +187,7 @@ extern "C" int sfmhip_estimate_normals_hybrid(sfmhip_ctx* ctx, const double* pts
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_n = nullptr, *d_dist = nullptr; int32_t* d_idx = nullptr;
     const size_t total = (size_t)n * K;
-    int rc = points_upload(ctx, hold, pts, n, d_p);
+    int rc = sfm_upload_async(ctx, hold, pts, 3 * (size_t)n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_n);
     if (rc == SFMHIP_OK) rc = hold.get(total * sizeof(int32_t), (void**)&d_idx);
     if (rc == SFMHIP_OK) rc = hold.get(total * sizeof(double), (void**)&d_dist);
@@ -196,6 +196,6 @@ extern "C" int sfmhip_estimate_normals_hybrid(sfmhip_ctx* ctx, const double* pts
         hipLaunchKernelGGL(normals_radius_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_idx, (const double*)d_dist, total, r);
         rc = sfm_normals_from_knn_enqueue(ctx, d_p, d_idx, n, K, d_n);
     }
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
-    return points_finish(ctx, hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
+    return sfm_finish(ctx, hipMemcpyAsync(normals, d_n, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
 }

@@ -1024,15 +1024,15 @@ int sfmhip_knn_points(sfmhip_ctx* ctx, const double* pts, int n, int K, int meth
     if (!idx && !dist) return SFMHIP_OK;
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_d = nullptr; int32_t* d_i = nullptr;
-    int rc = points_upload(ctx, hold, pts, n, d_p);
+    int rc = sfm_upload_async(ctx, hold, pts, 3 * (size_t)n, d_p);
     if (rc == SFMHIP_OK && idx) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_i);
     if (rc == SFMHIP_OK && dist) rc = hold.get((size_t)n * K * sizeof(double), (void**)&d_d);
     if (rc == SFMHIP_OK) rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     hipError_t e = hipSuccess;
     if (idx) e = hipMemcpyAsync(idx, d_i, (size_t)n * K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && dist) e = hipMemcpyAsync(dist, d_d, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    return points_finish(ctx, e);
+    return sfm_finish(ctx, e);
 }
 
 int sfmhip_statistical_outliers(sfmhip_ctx* ctx, const double* pts, int n, int K, double std_ratio, int method, uint8_t* keep, double* mean_dist, double stats[3])
@@ -1045,14 +1045,14 @@ int sfmhip_statistical_outliers(sfmhip_ctx* ctx, const double* pts, int n, int K
     const int nt = ceil_div(n, RED_TILE);
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_d = nullptr, *d_m = nullptr, *d_part = nullptr; int32_t* d_i = nullptr; uint8_t* d_keep = nullptr;
-    int rc = points_upload(ctx, hold, pts, n, d_p);
+    int rc = sfm_upload_async(ctx, hold, pts, 3 * (size_t)n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * K * sizeof(int32_t), (void**)&d_i);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * K * sizeof(double), (void**)&d_d);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(double), (void**)&d_m);
     if (rc == SFMHIP_OK) rc = hold.get(((size_t)2 * nt + 4) * sizeof(double), (void**)&d_part);       // tile sums, then stats[3]
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n, (void**)&d_keep);
     if (rc == SFMHIP_OK) rc = sfm_points_knn_enqueue(ctx, d_p, n, K, method, d_i, d_d);
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     double* d_stats = d_part + 2 * (size_t)nt;
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(points_mean_dist_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const int32_t*)d_i, (const double*)d_d, n, K, d_m);
@@ -1065,7 +1065,7 @@ int sfmhip_statistical_outliers(sfmhip_ctx* ctx, const double* pts, int n, int K
     if (e == hipSuccess) e = hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && mean_dist) e = hipMemcpyAsync(mean_dist, d_m, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && stats) e = hipMemcpyAsync(stats, d_stats, 3 * sizeof(double), hipMemcpyDeviceToHost, st);
-    return points_finish(ctx, e);
+    return sfm_finish(ctx, e);
 }
 
 int sfmhip_radius_count_dev(sfmhip_ctx* ctx, const double* d_pts, int n, double r, int method, int32_t* d_count)
@@ -1083,11 +1083,11 @@ static int radius_count_host(sfmhip_ctx* ctx, const double* pts, int n, double r
 {
     SfmPoolHold hold(ctx);
     double* d_p = nullptr; int32_t* d_c = nullptr; uint8_t* d_keep = nullptr;
-    int rc = points_upload(ctx, hold, pts, n, d_p);
+    int rc = sfm_upload_async(ctx, hold, pts, 3 * (size_t)n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_c);
     if (rc == SFMHIP_OK && keep) rc = hold.get((size_t)n, (void**)&d_keep);
     if (rc == SFMHIP_OK) rc = points_radius_count_enqueue(ctx, d_p, n, r, method, d_c);
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
     if (keep) {
@@ -1096,7 +1096,7 @@ static int radius_count_host(sfmhip_ctx* ctx, const double* pts, int n, double r
         if (e == hipSuccess) e = hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess && count) e = hipMemcpyAsync(count, d_c, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    return points_finish(ctx, e);
+    return sfm_finish(ctx, e);
 }
 
 int sfmhip_radius_count(sfmhip_ctx* ctx, const double* pts, int n, double r, int method, int32_t* count)
@@ -1141,18 +1141,18 @@ int sfmhip_voxel_downsample(sfmhip_ctx* ctx, const double* pts, int n, double vo
     *n_voxels = 0;
     SfmPoolHold hold(ctx);
     double *d_p = nullptr, *d_c = nullptr, *d_org = nullptr; int32_t *d_cnt = nullptr, *d_vof = nullptr, *d_nv = nullptr;
-    int rc = points_upload(ctx, hold, pts, n, d_p);
+    int rc = sfm_upload_async(ctx, hold, pts, 3 * (size_t)n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * 24, (void**)&d_c);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_cnt);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_vof);
     if (rc == SFMHIP_OK) rc = hold.get(256, (void**)&d_org);               // origin[3], then n_voxels
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     d_nv = (int32_t*)(d_org + 4);
     rc = voxel_downsample_enqueue(ctx, d_p, n, voxel, d_c, d_cnt, d_vof, d_nv, d_org);
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     hipStream_t st = ctx->stream;
     int32_t nv = 0;
-    rc = points_finish(ctx, hipMemcpyAsync(&nv, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    rc = sfm_finish(ctx, hipMemcpyAsync(&nv, d_nv, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (rc != SFMHIP_OK) return rc;
     if (nv < 0) {
         ctx->last_error = "bad argument: the voxel is too small for the cloud's extent (more than 2^21 voxels along an axis; filter far outliers first)";
@@ -1163,7 +1163,7 @@ int sfmhip_voxel_downsample(sfmhip_ctx* ctx, const double* pts, int n, double vo
     if (e == hipSuccess && counts && nv > 0) e = hipMemcpyAsync(counts, d_cnt, (size_t)nv * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && voxel_of) e = hipMemcpyAsync(voxel_of, d_vof, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && origin) e = hipMemcpyAsync(origin, d_org, 3 * sizeof(double), hipMemcpyDeviceToHost, st);
-    rc = points_finish(ctx, e);
+    rc = sfm_finish(ctx, e);
     if (rc == SFMHIP_OK) *n_voxels = nv;
     return rc;
 }
@@ -1185,14 +1185,14 @@ static int cluster_host(sfmhip_ctx* ctx, const double* pts, int n, double r, int
 {
     SfmPoolHold hold(ctx);
     double* d_p = nullptr; int32_t *d_lab = nullptr, *d_sz = nullptr, *d_cnt = nullptr, *d_head = nullptr; uint8_t* d_keep = nullptr;
-    int rc = points_upload(ctx, hold, pts, n, d_p);
+    int rc = sfm_upload_async(ctx, hold, pts, 3 * (size_t)n, d_p);
     if (rc == SFMHIP_OK) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_lab);
     if (rc == SFMHIP_OK && (sizes || keep)) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_sz);
     if (rc == SFMHIP_OK && count) rc = hold.get((size_t)n * sizeof(int32_t), (void**)&d_cnt);
     if (rc == SFMHIP_OK && keep) rc = hold.get((size_t)n, (void**)&d_keep);
     if (rc == SFMHIP_OK) rc = hold.get(256, (void**)&d_head);              // n_clusters, then the largest cluster's number and size
     if (rc == SFMHIP_OK) rc = cluster_dbscan_enqueue(ctx, d_p, n, r, min_points, method, d_lab, d_head, d_sz, d_cnt);
-    if (rc != SFMHIP_OK) return points_drain(ctx, rc);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     hipStream_t st = ctx->stream;
     if (keep) {
         hipLaunchKernelGGL(cluster_largest_kernel, dim3(1), dim3(256), 0, st, (const int32_t*)d_sz, (const int32_t*)d_head, d_head + 1);
@@ -1201,7 +1201,7 @@ static int cluster_host(sfmhip_ctx* ctx, const double* pts, int n, double r, int
     int32_t head[3] = { 0, -1, 0 };
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(head, d_head, (keep ? 3 : 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    rc = points_finish(ctx, e);
+    rc = sfm_finish(ctx, e);
     if (rc != SFMHIP_OK) return rc;
     if (head[0] < 0) {
         ctx->last_error = "clustering: a union exceeded its retry cap (the parent array broke its invariant); no result";
@@ -1212,7 +1212,7 @@ static int cluster_host(sfmhip_ctx* ctx, const double* pts, int n, double r, int
     if (e == hipSuccess && sizes && head[0] > 0) e = hipMemcpyAsync(sizes, d_sz, (size_t)head[0] * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && count) e = hipMemcpyAsync(count, d_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && keep) e = hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, st);
-    rc = points_finish(ctx, e);
+    rc = sfm_finish(ctx, e);
     if (rc != SFMHIP_OK) return rc;
     if (n_clusters) *n_clusters = head[0];
     if (largest_size) *largest_size = head[2];

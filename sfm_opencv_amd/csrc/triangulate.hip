@@ -230,21 +230,17 @@ int sfmhip_triangulate2_f32(sfmhip_ctx* ctx, const float P1[12], const float P2[
     SFM_DEVICE_GUARD(ctx);
     SFM_RANGE("sfmhip_triangulate2_f32");
     SFM_ARG_CHECK(ctx, ctx && P1 && P2 && xy1 && xy2 && n > 0 && (xyzw || xyz));
+    SfmPoolHold hold(ctx);
     float *d1 = nullptr, *d2 = nullptr, *dw = nullptr; double* dx = nullptr;
-    int rc = SFMHIP_OK;
-    hipError_t e = hipMalloc((void**)&d1, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d2, (size_t)n * 8);
-    if (e == hipSuccess && xyzw) e = hipMalloc((void**)&dw, (size_t)n * 16);
-    if (e == hipSuccess && xyz) e = hipMalloc((void**)&dx, (size_t)n * 24);
-    if (e == hipSuccess) e = hipMemcpyAsync(d1, xy1, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d2, xy2, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) rc = sfmhip_triangulate2_f32_dev(ctx, P1, P2, d1, d2, n, dw, dx);
-    if (e == hipSuccess && rc == SFMHIP_OK && xyzw) e = hipMemcpyAsync(xyzw, dw, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && rc == SFMHIP_OK && xyz) e = hipMemcpyAsync(xyz, dx, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = SFMHIP_E_HIP; }
-    (void)hipFree(d1); (void)hipFree(d2); (void)hipFree(dw); (void)hipFree(dx);
-    return rc;
+    int rc = sfm_upload_async(ctx, hold, xy1, 2 * (size_t)n, d1);
+    if (rc == SFMHIP_OK) rc = sfm_upload_async(ctx, hold, xy2, 2 * (size_t)n, d2);
+    if (rc == SFMHIP_OK && xyzw) rc = hold.get(&dw, 4 * (size_t)n);
+    if (rc == SFMHIP_OK && xyz) rc = hold.get(&dx, 3 * (size_t)n);
+    if (rc == SFMHIP_OK) rc = sfmhip_triangulate2_f32_dev(ctx, P1, P2, d1, d2, n, dw, dx);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
+    hipError_t e = xyzw ? hipMemcpyAsync(xyzw, dw, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+    if (e == hipSuccess && xyz) e = hipMemcpyAsync(xyz, dx, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream);
+    return sfm_finish(ctx, e);
 }
 
 
@@ -270,22 +266,24 @@ int sfmhip_triangulate_tracks(sfmhip_ctx* ctx, const double K4[4], const double*
     for (int c = 0; c < n_cam; ++c) angle_axis_to_Rt(ext6 + 6 * c, Rt.data() + 12 * c);
     const size_t b_rt = (Rt.size() * 8 + 255) / 256 * 256, b_st = (pt_start.size() * 4 + 255) / 256 * 256, b_oc = (ocam.size() * 4 + 255) / 256 * 256;
     const size_t b_uv = (ouv.size() * 8 + 255) / 256 * 256, b_pt = ((size_t)n_pt * 24 + 255) / 256 * 256, b_nv = ((size_t)n_pt * 4 + 255) / 256 * 256;
-    void* base = nullptr;
-    int rc = sfm_scratch(ctx, b_rt + b_st + b_oc + b_uv + b_pt + b_nv, &base); if (rc) return rc;
-    char* c0 = (char*)base;
+    SfmPoolHold hold(ctx);
+    char* c0 = nullptr;
+    const int rc = hold.get(b_rt + b_st + b_oc + b_uv + b_pt + b_nv, (void**)&c0); if (rc) return rc;
     double* d_rt = (double*)c0; int* d_st = (int*)(c0 + b_rt); int* d_oc = (int*)(c0 + b_rt + b_st); double* d_uv = (double*)(c0 + b_rt + b_st + b_oc);
     double* d_pt = (double*)(c0 + b_rt + b_st + b_oc + b_uv); int* d_nv = (int*)(c0 + b_rt + b_st + b_oc + b_uv + b_pt);
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_rt, Rt.data(), Rt.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_st, pt_start.data(), pt_start.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_oc, ocam.data(), ocam.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_uv, ouv.data(), ouv.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(triangulate_tracks_kernel, dim3((n_pt + 255) / 256), dim3(256), 0, ctx->stream, d_rt, K4[0], K4[1], K4[2], K4[3],
-                       d_st, d_oc, d_uv, n_pt, d_pt, d_nv);
-    SFM_HIP_TRY(ctx, hipGetLastError());
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(pts_out, d_pt, (size_t)n_pt * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_views_out) SFM_HIP_TRY(ctx, hipMemcpyAsync(n_views_out, d_nv, (size_t)n_pt * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SFMHIP_OK;
+    // (the host vectors are sources of these copies: every way out from here drains the stream in sfm_finish)
+    hipError_t e = hipMemcpyAsync(d_rt, Rt.data(), Rt.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_st, pt_start.data(), pt_start.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_oc, ocam.data(), ocam.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_uv, ouv.data(), ouv.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(triangulate_tracks_kernel, dim3((n_pt + 255) / 256), dim3(256), 0, ctx->stream, d_rt, K4[0], K4[1], K4[2], K4[3],
+                           d_st, d_oc, d_uv, n_pt, d_pt, d_nv);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(pts_out, d_pt, (size_t)n_pt * 24, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && n_views_out) e = hipMemcpyAsync(n_views_out, d_nv, (size_t)n_pt * 4, hipMemcpyDeviceToHost, ctx->stream);
+    return sfm_finish(ctx, e);
 }
 
 int sfmhip_reprojection_errors(sfmhip_ctx* ctx, const double K4[4], const double* ext6, int n_cam, const double* pts, int n_pt,
@@ -301,22 +299,23 @@ int sfmhip_reprojection_errors(sfmhip_ctx* ctx, const double K4[4], const double
     for (int c = 0; c < n_cam; ++c) angle_axis_to_Rt(ext6 + 6 * c, Rt.data() + 12 * c);
     const size_t b_rt = (Rt.size() * 8 + 255) / 256 * 256, b_pt = ((size_t)n_pt * 24 + 255) / 256 * 256, b_i = ((size_t)n_obs * 4 + 255) / 256 * 256;
     const size_t b_uv = ((size_t)n_obs * 16 + 255) / 256 * 256, b_e = ((size_t)n_obs * 8 + 255) / 256 * 256;
-    void* base = nullptr;
-    int rc = sfm_scratch(ctx, b_rt + b_pt + 2 * b_i + b_uv + b_e, &base); if (rc) return rc;
-    char* c0 = (char*)base;
+    SfmPoolHold hold(ctx);
+    char* c0 = nullptr;
+    const int rc = hold.get(b_rt + b_pt + 2 * b_i + b_uv + b_e, (void**)&c0); if (rc) return rc;
     double* d_rt = (double*)c0; double* d_pt = (double*)(c0 + b_rt); int* d_oc = (int*)(c0 + b_rt + b_pt); int* d_op = (int*)(c0 + b_rt + b_pt + b_i);
     double* d_uv = (double*)(c0 + b_rt + b_pt + 2 * b_i); double* d_e = (double*)(c0 + b_rt + b_pt + 2 * b_i + b_uv);
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_rt, Rt.data(), Rt.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_pt, pts, (size_t)n_pt * 24, hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_oc, obs_cam, (size_t)n_obs * 4, hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_op, obs_pt, (size_t)n_obs * 4, hipMemcpyHostToDevice, ctx->stream));
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(d_uv, obs_uv, (size_t)n_obs * 16, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(reprojection_error_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, ctx->stream, d_rt, K4[0], K4[1], K4[2], K4[3],
-                       d_pt, d_oc, d_op, d_uv, n_obs, d_e);
-    SFM_HIP_TRY(ctx, hipGetLastError());
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(err_out, d_e, (size_t)n_obs * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SFMHIP_OK;
+    hipError_t e = hipMemcpyAsync(d_rt, Rt.data(), Rt.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pt, pts, (size_t)n_pt * 24, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_oc, obs_cam, (size_t)n_obs * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_op, obs_pt, (size_t)n_obs * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_uv, obs_uv, (size_t)n_obs * 16, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(reprojection_error_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, ctx->stream, d_rt, K4[0], K4[1], K4[2], K4[3],
+                           d_pt, d_oc, d_op, d_uv, n_obs, d_e);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(err_out, d_e, (size_t)n_obs * 8, hipMemcpyDeviceToHost, ctx->stream);
+    return sfm_finish(ctx, e);
 }
 
 }  // extern "C"
