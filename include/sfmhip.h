@@ -493,6 +493,51 @@ int sfmhip_cluster_dbscan_dev(sfmhip_ctx*, const double* d_pts, int n, double r,
 int sfmhip_largest_cluster   (sfmhip_ctx*, const double* pts,   int n, double r, int min_points, int method,
                               uint8_t* keep, int32_t* labels /* may be NULL */, int* n_clusters /* may be NULL */, int* largest_size /* may be NULL */);
 
+/* RANSAC plane segmentation, one plane or several peeled off one after another (modelled on Open3D's segment_plane and PCL's
+ * SACSegmentation with SACMODEL_PLANE; not in the reference).  What follows is the definition; every integer output is a function of
+ * the input alone.
+ *   Inputs: pts n x 3 double; t: distance threshold, finite and >= 0; H: hypotheses per round, 1 <= H <= 65536; seed: uint64;
+ *     min_inliers >= 3; 1 <= max_planes <= 64.
+ *   Rounds p = 0, 1, .. < max_planes.  In round p the ACTIVE list A holds the points with three finite coordinates that still carry
+ *     label -1, in ascending original index; m = |A|.  m < 3: the call stops.
+ *   Random numbers: r(c) is splitmix64 on a 64-bit counter, all arithmetic mod 2^64:
+ *       z = seed + (c + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *       r = z ^ (z >> 31).
+ *   Triple of hypothesis h, 0 <= h < H, with g = p * H + h as a 64-bit value: three distinct positions in A,
+ *       u0 = r(3g) % m;   u1 = r(3g+1) % (m-1), u1 += (u1 >= u0);
+ *       u2 = r(3g+2) % (m-2), then with lo = min(u0,u1), hi = max(u0,u1): u2 += (u2 >= lo), then u2 += (u2 >= hi);
+ *       p0, p1, p2 = A[u0], A[u1], A[u2].
+ *   Plane of the hypothesis, fp64 without contraction, sqrt and division correctly rounded:
+ *       e1 = p1 - p0, e2 = p2 - p0;  mx = e1y*e2z - e1z*e2y, my = e1z*e2x - e1x*e2z, mz = e1x*e2y - e1y*e2x;
+ *       s = sqrt((mx*mx + my*my) + mz*mz);  the hypothesis is INVALID unless s is finite and s > 0;
+ *       (a,b,c) = (mx/s, my/s, mz/s);  d = -((a*p0x + b*p0y) + c*p0z).
+ *   Residual of a point: e = ((a*x + b*y) + c*z) + d; the point is an inlier iff fabs(e) <= t (inclusive, decided on the computed
+ *     value); count_h = the number of inliers among A.
+ *   Winner: the valid hypothesis with the largest count, the smallest h among equals.  No valid hypothesis, or a winner's count below
+ *     min_inliers: the call stops.  Otherwise every inlier of the winner gets label p, counts[p] = that count, winner[p] = h, and
+ *     planes[p] = the winner's (a,b,c,d), all four components negated when d < 0 and otherwise as computed.
+ *   Refined plane (optional, reported only: the labels are always those of the RANSAC winner): refined[p] is the least-squares plane
+ *     of the inliers of plane p: mean, then covariance about it divided by the count, both summed in fixed-order trees (a rerun gives
+ *     the same bits); the normal is the eigenvector of the smallest eigenvalue (the cyclic Jacobi of sfmhip_estimate_normals),
+ *     normalised; d = -((a*mean_x + b*mean_y) + c*mean_z); the same sign rule.
+ *   Outputs: labels n int32: the plane number, or -1 (non-finite points, points on no plane, everything once the call has stopped);
+ *     *n_planes: the number of planes found; planes, refined: max_planes x 4 double, NaN rows from *n_planes on; counts, winner:
+ *     max_planes int32, 0 and -1 from *n_planes on; sum(counts) == #(labels >= 0).  n == 0: OK, *n_planes = 0, no other pointer touched.
+ *   SFMHIP_E_ARG with the outputs left alone: t non-finite or negative, H or max_planes out of range, min_inliers < 3, a null required
+ *     pointer. */
+int sfmhip_segment_planes    (sfmhip_ctx*, const double* pts,   int n, double t, int H, uint64_t seed, int min_inliers, int max_planes,
+                              int32_t* labels, int* n_planes, double* planes, double* refined /* may be NULL */,
+                              int32_t* counts /* may be NULL */, int32_t* winner /* may be NULL */);
+/* the same on device arrays: enqueues on the context's stream, never synchronises; d_n_planes: one int32.  All max_planes rounds are
+ * enqueued: the stop flag and m live in device memory and a round after the stop does nothing. */
+int sfmhip_segment_planes_dev(sfmhip_ctx*, const double* d_pts, int n, double t, int H, uint64_t seed, int min_inliers, int max_planes,
+                              int32_t* d_labels, int32_t* d_n_planes, double* d_planes, double* d_refined /* may be NULL */,
+                              int32_t* d_counts /* may be NULL */, int32_t* d_winner /* may be NULL */);
+/* The max_planes = 1 case as a filter: keep[i] = 1 iff labels[i] == 0; plane = planes[0]; *count = counts[0].  No plane found: plane
+ * (and refined) NaN, keep all 0, *count = 0, and the call still returns SFMHIP_OK. */
+int sfmhip_segment_plane     (sfmhip_ctx*, const double* pts,   int n, double t, int H, uint64_t seed, int min_inliers,
+                              double plane[4], uint8_t* keep, int* count /* may be NULL */, double refined[4] /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

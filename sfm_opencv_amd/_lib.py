@@ -67,6 +67,7 @@ SYMBOLS = [
     "sfmhip_radius_count", "sfmhip_radius_count_dev", "sfmhip_radius_outliers", "sfmhip_voxel_downsample", "sfmhip_voxel_downsample_dev",
     "sfmhip_estimate_normals_hybrid",
     "sfmhip_cluster_dbscan", "sfmhip_cluster_dbscan_dev", "sfmhip_largest_cluster",
+    "sfmhip_segment_planes", "sfmhip_segment_planes_dev", "sfmhip_segment_plane",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -169,6 +170,9 @@ def load():
         "sfmhip_cluster_dbscan": (i32, [vp, vp, i32, f64, i32, i32, vp, C.POINTER(i32), vp, vp]),
         "sfmhip_cluster_dbscan_dev": (i32, [vp, vp, i32, f64, i32, i32, vp, vp, vp, vp]),
         "sfmhip_largest_cluster": (i32, [vp, vp, i32, f64, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+        "sfmhip_segment_planes": (i32, [vp, vp, i32, f64, i32, C.c_uint64, i32, i32, vp, C.POINTER(i32), vp, vp, vp, vp]),
+        "sfmhip_segment_planes_dev": (i32, [vp, vp, i32, f64, i32, C.c_uint64, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_segment_plane": (i32, [vp, vp, i32, f64, i32, C.c_uint64, i32, vp, vp, C.POINTER(i32), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

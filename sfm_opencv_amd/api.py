@@ -438,6 +438,41 @@ class Context:
         sizes = np.bincount(labels[labels >= 0], minlength=m.value).astype(np.int32)
         return keep.astype(bool), labels, sizes
 
+    def segment_planes(self, pts, threshold, max_planes=1, hypotheses=1024, seed=0, min_inliers=3):
+        """(labels int32 n, planes P x 4, counts int32 P, winner int32 P, refined P x 4): RANSAC plane segmentation as in Open3D's
+        segment_plane / PCL's SACSegmentation, up to max_planes planes peeled off one after another (sfmhip_segment_planes, where the
+        definition is).  labels: the plane number or -1; planes: (a, b, c, d) of the winning hypothesis, d >= 0; refined: the
+        least-squares plane of each plane's inliers.  P is the number of planes found.  Every integer output depends on the input alone."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n, mp = pts.shape[0], int(max_planes)
+        cap = max(mp, 0)
+        labels = np.full(n, -1, np.int32); planes = np.full((cap, 4), np.nan); refined = np.full((cap, 4), np.nan)
+        counts = np.zeros(cap, np.int32); winner = np.full(cap, -1, np.int32); m = C.c_int(0)
+        self._check(self.lib.sfmhip_segment_planes(self.h, pts.ctypes.data, n, float(threshold), int(hypotheses), int(seed) & (2 ** 64 - 1),
+                                                   int(min_inliers), mp, labels.ctypes.data, C.byref(m), planes.ctypes.data, refined.ctypes.data,
+                                                   counts.ctypes.data, winner.ctypes.data))
+        P = m.value
+        return labels, planes[:P].copy(), counts[:P].copy(), winner[:P].copy(), refined[:P].copy()
+
+    def segment_planes_dev(self, d_pts, n, threshold, max_planes, d_labels, d_n_planes, d_planes, d_refined=0, d_counts=0, d_winner=0,
+                           hypotheses=1024, seed=0, min_inliers=3):
+        """the same on device pointers (integers; 0 for d_refined / d_counts / d_winner: not wanted): enqueues on the context's stream,
+        never synchronises; the per-plane arrays hold max_planes rows, NaN / 0 / -1 from the number of planes on"""
+        p = lambda a: C.c_void_p(int(a)) if a else None      # noqa: E731
+        self._check(self.lib.sfmhip_segment_planes_dev(self.h, p(d_pts), int(n), float(threshold), int(hypotheses), int(seed) & (2 ** 64 - 1),
+                                                       int(min_inliers), int(max_planes), p(d_labels), p(d_n_planes), p(d_planes), p(d_refined),
+                                                       p(d_counts), p(d_winner)))
+
+    def segment_plane(self, pts, threshold, hypotheses=1024, seed=0, min_inliers=3):
+        """(plane float64 4, keep bool n, refined float64 4): the dominant plane as a filter (sfmhip_segment_plane); no plane found:
+        NaN planes and keep all False"""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = pts.shape[0]
+        plane = np.full(4, np.nan); refined = np.full(4, np.nan); keep = np.zeros(n, np.uint8); cnt = C.c_int(0)
+        self._check(self.lib.sfmhip_segment_plane(self.h, pts.ctypes.data, n, float(threshold), int(hypotheses), int(seed) & (2 ** 64 - 1),
+                                                  int(min_inliers), plane.ctypes.data, keep.ctypes.data, C.byref(cnt), refined.ctypes.data))
+        return plane, keep.astype(bool), refined
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)

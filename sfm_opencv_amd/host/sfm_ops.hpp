@@ -458,6 +458,34 @@ inline int filter_largest_cluster(const std::vector<Point3d>& pts3d, const doubl
     return kept;
 }
 
+// ---- RANSAC plane segmentation (extension; modelled on Open3D's segment_plane / pcl::SACSegmentation with SACMODEL_PLANE) -- up to
+// max_planes planes peeled off one after another (sfmhip_segment_planes, where the definition is): labels[i] = the plane of point i or
+// -1; planes[k] = the least-squares plane (a, b, c, d) of the inliers of plane k, d >= 0; counts[k] = its number of points.  Returns the
+// number of planes found, -1 on error.
+struct Plane4d { double a = 0, b = 0, c = 0, d = 0; };
+inline int segment_planes(const std::vector<Point3d>& pts3d, const double threshold, const int max_planes, const int min_inliers,
+                          std::vector<int32_t>& labels, std::vector<Plane4d>& planes, std::vector<int32_t>& counts,
+                          const int hypotheses = 1024, const uint64_t seed = 0)
+{
+    sfmhip_ctx* ctx = context();
+    labels.assign(pts3d.size(), -1);
+    planes.clear(); counts.clear();
+    if (!ctx) return -1;
+    if (pts3d.empty()) return 0;
+    const size_t cap = max_planes > 0 ? (size_t)max_planes : 0;
+    std::vector<Plane4d> ransac(cap), refined(cap);
+    std::vector<int32_t> cnt(cap);
+    int n_planes = 0;
+    if (sfmhip_segment_planes(ctx, &pts3d[0].x, (int)pts3d.size(), threshold, hypotheses, seed, min_inliers, max_planes, labels.data(), &n_planes,
+                              cap ? &ransac[0].a : nullptr, cap ? &refined[0].a : nullptr, cnt.data(), nullptr) != SFMHIP_OK) {
+        printf("[Err]: segment_planes: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    planes.assign(refined.begin(), refined.begin() + n_planes);
+    counts.assign(cnt.begin(), cnt.begin() + n_planes);
+    return n_planes;
+}
+
 // ---- voxel-grid down-sampling (extension; sfmhip_voxel_downsample) -- one centroid per occupied voxel of edge `voxel`, in ascending
 // voxel order; a voxel's colour is, per channel, the rounded mean (2 * sum + count) / (2 * count) in integers over its points (colors
 // may be shorter than pts3d: out_colors is then left empty).  Returns the number of voxels, -1 on error.

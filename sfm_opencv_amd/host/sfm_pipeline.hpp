@@ -236,6 +236,9 @@ struct PipelineOptions {
     double largest_cluster_r = -1.0;       // >= 0: ... and, of those, only the largest cluster at this distance with largest_cluster_min points for a core point (filter_largest_cluster; extension)
     int    largest_cluster_min = 1;
     double voxel_size = 0.0;               // > 0: ... and what is left replaced by one centroid per voxel of this edge (voxel_downsample; extension)
+    double planes_t = -1.0;                // >= 0: report up to planes_max planes of at least planes_min points within this distance on that cloud (segment_planes; extension, changes no file)
+    int    planes_max = 1;
+    int    planes_min = 3;
 };
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
@@ -355,6 +358,13 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         if (voxel_downsample(in_pts, in_colors, opt.voxel_size, ply_pts, ply_colors) < 0) return -1;
         printf("voxel grid: %zu points -> %zu voxels\n", in_pts.size(), ply_pts.size());
     }
+    if (opt.planes_t >= 0.0) {
+        std::vector<int32_t> labels, counts;
+        std::vector<Plane4d> planes;
+        if (segment_planes(ply_pts, opt.planes_t, opt.planes_max, opt.planes_min, labels, planes, counts) < 0) return -1;
+        for (size_t k = 0; k < planes.size(); ++k)
+            printf("plane %zu: %.17g %.17g %.17g %.17g (%d points)\n", k, planes[k].a, planes[k].b, planes[k].c, planes[k].d, (int)counts[k]);
+    }
     std::vector<Point3d> normals(ply_pts.size());
     estimate_normals(ply_pts, 10, normals);
 
@@ -408,7 +418,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -446,6 +456,15 @@ inline int driver_main(int argc, char** argv, bool nview)
             if (comma != std::string::npos) opt.largest_cluster_min = std::atoi(a.c_str() + comma + 1);
         }
         else if (a.rfind("--voxel-size=", 0) == 0) opt.voxel_size = std::atof(a.c_str() + 13);
+        else if (a.rfind("--planes=", 0) == 0) {                 // T[,MAX[,MIN_INLIERS]]: print up to MAX (1) planes of at least MIN_INLIERS (3) points within T of them, found on the cloud of the .ply
+            opt.planes_t = std::atof(a.c_str() + 9);
+            const size_t c1 = a.find(',', 9);
+            if (c1 != std::string::npos) {
+                opt.planes_max = std::atoi(a.c_str() + c1 + 1);
+                const size_t c2 = a.find(',', c1 + 1);
+                if (c2 != std::string::npos) opt.planes_min = std::atoi(a.c_str() + c2 + 1);
+            }
+        }
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
         else if (positional++ == 0) opt.out_dir = a;
     }
