@@ -538,6 +538,72 @@ int sfmhip_segment_planes_dev(sfmhip_ctx*, const double* d_pts, int n, double t,
 int sfmhip_segment_plane     (sfmhip_ctx*, const double* pts,   int n, double t, int H, uint64_t seed, int min_inliers,
                               double plane[4], uint8_t* keep, int* count /* may be NULL */, double refined[4] /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Two-view geometric verification: an epipolar RANSAC over many image pairs in one call (what  */
+/* colmap and OpenMVG run between matching and reconstruction; the reference rejects epipolar   */
+/* outliers for its first pair only, inside findEssentialMat, NView:1032).  What follows is     */
+/* the definition; mask, count and winner are functions of the input alone and F is prescribed  */
+/* bit for bit.  It contains no eigen-solver and no SVD: the eight-point null vector comes from */
+/* Gaussian elimination with complete pivoting.                                                 */
+/* ------------------------------------------------------------------------------------------ */
+/*   Input: n_pairs blocks of correspondences; block q starts at corr + 4*stride*q, a row is (x1, y1, x2, y2) in double, the first
+ *     counts[q] rows (0 <= counts[q] <= stride) are meaningful and the rows from counts[q] on are never read.  The coordinates are
+ *     whatever the caller passes: pixels, or normalised by K.
+ *   Parameters: t finite and >= 0, t2 = t*t; H: hypotheses per round, 1 <= H <= 65536; 1 <= rounds <= 8; seed: uint64, the same for
+ *     every pair, so a pair's outputs are a function of its own rows alone, whatever batch it is in; min_inliers >= 8.
+ *   Lists: L_0 = the rows of the block with four finite values, in ascending row index.  Scoring always runs over L_0; round p samples
+ *     from L_p.
+ *   Sample of hypothesis h of round p: m = |L_p|; m < 8: the pair stops.  With g = p*H + h and r(c) the splitmix64 of
+ *     sfmhip_segment_planes on this seed, for k = 0..7:  u = r(8g + k) % (m - k);  then for each position already chosen, taken in
+ *     ascending order s_0 < s_1 < ..: u += (u >= s_j);  u joins the chosen set.  Row k of the sample is L_p[u_k], in draw order.
+ *   Hypothesis (fp64, no contraction, division and sqrt correctly rounded):
+ *     1. A, 8 x 9, row k = [x2*x1, x2*y1, x2, y2*x1, y2*y1, y2, x1, y1, 1] of sample row k;  perm = 0..8.
+ *     2. for k = 0..7:  the pivot is the first maximum of |A[i][j]| over i = k..7, j = k..8 in row-major scan (i, then j); a NaN entry
+ *        is never chosen; nothing chosen: the pivot is (k,k).  Swap rows k and i; swap columns k and j, and perm[k] with perm[j].  The
+ *        hypothesis is INVALID if A[k][k] is zero or not finite.  For i = k+1..7: f = A[i][k] / A[k][k]; for j = k+1..8:
+ *        A[i][j] = A[i][j] - f*A[k][j].
+ *     3. z[8] = 1;  for k = 7..0:  s = A[k][k+1]*z[k+1], then s = s + A[k][j]*z[j] for j = k+2..8 ascending, then z[k] = -s / A[k][k].
+ *     4. f[perm[k]] = z[k] for k = 0..8.
+ *     5. ss = f0*f0, then ss = ss + fj*fj for ascending j;  nrm = sqrt(ss);  INVALID unless nrm is finite and > 0.
+ *     6. F = f / nrm, row-major 3 x 3.
+ *     No rank-2 projection is applied: a hypothesis is an exact fit of its eight rows, and what callers take from it is the inlier
+ *     set.  A caller that wants an essential matrix projects the winner on the host.
+ *   Residual of a row:  l0 = (F0*x1 + F1*y1) + F2;  l1 = (F3*x1 + F4*y1) + F5;  l2 = (F6*x1 + F7*y1) + F8;
+ *       m0 = (F0*x2 + F3*y2) + F6;  m1 = (F1*x2 + F4*y2) + F7;  e = (x2*l0 + y2*l1) + l2;  d = ((l0*l0 + l1*l1) + m0*m0) + m1*m1.
+ *     The row is an inlier iff e*e <= t2*d: the squared Sampson distance against t^2 with the division multiplied out, inclusive,
+ *     decided on the computed values.  count_h = the number of inliers in L_0.
+ *   Round and stop: the round's best is the valid hypothesis with the largest count, the smallest h among equals.  The pair stops if no
+ *     hypothesis is valid, and also if p > 0 and the round's best count is not strictly larger than the best so far.  Otherwise the
+ *     round's best becomes the pair's model and L_{p+1} is its inliers in ascending row index.
+ *   Outputs per pair.  The model's count below min_inliers, or no model: count = 0, winner = -1, F = nine NaN, mask all 0.  Otherwise
+ *     count = the model's count, winner = g of the model (it says which round produced it), F as computed (no sign rule: the elimination
+ *     fixes the sign), mask[stride*q + i] = 1 for the model's inliers and 0 for every other i < stride;  sum(mask row) == count.
+ *   mask: n_pairs x stride uint8; count_out: n_pairs int32; F: n_pairs x 9 double; winner: n_pairs int32.
+ *   SFMHIP_E_ARG with the outputs left alone: t non-finite or negative, H, rounds or min_inliers out of range, a negative stride or
+ *     n_pairs, a null required pointer.  n_pairs == 0: OK, no pointer touched.
+ *   Known limit: eight-point samples are degenerate on an exactly planar scene (the host's findEssentialMat has a homography branch for
+ *     it; this call has none). */
+int sfmhip_verify_pairs    (sfmhip_ctx*, const double* corr,   int stride, const int32_t* counts,   int n_pairs, double t, int H, int rounds,
+                            uint64_t seed, int min_inliers, uint8_t* mask,   int32_t* count_out,   double* F /* may be NULL */,
+                            int32_t* winner /* may be NULL */);
+/* the same on device arrays: enqueues on the context's stream, never synchronises.  All rounds are enqueued: a pair's stop flag and
+ * list length live in device memory and a round after the stop does nothing for that pair.  The outputs may not overlap the inputs. */
+int sfmhip_verify_pairs_dev(sfmhip_ctx*, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
+                            uint64_t seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F /* may be NULL */,
+                            int32_t* d_winner /* may be NULL */);
+/* The verification of match lists exactly as sfmhip_match_pairs_dev leaves them (d_matches: n_pairs x max_per_pair sfm_dmatch,
+ * d_counts: n_pairs int32), for sfmhip_triangulate2_matches_dev to consume.  d_kp: HOST array of n_sets DEVICE pointers to the images'
+ * sfm_keypoint arrays; pairs as in sfmhip_match_pairs_dev (host).  Row i of pair q is gathered as x = ((double)kp.x - cx) / fx,
+ * y = ((double)kp.y - cy) / fy with K4 = (fx, fy, cx, cy) -- (1, 1, 0, 0) leaves pixel coordinates -- from key point queryIdx of image
+ * pairs[2q] and key point trainIdx of image pairs[2q+1]; an element with a negative index is a NaN row.  Then sfmhip_verify_pairs_dev
+ * with stride = max_per_pair runs on these rows, and d_matches_out receives, in the same layout, the elements of every pair whose mask
+ * is set, in their order; d_counts_out[q] = the pair's count (0 where there is no model).  Enqueues only; the outputs may not overlap
+ * the inputs. */
+int sfmhip_verify_matches_dev(sfmhip_ctx*, const sfm_keypoint* const* d_kp, int n_sets, const int32_t* pairs, int n_pairs, const double K4[4],
+                              const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, double t, int H, int rounds,
+                              uint64_t seed, int min_inliers, sfm_dmatch* d_matches_out, int32_t* d_counts_out,
+                              double* d_F /* may be NULL */, int32_t* d_winner /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,14 @@ def _ptr(a):
     return a.data_ptr()
 
 
+def _dptr(a):
+    """a device address for the C-ABI: None / 0 -> NULL, an integer as it is, else a torch tensor's data_ptr()"""
+    if a is None:
+        return None
+    a = a.data_ptr() if hasattr(a, "data_ptr") else int(a)
+    return C.c_void_p(a) if a else None
+
+
 class DescSet:
     def __init__(self, ctx, handle, rows, keepalive=None):
         self.ctx, self.handle, self.rows, self._keep = ctx, handle, rows, keepalive
@@ -473,6 +481,46 @@ class Context:
                                                   int(min_inliers), plane.ctypes.data, keep.ctypes.data, C.byref(cnt), refined.ctypes.data))
         return plane, keep.astype(bool), refined
 
+    # ---------------------------------------------------------------- two-view geometric verification
+    def verify_pairs(self, corr_blocks, t, hypotheses=1024, rounds=3, seed=0, min_inliers=8):
+        """(masks, counts int32 n, F n x 3 x 3, winner int32 n): the epipolar RANSAC of sfmhip_verify_pairs (where the definition is) on
+        every block of corr_blocks, a sequence of (m_q, 4) arrays of rows (x1, y1, x2, y2), all pairs in one call.  masks[q]: bool m_q,
+        the rows the pair's model accepts; counts[q] = masks[q].sum(), 0 (with NaN F and winner -1) where no model reaches min_inliers.
+        Every output depends on the pair's own rows alone."""
+        blocks = [np.ascontiguousarray(b, np.float64).reshape(-1, 4) for b in corr_blocks]
+        n = len(blocks)
+        counts = np.array([len(b) for b in blocks], np.int32)
+        stride = int(counts.max()) if n else 0
+        corr = np.zeros((n, stride, 4))
+        for q, b in enumerate(blocks):
+            corr[q, :len(b)] = b
+        mask = np.zeros((n, stride), np.uint8); cnt = np.zeros(n, np.int32); F = np.full((n, 9), np.nan); win = np.full(n, -1, np.int32)
+        self._check(self.lib.sfmhip_verify_pairs(self.h, corr.ctypes.data, stride, counts.ctypes.data, n, float(t), int(hypotheses), int(rounds),
+                                                 int(seed) & (2 ** 64 - 1), int(min_inliers), mask.ctypes.data, cnt.ctypes.data, F.ctypes.data,
+                                                 win.ctypes.data))
+        return [mask[q, :c].astype(bool) for q, c in enumerate(counts.tolist())], cnt, F.reshape(n, 3, 3), win
+
+    def verify_pairs_dev(self, d_corr, stride, d_counts, n_pairs, t, d_mask, d_count_out, d_F=0, d_winner=0, hypotheses=1024, rounds=3, seed=0,
+                         min_inliers=8):
+        """the same on device arrays (torch tensors or integer addresses; 0 for d_F / d_winner: not wanted): d_corr n_pairs x stride x 4
+        float64, d_counts int32, d_mask n_pairs x stride uint8, d_count_out int32; enqueues on the context's stream, never synchronises"""
+        self._check(self.lib.sfmhip_verify_pairs_dev(self.h, _dptr(d_corr), int(stride), _dptr(d_counts), int(n_pairs), float(t), int(hypotheses),
+                                                     int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers), _dptr(d_mask), _dptr(d_count_out),
+                                                     _dptr(d_F), _dptr(d_winner)))
+
+    def verify_matches_dev(self, d_kp, pairs, K4, d_matches, max_per_pair, d_counts, t, d_matches_out, d_counts_out, d_F=0, d_winner=0,
+                           hypotheses=1024, rounds=3, seed=0, min_inliers=8):
+        """the match lists of match_pairs_dev verified on the device (sfmhip_verify_matches_dev): d_kp: one device KEYPOINT array per image
+        (torch tensors or addresses); pairs (n_pairs, 2); K4 = (fx, fy, cx, cy), (1, 1, 0, 0) for pixel coordinates; d_matches_out /
+        d_counts_out: the surviving elements in the layout of the input, for triangulate2_matches_dev.  Enqueues only."""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        K4 = np.ascontiguousarray(K4, np.float64).reshape(4)
+        arr = (C.c_void_p * len(d_kp))(*[_dptr(k) for k in d_kp])
+        self._check(self.lib.sfmhip_verify_matches_dev(self.h, arr, len(d_kp), pairs.ctypes.data, pairs.shape[0], K4.ctypes.data, _dptr(d_matches),
+                                                       int(max_per_pair), _dptr(d_counts), float(t), int(hypotheses), int(rounds),
+                                                       int(seed) & (2 ** 64 - 1), int(min_inliers), _dptr(d_matches_out), _dptr(d_counts_out),
+                                                       _dptr(d_F), _dptr(d_winner)))
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
@@ -699,6 +747,34 @@ def match_features_for_all(descriptor_for_all, ctx=None, cross_check=False):
         if len(m) == 0:
             print("[Warning]: zero matches between %d and %d." % (i, i + 1))
     return out
+
+
+def verify_matches_for_all(K, key_points_for_all, matches_for_all, px=1.0, hypotheses=1024, rounds=3, seed=0, min_inliers=15, ctx=None):
+    """Geometric verification of the chain's match lists (no reference counterpart: the reference rejects epipolar outliers for its first
+    pair only, NViewReconstuct.cpp:1032): matches_for_all[i] joins images i and i + 1, as match_features_for_all returns them.  The key
+    points are normalised by K, the threshold is px pixels (t = px / (0.5 (fx + fy))), all pairs run in one call of sfmhip_verify_pairs.
+    Returns (filtered lists, [(count, F 3 x 3)] per pair); a pair without a model of min_inliers rows keeps its matches as they are, with
+    a warning, count 0 and a NaN F."""
+    ctx = ctx or default_context()
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    blocks = []
+    for i, m in enumerate(matches_for_all):
+        a, b = key_points_for_all[i], key_points_for_all[i + 1]
+        q, t = m["queryIdx"], m["trainIdx"]
+        blocks.append(np.stack([(a["x"][q].astype(np.float64) - cx) / fx, (a["y"][q].astype(np.float64) - cy) / fy,
+                                (b["x"][t].astype(np.float64) - cx) / fx, (b["y"][t].astype(np.float64) - cy) / fy], 1).reshape(-1, 4))
+    if not blocks:
+        return [], []
+    masks, counts, F, _ = ctx.verify_pairs(blocks, px / (0.5 * (fx + fy)), hypotheses, rounds, seed, min_inliers)
+    out = []
+    for i, m in enumerate(matches_for_all):
+        if counts[i] == 0:
+            print("[Warning]: pair %d: no epipolar model with %d matches, the %d matches are kept as they are." % (i, min_inliers, len(m)))
+            out.append(m)
+        else:
+            out.append(m[masks[i]])
+    return out, [(int(c), f) for c, f in zip(counts, F)]
 
 
 def get_matched_points(p1, p2, matches):

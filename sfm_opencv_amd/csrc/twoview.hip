@@ -1,0 +1,521 @@
+// twoview.hip -- two-view geometric verification: an epipolar RANSAC over many image pairs in one call (what colmap and OpenMVG run between
+// matching and reconstruction; the reference has it for its first pair only, inside findEssentialMat).  The definition is in sfmhip.h at
+// sfmhip_verify_pairs and is followed to the letter here: the mask, count and winner are integer decisions on prescribed fp64 values and F
+// is prescribed bit for bit, the same for every run, batch and launch geometry.  The file is built like planes.hip.
+//
+// A round p, everything on the device and on one stream, every kernel over all pairs at once:
+//   twoview_prep_kernel     (once) one workgroup per pair: L_0, the rows with four finite values, packed in ascending row index into rows
+//                           of four doubles; the state of the pair; L_0 as the list round 0 samples from
+//   twoview_hyp_kernel      one thread per (pair, hypothesis): the eight rows from splitmix64, the 8 x 9 system, Gaussian elimination with
+//                           complete pivoting in registers, back-substitution, F or NaN, a valid bit
+//   twoview_score_kernel    the pairs x H x |L_0| part: the number of rows of L_0 every hypothesis accepts
+//   twoview_winner_kernel   one workgroup per pair: the valid hypothesis with the largest count, the smallest h among equals; it becomes
+//                           the pair's model, or the pair's stop flag is raised
+//   twoview_list_kernel     one workgroup per pair: the model's inliers among L_0 in ascending order, the list the next round samples from
+//   twoview_final_kernel    (once) mask, count, winner and F of every pair, or their "no model" values
+// All rounds are enqueued; the stop flag and the list length of a pair live in device memory, and once a pair has stopped every block of
+// a later round that belongs to it leaves at once.
+//
+// The shape of twoview_score_kernel is plane_score_kernel's.  LANES OWN HYPOTHESES: a workgroup of 256 threads takes 256 hypotheses
+// (blockIdx.x) of one pair (blockIdx.z) and a sequence of chunks of SCORE_CHUNK rows (blockIdx.y, then a stride of gridDim.y chunks); a
+// lane keeps its F (18 VGPRs) and its count in registers; the chunk is staged in LDS as rows of four doubles, and every lane reads the
+// SAME row at the same time: a broadcast, without bank conflicts.  Per row a wave issues 16 fp64 multiplications and 15 additions for
+// l, m, e and d (contraction is off: the residual is the prescribed formula), two more multiplications for e*e and t2*d, a compare and a
+// conditional add: 35 VALU instructions, which is what bounds the kernel (the account is in DESIGN.md 4c).  Counts: one integer
+// atomicAdd per lane at the very end.
+#include "common.hpp"
+#pragma clang fp contract(off)
+
+#define SCORE_CHUNK 512          // rows of L_0 staged per pass of twoview_score_kernel (16 KB of LDS)
+#define SCORE_MAX_WG 2048        // workgroups of twoview_score_kernel per pair at most; beyond that a workgroup strides over chunks
+#define HYP_THREADS 64           // hypotheses per workgroup of twoview_hyp_kernel
+#define TWOVIEW_H_MAX 65536
+#define TWOVIEW_ROUNDS_MAX 8
+#define TWOVIEW_PAIRS_PER_LAUNCH 32768      // gridDim.z of the scoring launch; a longer batch goes in slices (the pairs are independent)
+
+typedef unsigned long long pu64;
+typedef unsigned int pu32;
+
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// what the rounds of one pair share, in device memory
+struct TwoViewState {
+    int stop;                 // raised by the round that ends the pair; every later block of the pair leaves at once
+    int m;                    // |L_p|, the length of the list the current round samples from
+    int m0;                   // |L_0|, the rows every round scores
+    int best;                 // the model's count, -1 while there is no model
+    int winner;               // g = p * H + h of the model
+    int pad[3];
+    double F[9];              // the model
+};
+__device__ __forceinline__ bool round_dead(const TwoViewState* s) { return s->stop || s->m < 8; }
+
+__device__ __forceinline__ pu64 splitmix64(pu64 seed, pu64 c)
+{
+    pu64 z = seed + (c + 1ull) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// THE residual test: scoring, list building and the mask all call this, so the length of a list and the sum of a mask row equal the
+// model's count by construction.  False for a NaN F (an invalid hypothesis).
+__device__ __forceinline__ bool twoview_inlier(const double (&F)[9], double x1, double y1, double x2, double y2, double t2)
+{
+    const double l0 = (F[0] * x1 + F[1] * y1) + F[2];
+    const double l1 = (F[3] * x1 + F[4] * y1) + F[5];
+    const double l2 = (F[6] * x1 + F[7] * y1) + F[8];
+    const double m0 = (F[0] * x2 + F[3] * y2) + F[6];
+    const double m1 = (F[1] * x2 + F[4] * y2) + F[7];
+    const double e = (x2 * l0 + y2 * l1) + l2;
+    const double d = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
+    return e * e <= t2 * d;
+}
+__device__ __forceinline__ bool finite4(double a, double b, double c, double d) { return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d); }
+__device__ __forceinline__ int clamp_count(int c, int stride) { return c < 0 ? 0 : (c > stride ? stride : c); }
+
+// ordered compaction inside a workgroup of 256 threads: the number of flagged threads below this one, and how many there are in all.
+// Every thread of the workgroup calls it; sw: four ints of LDS.
+__device__ __forceinline__ int block_rank(bool f, int* sw, int& total)
+{
+    const pu64 b = __ballot(f);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();                                                     // the previous call's readers are done with sw
+    if (lane == 0) sw[wave] = __popcll(b);
+    __syncthreads();
+    int below = __popcll(b & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) below += sw[w];
+    total = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+    return below;
+}
+
+// one workgroup per pair: L_0 packed into act, the identity as the list of round 0, the state
+__global__ __launch_bounds__(256) void twoview_prep_kernel(const double* __restrict__ corr, int stride, const int32_t* __restrict__ counts,
+                                                           TwoViewState* __restrict__ state, double4* __restrict__ act, int32_t* __restrict__ list)
+{
+    __shared__ int sw[4];
+    const size_t q = blockIdx.x;
+    const int cnt = clamp_count(counts[q], stride);
+    const double* rows = corr + 4 * (size_t)stride * q;
+    int m = 0;
+    for (int base = 0; base < cnt; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        double x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+        bool f = false;
+        if (i < cnt) {
+            x1 = rows[4 * (size_t)i]; y1 = rows[4 * (size_t)i + 1]; x2 = rows[4 * (size_t)i + 2]; y2 = rows[4 * (size_t)i + 3];
+            f = finite4(x1, y1, x2, y2);
+        }
+        int total;
+        const int r = block_rank(f, sw, total);
+        if (f) { act[q * stride + m + r] = make_double4(x1, y1, x2, y2); list[q * stride + m + r] = m + r; }
+        m += total;
+    }
+    if (threadIdx.x == 0) {
+        TwoViewState* s = state + q;
+        s->stop = 0; s->m = m; s->m0 = m; s->best = -1; s->winner = -1;
+    }
+}
+
+// hypothesis h of round p of pair q: hyp[9 (q H + h) ..] = F, NaN where it is invalid (it then counts nobody); its counter cleared.
+// The 8 x 9 matrix stays in registers: every loop is unrolled, so every index is a constant, and the one thing the pivoting decides at
+// run time, which row and which column trade places, is done with selects over the candidates (SWAP_IF).  The same values move as in an
+// indexed swap, so the arithmetic is the prescribed one.  (With the matrix in LDS and indexed by the pivot the kernel waited on one
+// dependent LDS access after another: 179 us for 199 x 1024 hypotheses against the figure in DESIGN.md 4c for this form.)
+#define SWAP_IF(c, a, b) { const double ta_ = (a), tb_ = (b); (a) = (c) ? tb_ : ta_; (b) = (c) ? ta_ : tb_; }
+__global__ __launch_bounds__(HYP_THREADS) void twoview_hyp_kernel(const double4* __restrict__ act, const int32_t* __restrict__ list, int stride,
+                                                                  const TwoViewState* __restrict__ state, int p, int H, pu64 seed,
+                                                                  double* __restrict__ hyp, int32_t* __restrict__ hvalid, int32_t* __restrict__ hcnt)
+{
+    const size_t q = blockIdx.y;
+    const TwoViewState* s = state + q;
+    if (round_dead(s)) return;
+    const int h = blockIdx.x * HYP_THREADS + threadIdx.x;
+    if (h >= H) return;
+    const pu64 m = (pu64)s->m;
+    const pu64 g = (pu64)p * (pu64)H + (pu64)h;
+    double A[8][9];
+    // eight distinct positions in L_p; srt: the ones chosen so far in ascending order
+    pu64 srt[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        pu64 u = splitmix64(seed, 8ull * g + (pu64)k) % (m - (pu64)k);
+#pragma unroll
+        for (int j = 0; j < k; ++j) u += u >= srt[j] ? 1ull : 0ull;
+        const double4 r = act[q * stride + (size_t)list[q * stride + u]];
+        A[k][0] = r.z * r.x; A[k][1] = r.z * r.y; A[k][2] = r.z;
+        A[k][3] = r.w * r.x; A[k][4] = r.w * r.y; A[k][5] = r.w;
+        A[k][6] = r.x;       A[k][7] = r.y;       A[k][8] = 1.0;
+        srt[k] = u;
+#pragma unroll
+        for (int j = k; j > 0; --j) {
+            const pu64 lo = srt[j] < srt[j - 1] ? srt[j] : srt[j - 1], hi = srt[j] < srt[j - 1] ? srt[j - 1] : srt[j];
+            srt[j - 1] = lo; srt[j] = hi;
+        }
+    }
+    int perm[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) perm[j] = j;
+    bool valid = true;                                                   // an invalid hypothesis goes on computing values nobody uses
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        int at = k * 9 + k;
+        double best = -1.0;
+#pragma unroll
+        for (int i = k; i < 8; ++i)
+#pragma unroll
+            for (int j = k; j < 9; ++j) {
+                const double v = fabs(A[i][j]);
+                const bool gt = v > best;                                 // the first maximum; never true for a NaN
+                best = gt ? v : best; at = gt ? i * 9 + j : at;
+            }
+        const int pi = at / 9, pj = at - 9 * pi;
+        // rows k and pi (the columns below k of the rows from k on are never read again), then columns k and pj in every row
+#pragma unroll
+        for (int i = k + 1; i < 8; ++i)
+#pragma unroll
+            for (int j = k; j < 9; ++j) SWAP_IF(pi == i, A[k][j], A[i][j]);
+#pragma unroll
+        for (int c = k + 1; c < 9; ++c) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) SWAP_IF(pj == c, A[i][k], A[i][c]);
+            const int a = perm[k], b = perm[c];
+            perm[k] = pj == c ? b : a; perm[c] = pj == c ? a : b;
+        }
+        const double piv = A[k][k];
+        valid = valid && piv != 0.0 && isfinite(piv);
+#pragma unroll
+        for (int i = k + 1; i < 8; ++i) {
+            const double f = A[i][k] / piv;
+#pragma unroll
+            for (int j = k + 1; j < 9; ++j) A[i][j] = A[i][j] - f * A[k][j];
+        }
+    }
+    double z[9];
+    z[8] = 1.0;
+#pragma unroll
+    for (int k = 7; k >= 0; --k) {
+        double sum = A[k][k + 1] * z[k + 1];
+#pragma unroll
+        for (int j = k + 2; j < 9; ++j) sum = sum + A[k][j] * z[j];
+        z[k] = -sum / A[k][k];
+    }
+    double f[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {                                        // f[perm[k]] = z[k]
+        f[j] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[j] = perm[k] == j ? z[k] : f[j];
+    }
+    double ss = f[0] * f[0];
+#pragma unroll
+    for (int j = 1; j < 9; ++j) ss = ss + f[j] * f[j];
+    const double nrm = sqrt(ss);
+    valid = valid && isfinite(nrm) && nrm > 0.0;
+    const size_t at = q * (size_t)H + (size_t)h;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) hyp[9 * at + j] = valid ? f[j] / nrm : NAN;
+    hvalid[at] = valid ? 1 : 0;
+    hcnt[at] = 0;
+}
+#undef SWAP_IF
+
+// the pairs x H x |L_0| part (the shape is explained at the top of the file)
+__global__ __launch_bounds__(256) void twoview_score_kernel(const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
+                                                            const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
+{
+    __shared__ double4 tile[SCORE_CHUNK];
+    const size_t q = blockIdx.z;
+    const TwoViewState* s = state + q;
+    if (round_dead(s)) return;                                           // uniform over the workgroup
+    const int m0 = s->m0;
+    if ((long long)blockIdx.y * SCORE_CHUNK >= m0) return;
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    const bool live = h < H;
+    const bool wave_live = blockIdx.x * 256 + (int)(threadIdx.x & ~63u) < H;      // uniform over the wave
+    const size_t at = q * (size_t)H + (size_t)h;
+    double F[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) F[j] = live ? hyp[9 * at + j] : NAN;
+    const double4* rows = act + q * stride;
+    int count = 0;
+    for (int base = blockIdx.y * SCORE_CHUNK; base < m0; base += gridDim.y * SCORE_CHUNK) {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SCORE_CHUNK / 256; ++k) {
+            const int j = base + k * 256 + (int)threadIdx.x;
+            if (j < m0) tile[k * 256 + threadIdx.x] = rows[j];
+        }
+        __syncthreads();
+        if (!wave_live) continue;
+        const int cnt = m0 - base < SCORE_CHUNK ? m0 - base : SCORE_CHUNK;
+#pragma unroll 4
+        for (int r = 0; r < cnt; ++r) {
+            const double4 c = tile[r];
+            count += twoview_inlier(F, c.x, c.y, c.z, c.w, t2) ? 1 : 0;
+        }
+    }
+    if (live && count) atomicAdd(hcnt + at, count);
+}
+
+// one workgroup per pair: argmax of (count, then the smallest h) over the valid hypotheses; the pair's model, or its stop flag
+__global__ __launch_bounds__(256) void twoview_winner_kernel(TwoViewState* __restrict__ state, int p, int H, const double* __restrict__ hyp,
+                                                             const int32_t* __restrict__ hvalid, const int32_t* __restrict__ hcnt)
+{
+    __shared__ pu64 sb[256];
+    const size_t q = blockIdx.x;
+    TwoViewState* s = state + q;
+    const int stop = s->stop, m = s->m;
+    __syncthreads();                                                     // everybody has read the state before thread 0 may change it
+    if (stop) return;
+    if (m < 8) { if (threadIdx.x == 0) s->stop = 1; return; }
+    pu64 best = 0ull;
+    for (int h = threadIdx.x; h < H; h += 256) {
+        if (!hvalid[q * (size_t)H + h]) continue;
+        const pu64 v = ((pu64)((pu32)hcnt[q * (size_t)H + h] + 1u) << 32) | (pu64)(0xffffffffu - (pu32)h);      // a valid hypothesis: v > 0
+        best = v > best ? v : best;
+    }
+    sb[threadIdx.x] = best;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off && sb[threadIdx.x + off] > sb[threadIdx.x]) sb[threadIdx.x] = sb[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const pu64 w = sb[0];
+    if (!w) { s->stop = 1; return; }
+    const int cnt = (int)((pu32)(w >> 32) - 1u);
+    if (p > 0 && cnt <= s->best) { s->stop = 1; return; }
+    const int h = (int)(0xffffffffu - (pu32)w);
+    s->best = cnt;
+    s->winner = p * H + h;
+    for (int j = 0; j < 9; ++j) s->F[j] = hyp[9 * (q * (size_t)H + h) + j];
+}
+
+// one workgroup per pair: L_{p+1}, the positions in L_0 of the model's inliers, ascending
+__global__ __launch_bounds__(256) void twoview_list_kernel(const double4* __restrict__ act, int stride, TwoViewState* __restrict__ state, double t2,
+                                                           int32_t* __restrict__ list)
+{
+    __shared__ int sw[4];
+    const size_t q = blockIdx.x;
+    TwoViewState* s = state + q;
+    if (s->stop) return;
+    const int m0 = s->m0;
+    double F[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) F[j] = s->F[j];
+    int m = 0;
+    for (int base = 0; base < m0; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        bool f = false;
+        if (i < m0) { const double4 c = act[q * stride + i]; f = twoview_inlier(F, c.x, c.y, c.z, c.w, t2); }
+        int total;
+        const int r = block_rank(f, sw, total);
+        if (f) list[q * stride + m + r] = i;
+        m += total;
+    }
+    if (threadIdx.x == 0) s->m = m;
+}
+
+// the outputs of pair blockIdx.y; F_out / winner may be null
+__global__ __launch_bounds__(256) void twoview_final_kernel(const double* __restrict__ corr, int stride, const int32_t* __restrict__ counts,
+                                                            const TwoViewState* __restrict__ state, double t2, int min_inliers,
+                                                            uint8_t* __restrict__ mask, int32_t* __restrict__ count_out, double* __restrict__ F_out,
+                                                            int32_t* __restrict__ winner)
+{
+    const size_t q = blockIdx.y;
+    const TwoViewState* s = state + q;
+    const bool ok = s->best >= min_inliers;
+    double F[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) F[j] = ok ? s->F[j] : NAN;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) { count_out[q] = ok ? s->best : 0; if (winner) winner[q] = ok ? s->winner : -1; }
+        if (threadIdx.x < 9 && F_out) F_out[9 * q + threadIdx.x] = F[threadIdx.x];
+    }
+    if (i >= stride) return;
+    bool in = false;
+    if (ok && i < clamp_count(counts[q], stride)) {
+        const double* r = corr + 4 * ((size_t)stride * q + (size_t)i);
+        const double x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
+        in = finite4(x1, y1, x2, y2) && twoview_inlier(F, x1, y1, x2, y2, t2);
+    }
+    mask[q * stride + i] = in ? 1 : 0;
+}
+
+// ---- match lists: key points through sfm_dmatch into rows, and the surviving elements back out ------------------------------------------
+struct TwoViewKp { const sfm_keypoint* a; const sfm_keypoint* b; };
+
+__global__ __launch_bounds__(256) void twoview_gather_kernel(const TwoViewKp* __restrict__ kp, const sfm_dmatch* __restrict__ matches, int max_per_pair,
+                                                             const int32_t* __restrict__ counts, double fx, double fy, double cx, double cy,
+                                                             double* __restrict__ corr)
+{
+    const size_t q = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= clamp_count(counts[q], max_per_pair)) return;
+    const sfm_dmatch mm = matches[q * max_per_pair + i];
+    double x1 = NAN, y1 = NAN, x2 = NAN, y2 = NAN;                        // an element without a partner: a row that is never sampled nor kept
+    if (mm.queryIdx >= 0 && mm.trainIdx >= 0) {
+        const sfm_keypoint a = kp[q].a[mm.queryIdx], b = kp[q].b[mm.trainIdx];
+        x1 = ((double)a.x - cx) / fx; y1 = ((double)a.y - cy) / fy;
+        x2 = ((double)b.x - cx) / fx; y2 = ((double)b.y - cy) / fy;
+    }
+    double* r = corr + 4 * (q * max_per_pair + i);
+    r[0] = x1; r[1] = y1; r[2] = x2; r[3] = y2;
+}
+
+// one workgroup per pair: the elements whose mask is set, in their order
+__global__ __launch_bounds__(256) void twoview_compact_kernel(const sfm_dmatch* __restrict__ matches, int max_per_pair, const int32_t* __restrict__ counts,
+                                                              const uint8_t* __restrict__ mask, sfm_dmatch* __restrict__ out)
+{
+    __shared__ int sw[4];
+    const size_t q = blockIdx.x;
+    const int cnt = clamp_count(counts[q], max_per_pair);
+    int m = 0;
+    for (int base = 0; base < cnt; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        const bool f = i < cnt && mask[q * max_per_pair + i];
+        sfm_dmatch mm = { 0, 0, 0, 0.f };
+        if (f) mm = matches[q * max_per_pair + i];
+        int total;
+        const int r = block_rank(f, sw, total);
+        if (f) out[q * max_per_pair + m + r] = mm;
+        m += total;
+    }
+}
+
+// every round of up to TWOVIEW_PAIRS_PER_LAUNCH pairs on the context's stream; d_F / d_winner may be null
+static int twoview_enqueue_slice(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
+                                 pu64 seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F, int32_t* d_winner)
+{
+    hipStream_t st = ctx->stream;
+    const size_t P = (size_t)n_pairs, S = (size_t)stride;
+    const int hb = ceil_div(H, 256), nchunks = ceil_div(stride, SCORE_CHUNK), gy = std::max(1, std::min(nchunks, SCORE_MAX_WG / hb));
+    const double t2 = t * t;
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const size_t o_state = carve(P * sizeof(TwoViewState)), o_act = carve(P * S * sizeof(double4)), o_list = carve(P * S * 4),
+                 o_hyp = carve(P * (size_t)H * 9 * sizeof(double)), o_val = carve(P * (size_t)H * 4), o_cnt = carve(P * (size_t)H * 4);
+    SfmPoolHold hold(ctx);
+    char* w = nullptr;
+    const int rc = hold.get(off, (void**)&w);
+    if (rc != SFMHIP_OK) return rc;
+    TwoViewState* state = (TwoViewState*)(w + o_state);
+    double4* act = (double4*)(w + o_act);
+    int32_t *list = (int32_t*)(w + o_list), *hvalid = (int32_t*)(w + o_val), *hcnt = (int32_t*)(w + o_cnt);
+    double* hyp = (double*)(w + o_hyp);
+    hipLaunchKernelGGL(twoview_prep_kernel, dim3(n_pairs), dim3(256), 0, st, d_corr, stride, d_counts, state, act, list);
+    for (int p = 0; p < rounds; ++p) {
+        hipLaunchKernelGGL(twoview_hyp_kernel, dim3(ceil_div(H, HYP_THREADS), n_pairs), dim3(HYP_THREADS), 0, st, (const double4*)act, (const int32_t*)list,
+                           stride, (const TwoViewState*)state, p, H, seed, hyp, hvalid, hcnt);
+        hipLaunchKernelGGL(twoview_score_kernel, dim3(hb, gy, n_pairs), dim3(256), 0, st, (const double4*)act, stride, (const TwoViewState*)state,
+                           (const double*)hyp, H, t2, hcnt);
+        hipLaunchKernelGGL(twoview_winner_kernel, dim3(n_pairs), dim3(256), 0, st, state, p, H, (const double*)hyp, (const int32_t*)hvalid,
+                           (const int32_t*)hcnt);
+        if (p + 1 < rounds)
+            hipLaunchKernelGGL(twoview_list_kernel, dim3(n_pairs), dim3(256), 0, st, (const double4*)act, stride, state, t2, list);
+    }
+    hipLaunchKernelGGL(twoview_final_kernel, dim3(std::max(1, ceil_div(stride, 256)), n_pairs), dim3(256), 0, st, d_corr, stride, d_counts,
+                       (const TwoViewState*)state, t2, min_inliers, d_mask, d_count_out, d_F, d_winner);
+    SFM_HIP_TRY(ctx, hipGetLastError());
+    return SFMHIP_OK;
+}
+
+static int twoview_enqueue(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds, pu64 seed,
+                           int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F, int32_t* d_winner)
+{
+    for (int q0 = 0; q0 < n_pairs; q0 += TWOVIEW_PAIRS_PER_LAUNCH) {
+        const int rc = twoview_enqueue_slice(ctx, d_corr + 4 * (size_t)stride * q0, stride, d_counts + q0, std::min(TWOVIEW_PAIRS_PER_LAUNCH, n_pairs - q0), t, H,
+                                             rounds, seed, min_inliers, d_mask + (size_t)stride * q0, d_count_out + q0, d_F ? d_F + 9 * (size_t)q0 : nullptr,
+                                             d_winner ? d_winner + q0 : nullptr);
+        if (rc != SFMHIP_OK) return rc;
+    }
+    return SFMHIP_OK;
+}
+
+static inline bool twoview_args_ok(const sfmhip_ctx* ctx, int stride, int n_pairs, double t, int H, int rounds, int min_inliers)
+{
+    return ctx && stride >= 0 && n_pairs >= 0 && std::isfinite(t) && t >= 0.0 && H >= 1 && H <= TWOVIEW_H_MAX && rounds >= 1 &&
+           rounds <= TWOVIEW_ROUNDS_MAX && min_inliers >= 8;
+}
+
+extern "C" {
+
+int sfmhip_verify_pairs_dev(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
+                            uint64_t seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F, int32_t* d_winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_pairs_dev");
+    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, stride, n_pairs, t, H, rounds, min_inliers));
+    if (n_pairs == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, (d_corr || stride == 0) && d_counts && (d_mask || stride == 0) && d_count_out);
+    return twoview_enqueue(ctx, d_corr, stride, d_counts, n_pairs, t, H, rounds, (pu64)seed, min_inliers, d_mask, d_count_out, d_F, d_winner);
+}
+
+int sfmhip_verify_pairs(sfmhip_ctx* ctx, const double* corr, int stride, const int32_t* counts, int n_pairs, double t, int H, int rounds, uint64_t seed,
+                        int min_inliers, uint8_t* mask, int32_t* count_out, double* F, int32_t* winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_pairs");
+    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, stride, n_pairs, t, H, rounds, min_inliers));
+    if (n_pairs == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, (corr || stride == 0) && counts && (mask || stride == 0) && count_out);
+    const size_t P = (size_t)n_pairs, S = (size_t)stride;
+    SfmPoolHold hold(ctx);
+    double* d_corr = nullptr; int32_t* d_counts = nullptr; uint8_t* d_mask = nullptr; char* d_head = nullptr;
+    // count, then winner, F
+    const size_t o_wn = align256(P * 4), o_F = o_wn + align256(P * 4), head_bytes = o_F + align256(P * 9 * sizeof(double));
+    int rc = hold.get(&d_corr, P * S * 4);
+    if (rc == SFMHIP_OK && S) rc = sfm_upload(ctx, d_corr, corr, P * S * 4 * sizeof(double));
+    if (rc == SFMHIP_OK) rc = sfm_upload_async(ctx, hold, counts, P, d_counts);
+    if (rc == SFMHIP_OK) rc = hold.get(&d_mask, P * S);
+    if (rc == SFMHIP_OK) rc = hold.get(head_bytes, (void**)&d_head);
+    if (rc == SFMHIP_OK)
+        rc = twoview_enqueue(ctx, d_corr, stride, d_counts, n_pairs, t, H, rounds, (pu64)seed, min_inliers, d_mask, (int32_t*)d_head,
+                             F ? (double*)(d_head + o_F) : nullptr, winner ? (int32_t*)(d_head + o_wn) : nullptr);
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipSuccess;
+    if (S) e = hipMemcpyAsync(mask, d_mask, P * S, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(count_out, d_head, P * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && F) e = hipMemcpyAsync(F, d_head + o_F, P * 9 * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && winner) e = hipMemcpyAsync(winner, d_head + o_wn, P * 4, hipMemcpyDeviceToHost, st);
+    return sfm_finish(ctx, e);
+}
+
+int sfmhip_verify_matches_dev(sfmhip_ctx* ctx, const sfm_keypoint* const* d_kp, int n_sets, const int32_t* pairs, int n_pairs, const double K4[4],
+                              const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, double t, int H, int rounds, uint64_t seed,
+                              int min_inliers, sfm_dmatch* d_matches_out, int32_t* d_counts_out, double* d_F, int32_t* d_winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_matches_dev");
+    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, max_per_pair, n_pairs, t, H, rounds, min_inliers) && n_sets >= 0);
+    if (n_pairs == 0) return SFMHIP_OK;
+    SFM_ARG_CHECK(ctx, d_kp && pairs && K4 && (d_matches || max_per_pair == 0) && d_counts && (d_matches_out || max_per_pair == 0) && d_counts_out);
+    SFM_ARG_CHECK(ctx, std::isfinite(K4[0]) && std::isfinite(K4[1]) && std::isfinite(K4[2]) && std::isfinite(K4[3]) && K4[0] != 0.0 && K4[1] != 0.0);
+    std::vector<TwoViewKp> tbl((size_t)n_pairs);
+    for (int q = 0; q < n_pairs; ++q) {
+        const int a = pairs[2 * q], b = pairs[2 * q + 1];
+        SFM_ARG_CHECK(ctx, a >= 0 && a < n_sets && b >= 0 && b < n_sets);
+        tbl[(size_t)q] = { d_kp[a], d_kp[b] };
+    }
+    const size_t P = (size_t)n_pairs, S = (size_t)max_per_pair;
+    SfmPoolHold hold(ctx);
+    TwoViewKp* d_tbl = nullptr; double* d_corr = nullptr; uint8_t* d_mask = nullptr;
+    int rc = sfm_upload_async(ctx, hold, tbl.data(), P, d_tbl);           // pageable source: consumed when the call returns
+    if (rc == SFMHIP_OK) rc = hold.get(&d_corr, P * S * 4);
+    if (rc == SFMHIP_OK) rc = hold.get(&d_mask, P * S);
+    if (rc != SFMHIP_OK) return rc;
+    hipStream_t st = ctx->stream;
+    for (int q0 = 0; q0 < n_pairs; q0 += TWOVIEW_PAIRS_PER_LAUNCH)
+        hipLaunchKernelGGL(twoview_gather_kernel, dim3(std::max(1, ceil_div(max_per_pair, 256)), std::min(TWOVIEW_PAIRS_PER_LAUNCH, n_pairs - q0)), dim3(256), 0, st,
+                           (const TwoViewKp*)d_tbl + q0, d_matches + S * q0, max_per_pair, d_counts + q0, K4[0], K4[1], K4[2], K4[3], d_corr + 4 * S * q0);
+    rc = twoview_enqueue(ctx, d_corr, max_per_pair, d_counts, n_pairs, t, H, rounds, (pu64)seed, min_inliers, d_mask, d_counts_out, d_F, d_winner);
+    if (rc != SFMHIP_OK) return rc;
+    hipLaunchKernelGGL(twoview_compact_kernel, dim3(n_pairs), dim3(256), 0, st, d_matches, max_per_pair, d_counts, (const uint8_t*)d_mask, d_matches_out);
+    SFM_HIP_TRY(ctx, hipGetLastError());
+    return SFMHIP_OK;
+}
+
+}

@@ -193,6 +193,60 @@ inline void match_features_for_all(const std::vector<Mat>& descriptor_for_all, s
     }
 }
 
+// ---- two-view geometric verification (extension; what colmap / OpenMVG run between matching and reconstruction; the reference rejects
+// epipolar outliers for its first pair only, inside findEssentialMat, NView:1032) -- matches_for_all[i] joins images i and i + 1.  The key
+// points are normalised by K, the threshold is px pixels (t = px / (0.5 (fx + fy))), all pairs run in one call of sfmhip_verify_pairs
+// (where the definition is).  A pair whose model keeps at least min_inliers matches is replaced by the kept ones, in their order; any
+// other pair keeps its matches as they are, with a warning, so the chain cannot break.  counts[i] = the matches kept by the model of
+// pair i (0: none); F (may be null): 9 doubles per pair on normalised coordinates, NaN where there is no model.  Returns 0, -1 on error.
+inline int verify_matches_for_all(const Mat& K, const std::vector<std::vector<KeyPoint>>& key_points_for_all,
+                                  std::vector<std::vector<DMatch>>& matches_for_all, std::vector<int32_t>& counts, const double px = 1.0,
+                                  const int hypotheses = 1024, const int rounds = 3, const int min_inliers = 15, const uint64_t seed = 0,
+                                  std::vector<double>* F = nullptr)
+{
+    const int n_pairs = (int)matches_for_all.size();
+    counts.assign((size_t)n_pairs, 0);
+    if (F) F->assign((size_t)n_pairs * 9, std::nan(""));
+    sfmhip_ctx* ctx = context();
+    if (!ctx || (int)key_points_for_all.size() < n_pairs + 1) return -1;
+    if (n_pairs == 0) return 0;
+    const double fx = K.at<double>(0, 0), fy = K.at<double>(1, 1), cx = K.at<double>(0, 2), cy = K.at<double>(1, 2);
+    size_t stride = 0;
+    for (const auto& m : matches_for_all) stride = m.size() > stride ? m.size() : stride;
+    std::vector<double> corr((size_t)n_pairs * stride * 4, 0.0);
+    std::vector<int32_t> rows((size_t)n_pairs);
+    std::vector<uint8_t> mask((size_t)n_pairs * stride, 0);
+    for (int i = 0; i < n_pairs; ++i) {
+        const auto& m = matches_for_all[(size_t)i];
+        rows[(size_t)i] = (int32_t)m.size();
+        double* r = corr.data() + (size_t)i * stride * 4;
+        for (size_t k = 0; k < m.size(); ++k, r += 4) {
+            const KeyPoint& a = key_points_for_all[(size_t)i][(size_t)m[k].queryIdx];
+            const KeyPoint& b = key_points_for_all[(size_t)i + 1][(size_t)m[k].trainIdx];
+            r[0] = ((double)a.pt.x - cx) / fx; r[1] = ((double)a.pt.y - cy) / fy;
+            r[2] = ((double)b.pt.x - cx) / fx; r[3] = ((double)b.pt.y - cy) / fy;
+        }
+    }
+    if (sfmhip_verify_pairs(ctx, corr.data(), (int)stride, rows.data(), n_pairs, px / (0.5 * (fx + fy)), hypotheses, rounds, seed, min_inliers, mask.data(),
+                            counts.data(), F ? F->data() : nullptr, nullptr) != SFMHIP_OK) {
+        printf("[Err]: verify_matches_for_all: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    for (int i = 0; i < n_pairs; ++i) {
+        auto& m = matches_for_all[(size_t)i];
+        if (counts[(size_t)i] == 0) {
+            printf("[Warning]: pair %d: no epipolar model with %d matches, the %zu matches are kept as they are.\n", i, min_inliers, m.size());
+            continue;
+        }
+        const uint8_t* keep = mask.data() + (size_t)i * stride;
+        size_t w = 0;
+        for (size_t k = 0; k < m.size(); ++k)
+            if (keep[k]) m[w++] = m[k];
+        m.resize(w);
+    }
+    return 0;
+}
+
 inline void get_matched_points(const std::vector<KeyPoint>& p1, const std::vector<KeyPoint>& p2, const std::vector<DMatch> matches,
                                std::vector<Point2f>& out_p1, std::vector<Point2f>& out_p2)
 {

@@ -239,6 +239,9 @@ struct PipelineOptions {
     double planes_t = -1.0;                // >= 0: report up to planes_max planes of at least planes_min points within this distance on that cloud (segment_planes; extension, changes no file)
     int    planes_max = 1;
     int    planes_min = 3;
+    double verify_px = -1.0;               // >= 0: right after matching, every pair keeps only the matches within this many pixels of its epipolar model (verify_matches_for_all; extension, not reference behaviour)
+    int    verify_h = 1024;                // ... hypotheses per round
+    int    verify_rounds = 3;              // ... rounds
 };
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
@@ -249,6 +252,14 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
     std::vector<std::vector<DMatch>> matches_for_all;
     match_features_for_all(f.descriptor_for_all, matches_for_all, opt.cross_check);
     if (matches_for_all.empty()) { printf("[Err]: fewer than two usable images.\n"); return -1; }
+    if (opt.verify_px >= 0.0) {
+        // 15: the gate find_transform puts on the inliers of findEssentialMat (NView:1042)
+        std::vector<size_t> before;
+        for (const auto& m : matches_for_all) before.push_back(m.size());
+        std::vector<int32_t> kept;
+        if (verify_matches_for_all(K, kpts_for_all, matches_for_all, kept, opt.verify_px, opt.verify_h, opt.verify_rounds, 15) < 0) return -1;
+        for (size_t i = 0; i < before.size(); ++i) printf("pair %zu: verified %d of %zu\n", i, (int)kept[i], before[i]);
+    }
 
     std::vector<Point3d> pts3d;
     std::vector<std::vector<int>> inds_2d_to_3d;
@@ -418,7 +429,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -463,6 +474,16 @@ inline int driver_main(int argc, char** argv, bool nview)
                 opt.planes_max = std::atoi(a.c_str() + c1 + 1);
                 const size_t c2 = a.find(',', c1 + 1);
                 if (c2 != std::string::npos) opt.planes_min = std::atoi(a.c_str() + c2 + 1);
+            }
+        }
+        else if (a == "--verify-matches") opt.verify_px = 1.0;   // findEssentialMat's threshold (NView:1032)
+        else if (a.rfind("--verify-matches=", 0) == 0) {         // PX[,H[,ROUNDS]]: after matching, keep of every pair only the matches within PX (1.0) pixels of its epipolar model: H (1024) hypotheses in each of ROUNDS (3) rounds
+            opt.verify_px = std::atof(a.c_str() + 17);
+            const size_t c1 = a.find(',', 17);
+            if (c1 != std::string::npos) {
+                opt.verify_h = std::atoi(a.c_str() + c1 + 1);
+                const size_t c2 = a.find(',', c1 + 1);
+                if (c2 != std::string::npos) opt.verify_rounds = std::atoi(a.c_str() + c2 + 1);
             }
         }
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
