@@ -581,8 +581,9 @@ int sfmhip_segment_plane     (sfmhip_ctx*, const double* pts,   int n, double t,
  *   mask: n_pairs x stride uint8; count_out: n_pairs int32; F: n_pairs x 9 double; winner: n_pairs int32.
  *   SFMHIP_E_ARG with the outputs left alone: t non-finite or negative, H, rounds or min_inliers out of range, a negative stride or
  *     n_pairs, a null required pointer.  n_pairs == 0: OK, no pointer touched.
- *   Known limit: eight-point samples are degenerate on an exactly planar scene (the host's findEssentialMat has a homography branch for
- *     it; this call has none). */
+ *   Known limit: eight-point samples are degenerate on an exactly planar scene, and a pair related by a pure rotation or seeing one plane
+ *     is accepted with a high count although its F is not determined (every [v]x H fits it).  This call alone cannot tell;
+ *     sfmhip_two_view_geometry below runs a homography RANSAC beside it and says which pairs are of that kind. */
 int sfmhip_verify_pairs    (sfmhip_ctx*, const double* corr,   int stride, const int32_t* counts,   int n_pairs, double t, int H, int rounds,
                             uint64_t seed, int min_inliers, uint8_t* mask,   int32_t* count_out,   double* F /* may be NULL */,
                             int32_t* winner /* may be NULL */);
@@ -603,6 +604,63 @@ int sfmhip_verify_matches_dev(sfmhip_ctx*, const sfm_keypoint* const* d_kp, int 
                               const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, double t, int H, int rounds,
                               uint64_t seed, int min_inliers, sfm_dmatch* d_matches_out, int32_t* d_counts_out,
                               double* d_F /* may be NULL */, int32_t* d_winner /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Homography RANSAC and F/H model selection (what colmap and OpenMVG run beside the epipolar   */
+/* RANSAC: a pair whose matches a homography explains nearly as well as F is planar or          */
+/* panoramic, and its two-view pose is ill-determined).  Again the definition: every integer    */
+/* output is a function of the input alone and Hm is prescribed bit for bit.                    */
+/* ------------------------------------------------------------------------------------------ */
+/*   sfmhip_verify_pairs_h: input blocks, counts, stride, L_0, seed, H (1..65536) and rounds (1..8) as in sfmhip_verify_pairs;
+ *     min_inliers >= 4.
+ *   Sample of hypothesis h of round p: m = |L_p|; m < 4: the pair stops.  With g = p*H + h, for k = 0..3:  u = r(4g + k) % (m - k);
+ *     then the rule of the eight-row sample: for each position already chosen, in ascending order, u += (u >= s_j).  Row k of the sample
+ *     is L_p[u_k], in draw order.
+ *   Hypothesis: A, 8 x 9; sample row k = (x1, y1, x2, y2) gives
+ *       row 2k   = [x1, y1, 1, 0, 0, 0, -(x2*x1), -(x2*y1), -x2]
+ *       row 2k+1 = [0, 0, 0, x1, y1, 1, -(y2*x1), -(y2*y1), -y2];
+ *     then steps 2 to 6 of the sfmhip_verify_pairs hypothesis unchanged.  Hm = h / nrm, row-major 3 x 3, maps image 1 to image 2.  No
+ *     further degeneracy test: three collinear rows give an ill-conditioned system whose hypothesis scores few rows, a repeated row an
+ *     exact zero pivot.
+ *   Residual of a row (fp64, no contraction):  u = (H0*x1 + H1*y1) + H2;  v = (H3*x1 + H4*y1) + H5;  w = (H6*x1 + H7*y1) + H8;
+ *       du = u - x2*w;  dv = v - y2*w.  The row is an inlier iff du*du + dv*dv <= t2*(w*w): the squared forward transfer distance against
+ *     t^2 with the division multiplied out, inclusive, decided on the computed values.  The sign of w is not tested (as in OpenCV's
+ *     findHomography).  The transfer distance is a 2-D point distance that carries the noise of both images, where the Sampson distance
+ *     is a distance to a line: at equal noise a homography wants about twice F's threshold.
+ *   Round, stop rule, outputs (mask, count, winner, the nine NaN of "no model") and errors: exactly as for F, with 4 where F has 8. */
+int sfmhip_verify_pairs_h    (sfmhip_ctx*, const double* corr,   int stride, const int32_t* counts,   int n_pairs, double t, int H, int rounds,
+                              uint64_t seed, int min_inliers, uint8_t* mask,   int32_t* count_out,   double* Hm /* may be NULL */,
+                              int32_t* winner /* may be NULL */);
+/* the same on device arrays: enqueues only */
+int sfmhip_verify_pairs_h_dev(sfmhip_ctx*, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
+                              uint64_t seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_Hm /* may be NULL */,
+                              int32_t* d_winner /* may be NULL */);
+/* Both models and the decision.  min_inliers >= 8; hf_ratio finite and > 0; t_f, t_h finite and >= 0.  Per pair, cF, winner_F and F are
+ * what sfmhip_verify_pairs returns for (t_f, H, rounds, seed, min_inliers), and cH, winner_H and Hm what sfmhip_verify_pairs_h returns for
+ * (t_h, the same).  kind (int32):
+ *     cF == 0 && cH == 0:                                                   kind = 0 (none); mask all 0, count = 0;
+ *     else if cH > 0 && (double)cH >= hf_ratio * (double)cF (the computed fp64 product):
+ *                                                                           kind = 2 (planar or panoramic); mask and count are H's;
+ *     else:                                                                 kind = 1 (general); mask and count are F's.
+ * counts2 (n_pairs x 2: cF, cH), F, Hm and winners (n_pairs x 2: winner_F, winner_H) always report both models.  SFMHIP_E_ARG with the
+ * outputs left alone as above; n_pairs == 0: OK, no pointer touched. */
+int sfmhip_two_view_geometry    (sfmhip_ctx*, const double* corr,   int stride, const int32_t* counts,   int n_pairs, double t_f, double t_h, int H,
+                                 int rounds, uint64_t seed, int min_inliers, double hf_ratio, int32_t* kind, uint8_t* mask, int32_t* count_out,
+                                 int32_t* counts2 /* may be NULL */, double* F /* may be NULL */, double* Hm /* may be NULL */,
+                                 int32_t* winners /* may be NULL */);
+/* the same on device arrays: enqueues only and never synchronises; no round and no selection waits on the host */
+int sfmhip_two_view_geometry_dev(sfmhip_ctx*, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t_f, double t_h, int H,
+                                 int rounds, uint64_t seed, int min_inliers, double hf_ratio, int32_t* d_kind, uint8_t* d_mask, int32_t* d_count_out,
+                                 int32_t* d_counts2 /* may be NULL */, double* d_F /* may be NULL */, double* d_Hm /* may be NULL */,
+                                 int32_t* d_winners /* may be NULL */);
+/* sfmhip_verify_matches_dev with the selection: the same gather through K4, then sfmhip_two_view_geometry_dev on the rows, then the
+ * ordered compaction of the selected mask into d_matches_out / d_counts_out (d_counts_out[q] = the selected model's count, 0 for kind
+ * 0), for sfmhip_triangulate2_matches_dev to consume; d_kind: n_pairs int32. */
+int sfmhip_two_view_geometry_matches_dev(sfmhip_ctx*, const sfm_keypoint* const* d_kp, int n_sets, const int32_t* pairs, int n_pairs,
+                                         const double K4[4], const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, double t_f,
+                                         double t_h, int H, int rounds, uint64_t seed, int min_inliers, double hf_ratio, int32_t* d_kind,
+                                         sfm_dmatch* d_matches_out, int32_t* d_counts_out, int32_t* d_counts2 /* may be NULL */,
+                                         double* d_F /* may be NULL */, double* d_Hm /* may be NULL */, int32_t* d_winners /* may be NULL */);
 
 #ifdef __cplusplus
 }

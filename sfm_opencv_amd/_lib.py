@@ -69,6 +69,8 @@ SYMBOLS = [
     "sfmhip_cluster_dbscan", "sfmhip_cluster_dbscan_dev", "sfmhip_largest_cluster",
     "sfmhip_segment_planes", "sfmhip_segment_planes_dev", "sfmhip_segment_plane",
     "sfmhip_verify_pairs", "sfmhip_verify_pairs_dev", "sfmhip_verify_matches_dev",
+    "sfmhip_verify_pairs_h", "sfmhip_verify_pairs_h_dev",
+    "sfmhip_two_view_geometry", "sfmhip_two_view_geometry_dev", "sfmhip_two_view_geometry_matches_dev",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -177,6 +179,12 @@ def load():
         "sfmhip_verify_pairs": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
         "sfmhip_verify_pairs_dev": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
         "sfmhip_verify_matches_dev": (i32, [vp, C.POINTER(vp), i32, vp, i32, vp, vp, i32, vp, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
+        "sfmhip_verify_pairs_h": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
+        "sfmhip_verify_pairs_h_dev": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
+        "sfmhip_two_view_geometry": (i32, [vp, vp, i32, vp, i32, f64, f64, i32, i32, C.c_uint64, i32, f64, vp, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_two_view_geometry_dev": (i32, [vp, vp, i32, vp, i32, f64, f64, i32, i32, C.c_uint64, i32, f64, vp, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_two_view_geometry_matches_dev": (i32, [vp, C.POINTER(vp), i32, vp, i32, vp, vp, i32, vp, f64, f64, i32, i32, C.c_uint64, i32, f64,
+                                                       vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

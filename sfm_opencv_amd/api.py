@@ -521,6 +521,70 @@ class Context:
                                                        int(seed) & (2 ** 64 - 1), int(min_inliers), _dptr(d_matches_out), _dptr(d_counts_out),
                                                        _dptr(d_F), _dptr(d_winner)))
 
+    # ---------------------------------------------------------------- homography RANSAC and F/H model selection
+    @staticmethod
+    def _corr_blocks(corr_blocks):
+        """(corr n x stride x 4, counts int32 n, n, stride) of a sequence of (m_q, 4) arrays"""
+        blocks = [np.ascontiguousarray(b, np.float64).reshape(-1, 4) for b in corr_blocks]
+        n = len(blocks)
+        counts = np.array([len(b) for b in blocks], np.int32)
+        stride = int(counts.max()) if n else 0
+        corr = np.zeros((n, stride, 4))
+        for q, b in enumerate(blocks):
+            corr[q, :len(b)] = b
+        return corr, counts, n, stride
+
+    def verify_pairs_h(self, corr_blocks, t, hypotheses=1024, rounds=3, seed=0, min_inliers=4):
+        """(masks, counts int32 n, Hm n x 3 x 3, winner int32 n): the four-point homography RANSAC of sfmhip_verify_pairs_h on every block
+        of corr_blocks, in the form of verify_pairs; Hm maps image 1 to image 2."""
+        corr, counts, n, stride = self._corr_blocks(corr_blocks)
+        mask = np.zeros((n, stride), np.uint8); cnt = np.zeros(n, np.int32); Hm = np.full((n, 9), np.nan); win = np.full(n, -1, np.int32)
+        self._check(self.lib.sfmhip_verify_pairs_h(self.h, corr.ctypes.data, stride, counts.ctypes.data, n, float(t), int(hypotheses), int(rounds),
+                                                   int(seed) & (2 ** 64 - 1), int(min_inliers), mask.ctypes.data, cnt.ctypes.data, Hm.ctypes.data,
+                                                   win.ctypes.data))
+        return [mask[q, :c].astype(bool) for q, c in enumerate(counts.tolist())], cnt, Hm.reshape(n, 3, 3), win
+
+    def verify_pairs_h_dev(self, d_corr, stride, d_counts, n_pairs, t, d_mask, d_count_out, d_Hm=0, d_winner=0, hypotheses=1024, rounds=3, seed=0,
+                           min_inliers=4):
+        """the same on device arrays, in the form of verify_pairs_dev; enqueues only"""
+        self._check(self.lib.sfmhip_verify_pairs_h_dev(self.h, _dptr(d_corr), int(stride), _dptr(d_counts), int(n_pairs), float(t), int(hypotheses),
+                                                       int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers), _dptr(d_mask), _dptr(d_count_out),
+                                                       _dptr(d_Hm), _dptr(d_winner)))
+
+    def two_view_geometry(self, corr_blocks, t_f, t_h, hypotheses=1024, rounds=3, seed=0, min_inliers=8, hf_ratio=0.8):
+        """(kind int32 n, masks, counts int32 n, counts2 int32 n x 2, F n x 3 x 3, Hm n x 3 x 3, winners int32 n x 2): both RANSACs and
+        the selection of sfmhip_two_view_geometry.  kind 0: no model, 1: general (masks[q], counts[q] are F's), 2: planar or panoramic
+        (they are the homography's); counts2, F, Hm and winners report both models whatever the kind."""
+        corr, counts, n, stride = self._corr_blocks(corr_blocks)
+        kind = np.zeros(n, np.int32); mask = np.zeros((n, stride), np.uint8); cnt = np.zeros(n, np.int32); c2 = np.zeros((n, 2), np.int32)
+        F = np.full((n, 9), np.nan); Hm = np.full((n, 9), np.nan); win = np.full((n, 2), -1, np.int32)
+        self._check(self.lib.sfmhip_two_view_geometry(self.h, corr.ctypes.data, stride, counts.ctypes.data, n, float(t_f), float(t_h), int(hypotheses),
+                                                      int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers), float(hf_ratio), kind.ctypes.data,
+                                                      mask.ctypes.data, cnt.ctypes.data, c2.ctypes.data, F.ctypes.data, Hm.ctypes.data, win.ctypes.data))
+        return kind, [mask[q, :c].astype(bool) for q, c in enumerate(counts.tolist())], cnt, c2, F.reshape(n, 3, 3), Hm.reshape(n, 3, 3), win
+
+    def two_view_geometry_dev(self, d_corr, stride, d_counts, n_pairs, t_f, t_h, d_kind, d_mask, d_count_out, d_counts2=0, d_F=0, d_Hm=0, d_winners=0,
+                              hypotheses=1024, rounds=3, seed=0, min_inliers=8, hf_ratio=0.8):
+        """the same on device arrays (0: not wanted): d_kind int32 n_pairs, d_counts2 / d_winners int32 n_pairs x 2; enqueues only, no
+        round and no selection waits on the host"""
+        self._check(self.lib.sfmhip_two_view_geometry_dev(self.h, _dptr(d_corr), int(stride), _dptr(d_counts), int(n_pairs), float(t_f), float(t_h),
+                                                          int(hypotheses), int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers), float(hf_ratio),
+                                                          _dptr(d_kind), _dptr(d_mask), _dptr(d_count_out), _dptr(d_counts2), _dptr(d_F), _dptr(d_Hm),
+                                                          _dptr(d_winners)))
+
+    def two_view_geometry_matches_dev(self, d_kp, pairs, K4, d_matches, max_per_pair, d_counts, t_f, t_h, d_kind, d_matches_out, d_counts_out,
+                                      d_counts2=0, d_F=0, d_Hm=0, d_winners=0, hypotheses=1024, rounds=3, seed=0, min_inliers=8, hf_ratio=0.8):
+        """verify_matches_dev with the selection (sfmhip_two_view_geometry_matches_dev): d_matches_out / d_counts_out receive the elements
+        the selected model of every pair keeps, for triangulate2_matches_dev; d_kind says which model that was.  Enqueues only."""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        K4 = np.ascontiguousarray(K4, np.float64).reshape(4)
+        arr = (C.c_void_p * len(d_kp))(*[_dptr(k) for k in d_kp])
+        self._check(self.lib.sfmhip_two_view_geometry_matches_dev(self.h, arr, len(d_kp), pairs.ctypes.data, pairs.shape[0], K4.ctypes.data,
+                                                                  _dptr(d_matches), int(max_per_pair), _dptr(d_counts), float(t_f), float(t_h),
+                                                                  int(hypotheses), int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers),
+                                                                  float(hf_ratio), _dptr(d_kind), _dptr(d_matches_out), _dptr(d_counts_out),
+                                                                  _dptr(d_counts2), _dptr(d_F), _dptr(d_Hm), _dptr(d_winners)))
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
@@ -775,6 +839,41 @@ def verify_matches_for_all(K, key_points_for_all, matches_for_all, px=1.0, hypot
         else:
             out.append(m[masks[i]])
     return out, [(int(c), f) for c, f in zip(counts, F)]
+
+
+GEOMETRY_KINDS = ("none", "general", "planar-or-panoramic")      # kind 0, 1, 2 of sfmhip_two_view_geometry
+
+
+def two_view_geometry_for_all(K, key_points_for_all, matches_for_all, px=1.0, px_h=2.0, hypotheses=1024, rounds=3, seed=0, min_inliers=15,
+                              hf_ratio=0.8, ctx=None):
+    """verify_matches_for_all with a homography RANSAC beside the epipolar one and the F/H selection of sfmhip_two_view_geometry: the
+    thresholds are px pixels for F and px_h pixels for the homography (a transfer distance carries the noise of both images).  Returns
+    (kept lists, [(kind, count, cF, cH, F 3 x 3, Hm 3 x 3)] per pair): a pair of kind 1 (general) keeps F's inliers, a pair of kind 2
+    (planar or panoramic: its two-view pose is ill-determined, a warning says so) the homography's, and a pair of kind 0 keeps its
+    matches as they are, with a warning."""
+    ctx = ctx or default_context()
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    blocks = []
+    for i, m in enumerate(matches_for_all):
+        a, b = key_points_for_all[i], key_points_for_all[i + 1]
+        q, t = m["queryIdx"], m["trainIdx"]
+        blocks.append(np.stack([(a["x"][q].astype(np.float64) - cx) / fx, (a["y"][q].astype(np.float64) - cy) / fy,
+                                (b["x"][t].astype(np.float64) - cx) / fx, (b["y"][t].astype(np.float64) - cy) / fy], 1).reshape(-1, 4))
+    if not blocks:
+        return [], []
+    f = 0.5 * (fx + fy)
+    kind, masks, counts, c2, F, Hm, _ = ctx.two_view_geometry(blocks, px / f, px_h / f, hypotheses, rounds, seed, min_inliers, hf_ratio)
+    out = []
+    for i, m in enumerate(matches_for_all):
+        if kind[i] == 0:
+            print("[Warning]: pair %d: no two-view model with %d matches, the %d matches are kept as they are." % (i, min_inliers, len(m)))
+            out.append(m)
+        else:
+            if kind[i] == 2:
+                print("[Warning]: pair %d: planar or panoramic (H explains %d matches, F %d): its two-view pose is ill-determined." % (i, c2[i, 1], c2[i, 0]))
+            out.append(m[masks[i]])
+    return out, [(int(kind[i]), int(counts[i]), int(c2[i, 0]), int(c2[i, 1]), F[i], Hm[i]) for i in range(len(blocks))]
 
 
 def get_matched_points(p1, p2, matches):

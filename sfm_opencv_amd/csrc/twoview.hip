@@ -23,6 +23,15 @@
 // l, m, e and d (contraction is off: the residual is the prescribed formula), two more multiplications for e*e and t2*d, a compare and a
 // conditional add: 35 VALU instructions, which is what bounds the kernel (the account is in DESIGN.md 4c).  Counts: one integer
 // atomicAdd per lane at the very end.
+//
+// TWO MODELS share this machinery: the fundamental matrix above (EpipolarModel) and the four-point homography of sfmhip_verify_pairs_h
+// (HomographyModel), which is also the null vector of an 8 x 9 system.  A model supplies its inlier test and the shortest list a round
+// may sample from; the per-pair kernels (winner, list, final) are templates over it, the elimination (null_vector_8x9) and the scoring
+// loop (score_rows) are one __device__ body each that the two hypothesis kernels and the two scoring kernels call, and prep runs once per
+// call whatever the number of models.  homography_hyp_kernel differs from twoview_hyp_kernel in the sample (four rows) and the design
+// matrix; homography_score_kernel in the residual: 12 multiplications, 9 additions, a compare and a conditional add per row, 23 VALU
+// instructions against 35.  sfmhip_two_view_geometry runs both models over the same packed rows, one after the other through the same
+// pairs x H hypothesis areas, and geometry_select_kernel then decides per pair which mask is the pair's (the rule is in sfmhip.h).
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -46,9 +55,9 @@ struct TwoViewState {
     int best;                 // the model's count, -1 while there is no model
     int winner;               // g = p * H + h of the model
     int pad[3];
-    double F[9];              // the model
+    double F[9];              // the model (F, or the homography)
 };
-__device__ __forceinline__ bool round_dead(const TwoViewState* s) { return s->stop || s->m < 8; }
+template <class M> __device__ __forceinline__ bool round_dead(const TwoViewState* s) { return s->stop || s->m < M::MIN_ROWS; }
 
 __device__ __forceinline__ pu64 splitmix64(pu64 seed, pu64 c)
 {
@@ -71,6 +80,26 @@ __device__ __forceinline__ bool twoview_inlier(const double (&F)[9], double x1, 
     const double d = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
     return e * e <= t2 * d;
 }
+// THE transfer test of the homography model, under the same rule: the squared forward transfer distance against t^2 with the division by
+// w^2 multiplied out.  False for a NaN H.
+__device__ __forceinline__ bool homography_inlier(const double (&Hm)[9], double x1, double y1, double x2, double y2, double t2)
+{
+    const double u = (Hm[0] * x1 + Hm[1] * y1) + Hm[2];
+    const double v = (Hm[3] * x1 + Hm[4] * y1) + Hm[5];
+    const double w = (Hm[6] * x1 + Hm[7] * y1) + Hm[8];
+    const double du = u - x2 * w;
+    const double dv = v - y2 * w;
+    return du * du + dv * dv <= t2 * (w * w);
+}
+// what a model supplies to the kernels that are templates over it
+struct EpipolarModel {
+    static constexpr int MIN_ROWS = 8;
+    static __device__ __forceinline__ bool inlier(const double (&F)[9], double x1, double y1, double x2, double y2, double t2) { return twoview_inlier(F, x1, y1, x2, y2, t2); }
+};
+struct HomographyModel {
+    static constexpr int MIN_ROWS = 4;
+    static __device__ __forceinline__ bool inlier(const double (&Hm)[9], double x1, double y1, double x2, double y2, double t2) { return homography_inlier(Hm, x1, y1, x2, y2, t2); }
+};
 __device__ __forceinline__ bool finite4(double a, double b, double c, double d) { return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d); }
 __device__ __forceinline__ int clamp_count(int c, int stride) { return c < 0 ? 0 : (c > stride ? stride : c); }
 
@@ -89,9 +118,11 @@ __device__ __forceinline__ int block_rank(bool f, int* sw, int& total)
     return below;
 }
 
-// one workgroup per pair: L_0 packed into act, the identity as the list of round 0, the state
+// one workgroup per pair: L_0 packed into act, the identity as the list of round 0, the state; state2 / list2: the same for a second
+// model that runs over the same rows, or null
 __global__ __launch_bounds__(256) void twoview_prep_kernel(const double* __restrict__ corr, int stride, const int32_t* __restrict__ counts,
-                                                           TwoViewState* __restrict__ state, double4* __restrict__ act, int32_t* __restrict__ list)
+                                                           TwoViewState* __restrict__ state, double4* __restrict__ act, int32_t* __restrict__ list,
+                                                           TwoViewState* __restrict__ state2, int32_t* __restrict__ list2)
 {
     __shared__ int sw[4];
     const size_t q = blockIdx.x;
@@ -108,51 +139,29 @@ __global__ __launch_bounds__(256) void twoview_prep_kernel(const double* __restr
         }
         int total;
         const int r = block_rank(f, sw, total);
-        if (f) { act[q * stride + m + r] = make_double4(x1, y1, x2, y2); list[q * stride + m + r] = m + r; }
+        if (f) {
+            act[q * stride + m + r] = make_double4(x1, y1, x2, y2); list[q * stride + m + r] = m + r;
+            if (list2) list2[q * stride + m + r] = m + r;
+        }
         m += total;
     }
     if (threadIdx.x == 0) {
         TwoViewState* s = state + q;
         s->stop = 0; s->m = m; s->m0 = m; s->best = -1; s->winner = -1;
+        if (state2) { s = state2 + q; s->stop = 0; s->m = m; s->m0 = m; s->best = -1; s->winner = -1; }
     }
 }
 
-// hypothesis h of round p of pair q: hyp[9 (q H + h) ..] = F, NaN where it is invalid (it then counts nobody); its counter cleared.
-// The 8 x 9 matrix stays in registers: every loop is unrolled, so every index is a constant, and the one thing the pivoting decides at
+// The sampling-free part of a hypothesis, steps 2 to 6 of the definition: the unit null vector of the 8 x 9 system A at hyp[9 at ..], NaN
+// where the hypothesis is invalid (it then counts nobody); its valid bit; its counter cleared.
+// The matrix stays in registers: every loop is unrolled, so every index is a constant, and the one thing the pivoting decides at
 // run time, which row and which column trade places, is done with selects over the candidates (SWAP_IF).  The same values move as in an
 // indexed swap, so the arithmetic is the prescribed one.  (With the matrix in LDS and indexed by the pivot the kernel waited on one
 // dependent LDS access after another: 179 us for 199 x 1024 hypotheses against the figure in DESIGN.md 4c for this form.)
 #define SWAP_IF(c, a, b) { const double ta_ = (a), tb_ = (b); (a) = (c) ? tb_ : ta_; (b) = (c) ? ta_ : tb_; }
-__global__ __launch_bounds__(HYP_THREADS) void twoview_hyp_kernel(const double4* __restrict__ act, const int32_t* __restrict__ list, int stride,
-                                                                  const TwoViewState* __restrict__ state, int p, int H, pu64 seed,
-                                                                  double* __restrict__ hyp, int32_t* __restrict__ hvalid, int32_t* __restrict__ hcnt)
+__device__ __forceinline__ void null_vector_8x9(double (&A)[8][9], size_t at, double* __restrict__ hyp, int32_t* __restrict__ hvalid,
+                                                int32_t* __restrict__ hcnt)
 {
-    const size_t q = blockIdx.y;
-    const TwoViewState* s = state + q;
-    if (round_dead(s)) return;
-    const int h = blockIdx.x * HYP_THREADS + threadIdx.x;
-    if (h >= H) return;
-    const pu64 m = (pu64)s->m;
-    const pu64 g = (pu64)p * (pu64)H + (pu64)h;
-    double A[8][9];
-    // eight distinct positions in L_p; srt: the ones chosen so far in ascending order
-    pu64 srt[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        pu64 u = splitmix64(seed, 8ull * g + (pu64)k) % (m - (pu64)k);
-#pragma unroll
-        for (int j = 0; j < k; ++j) u += u >= srt[j] ? 1ull : 0ull;
-        const double4 r = act[q * stride + (size_t)list[q * stride + u]];
-        A[k][0] = r.z * r.x; A[k][1] = r.z * r.y; A[k][2] = r.z;
-        A[k][3] = r.w * r.x; A[k][4] = r.w * r.y; A[k][5] = r.w;
-        A[k][6] = r.x;       A[k][7] = r.y;       A[k][8] = 1.0;
-        srt[k] = u;
-#pragma unroll
-        for (int j = k; j > 0; --j) {
-            const pu64 lo = srt[j] < srt[j - 1] ? srt[j] : srt[j - 1], hi = srt[j] < srt[j - 1] ? srt[j - 1] : srt[j];
-            srt[j - 1] = lo; srt[j] = hi;
-        }
-    }
     int perm[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) perm[j] = j;
@@ -212,7 +221,6 @@ __global__ __launch_bounds__(HYP_THREADS) void twoview_hyp_kernel(const double4*
     for (int j = 1; j < 9; ++j) ss = ss + f[j] * f[j];
     const double nrm = sqrt(ss);
     valid = valid && isfinite(nrm) && nrm > 0.0;
-    const size_t at = q * (size_t)H + (size_t)h;
 #pragma unroll
     for (int j = 0; j < 9; ++j) hyp[9 * at + j] = valid ? f[j] / nrm : NAN;
     hvalid[at] = valid ? 1 : 0;
@@ -220,14 +228,82 @@ __global__ __launch_bounds__(HYP_THREADS) void twoview_hyp_kernel(const double4*
 }
 #undef SWAP_IF
 
-// the pairs x H x |L_0| part (the shape is explained at the top of the file)
-__global__ __launch_bounds__(256) void twoview_score_kernel(const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
-                                                            const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
+// hypothesis h of round p of pair q: hyp[9 (q H + h) ..] = F from eight rows of L_p
+__global__ __launch_bounds__(HYP_THREADS) void twoview_hyp_kernel(const double4* __restrict__ act, const int32_t* __restrict__ list, int stride,
+                                                                  const TwoViewState* __restrict__ state, int p, int H, pu64 seed,
+                                                                  double* __restrict__ hyp, int32_t* __restrict__ hvalid, int32_t* __restrict__ hcnt)
 {
-    __shared__ double4 tile[SCORE_CHUNK];
+    const size_t q = blockIdx.y;
+    const TwoViewState* s = state + q;
+    if (round_dead<EpipolarModel>(s)) return;
+    const int h = blockIdx.x * HYP_THREADS + threadIdx.x;
+    if (h >= H) return;
+    const pu64 m = (pu64)s->m;
+    const pu64 g = (pu64)p * (pu64)H + (pu64)h;
+    double A[8][9];
+    // eight distinct positions in L_p; srt: the ones chosen so far in ascending order
+    pu64 srt[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        pu64 u = splitmix64(seed, 8ull * g + (pu64)k) % (m - (pu64)k);
+#pragma unroll
+        for (int j = 0; j < k; ++j) u += u >= srt[j] ? 1ull : 0ull;
+        const double4 r = act[q * stride + (size_t)list[q * stride + u]];
+        A[k][0] = r.z * r.x; A[k][1] = r.z * r.y; A[k][2] = r.z;
+        A[k][3] = r.w * r.x; A[k][4] = r.w * r.y; A[k][5] = r.w;
+        A[k][6] = r.x;       A[k][7] = r.y;       A[k][8] = 1.0;
+        srt[k] = u;
+#pragma unroll
+        for (int j = k; j > 0; --j) {
+            const pu64 lo = srt[j] < srt[j - 1] ? srt[j] : srt[j - 1], hi = srt[j] < srt[j - 1] ? srt[j - 1] : srt[j];
+            srt[j - 1] = lo; srt[j] = hi;
+        }
+    }
+    null_vector_8x9(A, q * (size_t)H + (size_t)h, hyp, hvalid, hcnt);
+}
+
+// the same for the homography: four rows of L_p, two rows of the system each
+__global__ __launch_bounds__(HYP_THREADS) void homography_hyp_kernel(const double4* __restrict__ act, const int32_t* __restrict__ list, int stride,
+                                                                     const TwoViewState* __restrict__ state, int p, int H, pu64 seed,
+                                                                     double* __restrict__ hyp, int32_t* __restrict__ hvalid, int32_t* __restrict__ hcnt)
+{
+    const size_t q = blockIdx.y;
+    const TwoViewState* s = state + q;
+    if (round_dead<HomographyModel>(s)) return;
+    const int h = blockIdx.x * HYP_THREADS + threadIdx.x;
+    if (h >= H) return;
+    const pu64 m = (pu64)s->m;
+    const pu64 g = (pu64)p * (pu64)H + (pu64)h;
+    double A[8][9];
+    pu64 srt[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pu64 u = splitmix64(seed, 4ull * g + (pu64)k) % (m - (pu64)k);
+#pragma unroll
+        for (int j = 0; j < k; ++j) u += u >= srt[j] ? 1ull : 0ull;
+        const double4 r = act[q * stride + (size_t)list[q * stride + u]];
+        A[2 * k][0] = r.x; A[2 * k][1] = r.y; A[2 * k][2] = 1.0; A[2 * k][3] = 0.0; A[2 * k][4] = 0.0; A[2 * k][5] = 0.0;
+        A[2 * k][6] = -(r.z * r.x); A[2 * k][7] = -(r.z * r.y); A[2 * k][8] = -r.z;
+        A[2 * k + 1][0] = 0.0; A[2 * k + 1][1] = 0.0; A[2 * k + 1][2] = 0.0; A[2 * k + 1][3] = r.x; A[2 * k + 1][4] = r.y; A[2 * k + 1][5] = 1.0;
+        A[2 * k + 1][6] = -(r.w * r.x); A[2 * k + 1][7] = -(r.w * r.y); A[2 * k + 1][8] = -r.w;
+        srt[k] = u;
+#pragma unroll
+        for (int j = k; j > 0; --j) {
+            const pu64 lo = srt[j] < srt[j - 1] ? srt[j] : srt[j - 1], hi = srt[j] < srt[j - 1] ? srt[j - 1] : srt[j];
+            srt[j - 1] = lo; srt[j] = hi;
+        }
+    }
+    null_vector_8x9(A, q * (size_t)H + (size_t)h, hyp, hvalid, hcnt);
+}
+
+// the pairs x H x |L_0| part (the shape is explained at the top of the file); tile: SCORE_CHUNK rows of LDS
+template <class M>
+__device__ __forceinline__ void score_rows(double4* tile, const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
+                                           const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
+{
     const size_t q = blockIdx.z;
     const TwoViewState* s = state + q;
-    if (round_dead(s)) return;                                           // uniform over the workgroup
+    if (round_dead<M>(s)) return;                                        // uniform over the workgroup
     const int m0 = s->m0;
     if ((long long)blockIdx.y * SCORE_CHUNK >= m0) return;
     const int h = blockIdx.x * 256 + threadIdx.x;
@@ -252,13 +328,26 @@ __global__ __launch_bounds__(256) void twoview_score_kernel(const double4* __res
 #pragma unroll 4
         for (int r = 0; r < cnt; ++r) {
             const double4 c = tile[r];
-            count += twoview_inlier(F, c.x, c.y, c.z, c.w, t2) ? 1 : 0;
+            count += M::inlier(F, c.x, c.y, c.z, c.w, t2) ? 1 : 0;
         }
     }
     if (live && count) atomicAdd(hcnt + at, count);
 }
+__global__ __launch_bounds__(256) void twoview_score_kernel(const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
+                                                            const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
+{
+    __shared__ double4 tile[SCORE_CHUNK];
+    score_rows<EpipolarModel>(tile, act, stride, state, hyp, H, t2, hcnt);
+}
+__global__ __launch_bounds__(256) void homography_score_kernel(const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
+                                                               const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
+{
+    __shared__ double4 tile[SCORE_CHUNK];
+    score_rows<HomographyModel>(tile, act, stride, state, hyp, H, t2, hcnt);
+}
 
 // one workgroup per pair: argmax of (count, then the smallest h) over the valid hypotheses; the pair's model, or its stop flag
+template <class M>
 __global__ __launch_bounds__(256) void twoview_winner_kernel(TwoViewState* __restrict__ state, int p, int H, const double* __restrict__ hyp,
                                                              const int32_t* __restrict__ hvalid, const int32_t* __restrict__ hcnt)
 {
@@ -268,7 +357,7 @@ __global__ __launch_bounds__(256) void twoview_winner_kernel(TwoViewState* __res
     const int stop = s->stop, m = s->m;
     __syncthreads();                                                     // everybody has read the state before thread 0 may change it
     if (stop) return;
-    if (m < 8) { if (threadIdx.x == 0) s->stop = 1; return; }
+    if (m < M::MIN_ROWS) { if (threadIdx.x == 0) s->stop = 1; return; }
     pu64 best = 0ull;
     for (int h = threadIdx.x; h < H; h += 256) {
         if (!hvalid[q * (size_t)H + h]) continue;
@@ -293,6 +382,7 @@ __global__ __launch_bounds__(256) void twoview_winner_kernel(TwoViewState* __res
 }
 
 // one workgroup per pair: L_{p+1}, the positions in L_0 of the model's inliers, ascending
+template <class M>
 __global__ __launch_bounds__(256) void twoview_list_kernel(const double4* __restrict__ act, int stride, TwoViewState* __restrict__ state, double t2,
                                                            int32_t* __restrict__ list)
 {
@@ -308,7 +398,7 @@ __global__ __launch_bounds__(256) void twoview_list_kernel(const double4* __rest
     for (int base = 0; base < m0; base += 256) {
         const int i = base + (int)threadIdx.x;
         bool f = false;
-        if (i < m0) { const double4 c = act[q * stride + i]; f = twoview_inlier(F, c.x, c.y, c.z, c.w, t2); }
+        if (i < m0) { const double4 c = act[q * stride + i]; f = M::inlier(F, c.x, c.y, c.z, c.w, t2); }
         int total;
         const int r = block_rank(f, sw, total);
         if (f) list[q * stride + m + r] = i;
@@ -317,7 +407,8 @@ __global__ __launch_bounds__(256) void twoview_list_kernel(const double4* __rest
     if (threadIdx.x == 0) s->m = m;
 }
 
-// the outputs of pair blockIdx.y; F_out / winner may be null
+// the outputs of pair blockIdx.y for one model; F_out / winner may be null
+template <class M>
 __global__ __launch_bounds__(256) void twoview_final_kernel(const double* __restrict__ corr, int stride, const int32_t* __restrict__ counts,
                                                             const TwoViewState* __restrict__ state, double t2, int min_inliers,
                                                             uint8_t* __restrict__ mask, int32_t* __restrict__ count_out, double* __restrict__ F_out,
@@ -339,9 +430,31 @@ __global__ __launch_bounds__(256) void twoview_final_kernel(const double* __rest
     if (ok && i < clamp_count(counts[q], stride)) {
         const double* r = corr + 4 * ((size_t)stride * q + (size_t)i);
         const double x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
-        in = finite4(x1, y1, x2, y2) && twoview_inlier(F, x1, y1, x2, y2, t2);
+        in = finite4(x1, y1, x2, y2) && M::inlier(F, x1, y1, x2, y2, t2);
     }
     mask[q * stride + i] = in ? 1 : 0;
+}
+
+// the model selection of sfmhip_two_view_geometry for pair blockIdx.y: kind from the two counts, the selected mask, and both models' counts
+// and winners side by side; counts2 / winners may be null
+__global__ __launch_bounds__(256) void geometry_select_kernel(int stride, const int32_t* __restrict__ cF, const int32_t* __restrict__ cH,
+                                                              const int32_t* __restrict__ wF, const int32_t* __restrict__ wH,
+                                                              const uint8_t* __restrict__ maskF, const uint8_t* __restrict__ maskH, double hf_ratio,
+                                                              int32_t* __restrict__ kind, uint8_t* __restrict__ mask, int32_t* __restrict__ count_out,
+                                                              int32_t* __restrict__ counts2, int32_t* __restrict__ winners)
+{
+    const size_t q = blockIdx.y;
+    const int nf = cF[q], nh = cH[q];
+    const int k = (nf == 0 && nh == 0) ? 0 : (nh > 0 && (double)nh >= hf_ratio * (double)nf) ? 2 : 1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        kind[q] = k;
+        count_out[q] = k == 2 ? nh : k == 1 ? nf : 0;
+        if (counts2) { counts2[2 * q] = nf; counts2[2 * q + 1] = nh; }
+        if (winners) { winners[2 * q] = wF[q]; winners[2 * q + 1] = wH[q]; }
+    }
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= stride) return;
+    mask[q * stride + i] = k == 2 ? maskH[q * stride + i] : k == 1 ? maskF[q * stride + i] : 0;
 }
 
 // ---- match lists: key points through sfm_dmatch into rows, and the surviving elements back out ------------------------------------------
@@ -385,114 +498,173 @@ __global__ __launch_bounds__(256) void twoview_compact_kernel(const sfm_dmatch* 
     }
 }
 
-// every round of up to TWOVIEW_PAIRS_PER_LAUNCH pairs on the context's stream; d_F / d_winner may be null
-static int twoview_enqueue_slice(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
-                                 pu64 seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F, int32_t* d_winner)
+// what a call computes, and where its outputs go
+enum { GEOM_F = 1, GEOM_H = 2, GEOM_BOTH = 3 };
+struct GeomOut {
+    uint8_t* mask; int32_t* count;           // the model's (GEOM_F, GEOM_H) or the selected one's (GEOM_BOTH)
+    double* F; int32_t* winF;                // may be null
+    double* Hm; int32_t* winH;               // may be null
+    int32_t* kind; int32_t* counts2; int32_t* winners;      // GEOM_BOTH only; counts2, winners (n x 2 each) may be null
+};
+static GeomOut geom_out_at(const GeomOut& o, size_t q0, size_t stride)
+{
+    GeomOut r = o;
+    r.mask = o.mask + stride * q0; r.count = o.count + q0;
+    if (o.F) r.F = o.F + 9 * q0;
+    if (o.winF) r.winF = o.winF + q0;
+    if (o.Hm) r.Hm = o.Hm + 9 * q0;
+    if (o.winH) r.winH = o.winH + q0;
+    if (o.kind) r.kind = o.kind + q0;
+    if (o.counts2) r.counts2 = o.counts2 + 2 * q0;
+    if (o.winners) r.winners = o.winners + 2 * q0;
+    return r;
+}
+struct GeomParams { double t_f, t_h; int H, rounds; pu64 seed; int min_inliers; double hf_ratio; };
+
+// the scratch areas the rounds of one model work in
+struct RoundAreas { TwoViewState* state; double4* act; int32_t* list; double* hyp; int32_t *hvalid, *hcnt; };
+
+// every round of one model over n_pairs pairs, then its final kernel
+template <class M>
+static void enqueue_model(hipStream_t st, const RoundAreas& a, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t,
+                          const GeomParams& g, uint8_t* d_mask, int32_t* d_count_out, double* d_model, int32_t* d_winner)
+{
+    constexpr bool epipolar = M::MIN_ROWS == 8;
+    const int H = g.H, hb = ceil_div(H, 256), nchunks = ceil_div(stride, SCORE_CHUNK), gy = std::max(1, std::min(nchunks, SCORE_MAX_WG / hb));
+    const double t2 = t * t;
+    const auto hyp_kernel = epipolar ? twoview_hyp_kernel : homography_hyp_kernel;
+    const auto score_kernel = epipolar ? twoview_score_kernel : homography_score_kernel;
+    for (int p = 0; p < g.rounds; ++p) {
+        hipLaunchKernelGGL(hyp_kernel, dim3(ceil_div(H, HYP_THREADS), n_pairs), dim3(HYP_THREADS), 0, st,
+                           (const double4*)a.act, (const int32_t*)a.list, stride, (const TwoViewState*)a.state, p, H, g.seed, a.hyp, a.hvalid, a.hcnt);
+        hipLaunchKernelGGL(score_kernel, dim3(hb, gy, n_pairs), dim3(256), 0, st, (const double4*)a.act, stride,
+                           (const TwoViewState*)a.state, (const double*)a.hyp, H, t2, a.hcnt);
+        hipLaunchKernelGGL(twoview_winner_kernel<M>, dim3(n_pairs), dim3(256), 0, st, a.state, p, H, (const double*)a.hyp, (const int32_t*)a.hvalid,
+                           (const int32_t*)a.hcnt);
+        if (p + 1 < g.rounds)
+            hipLaunchKernelGGL(twoview_list_kernel<M>, dim3(n_pairs), dim3(256), 0, st, (const double4*)a.act, stride, a.state, t2, a.list);
+    }
+    hipLaunchKernelGGL(twoview_final_kernel<M>, dim3(std::max(1, ceil_div(stride, 256)), n_pairs), dim3(256), 0, st, d_corr, stride, d_counts,
+                       (const TwoViewState*)a.state, t2, g.min_inliers, d_mask, d_count_out, d_model, d_winner);
+}
+
+// up to TWOVIEW_PAIRS_PER_LAUNCH pairs on the context's stream: prep once, then the model(s), then (GEOM_BOTH) the selection.  The two
+// models of GEOM_BOTH have a state and a list each and share the packed rows and the pairs x H hypothesis, valid and counter areas.
+static int twoview_enqueue_slice(sfmhip_ctx* ctx, int models, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, const GeomParams& g,
+                                 const GeomOut& o)
 {
     hipStream_t st = ctx->stream;
-    const size_t P = (size_t)n_pairs, S = (size_t)stride;
-    const int hb = ceil_div(H, 256), nchunks = ceil_div(stride, SCORE_CHUNK), gy = std::max(1, std::min(nchunks, SCORE_MAX_WG / hb));
-    const double t2 = t * t;
+    const size_t P = (size_t)n_pairs, S = (size_t)stride, H = (size_t)g.H;
+    const bool both = models == GEOM_BOTH;
     size_t off = 0;
     auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
     const size_t o_state = carve(P * sizeof(TwoViewState)), o_act = carve(P * S * sizeof(double4)), o_list = carve(P * S * 4),
-                 o_hyp = carve(P * (size_t)H * 9 * sizeof(double)), o_val = carve(P * (size_t)H * 4), o_cnt = carve(P * (size_t)H * 4);
+                 o_hyp = carve(P * H * 9 * sizeof(double)), o_val = carve(P * H * 4), o_cnt = carve(P * H * 4);
+    const size_t o_state2 = carve(both ? P * sizeof(TwoViewState) : 0), o_list2 = carve(both ? P * S * 4 : 0), o_maskF = carve(both ? P * S : 0),
+                 o_maskH = carve(both ? P * S : 0), o_head = carve(both ? 4 * align256(P * 4) : 0);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(off, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
-    TwoViewState* state = (TwoViewState*)(w + o_state);
-    double4* act = (double4*)(w + o_act);
-    int32_t *list = (int32_t*)(w + o_list), *hvalid = (int32_t*)(w + o_val), *hcnt = (int32_t*)(w + o_cnt);
-    double* hyp = (double*)(w + o_hyp);
-    hipLaunchKernelGGL(twoview_prep_kernel, dim3(n_pairs), dim3(256), 0, st, d_corr, stride, d_counts, state, act, list);
-    for (int p = 0; p < rounds; ++p) {
-        hipLaunchKernelGGL(twoview_hyp_kernel, dim3(ceil_div(H, HYP_THREADS), n_pairs), dim3(HYP_THREADS), 0, st, (const double4*)act, (const int32_t*)list,
-                           stride, (const TwoViewState*)state, p, H, seed, hyp, hvalid, hcnt);
-        hipLaunchKernelGGL(twoview_score_kernel, dim3(hb, gy, n_pairs), dim3(256), 0, st, (const double4*)act, stride, (const TwoViewState*)state,
-                           (const double*)hyp, H, t2, hcnt);
-        hipLaunchKernelGGL(twoview_winner_kernel, dim3(n_pairs), dim3(256), 0, st, state, p, H, (const double*)hyp, (const int32_t*)hvalid,
-                           (const int32_t*)hcnt);
-        if (p + 1 < rounds)
-            hipLaunchKernelGGL(twoview_list_kernel, dim3(n_pairs), dim3(256), 0, st, (const double4*)act, stride, state, t2, list);
+    RoundAreas a = { (TwoViewState*)(w + o_state), (double4*)(w + o_act), (int32_t*)(w + o_list), (double*)(w + o_hyp), (int32_t*)(w + o_val),
+                     (int32_t*)(w + o_cnt) };
+    RoundAreas a2 = a;
+    a2.state = (TwoViewState*)(w + o_state2); a2.list = (int32_t*)(w + o_list2);
+    hipLaunchKernelGGL(twoview_prep_kernel, dim3(n_pairs), dim3(256), 0, st, d_corr, stride, d_counts, a.state, a.act, a.list,
+                       both ? a2.state : (TwoViewState*)nullptr, both ? a2.list : (int32_t*)nullptr);
+    if (models == GEOM_F)
+        enqueue_model<EpipolarModel>(st, a, d_corr, stride, d_counts, n_pairs, g.t_f, g, o.mask, o.count, o.F, o.winF);
+    else if (models == GEOM_H)
+        enqueue_model<HomographyModel>(st, a, d_corr, stride, d_counts, n_pairs, g.t_h, g, o.mask, o.count, o.Hm, o.winH);
+    else {
+        uint8_t *maskF = (uint8_t*)(w + o_maskF), *maskH = (uint8_t*)(w + o_maskH);
+        int32_t *cF = (int32_t*)(w + o_head), *cH = (int32_t*)(w + o_head + align256(P * 4)), *wF = (int32_t*)(w + o_head + 2 * align256(P * 4)),
+                *wH = (int32_t*)(w + o_head + 3 * align256(P * 4));
+        enqueue_model<EpipolarModel>(st, a, d_corr, stride, d_counts, n_pairs, g.t_f, g, maskF, cF, o.F, wF);
+        enqueue_model<HomographyModel>(st, a2, d_corr, stride, d_counts, n_pairs, g.t_h, g, maskH, cH, o.Hm, wH);
+        hipLaunchKernelGGL(geometry_select_kernel, dim3(std::max(1, ceil_div(stride, 256)), n_pairs), dim3(256), 0, st, stride, (const int32_t*)cF,
+                           (const int32_t*)cH, (const int32_t*)wF, (const int32_t*)wH, (const uint8_t*)maskF, (const uint8_t*)maskH, g.hf_ratio, o.kind,
+                           o.mask, o.count, o.counts2, o.winners);
     }
-    hipLaunchKernelGGL(twoview_final_kernel, dim3(std::max(1, ceil_div(stride, 256)), n_pairs), dim3(256), 0, st, d_corr, stride, d_counts,
-                       (const TwoViewState*)state, t2, min_inliers, d_mask, d_count_out, d_F, d_winner);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;
 }
 
-static int twoview_enqueue(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds, pu64 seed,
-                           int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F, int32_t* d_winner)
+static int twoview_enqueue(sfmhip_ctx* ctx, int models, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, const GeomParams& g,
+                           const GeomOut& o)
 {
     for (int q0 = 0; q0 < n_pairs; q0 += TWOVIEW_PAIRS_PER_LAUNCH) {
-        const int rc = twoview_enqueue_slice(ctx, d_corr + 4 * (size_t)stride * q0, stride, d_counts + q0, std::min(TWOVIEW_PAIRS_PER_LAUNCH, n_pairs - q0), t, H,
-                                             rounds, seed, min_inliers, d_mask + (size_t)stride * q0, d_count_out + q0, d_F ? d_F + 9 * (size_t)q0 : nullptr,
-                                             d_winner ? d_winner + q0 : nullptr);
+        const int rc = twoview_enqueue_slice(ctx, models, d_corr + 4 * (size_t)stride * q0, stride, d_counts + q0, std::min(TWOVIEW_PAIRS_PER_LAUNCH, n_pairs - q0),
+                                             g, geom_out_at(o, (size_t)q0, (size_t)stride));
         if (rc != SFMHIP_OK) return rc;
     }
     return SFMHIP_OK;
 }
 
-static inline bool twoview_args_ok(const sfmhip_ctx* ctx, int stride, int n_pairs, double t, int H, int rounds, int min_inliers)
+static inline bool thr_ok(double t) { return std::isfinite(t) && t >= 0.0; }
+static inline bool twoview_args_ok(const sfmhip_ctx* ctx, int models, int stride, int n_pairs, const GeomParams& g)
 {
-    return ctx && stride >= 0 && n_pairs >= 0 && std::isfinite(t) && t >= 0.0 && H >= 1 && H <= TWOVIEW_H_MAX && rounds >= 1 &&
-           rounds <= TWOVIEW_ROUNDS_MAX && min_inliers >= 8;
+    return ctx && stride >= 0 && n_pairs >= 0 && (!(models & GEOM_F) || thr_ok(g.t_f)) && (!(models & GEOM_H) || thr_ok(g.t_h)) && g.H >= 1 &&
+           g.H <= TWOVIEW_H_MAX && g.rounds >= 1 && g.rounds <= TWOVIEW_ROUNDS_MAX && g.min_inliers >= (models == GEOM_H ? 4 : 8) &&
+           (models != GEOM_BOTH || (std::isfinite(g.hf_ratio) && g.hf_ratio > 0.0));
 }
 
-extern "C" {
-
-int sfmhip_verify_pairs_dev(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
-                            uint64_t seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F, int32_t* d_winner)
+// the device form of all three calls
+static int geometry_dev(sfmhip_ctx* ctx, int models, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, const GeomParams& g,
+                        const GeomOut& o)
 {
-    SFM_DEVICE_GUARD(ctx);
-    SFM_RANGE("sfmhip_verify_pairs_dev");
-    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, stride, n_pairs, t, H, rounds, min_inliers));
+    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, models, stride, n_pairs, g));
     if (n_pairs == 0) return SFMHIP_OK;
-    SFM_ARG_CHECK(ctx, (d_corr || stride == 0) && d_counts && (d_mask || stride == 0) && d_count_out);
-    return twoview_enqueue(ctx, d_corr, stride, d_counts, n_pairs, t, H, rounds, (pu64)seed, min_inliers, d_mask, d_count_out, d_F, d_winner);
+    SFM_ARG_CHECK(ctx, (d_corr || stride == 0) && d_counts && (o.mask || stride == 0) && o.count && (models != GEOM_BOTH || o.kind));
+    return twoview_enqueue(ctx, models, d_corr, stride, d_counts, n_pairs, g, o);
 }
 
-int sfmhip_verify_pairs(sfmhip_ctx* ctx, const double* corr, int stride, const int32_t* counts, int n_pairs, double t, int H, int rounds, uint64_t seed,
-                        int min_inliers, uint8_t* mask, int32_t* count_out, double* F, int32_t* winner)
+// the host form of all three calls: blocks and counts up, the outputs the caller wants back.  o holds HOST pointers.
+static int geometry_host(sfmhip_ctx* ctx, int models, const double* corr, int stride, const int32_t* counts, int n_pairs, const GeomParams& g, const GeomOut& o)
 {
-    SFM_DEVICE_GUARD(ctx);
-    SFM_RANGE("sfmhip_verify_pairs");
-    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, stride, n_pairs, t, H, rounds, min_inliers));
+    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, models, stride, n_pairs, g));
     if (n_pairs == 0) return SFMHIP_OK;
-    SFM_ARG_CHECK(ctx, (corr || stride == 0) && counts && (mask || stride == 0) && count_out);
+    SFM_ARG_CHECK(ctx, (corr || stride == 0) && counts && (o.mask || stride == 0) && o.count && (models != GEOM_BOTH || o.kind));
     const size_t P = (size_t)n_pairs, S = (size_t)stride;
     SfmPoolHold hold(ctx);
     double* d_corr = nullptr; int32_t* d_counts = nullptr; uint8_t* d_mask = nullptr; char* d_head = nullptr;
-    // count, then winner, F
-    const size_t o_wn = align256(P * 4), o_F = o_wn + align256(P * 4), head_bytes = o_F + align256(P * 9 * sizeof(double));
+    // count, then winner F, winner H, kind, counts2, winners, F, Hm
+    const size_t i4 = align256(P * 4), i8 = align256(P * 8), d9 = align256(P * 9 * sizeof(double));
+    const size_t o_wf = i4, o_wh = o_wf + i4, o_kind = o_wh + i4, o_c2 = o_kind + i4, o_w2 = o_c2 + i8, o_F = o_w2 + i8, o_Hm = o_F + d9, head_bytes = o_Hm + d9;
     int rc = hold.get(&d_corr, P * S * 4);
     if (rc == SFMHIP_OK && S) rc = sfm_upload(ctx, d_corr, corr, P * S * 4 * sizeof(double));
     if (rc == SFMHIP_OK) rc = sfm_upload_async(ctx, hold, counts, P, d_counts);
     if (rc == SFMHIP_OK) rc = hold.get(&d_mask, P * S);
     if (rc == SFMHIP_OK) rc = hold.get(head_bytes, (void**)&d_head);
-    if (rc == SFMHIP_OK)
-        rc = twoview_enqueue(ctx, d_corr, stride, d_counts, n_pairs, t, H, rounds, (pu64)seed, min_inliers, d_mask, (int32_t*)d_head,
-                             F ? (double*)(d_head + o_F) : nullptr, winner ? (int32_t*)(d_head + o_wn) : nullptr);
+    GeomOut d = { d_mask, (int32_t*)d_head, o.F ? (double*)(d_head + o_F) : nullptr, o.winF ? (int32_t*)(d_head + o_wf) : nullptr,
+                  o.Hm ? (double*)(d_head + o_Hm) : nullptr, o.winH ? (int32_t*)(d_head + o_wh) : nullptr, o.kind ? (int32_t*)(d_head + o_kind) : nullptr,
+                  o.counts2 ? (int32_t*)(d_head + o_c2) : nullptr, o.winners ? (int32_t*)(d_head + o_w2) : nullptr };
+    if (rc == SFMHIP_OK) rc = twoview_enqueue(ctx, models, d_corr, stride, d_counts, n_pairs, g, d);
     if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
-    if (S) e = hipMemcpyAsync(mask, d_mask, P * S, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(count_out, d_head, P * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && F) e = hipMemcpyAsync(F, d_head + o_F, P * 9 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && winner) e = hipMemcpyAsync(winner, d_head + o_wn, P * 4, hipMemcpyDeviceToHost, st);
+    auto back = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
+    back(o.mask, d.mask, P * S);
+    back(o.count, d.count, P * 4);
+    back(o.F, d.F, P * 9 * sizeof(double));
+    back(o.winF, d.winF, P * 4);
+    back(o.Hm, d.Hm, P * 9 * sizeof(double));
+    back(o.winH, d.winH, P * 4);
+    back(o.kind, d.kind, P * 4);
+    back(o.counts2, d.counts2, P * 8);
+    back(o.winners, d.winners, P * 8);
     return sfm_finish(ctx, e);
 }
 
-int sfmhip_verify_matches_dev(sfmhip_ctx* ctx, const sfm_keypoint* const* d_kp, int n_sets, const int32_t* pairs, int n_pairs, const double K4[4],
-                              const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, double t, int H, int rounds, uint64_t seed,
-                              int min_inliers, sfm_dmatch* d_matches_out, int32_t* d_counts_out, double* d_F, int32_t* d_winner)
+// the match-list form: gather through K4, the model(s), the ordered compaction of the resulting mask
+static int geometry_matches_dev(sfmhip_ctx* ctx, int models, const sfm_keypoint* const* d_kp, int n_sets, const int32_t* pairs, int n_pairs, const double K4[4],
+                                const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, const GeomParams& g, sfm_dmatch* d_matches_out,
+                                GeomOut o)
 {
-    SFM_DEVICE_GUARD(ctx);
-    SFM_RANGE("sfmhip_verify_matches_dev");
-    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, max_per_pair, n_pairs, t, H, rounds, min_inliers) && n_sets >= 0);
+    SFM_ARG_CHECK(ctx, twoview_args_ok(ctx, models, max_per_pair, n_pairs, g) && n_sets >= 0);
     if (n_pairs == 0) return SFMHIP_OK;
-    SFM_ARG_CHECK(ctx, d_kp && pairs && K4 && (d_matches || max_per_pair == 0) && d_counts && (d_matches_out || max_per_pair == 0) && d_counts_out);
+    SFM_ARG_CHECK(ctx, d_kp && pairs && K4 && (d_matches || max_per_pair == 0) && d_counts && (d_matches_out || max_per_pair == 0) && o.count &&
+                           (models != GEOM_BOTH || o.kind));
     SFM_ARG_CHECK(ctx, std::isfinite(K4[0]) && std::isfinite(K4[1]) && std::isfinite(K4[2]) && std::isfinite(K4[3]) && K4[0] != 0.0 && K4[1] != 0.0);
     std::vector<TwoViewKp> tbl((size_t)n_pairs);
     for (int q = 0; q < n_pairs; ++q) {
@@ -511,11 +683,93 @@ int sfmhip_verify_matches_dev(sfmhip_ctx* ctx, const sfm_keypoint* const* d_kp, 
     for (int q0 = 0; q0 < n_pairs; q0 += TWOVIEW_PAIRS_PER_LAUNCH)
         hipLaunchKernelGGL(twoview_gather_kernel, dim3(std::max(1, ceil_div(max_per_pair, 256)), std::min(TWOVIEW_PAIRS_PER_LAUNCH, n_pairs - q0)), dim3(256), 0, st,
                            (const TwoViewKp*)d_tbl + q0, d_matches + S * q0, max_per_pair, d_counts + q0, K4[0], K4[1], K4[2], K4[3], d_corr + 4 * S * q0);
-    rc = twoview_enqueue(ctx, d_corr, max_per_pair, d_counts, n_pairs, t, H, rounds, (pu64)seed, min_inliers, d_mask, d_counts_out, d_F, d_winner);
+    o.mask = d_mask;
+    rc = twoview_enqueue(ctx, models, d_corr, max_per_pair, d_counts, n_pairs, g, o);
     if (rc != SFMHIP_OK) return rc;
     hipLaunchKernelGGL(twoview_compact_kernel, dim3(n_pairs), dim3(256), 0, st, d_matches, max_per_pair, d_counts, (const uint8_t*)d_mask, d_matches_out);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return SFMHIP_OK;
+}
+
+extern "C" {
+
+int sfmhip_verify_pairs_dev(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
+                            uint64_t seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_F, int32_t* d_winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_pairs_dev");
+    return geometry_dev(ctx, GEOM_F, d_corr, stride, d_counts, n_pairs, GeomParams{ t, 0.0, H, rounds, (pu64)seed, min_inliers, 0.0 },
+                        GeomOut{ d_mask, d_count_out, d_F, d_winner, nullptr, nullptr, nullptr, nullptr, nullptr });
+}
+
+int sfmhip_verify_pairs(sfmhip_ctx* ctx, const double* corr, int stride, const int32_t* counts, int n_pairs, double t, int H, int rounds, uint64_t seed,
+                        int min_inliers, uint8_t* mask, int32_t* count_out, double* F, int32_t* winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_pairs");
+    return geometry_host(ctx, GEOM_F, corr, stride, counts, n_pairs, GeomParams{ t, 0.0, H, rounds, (pu64)seed, min_inliers, 0.0 },
+                         GeomOut{ mask, count_out, F, winner, nullptr, nullptr, nullptr, nullptr, nullptr });
+}
+
+int sfmhip_verify_matches_dev(sfmhip_ctx* ctx, const sfm_keypoint* const* d_kp, int n_sets, const int32_t* pairs, int n_pairs, const double K4[4],
+                              const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, double t, int H, int rounds, uint64_t seed,
+                              int min_inliers, sfm_dmatch* d_matches_out, int32_t* d_counts_out, double* d_F, int32_t* d_winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_matches_dev");
+    return geometry_matches_dev(ctx, GEOM_F, d_kp, n_sets, pairs, n_pairs, K4, d_matches, max_per_pair, d_counts,
+                                GeomParams{ t, 0.0, H, rounds, (pu64)seed, min_inliers, 0.0 }, d_matches_out,
+                                GeomOut{ nullptr, d_counts_out, d_F, d_winner, nullptr, nullptr, nullptr, nullptr, nullptr });
+}
+
+int sfmhip_verify_pairs_h_dev(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t, int H, int rounds,
+                              uint64_t seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_Hm, int32_t* d_winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_pairs_h_dev");
+    return geometry_dev(ctx, GEOM_H, d_corr, stride, d_counts, n_pairs, GeomParams{ 0.0, t, H, rounds, (pu64)seed, min_inliers, 0.0 },
+                        GeomOut{ d_mask, d_count_out, nullptr, nullptr, d_Hm, d_winner, nullptr, nullptr, nullptr });
+}
+
+int sfmhip_verify_pairs_h(sfmhip_ctx* ctx, const double* corr, int stride, const int32_t* counts, int n_pairs, double t, int H, int rounds, uint64_t seed,
+                          int min_inliers, uint8_t* mask, int32_t* count_out, double* Hm, int32_t* winner)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_verify_pairs_h");
+    return geometry_host(ctx, GEOM_H, corr, stride, counts, n_pairs, GeomParams{ 0.0, t, H, rounds, (pu64)seed, min_inliers, 0.0 },
+                         GeomOut{ mask, count_out, nullptr, nullptr, Hm, winner, nullptr, nullptr, nullptr });
+}
+
+int sfmhip_two_view_geometry_dev(sfmhip_ctx* ctx, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t_f, double t_h, int H,
+                                 int rounds, uint64_t seed, int min_inliers, double hf_ratio, int32_t* d_kind, uint8_t* d_mask, int32_t* d_count_out,
+                                 int32_t* d_counts2, double* d_F, double* d_Hm, int32_t* d_winners)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_two_view_geometry_dev");
+    return geometry_dev(ctx, GEOM_BOTH, d_corr, stride, d_counts, n_pairs, GeomParams{ t_f, t_h, H, rounds, (pu64)seed, min_inliers, hf_ratio },
+                        GeomOut{ d_mask, d_count_out, d_F, nullptr, d_Hm, nullptr, d_kind, d_counts2, d_winners });
+}
+
+int sfmhip_two_view_geometry(sfmhip_ctx* ctx, const double* corr, int stride, const int32_t* counts, int n_pairs, double t_f, double t_h, int H, int rounds,
+                             uint64_t seed, int min_inliers, double hf_ratio, int32_t* kind, uint8_t* mask, int32_t* count_out, int32_t* counts2, double* F,
+                             double* Hm, int32_t* winners)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_two_view_geometry");
+    return geometry_host(ctx, GEOM_BOTH, corr, stride, counts, n_pairs, GeomParams{ t_f, t_h, H, rounds, (pu64)seed, min_inliers, hf_ratio },
+                         GeomOut{ mask, count_out, F, nullptr, Hm, nullptr, kind, counts2, winners });
+}
+
+int sfmhip_two_view_geometry_matches_dev(sfmhip_ctx* ctx, const sfm_keypoint* const* d_kp, int n_sets, const int32_t* pairs, int n_pairs, const double K4[4],
+                                         const sfm_dmatch* d_matches, int max_per_pair, const int32_t* d_counts, double t_f, double t_h, int H, int rounds,
+                                         uint64_t seed, int min_inliers, double hf_ratio, int32_t* d_kind, sfm_dmatch* d_matches_out, int32_t* d_counts_out,
+                                         int32_t* d_counts2, double* d_F, double* d_Hm, int32_t* d_winners)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_two_view_geometry_matches_dev");
+    return geometry_matches_dev(ctx, GEOM_BOTH, d_kp, n_sets, pairs, n_pairs, K4, d_matches, max_per_pair, d_counts,
+                                GeomParams{ t_f, t_h, H, rounds, (pu64)seed, min_inliers, hf_ratio }, d_matches_out,
+                                GeomOut{ nullptr, d_counts_out, d_F, nullptr, d_Hm, nullptr, d_kind, d_counts2, d_winners });
 }
 
 }

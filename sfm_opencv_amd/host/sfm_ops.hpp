@@ -193,6 +193,37 @@ inline void match_features_for_all(const std::vector<Mat>& descriptor_for_all, s
     }
 }
 
+// the rows (x1, y1, x2, y2) of every pair's matches on coordinates normalised by K, in blocks of `stride` rows (the longest list)
+inline void pair_rows_for_all(const Mat& K, const std::vector<std::vector<KeyPoint>>& key_points_for_all,
+                              const std::vector<std::vector<DMatch>>& matches_for_all, std::vector<double>& corr, std::vector<int32_t>& rows, size_t& stride)
+{
+    const size_t n_pairs = matches_for_all.size();
+    const double fx = K.at<double>(0, 0), fy = K.at<double>(1, 1), cx = K.at<double>(0, 2), cy = K.at<double>(1, 2);
+    stride = 0;
+    for (const auto& m : matches_for_all) stride = m.size() > stride ? m.size() : stride;
+    corr.assign(n_pairs * stride * 4, 0.0);
+    rows.assign(n_pairs, 0);
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const auto& m = matches_for_all[i];
+        rows[i] = (int32_t)m.size();
+        double* r = corr.data() + i * stride * 4;
+        for (size_t k = 0; k < m.size(); ++k, r += 4) {
+            const KeyPoint& a = key_points_for_all[i][(size_t)m[k].queryIdx];
+            const KeyPoint& b = key_points_for_all[i + 1][(size_t)m[k].trainIdx];
+            r[0] = ((double)a.pt.x - cx) / fx; r[1] = ((double)a.pt.y - cy) / fy;
+            r[2] = ((double)b.pt.x - cx) / fx; r[3] = ((double)b.pt.y - cy) / fy;
+        }
+    }
+}
+// the elements of m whose flag is set, in their order
+inline void keep_masked(std::vector<DMatch>& m, const uint8_t* keep)
+{
+    size_t w = 0;
+    for (size_t k = 0; k < m.size(); ++k)
+        if (keep[k]) m[w++] = m[k];
+    m.resize(w);
+}
+
 // ---- two-view geometric verification (extension; what colmap / OpenMVG run between matching and reconstruction; the reference rejects
 // epipolar outliers for its first pair only, inside findEssentialMat, NView:1032) -- matches_for_all[i] joins images i and i + 1.  The key
 // points are normalised by K, the threshold is px pixels (t = px / (0.5 (fx + fy))), all pairs run in one call of sfmhip_verify_pairs
@@ -210,23 +241,12 @@ inline int verify_matches_for_all(const Mat& K, const std::vector<std::vector<Ke
     sfmhip_ctx* ctx = context();
     if (!ctx || (int)key_points_for_all.size() < n_pairs + 1) return -1;
     if (n_pairs == 0) return 0;
-    const double fx = K.at<double>(0, 0), fy = K.at<double>(1, 1), cx = K.at<double>(0, 2), cy = K.at<double>(1, 2);
+    const double fx = K.at<double>(0, 0), fy = K.at<double>(1, 1);
     size_t stride = 0;
-    for (const auto& m : matches_for_all) stride = m.size() > stride ? m.size() : stride;
-    std::vector<double> corr((size_t)n_pairs * stride * 4, 0.0);
-    std::vector<int32_t> rows((size_t)n_pairs);
+    std::vector<double> corr;
+    std::vector<int32_t> rows;
+    pair_rows_for_all(K, key_points_for_all, matches_for_all, corr, rows, stride);
     std::vector<uint8_t> mask((size_t)n_pairs * stride, 0);
-    for (int i = 0; i < n_pairs; ++i) {
-        const auto& m = matches_for_all[(size_t)i];
-        rows[(size_t)i] = (int32_t)m.size();
-        double* r = corr.data() + (size_t)i * stride * 4;
-        for (size_t k = 0; k < m.size(); ++k, r += 4) {
-            const KeyPoint& a = key_points_for_all[(size_t)i][(size_t)m[k].queryIdx];
-            const KeyPoint& b = key_points_for_all[(size_t)i + 1][(size_t)m[k].trainIdx];
-            r[0] = ((double)a.pt.x - cx) / fx; r[1] = ((double)a.pt.y - cy) / fy;
-            r[2] = ((double)b.pt.x - cx) / fx; r[3] = ((double)b.pt.y - cy) / fy;
-        }
-    }
     if (sfmhip_verify_pairs(ctx, corr.data(), (int)stride, rows.data(), n_pairs, px / (0.5 * (fx + fy)), hypotheses, rounds, seed, min_inliers, mask.data(),
                             counts.data(), F ? F->data() : nullptr, nullptr) != SFMHIP_OK) {
         printf("[Err]: verify_matches_for_all: %s\n", sfmhip_last_error(ctx));
@@ -238,11 +258,51 @@ inline int verify_matches_for_all(const Mat& K, const std::vector<std::vector<Ke
             printf("[Warning]: pair %d: no epipolar model with %d matches, the %zu matches are kept as they are.\n", i, min_inliers, m.size());
             continue;
         }
-        const uint8_t* keep = mask.data() + (size_t)i * stride;
-        size_t w = 0;
-        for (size_t k = 0; k < m.size(); ++k)
-            if (keep[k]) m[w++] = m[k];
-        m.resize(w);
+        keep_masked(m, mask.data() + (size_t)i * stride);
+    }
+    return 0;
+}
+
+// ---- the same with a homography RANSAC beside the epipolar one and the F/H selection of sfmhip_two_view_geometry (where the definition
+// is): px pixels for F, px_h pixels for the homography (a transfer distance carries the noise of both images).  kind[i]: 0 no model
+// (the pair keeps its matches, with a warning), 1 general (the pair keeps F's inliers), 2 planar or panoramic (it keeps the
+// homography's; its two-view pose is ill-determined and a warning says so).  counts[i]: the matches kept by the selected model;
+// counts2: (cF, cH) per pair.  Returns 0, -1 on error.
+inline int two_view_geometry_for_all(const Mat& K, const std::vector<std::vector<KeyPoint>>& key_points_for_all,
+                                     std::vector<std::vector<DMatch>>& matches_for_all, std::vector<int32_t>& kind, std::vector<int32_t>& counts,
+                                     std::vector<int32_t>& counts2, const double px = 1.0, const double px_h = 2.0, const int hypotheses = 1024,
+                                     const int rounds = 3, const double hf_ratio = 0.8, const int min_inliers = 15, const uint64_t seed = 0,
+                                     std::vector<double>* F = nullptr, std::vector<double>* Hm = nullptr)
+{
+    const int n_pairs = (int)matches_for_all.size();
+    kind.assign((size_t)n_pairs, 0); counts.assign((size_t)n_pairs, 0); counts2.assign((size_t)n_pairs * 2, 0);
+    if (F) F->assign((size_t)n_pairs * 9, std::nan(""));
+    if (Hm) Hm->assign((size_t)n_pairs * 9, std::nan(""));
+    sfmhip_ctx* ctx = context();
+    if (!ctx || (int)key_points_for_all.size() < n_pairs + 1) return -1;
+    if (n_pairs == 0) return 0;
+    const double f = 0.5 * (K.at<double>(0, 0) + K.at<double>(1, 1));
+    size_t stride = 0;
+    std::vector<double> corr;
+    std::vector<int32_t> rows;
+    pair_rows_for_all(K, key_points_for_all, matches_for_all, corr, rows, stride);
+    std::vector<uint8_t> mask((size_t)n_pairs * stride, 0);
+    if (sfmhip_two_view_geometry(ctx, corr.data(), (int)stride, rows.data(), n_pairs, px / f, px_h / f, hypotheses, rounds, seed, min_inliers, hf_ratio,
+                                 kind.data(), mask.data(), counts.data(), counts2.data(), F ? F->data() : nullptr, Hm ? Hm->data() : nullptr,
+                                 nullptr) != SFMHIP_OK) {
+        printf("[Err]: two_view_geometry_for_all: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    for (int i = 0; i < n_pairs; ++i) {
+        auto& m = matches_for_all[(size_t)i];
+        if (kind[(size_t)i] == 0) {
+            printf("[Warning]: pair %d: no two-view model with %d matches, the %zu matches are kept as they are.\n", i, min_inliers, m.size());
+            continue;
+        }
+        if (kind[(size_t)i] == 2)
+            printf("[Warning]: pair %d: planar or panoramic (H explains %d matches, F %d): its two-view pose is ill-determined.\n", i,
+                   (int)counts2[2 * (size_t)i + 1], (int)counts2[2 * (size_t)i]);
+        keep_masked(m, mask.data() + (size_t)i * stride);
     }
     return 0;
 }

@@ -242,6 +242,11 @@ struct PipelineOptions {
     double verify_px = -1.0;               // >= 0: right after matching, every pair keeps only the matches within this many pixels of its epipolar model (verify_matches_for_all; extension, not reference behaviour)
     int    verify_h = 1024;                // ... hypotheses per round
     int    verify_rounds = 3;              // ... rounds
+    double geometry_px = -1.0;             // >= 0: in the place of verify_px, with a homography RANSAC beside the epipolar one and the F/H selection (two_view_geometry_for_all; extension): F's threshold in pixels
+    double geometry_px_h = 2.0;            // ... the homography's threshold in pixels
+    int    geometry_h = 1024;              // ... hypotheses per round
+    int    geometry_rounds = 3;            // ... rounds
+    double geometry_ratio = 0.8;           // ... a pair is planar or panoramic when cH >= ratio * cF
 };
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
@@ -259,6 +264,16 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         std::vector<int32_t> kept;
         if (verify_matches_for_all(K, kpts_for_all, matches_for_all, kept, opt.verify_px, opt.verify_h, opt.verify_rounds, 15) < 0) return -1;
         for (size_t i = 0; i < before.size(); ++i) printf("pair %zu: verified %d of %zu\n", i, (int)kept[i], before[i]);
+    }
+    if (opt.geometry_px >= 0.0) {
+        std::vector<size_t> before;
+        for (const auto& m : matches_for_all) before.push_back(m.size());
+        std::vector<int32_t> kind, kept, both;
+        if (two_view_geometry_for_all(K, kpts_for_all, matches_for_all, kind, kept, both, opt.geometry_px, opt.geometry_px_h, opt.geometry_h,
+                                      opt.geometry_rounds, opt.geometry_ratio, 15) < 0) return -1;
+        static const char* const names[3] = { "none", "general", "planar-or-panoramic" };
+        for (size_t i = 0; i < before.size(); ++i)
+            printf("pair %zu: geometry %s, kept %d of %zu (F %d, H %d)\n", i, names[kind[i]], (int)kept[i], before[i], (int)both[2 * i], (int)both[2 * i + 1]);
     }
 
     std::vector<Point3d> pts3d;
@@ -429,7 +444,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]] [--two-view-geometry[=PX[,PXH[,H[,ROUNDS[,RATIO]]]]]]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -486,9 +501,20 @@ inline int driver_main(int argc, char** argv, bool nview)
                 if (c2 != std::string::npos) opt.verify_rounds = std::atoi(a.c_str() + c2 + 1);
             }
         }
+        else if (a == "--two-view-geometry") opt.geometry_px = 1.0;
+        else if (a.rfind("--two-view-geometry=", 0) == 0) {      // PX[,PXH[,H[,ROUNDS[,RATIO]]]]: in the place of --verify-matches: an epipolar RANSAC within PX (1.0) pixels and a homography RANSAC within PXH (2.0) pixels, H (1024) hypotheses in each of ROUNDS (3) rounds; a pair is planar or panoramic when the homography keeps at least RATIO (0.8) times F's matches
+            std::vector<std::string> v;
+            for (size_t at = 20; at <= a.size();) { size_t e = a.find(',', at); if (e == std::string::npos) e = a.size(); v.push_back(a.substr(at, e - at)); at = e + 1; }
+            opt.geometry_px = std::atof(v[0].c_str());
+            if (v.size() > 1) opt.geometry_px_h = std::atof(v[1].c_str());
+            if (v.size() > 2) opt.geometry_h = std::atoi(v[2].c_str());
+            if (v.size() > 3) opt.geometry_rounds = std::atoi(v[3].c_str());
+            if (v.size() > 4) opt.geometry_ratio = std::atof(v[4].c_str());
+        }
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
         else if (positional++ == 0) opt.out_dir = a;
     }
+    if (opt.verify_px >= 0.0 && opt.geometry_px >= 0.0) { printf("[Err]: --verify-matches and --two-view-geometry exclude each other.\n"); return 1; }
     Features f;
     if (is_directory(argv[1])) {
         // the reference's own entry: a directory of images (.jpg / .jpeg through sfm_jpeg.hpp, else binary .ppm / .pgm)
