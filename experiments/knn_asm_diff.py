@@ -1,7 +1,8 @@
 """Compare kernels of two gfx950 device assemblies of one source file (hipcc <the object's flags> --cuda-device-only -S): resource
 numbers, instruction count and opcode histogram per kernel; for kernels whose opcode sequence differs, the differing runs and where
 each lies: in which loop of the branch's kernel (loops are found by their back-branches and described by what they hold: barriers,
-LDS reads, global loads, MFMAs), or outside every loop.  For a kernel with MFMAs the place is given relative to its stage loop (head
+LDS reads, global loads, MFMAs), or outside every loop; where both sides have the same number of loops, the fp64 VALU count and the
+opcode histogram of each pair of loop bodies.  For a kernel with MFMAs the place is given relative to its stage loop (head
 label .. last back-branch) and the MFMA stream inside it.
 
     python3 experiments/knn_asm_diff.py parent.s branch.s [kernel ...]
@@ -128,6 +129,12 @@ def compare(a_path, b_path, name):
             for q in ls:
                 depth = sum(1 for o in ls if o[0] <= q[0] and q[1] <= o[1]) - 1
                 print("  %s loop %s%s: instructions %d .. %d (%d), holds %s" % (tag, "  " * depth, q[2], q[0], q[1], q[1] - q[0] + 1, holds(ops, q)))
+        if len(lsa) == len(lsb):                                     # the loops pair up in order: what each pair's bodies hold
+            for qa, qb in zip(lsa, lsb):
+                ca, cb = (collections.Counter(o[1] for o in ops[q[0]:q[1] + 1]) for ops, q in ((oa, qa), (ob, qb)))
+                f64 = [sum(v for k, v in c.items() if "f64" in k) for c in (ca, cb)]
+                print("  loop %s / %s: fp64 VALU %d / %d, opcode histogram %s" % (qa[2], qb[2], f64[0], f64[1], "identical" if ca == cb else
+                      "difference (branch - parent) %s" % {k: cb[k] - ca[k] for k in sorted(set(ca) | set(cb)) if ca[k] != cb[k]}))
     count = collections.Counter()
     for tag, i1, i2, j1, j2 in difflib.SequenceMatcher(None, sa, sb, autojunk=False).get_opcodes():
         if tag == "equal":

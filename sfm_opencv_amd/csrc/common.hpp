@@ -210,6 +210,14 @@ static inline int sfm_finish(sfmhip_ctx* ctx, hipError_t e)
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline int ceil_div(int x, int m) { return (x + m - 1) / m; }
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// one pool block carved into areas that start at multiples of 256 bytes: carve(n) is the offset of the next area of n bytes, and
+// carve.bytes the size of the block that holds the areas handed out so far
+struct SfmCarve {
+    size_t bytes = 0;
+    size_t operator()(size_t n) { const size_t at = bytes; bytes += align256(n); return at; }
+};
 
 // descriptor set (one image), see match.hip
 struct sfmhip_descset {

@@ -15,29 +15,19 @@
 // All max_planes rounds are enqueued; the stop flag and m live in device memory, and after the stop every kernel of a round leaves at
 // once (the launches cover an upper bound, n points).
 //
-// The shape of plane_score_kernel.  LANES OWN HYPOTHESES: a workgroup of 256 threads takes 256 hypotheses (blockIdx.x) and a sequence of
-// chunks of SCORE_CHUNK active points (blockIdx.y, then a stride of gridDim.y chunks); a lane keeps its plane (8 VGPRs) and its count in
-// registers; the chunk is staged in LDS as rows of four doubles, and every lane reads the SAME row at the same time: identical addresses
-// are a broadcast, without bank conflicts.  Per point a wave issues 3 fp64 mul + 3 fp64 add (contraction is off: the residual is the
-// prescribed formula), a compare on |e| and a conditional add: eight VALU instructions, which is what bounds the kernel (measured and
-// accounted for in DESIGN.md 4b; a variant with two hypotheses per lane, half the LDS reads per residual, was 3 % faster and was not
-// kept).  A wave none of whose lanes has a hypothesis (H = 65: three waves of the second block) only helps with the staging.  Counts:
-// one integer atomicAdd per lane at the very end, so a counter takes at most gridDim.y <= SCORE_MAX_WG adds per round, from different
-// workgroups at different times; integer sums are exact in any order.
+// plane_score_kernel is the scoring loop of ransac.hpp, which explains its shape, with PlaneModel: a lane keeps its plane in 8 VGPRs, and
+// per point a wave issues 3 fp64 mul + 3 fp64 add (contraction is off: the residual is the prescribed formula), a compare on |e| and a
+// conditional add: eight VALU instructions, which is what bounds the kernel (measured and accounted for in DESIGN.md 4b; a variant with
+// two hypotheses per lane, half the LDS reads per residual, was 3 % faster and was not kept).  The sampler and the winner reduction are
+// ransac.hpp's too; what is here is the plane: its active list, its three-point hypothesis, its residual, what a round writes, the refit.
 #include "common.hpp"
 #pragma clang fp contract(off)
 #include "eig3.hpp"
+#include "ransac.hpp"
 
-#define SCORE_CHUNK 512          // active points staged per pass of plane_score_kernel (16 KB of LDS)
-#define SCORE_MAX_WG 2048        // workgroups of plane_score_kernel at most (8 per CU of the MI355X); beyond that a workgroup strides over chunks
 #define REFIT_TILE 4096
 #define PLANES_H_MAX 65536
 #define PLANES_MAX 64
-
-typedef unsigned long long pu64;
-typedef unsigned int pu32;
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // what the rounds share, in device memory
 struct PlaneState {
@@ -49,14 +39,6 @@ struct PlaneState {
 };
 __device__ __forceinline__ bool round_dead(const PlaneState* s) { return s->stop || s->m < 3; }
 
-__device__ __forceinline__ pu64 splitmix64(pu64 seed, pu64 c)
-{
-    pu64 z = seed + (c + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // THE residual: scoring and labelling both call this, so the number of points labelled equals the winner's count by construction
 __device__ __forceinline__ double plane_residual(double a, double b, double c, double d, double x, double y, double z)
 {
@@ -66,6 +48,11 @@ __device__ __forceinline__ bool plane_inlier(double a, double b, double c, doubl
 {
     return fabs(plane_residual(a, b, c, d, x, y, z)) <= t;               // false for a NaN residual (an invalid hypothesis)
 }
+// what the scoring loop of ransac.hpp needs to know about a plane
+struct PlaneModel {
+    static constexpr int NPAR = 4, UNROLL = 8;
+    static __device__ __forceinline__ bool inlier(const double (&P)[4], const double4& q, double t) { return plane_inlier(P[0], P[1], P[2], P[3], q.x, q.y, q.z, t); }
+};
 // all four components negated when d < 0
 __device__ __forceinline__ void plane_store_signed(double* __restrict__ out, double a, double b, double c, double d)
 {
@@ -117,16 +104,9 @@ __global__ __launch_bounds__(256) void plane_hyp_kernel(const double4* __restric
     if (round_dead(state)) return;
     const int h = blockIdx.x * 256 + threadIdx.x;
     if (h >= H) return;
-    const pu64 m = (pu64)state->m;
-    const pu64 g = (pu64)p * (pu64)H + (pu64)h;
-    pu64 u0 = splitmix64(seed, 3ull * g) % m;
-    pu64 u1 = splitmix64(seed, 3ull * g + 1ull) % (m - 1ull);
-    u1 += u1 >= u0 ? 1ull : 0ull;
-    pu64 u2 = splitmix64(seed, 3ull * g + 2ull) % (m - 2ull);
-    const pu64 lo = u0 < u1 ? u0 : u1, hi = u0 < u1 ? u1 : u0;
-    u2 += u2 >= lo ? 1ull : 0ull;
-    u2 += u2 >= hi ? 1ull : 0ull;
-    const double4 p0 = act[u0], p1 = act[u1], p2 = act[u2];
+    pu64 u[3];
+    ransac_sample_distinct<3>(seed, (pu64)p * (pu64)H + (pu64)h, (pu64)state->m, u);
+    const double4 p0 = act[u[0]], p1 = act[u[1]], p2 = act[u[2]];
     const double e1x = p1.x - p0.x, e1y = p1.y - p0.y, e1z = p1.z - p0.z;
     const double e2x = p2.x - p0.x, e2y = p2.y - p0.y, e2z = p2.z - p0.z;
     const double mx = e1y * e2z - e1z * e2y, my = e1z * e2x - e1x * e2z, mz = e1x * e2y - e1y * e2x;
@@ -142,36 +122,14 @@ __global__ __launch_bounds__(256) void plane_hyp_kernel(const double4* __restric
     hcnt[h] = 0;
 }
 
-// the H x m part (the shape is explained at the top of the file)
+// the H x m part: ransac_score over the active list
 __global__ __launch_bounds__(256) void plane_score_kernel(const double4* __restrict__ act, const PlaneState* __restrict__ state, const double* __restrict__ hyp,
                                                           int H, double t, int32_t* __restrict__ hcnt)
 {
     __shared__ double4 tile[SCORE_CHUNK];
     if (round_dead(state)) return;                                       // uniform over the grid
-    const long long m = state->m;
     const int h = blockIdx.x * 256 + threadIdx.x;
-    const bool live = h < H;
-    const bool wave_live = blockIdx.x * 256 + (int)(threadIdx.x & ~63u) < H;      // uniform over the wave
-    const double a = live ? hyp[4 * (size_t)h] : NAN, b = live ? hyp[4 * (size_t)h + 1] : NAN, c = live ? hyp[4 * (size_t)h + 2] : NAN,
-                 d = live ? hyp[4 * (size_t)h + 3] : NAN;
-    int count = 0;
-    for (long long base = (long long)blockIdx.y * SCORE_CHUNK; base < m; base += (long long)gridDim.y * SCORE_CHUNK) {
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < SCORE_CHUNK / 256; ++k) {
-            const long long j = base + k * 256 + threadIdx.x;
-            if (j < m) tile[k * 256 + threadIdx.x] = act[j];
-        }
-        __syncthreads();
-        if (!wave_live) continue;
-        const int cnt = m - base < SCORE_CHUNK ? (int)(m - base) : SCORE_CHUNK;
-#pragma unroll 8
-        for (int s = 0; s < cnt; ++s) {
-            const double4 q = tile[s];
-            count += plane_inlier(a, b, c, d, q.x, q.y, q.z, t) ? 1 : 0;
-        }
-    }
-    if (live && count) atomicAdd(hcnt + h, count);
+    ransac_score<PlaneModel>(tile, act, state->m, h < H ? hyp + 4 * (size_t)h : nullptr, t, hcnt + h);
 }
 
 // one workgroup: argmax of (count, then the smallest h) over the valid hypotheses; the round's outputs, or the stop flag
@@ -181,25 +139,10 @@ __global__ __launch_bounds__(256) void plane_winner_kernel(PlaneState* __restric
 {
     __shared__ pu64 sb[256];
     if (state->stop) return;
-    const bool dead = state->m < 3;
-    pu64 best = 0ull;
-    if (!dead)
-        for (int h = threadIdx.x; h < H; h += 256) {
-            if (!hvalid[h]) continue;
-            const pu64 v = ((pu64)((pu32)hcnt[h] + 1u) << 32) | (pu64)(0xffffffffu - (pu32)h);      // a valid hypothesis: v > 0
-            best = v > best ? v : best;
-        }
-    sb[threadIdx.x] = best;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off && sb[threadIdx.x + off] > sb[threadIdx.x]) sb[threadIdx.x] = sb[threadIdx.x + off];
-        __syncthreads();
-    }
+    const pu64 w = ransac_block_winner(hvalid, hcnt, state->m < 3 ? 0 : H, sb);      // a round without three active points: no hypothesis
     if (threadIdx.x != 0) return;
-    const pu64 w = sb[0];
-    const int cnt = w ? (int)((pu32)(w >> 32) - 1u) : 0;
-    if (!w || cnt < min_inliers) { state->stop = 1; return; }
-    const int h = (int)(0xffffffffu - (pu32)w);
+    if (!w || ransac_key_count(w) < min_inliers) { state->stop = 1; return; }
+    const int cnt = ransac_key_count(w), h = ransac_key_h(w);
     const double a = hyp[4 * (size_t)h], b = hyp[4 * (size_t)h + 1], c = hyp[4 * (size_t)h + 2], d = hyp[4 * (size_t)h + 3];
     state->wplane[0] = a; state->wplane[1] = b; state->wplane[2] = c; state->wplane[3] = d;
     plane_store_signed(planes + 4 * (size_t)p, a, b, c, d);
@@ -297,15 +240,14 @@ static int planes_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double t,
     hipStream_t st = ctx->stream;
     const size_t N = (size_t)n, scan_w = sfm_scan_bsum_words(N + 1);
     const int nb = ceil_div(n, 256), nb1 = ceil_div(n + 1, 256), hb = ceil_div(H, 256), nt = ceil_div(n, REFIT_TILE);
-    const int nchunks = ceil_div(n, SCORE_CHUNK), gy = std::max(1, std::min(nchunks, SCORE_MAX_WG / hb));
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    const int gy = ransac_score_grid_y(n, hb);
+    SfmCarve carve;
     const size_t o_state = carve(sizeof(PlaneState)), o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4), o_act = carve(N * sizeof(double4)),
                  o_hyp = carve((size_t)H * 4 * sizeof(double)), o_val = carve((size_t)H * 4), o_cnt = carve((size_t)H * 4),
                  o_part = carve(d_refined ? (size_t)6 * nt * sizeof(double) : 0);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
-    const int rc = hold.get(off, (void**)&w);
+    const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
     PlaneState* state = (PlaneState*)(w + o_state);
     pu32* flag = (pu32*)(w + o_flag);

@@ -352,8 +352,6 @@ __global__ __launch_bounds__(NTILE) void points_knn_grid_kernel(const pu64* __re
 #define POINTS_AUTO_GRID_FROM 300000
 int sfm_points_auto_method(int n) { return n >= POINTS_AUTO_GRID_FROM ? SFMHIP_POINTS_GRID : SFMHIP_POINTS_BRUTE; }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the binning shared by the two grid searches: cell statistics, keys, stable sort, the cloud gathered into cell order, an empty fallback
 // list.  Everything lives in one block of the cache that `hold` gives back.
 struct PointsGrid { const double* params; const pu64* keys; const pu32* order; const double* spts; pu32* list; };
@@ -368,12 +366,11 @@ static int points_grid_enqueue(sfmhip_ctx* ctx, SfmPoolHold& hold, const double*
     }
     // one block of the cache, carved up
     const size_t N = (size_t)n, hist_w = sfm_radix_sort_hist_words(N), bsum_w = sfm_radix_sort_bsum_words(N);
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    SfmCarve carve;
     const size_t o_par = carve(8 * sizeof(double)), o_k0 = carve(N * 8), o_k1 = carve(N * 8), o_v0 = carve(N * 4), o_v1 = carve(N * 4),
                  o_hist = carve(hist_w * 4), o_bsum = carve(bsum_w * 4), o_spts = carve(N * 24), o_list = carve(N * 4);
     char* w = nullptr;
-    const int rc = hold.get(off, (void**)&w);
+    const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
     double* params = (double*)(w + o_par);
     pu64* k[2] = { (pu64*)(w + o_k0), (pu64*)(w + o_k1) };
@@ -710,14 +707,13 @@ static int voxel_downsample_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n,
     hipStream_t st = ctx->stream;
     const size_t N = (size_t)n, hist_w = sfm_radix_sort_hist_words(N), bsum_w = sfm_radix_sort_bsum_words(N), scan_w = sfm_scan_bsum_words(N + 1);
     const int nt = ceil_div(n, RED_TILE), nb = ceil_div(n, 256);
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    SfmCarve carve;
     const size_t o_org = carve(4 * sizeof(double)), o_ovf = carve(sizeof(pu32)), o_part = carve((size_t)3 * nt * sizeof(double)), o_k0 = carve(N * 8),
                  o_k1 = carve(N * 8), o_v0 = carve(N * 4), o_v1 = carve(N * 4), o_hist = carve(hist_w * 4), o_bsum = carve(bsum_w * 4),
                  o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
-    const int rc = hold.get(off, (void**)&w);
+    const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
     double* origin = (double*)(w + o_org);
     pu32* overflow = (pu32*)(w + o_ovf);
@@ -955,13 +951,12 @@ static int cluster_dbscan_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, d
     hipStream_t st = ctx->stream;
     const size_t N = (size_t)n, scan_w = sfm_scan_bsum_words(N + 1);
     const int nb = ceil_div(n, NTILE), nb256 = ceil_div(n, 256);
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    SfmCarve carve;
     const size_t o_err = carve(sizeof(pu32)), o_core = carve(N), o_par = carve(N * 4), o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4),
                  o_cnt = carve(d_count ? 0 : N * 4);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
-    int rc = hold.get(off, (void**)&w);
+    int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
     pu32* err = (pu32*)(w + o_err);
     uint8_t* core = (uint8_t*)(w + o_core);

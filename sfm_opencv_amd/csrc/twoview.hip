@@ -1,7 +1,8 @@
 // twoview.hip -- two-view geometric verification: an epipolar RANSAC over many image pairs in one call (what colmap and OpenMVG run between
 // matching and reconstruction; the reference has it for its first pair only, inside findEssentialMat).  The definition is in sfmhip.h at
 // sfmhip_verify_pairs and is followed to the letter here: the mask, count and winner are integer decisions on prescribed fp64 values and F
-// is prescribed bit for bit, the same for every run, batch and launch geometry.  The file is built like planes.hip.
+// is prescribed bit for bit, the same for every run, batch and launch geometry.  The sampler, the scoring loop and the winner reduction
+// are ransac.hpp's, as in planes.hip.
 //
 // A round p, everything on the device and on one stream, every kernel over all pairs at once:
 //   twoview_prep_kernel     (once) one workgroup per pair: L_0, the rows with four finite values, packed in ascending row index into rows
@@ -16,36 +17,27 @@
 // All rounds are enqueued; the stop flag and the list length of a pair live in device memory, and once a pair has stopped every block of
 // a later round that belongs to it leaves at once.
 //
-// The shape of twoview_score_kernel is plane_score_kernel's.  LANES OWN HYPOTHESES: a workgroup of 256 threads takes 256 hypotheses
-// (blockIdx.x) of one pair (blockIdx.z) and a sequence of chunks of SCORE_CHUNK rows (blockIdx.y, then a stride of gridDim.y chunks); a
-// lane keeps its F (18 VGPRs) and its count in registers; the chunk is staged in LDS as rows of four doubles, and every lane reads the
-// SAME row at the same time: a broadcast, without bank conflicts.  Per row a wave issues 16 fp64 multiplications and 15 additions for
-// l, m, e and d (contraction is off: the residual is the prescribed formula), two more multiplications for e*e and t2*d, a compare and a
-// conditional add: 35 VALU instructions, which is what bounds the kernel (the account is in DESIGN.md 4c).  Counts: one integer
-// atomicAdd per lane at the very end.
+// twoview_score_kernel is the scoring loop of ransac.hpp, which explains its shape, over the rows of one pair (blockIdx.z): a lane keeps
+// its F in 18 VGPRs, and per row a wave issues 16 fp64 multiplications and 15 additions for l, m, e and d (contraction is off: the
+// residual is the prescribed formula), two more multiplications for e*e and t2*d, a compare and a conditional add: 35 VALU
+// instructions, which is what bounds the kernel (the account is in DESIGN.md 4c).
 //
-// TWO MODELS share this machinery: the fundamental matrix above (EpipolarModel) and the four-point homography of sfmhip_verify_pairs_h
-// (HomographyModel), which is also the null vector of an 8 x 9 system.  A model supplies its inlier test and the shortest list a round
-// may sample from; the per-pair kernels (winner, list, final) are templates over it, the elimination (null_vector_8x9) and the scoring
-// loop (score_rows) are one __device__ body each that the two hypothesis kernels and the two scoring kernels call, and prep runs once per
-// call whatever the number of models.  homography_hyp_kernel differs from twoview_hyp_kernel in the sample (four rows) and the design
-// matrix; homography_score_kernel in the residual: 12 multiplications, 9 additions, a compare and a conditional add per row, 23 VALU
-// instructions against 35.  sfmhip_two_view_geometry runs both models over the same packed rows, one after the other through the same
-// pairs x H hypothesis areas, and geometry_select_kernel then decides per pair which mask is the pair's (the rule is in sfmhip.h).
+// TWO MODELS share this file: the fundamental matrix above (EpipolarModel) and the four-point homography of sfmhip_verify_pairs_h
+// (HomographyModel), which is also the null vector of an 8 x 9 system.  A model supplies the size of its sample (also the shortest list a
+// round may sample from), the rows of the system a sampled row gives, and its inlier test; the hypothesis, scoring and per-pair kernels
+// (winner, list, final) are one body each over it, and prep runs once per call whatever the number of models.  homography_hyp_kernel
+// differs from twoview_hyp_kernel in the sample (four rows) and the design matrix; homography_score_kernel in the residual: 12
+// multiplications, 9 additions, a compare and a conditional add per row, 23 VALU instructions against 35.  sfmhip_two_view_geometry
+// runs both models over the same packed rows, one after the other through the same pairs x H hypothesis areas, and
+// geometry_select_kernel then decides per pair which mask is the pair's (the rule is in sfmhip.h).
 #include "common.hpp"
 #pragma clang fp contract(off)
+#include "ransac.hpp"
 
-#define SCORE_CHUNK 512          // rows of L_0 staged per pass of twoview_score_kernel (16 KB of LDS)
-#define SCORE_MAX_WG 2048        // workgroups of twoview_score_kernel per pair at most; beyond that a workgroup strides over chunks
 #define HYP_THREADS 64           // hypotheses per workgroup of twoview_hyp_kernel
 #define TWOVIEW_H_MAX 65536
 #define TWOVIEW_ROUNDS_MAX 8
 #define TWOVIEW_PAIRS_PER_LAUNCH 32768      // gridDim.z of the scoring launch; a longer batch goes in slices (the pairs are independent)
-
-typedef unsigned long long pu64;
-typedef unsigned int pu32;
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // what the rounds of one pair share, in device memory
 struct TwoViewState {
@@ -57,15 +49,7 @@ struct TwoViewState {
     int pad[3];
     double F[9];              // the model (F, or the homography)
 };
-template <class M> __device__ __forceinline__ bool round_dead(const TwoViewState* s) { return s->stop || s->m < M::MIN_ROWS; }
-
-__device__ __forceinline__ pu64 splitmix64(pu64 seed, pu64 c)
-{
-    pu64 z = seed + (c + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+template <class M> __device__ __forceinline__ bool round_dead(const TwoViewState* s) { return s->stop || s->m < M::SAMPLE; }
 
 // THE residual test: scoring, list building and the mask all call this, so the length of a list and the sum of a mask row equal the
 // model's count by construction.  False for a NaN F (an invalid hypothesis).
@@ -91,14 +75,29 @@ __device__ __forceinline__ bool homography_inlier(const double (&Hm)[9], double 
     const double dv = v - y2 * w;
     return du * du + dv * dv <= t2 * (w * w);
 }
-// what a model supplies to the kernels that are templates over it
+// What a model supplies to the bodies that are templates over it.  SAMPLE: the rows a hypothesis draws, which is also the shortest list a
+// round may sample from; design: the rows of the 8 x 9 system that sample k gives (one for F, two for the homography); NPAR, UNROLL and
+// inlier: for the scoring loop of ransac.hpp (r: a row x1, y1, x2, y2)
 struct EpipolarModel {
-    static constexpr int MIN_ROWS = 8;
-    static __device__ __forceinline__ bool inlier(const double (&F)[9], double x1, double y1, double x2, double y2, double t2) { return twoview_inlier(F, x1, y1, x2, y2, t2); }
+    static constexpr int SAMPLE = 8, NPAR = 9, UNROLL = 4;
+    static __device__ __forceinline__ void design(int k, const double4& r, double (&A)[8][9])
+    {
+        A[k][0] = r.z * r.x; A[k][1] = r.z * r.y; A[k][2] = r.z;
+        A[k][3] = r.w * r.x; A[k][4] = r.w * r.y; A[k][5] = r.w;
+        A[k][6] = r.x;       A[k][7] = r.y;       A[k][8] = 1.0;
+    }
+    static __device__ __forceinline__ bool inlier(const double (&F)[9], const double4& r, double t2) { return twoview_inlier(F, r.x, r.y, r.z, r.w, t2); }
 };
 struct HomographyModel {
-    static constexpr int MIN_ROWS = 4;
-    static __device__ __forceinline__ bool inlier(const double (&Hm)[9], double x1, double y1, double x2, double y2, double t2) { return homography_inlier(Hm, x1, y1, x2, y2, t2); }
+    static constexpr int SAMPLE = 4, NPAR = 9, UNROLL = 4;
+    static __device__ __forceinline__ void design(int k, const double4& r, double (&A)[8][9])
+    {
+        A[2 * k][0] = r.x; A[2 * k][1] = r.y; A[2 * k][2] = 1.0; A[2 * k][3] = 0.0; A[2 * k][4] = 0.0; A[2 * k][5] = 0.0;
+        A[2 * k][6] = -(r.z * r.x); A[2 * k][7] = -(r.z * r.y); A[2 * k][8] = -r.z;
+        A[2 * k + 1][0] = 0.0; A[2 * k + 1][1] = 0.0; A[2 * k + 1][2] = 0.0; A[2 * k + 1][3] = r.x; A[2 * k + 1][4] = r.y; A[2 * k + 1][5] = 1.0;
+        A[2 * k + 1][6] = -(r.w * r.x); A[2 * k + 1][7] = -(r.w * r.y); A[2 * k + 1][8] = -r.w;
+    }
+    static __device__ __forceinline__ bool inlier(const double (&Hm)[9], const double4& r, double t2) { return homography_inlier(Hm, r.x, r.y, r.z, r.w, t2); }
 };
 __device__ __forceinline__ bool finite4(double a, double b, double c, double d) { return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d); }
 __device__ __forceinline__ int clamp_count(int c, int stride) { return c < 0 ? 0 : (c > stride ? stride : c); }
@@ -228,123 +227,64 @@ __device__ __forceinline__ void null_vector_8x9(double (&A)[8][9], size_t at, do
 }
 #undef SWAP_IF
 
-// hypothesis h of round p of pair q: hyp[9 (q H + h) ..] = F from eight rows of L_p
+// hypothesis h of round p of pair q: hyp[9 (q H + h) ..] = the model from M::SAMPLE distinct rows of L_p
+template <class M>
+__device__ __forceinline__ void hypothesis(const double4* __restrict__ act, const int32_t* __restrict__ list, int stride, const TwoViewState* __restrict__ state,
+                                           int p, int H, pu64 seed, double* __restrict__ hyp, int32_t* __restrict__ hvalid, int32_t* __restrict__ hcnt)
+{
+    const size_t q = blockIdx.y;
+    const TwoViewState* s = state + q;
+    if (round_dead<M>(s)) return;
+    const int h = blockIdx.x * HYP_THREADS + threadIdx.x;
+    if (h >= H) return;
+    pu64 u[M::SAMPLE];
+    ransac_sample_distinct<M::SAMPLE>(seed, (pu64)p * (pu64)H + (pu64)h, (pu64)s->m, u);
+    double A[8][9];
+#pragma unroll
+    for (int k = 0; k < M::SAMPLE; ++k) M::design(k, act[q * stride + (size_t)list[q * stride + u[k]]], A);
+    null_vector_8x9(A, q * (size_t)H + (size_t)h, hyp, hvalid, hcnt);
+}
 __global__ __launch_bounds__(HYP_THREADS) void twoview_hyp_kernel(const double4* __restrict__ act, const int32_t* __restrict__ list, int stride,
                                                                   const TwoViewState* __restrict__ state, int p, int H, pu64 seed,
                                                                   double* __restrict__ hyp, int32_t* __restrict__ hvalid, int32_t* __restrict__ hcnt)
 {
-    const size_t q = blockIdx.y;
-    const TwoViewState* s = state + q;
-    if (round_dead<EpipolarModel>(s)) return;
-    const int h = blockIdx.x * HYP_THREADS + threadIdx.x;
-    if (h >= H) return;
-    const pu64 m = (pu64)s->m;
-    const pu64 g = (pu64)p * (pu64)H + (pu64)h;
-    double A[8][9];
-    // eight distinct positions in L_p; srt: the ones chosen so far in ascending order
-    pu64 srt[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        pu64 u = splitmix64(seed, 8ull * g + (pu64)k) % (m - (pu64)k);
-#pragma unroll
-        for (int j = 0; j < k; ++j) u += u >= srt[j] ? 1ull : 0ull;
-        const double4 r = act[q * stride + (size_t)list[q * stride + u]];
-        A[k][0] = r.z * r.x; A[k][1] = r.z * r.y; A[k][2] = r.z;
-        A[k][3] = r.w * r.x; A[k][4] = r.w * r.y; A[k][5] = r.w;
-        A[k][6] = r.x;       A[k][7] = r.y;       A[k][8] = 1.0;
-        srt[k] = u;
-#pragma unroll
-        for (int j = k; j > 0; --j) {
-            const pu64 lo = srt[j] < srt[j - 1] ? srt[j] : srt[j - 1], hi = srt[j] < srt[j - 1] ? srt[j - 1] : srt[j];
-            srt[j - 1] = lo; srt[j] = hi;
-        }
-    }
-    null_vector_8x9(A, q * (size_t)H + (size_t)h, hyp, hvalid, hcnt);
+    hypothesis<EpipolarModel>(act, list, stride, state, p, H, seed, hyp, hvalid, hcnt);
 }
-
-// the same for the homography: four rows of L_p, two rows of the system each
 __global__ __launch_bounds__(HYP_THREADS) void homography_hyp_kernel(const double4* __restrict__ act, const int32_t* __restrict__ list, int stride,
                                                                      const TwoViewState* __restrict__ state, int p, int H, pu64 seed,
                                                                      double* __restrict__ hyp, int32_t* __restrict__ hvalid, int32_t* __restrict__ hcnt)
 {
-    const size_t q = blockIdx.y;
-    const TwoViewState* s = state + q;
-    if (round_dead<HomographyModel>(s)) return;
-    const int h = blockIdx.x * HYP_THREADS + threadIdx.x;
-    if (h >= H) return;
-    const pu64 m = (pu64)s->m;
-    const pu64 g = (pu64)p * (pu64)H + (pu64)h;
-    double A[8][9];
-    pu64 srt[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        pu64 u = splitmix64(seed, 4ull * g + (pu64)k) % (m - (pu64)k);
-#pragma unroll
-        for (int j = 0; j < k; ++j) u += u >= srt[j] ? 1ull : 0ull;
-        const double4 r = act[q * stride + (size_t)list[q * stride + u]];
-        A[2 * k][0] = r.x; A[2 * k][1] = r.y; A[2 * k][2] = 1.0; A[2 * k][3] = 0.0; A[2 * k][4] = 0.0; A[2 * k][5] = 0.0;
-        A[2 * k][6] = -(r.z * r.x); A[2 * k][7] = -(r.z * r.y); A[2 * k][8] = -r.z;
-        A[2 * k + 1][0] = 0.0; A[2 * k + 1][1] = 0.0; A[2 * k + 1][2] = 0.0; A[2 * k + 1][3] = r.x; A[2 * k + 1][4] = r.y; A[2 * k + 1][5] = 1.0;
-        A[2 * k + 1][6] = -(r.w * r.x); A[2 * k + 1][7] = -(r.w * r.y); A[2 * k + 1][8] = -r.w;
-        srt[k] = u;
-#pragma unroll
-        for (int j = k; j > 0; --j) {
-            const pu64 lo = srt[j] < srt[j - 1] ? srt[j] : srt[j - 1], hi = srt[j] < srt[j - 1] ? srt[j - 1] : srt[j];
-            srt[j - 1] = lo; srt[j] = hi;
-        }
-    }
-    null_vector_8x9(A, q * (size_t)H + (size_t)h, hyp, hvalid, hcnt);
+    hypothesis<HomographyModel>(act, list, stride, state, p, H, seed, hyp, hvalid, hcnt);
 }
 
-// the pairs x H x |L_0| part (the shape is explained at the top of the file); tile: SCORE_CHUNK rows of LDS
+// the pairs x H x |L_0| part: ransac_score over the rows of pair blockIdx.z
 template <class M>
-__device__ __forceinline__ void score_rows(double4* tile, const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
+__device__ __forceinline__ void score_pair(double4* tile, const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
                                            const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
 {
     const size_t q = blockIdx.z;
     const TwoViewState* s = state + q;
     if (round_dead<M>(s)) return;                                        // uniform over the workgroup
-    const int m0 = s->m0;
-    if ((long long)blockIdx.y * SCORE_CHUNK >= m0) return;
     const int h = blockIdx.x * 256 + threadIdx.x;
-    const bool live = h < H;
-    const bool wave_live = blockIdx.x * 256 + (int)(threadIdx.x & ~63u) < H;      // uniform over the wave
     const size_t at = q * (size_t)H + (size_t)h;
-    double F[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) F[j] = live ? hyp[9 * at + j] : NAN;
-    const double4* rows = act + q * stride;
-    int count = 0;
-    for (int base = blockIdx.y * SCORE_CHUNK; base < m0; base += gridDim.y * SCORE_CHUNK) {
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < SCORE_CHUNK / 256; ++k) {
-            const int j = base + k * 256 + (int)threadIdx.x;
-            if (j < m0) tile[k * 256 + threadIdx.x] = rows[j];
-        }
-        __syncthreads();
-        if (!wave_live) continue;
-        const int cnt = m0 - base < SCORE_CHUNK ? m0 - base : SCORE_CHUNK;
-#pragma unroll 4
-        for (int r = 0; r < cnt; ++r) {
-            const double4 c = tile[r];
-            count += M::inlier(F, c.x, c.y, c.z, c.w, t2) ? 1 : 0;
-        }
-    }
-    if (live && count) atomicAdd(hcnt + at, count);
+    ransac_score<M>(tile, act + q * stride, s->m0, h < H ? hyp + 9 * at : nullptr, t2, hcnt + at);
 }
 __global__ __launch_bounds__(256) void twoview_score_kernel(const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
                                                             const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
 {
     __shared__ double4 tile[SCORE_CHUNK];
-    score_rows<EpipolarModel>(tile, act, stride, state, hyp, H, t2, hcnt);
+    score_pair<EpipolarModel>(tile, act, stride, state, hyp, H, t2, hcnt);
 }
 __global__ __launch_bounds__(256) void homography_score_kernel(const double4* __restrict__ act, int stride, const TwoViewState* __restrict__ state,
                                                                const double* __restrict__ hyp, int H, double t2, int32_t* __restrict__ hcnt)
 {
     __shared__ double4 tile[SCORE_CHUNK];
-    score_rows<HomographyModel>(tile, act, stride, state, hyp, H, t2, hcnt);
+    score_pair<HomographyModel>(tile, act, stride, state, hyp, H, t2, hcnt);
 }
+// the two kernels above of a model, for the host
+template <class M> struct KernelsOf;
+template <> struct KernelsOf<EpipolarModel> { static constexpr auto hyp = twoview_hyp_kernel; static constexpr auto score = twoview_score_kernel; };
+template <> struct KernelsOf<HomographyModel> { static constexpr auto hyp = homography_hyp_kernel; static constexpr auto score = homography_score_kernel; };
 
 // one workgroup per pair: argmax of (count, then the smallest h) over the valid hypotheses; the pair's model, or its stop flag
 template <class M>
@@ -357,25 +297,12 @@ __global__ __launch_bounds__(256) void twoview_winner_kernel(TwoViewState* __res
     const int stop = s->stop, m = s->m;
     __syncthreads();                                                     // everybody has read the state before thread 0 may change it
     if (stop) return;
-    if (m < M::MIN_ROWS) { if (threadIdx.x == 0) s->stop = 1; return; }
-    pu64 best = 0ull;
-    for (int h = threadIdx.x; h < H; h += 256) {
-        if (!hvalid[q * (size_t)H + h]) continue;
-        const pu64 v = ((pu64)((pu32)hcnt[q * (size_t)H + h] + 1u) << 32) | (pu64)(0xffffffffu - (pu32)h);      // a valid hypothesis: v > 0
-        best = v > best ? v : best;
-    }
-    sb[threadIdx.x] = best;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off && sb[threadIdx.x + off] > sb[threadIdx.x]) sb[threadIdx.x] = sb[threadIdx.x + off];
-        __syncthreads();
-    }
+    if (m < M::SAMPLE) { if (threadIdx.x == 0) s->stop = 1; return; }
+    const pu64 w = ransac_block_winner(hvalid + q * (size_t)H, hcnt + q * (size_t)H, H, sb);
     if (threadIdx.x != 0) return;
-    const pu64 w = sb[0];
     if (!w) { s->stop = 1; return; }
-    const int cnt = (int)((pu32)(w >> 32) - 1u);
+    const int cnt = ransac_key_count(w), h = ransac_key_h(w);
     if (p > 0 && cnt <= s->best) { s->stop = 1; return; }
-    const int h = (int)(0xffffffffu - (pu32)w);
     s->best = cnt;
     s->winner = p * H + h;
     for (int j = 0; j < 9; ++j) s->F[j] = hyp[9 * (q * (size_t)H + h) + j];
@@ -398,7 +325,7 @@ __global__ __launch_bounds__(256) void twoview_list_kernel(const double4* __rest
     for (int base = 0; base < m0; base += 256) {
         const int i = base + (int)threadIdx.x;
         bool f = false;
-        if (i < m0) { const double4 c = act[q * stride + i]; f = M::inlier(F, c.x, c.y, c.z, c.w, t2); }
+        if (i < m0) f = M::inlier(F, act[q * stride + i], t2);
         int total;
         const int r = block_rank(f, sw, total);
         if (f) list[q * stride + m + r] = i;
@@ -430,7 +357,7 @@ __global__ __launch_bounds__(256) void twoview_final_kernel(const double* __rest
     if (ok && i < clamp_count(counts[q], stride)) {
         const double* r = corr + 4 * ((size_t)stride * q + (size_t)i);
         const double x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
-        in = finite4(x1, y1, x2, y2) && M::inlier(F, x1, y1, x2, y2, t2);
+        in = finite4(x1, y1, x2, y2) && M::inlier(F, make_double4(x1, y1, x2, y2), t2);
     }
     mask[q * stride + i] = in ? 1 : 0;
 }
@@ -529,15 +456,12 @@ template <class M>
 static void enqueue_model(hipStream_t st, const RoundAreas& a, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs, double t,
                           const GeomParams& g, uint8_t* d_mask, int32_t* d_count_out, double* d_model, int32_t* d_winner)
 {
-    constexpr bool epipolar = M::MIN_ROWS == 8;
-    const int H = g.H, hb = ceil_div(H, 256), nchunks = ceil_div(stride, SCORE_CHUNK), gy = std::max(1, std::min(nchunks, SCORE_MAX_WG / hb));
+    const int H = g.H, hb = ceil_div(H, 256), gy = ransac_score_grid_y(stride, hb);
     const double t2 = t * t;
-    const auto hyp_kernel = epipolar ? twoview_hyp_kernel : homography_hyp_kernel;
-    const auto score_kernel = epipolar ? twoview_score_kernel : homography_score_kernel;
     for (int p = 0; p < g.rounds; ++p) {
-        hipLaunchKernelGGL(hyp_kernel, dim3(ceil_div(H, HYP_THREADS), n_pairs), dim3(HYP_THREADS), 0, st,
+        hipLaunchKernelGGL(KernelsOf<M>::hyp, dim3(ceil_div(H, HYP_THREADS), n_pairs), dim3(HYP_THREADS), 0, st,
                            (const double4*)a.act, (const int32_t*)a.list, stride, (const TwoViewState*)a.state, p, H, g.seed, a.hyp, a.hvalid, a.hcnt);
-        hipLaunchKernelGGL(score_kernel, dim3(hb, gy, n_pairs), dim3(256), 0, st, (const double4*)a.act, stride,
+        hipLaunchKernelGGL(KernelsOf<M>::score, dim3(hb, gy, n_pairs), dim3(256), 0, st, (const double4*)a.act, stride,
                            (const TwoViewState*)a.state, (const double*)a.hyp, H, t2, a.hcnt);
         hipLaunchKernelGGL(twoview_winner_kernel<M>, dim3(n_pairs), dim3(256), 0, st, a.state, p, H, (const double*)a.hyp, (const int32_t*)a.hvalid,
                            (const int32_t*)a.hcnt);
@@ -556,15 +480,14 @@ static int twoview_enqueue_slice(sfmhip_ctx* ctx, int models, const double* d_co
     hipStream_t st = ctx->stream;
     const size_t P = (size_t)n_pairs, S = (size_t)stride, H = (size_t)g.H;
     const bool both = models == GEOM_BOTH;
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
+    SfmCarve carve;
     const size_t o_state = carve(P * sizeof(TwoViewState)), o_act = carve(P * S * sizeof(double4)), o_list = carve(P * S * 4),
                  o_hyp = carve(P * H * 9 * sizeof(double)), o_val = carve(P * H * 4), o_cnt = carve(P * H * 4);
     const size_t o_state2 = carve(both ? P * sizeof(TwoViewState) : 0), o_list2 = carve(both ? P * S * 4 : 0), o_maskF = carve(both ? P * S : 0),
                  o_maskH = carve(both ? P * S : 0), o_head = carve(both ? 4 * align256(P * 4) : 0);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
-    const int rc = hold.get(off, (void**)&w);
+    const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
     RoundAreas a = { (TwoViewState*)(w + o_state), (double4*)(w + o_act), (int32_t*)(w + o_list), (double*)(w + o_hyp), (int32_t*)(w + o_val),
                      (int32_t*)(w + o_cnt) };

@@ -14,7 +14,7 @@ import pytest
 import homography_ref as hr
 import twoview_ref as tv
 from sfm_opencv_amd import _lib, api, features_io
-from test_twoview_gpu import _bits, _blocks, _match_scene
+from test_twoview_gpu import _bits, _blocks, _check_winner_in_parts, _match_scene, _subset
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -92,6 +92,22 @@ def test_single_pair_equals_the_reference(ctx, H):
                 assert got[1][0] == 0 and got[2][0] == -1 and np.isnan(got[3]).all() and not got[0].any()
             elif H >= 256 and m >= CHUNK - 1:
                 assert got[1][0] >= 0.5 * m                           # 70 % of the rows are true matches on one plane
+
+
+def test_a_workgroup_that_strides_over_several_chunks(ctx):
+    # the shape and the parts of the test of this name in test_twoview_gpu.py, through homography_score_kernel
+    H, m, seed = 65536, 8 * CHUNK + 2 * CHUNK + 7, 21
+    rows = hr.scene_rows("planar", m, out=0.3, seed=12)
+    got = _raw_h(ctx, *_blocks([rows]), T2, H, 1, seed, 4)
+    pos = hr.samples_h(seed, 0, H, m)
+    srt = np.sort(pos, axis=1)
+    assert pos.min() >= 0 and pos.max() < m and (srt[:, 1:] > srt[:, :-1]).all()
+    assert 0 <= got[2][0] < H
+    sub = np.union1d(_subset(H), [got[2][0]])
+    Hm, valid = hr.null_vectors(hr.design_h(rows[pos[sub]]))
+    cnt = hr.counts_of_h(Hm, valid, rows, T2 * T2)
+    _check_winner_in_parts(got, sub, Hm, valid, cnt, hr.inliers_h(got[3][0], rows, T2 * T2)[0])
+    assert got[1][0] >= 0.5 * m
 
 
 # ---- input edges -----------------------------------------------------------------------------------------------------------------------

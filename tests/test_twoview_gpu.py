@@ -83,6 +83,46 @@ def test_single_pair_equals_the_reference(ctx, H):
                 assert got[1][0] >= 0.5 * m                           # 70 % of the rows are true matches
 
 
+def _subset(H, n=512):
+    """n fixed values of h in ascending order, the edges of the first two hypothesis blocks and the last h among them"""
+    must = [0, 255, 256, H - 1]
+    rest = [int(h) for h in np.random.default_rng(1).permutation(H)[:n] if h not in must][:n - len(must)]
+    return np.array(sorted(must + rest))
+
+
+def _check_winner_in_parts(got, sub, models, valid, cnt, inl):
+    """one pair, one round: the library's outputs against the restatement's models / valid bits / counts of the hypotheses sub (ascending,
+    the library's winner among them) and the winner's reference inliers inl"""
+    win = int(got[2][0])
+    k = int(np.searchsorted(sub, win))
+    assert sub[k] == win and valid[k]
+    assert np.array_equal(_bits(got[3][0]), _bits(models[k]))
+    assert np.array_equal(got[0][0], inl.astype(np.uint8))
+    assert got[1][0] == got[0][0].sum() and got[1][0] == cnt[k]
+    print(f"winner {win}, count {cnt[k]}; {int(valid.sum())} of {len(sub)} reference hypotheses valid, largest other count {np.delete(cnt, k).max()}")
+    assert (cnt[valid] <= cnt[k]).all()
+    assert (sub[valid & (cnt == cnt[k])] >= win).all()                   # a count equal to the winner's only at a larger h
+
+
+def test_a_workgroup_that_strides_over_several_chunks(ctx):
+    # H = 65536 is 256 blocks of 256 hypotheses, which leaves SCORE_MAX_WG / 256 = 8 workgroups along the rows: 8 * CHUNK rows are one
+    # chunk each, the 11 chunks of this list make the first three workgroups take two (the last one partial).  The restatement over all
+    # H hypotheses takes half a minute here, so it is applied in parts: the samples of all H (integer work), the hypotheses and counts
+    # of 512 fixed values of h and of the library's winner.
+    H, m, seed = 65536, 8 * CHUNK + 2 * CHUNK + 7, 21
+    rows = tv.scene_rows(m, out=0.3, seed=12)
+    got = _raw(ctx, *_blocks([rows]), T1, H, 1, seed, 8)
+    pos = tv.samples(seed, 0, H, m)
+    srt = np.sort(pos, axis=1)
+    assert pos.min() >= 0 and pos.max() < m and (srt[:, 1:] > srt[:, :-1]).all()
+    assert 0 <= got[2][0] < H
+    sub = np.union1d(_subset(H), [got[2][0]])
+    F, valid = tv.null_vectors(tv.design(rows[pos[sub]]))
+    cnt = tv.counts_of(F, valid, rows, T1 * T1)
+    _check_winner_in_parts(got, sub, F, valid, cnt, tv.inliers(got[3][0], rows, T1 * T1)[0])
+    assert got[1][0] >= 0.5 * m
+
+
 def test_rows_behind_the_count_are_never_read(ctx):
     rows = _cached(("rows", 300), lambda: tv.scene_rows(300, out=0.3, seed=3))
     ref = tv.verify_pairs(*_blocks([rows]), T1, 256, 3, 5, 8)
