@@ -662,6 +662,47 @@ int sfmhip_two_view_geometry_matches_dev(sfmhip_ctx*, const sfm_keypoint* const*
                                          sfm_dmatch* d_matches_out, int32_t* d_counts_out, int32_t* d_counts2 /* may be NULL */,
                                          double* d_F /* may be NULL */, double* d_Hm /* may be NULL */, int32_t* d_winners /* may be NULL */);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Image registration: a six-point DLT RANSAC for the absolute pose of many views in one call   */
+/* (cv::solvePnPRansac, reference NView:1415; one call registers every candidate image against  */
+/* a fixed cloud).  Again the definition: every integer output is a function of the input alone */
+/* and P is prescribed bit for bit.                                                             */
+/* ------------------------------------------------------------------------------------------ */
+/*   sfmhip_register_views: n_views blocks of 2D-3D correspondences; block q starts at corr + 5*stride*q, a row is (X, Y, Z, x, y) in
+ *     double: a 3-D point and its observation, in pixels or normalised by K (the caller's business, as for F); the first counts[q] rows
+ *     are meaningful and the rows behind them are never read.  L_0 = the rows with five finite values, in ascending row index.  t, H
+ *     (1..65536), rounds (1..8) and seed as in sfmhip_verify_pairs; min_inliers >= 6.
+ *   Sample of hypothesis h of round p: m = |L_p|; m < 6: the view stops.  With g = p*H + h, for k = 0..5:  u = r(6g + k) % (m - k); then
+ *     the rule of the eight-row sample: for each position already chosen, in ascending order, u += (u >= s_j).
+ *   Hypothesis: A, 11 x 12; sample row k = (X, Y, Z, x, y) gives
+ *       row 2k   = [X, Y, Z, 1, 0, 0, 0, 0, -(x*X), -(x*Y), -(x*Z), -x]
+ *       row 2k+1 = [0, 0, 0, 0, X, Y, Z, 1, -(y*X), -(y*Y), -(y*Z), -y];
+ *     row 11, the second row of sample 5, is left out.  Then steps 2 to 6 of the sfmhip_verify_pairs hypothesis with 11 rows and 12
+ *     columns: the pivot scan over i = k..10, j = k..11, z[11] = 1, back-substitution k = 10..0.  P = p / nrm, row-major 3 x 4.
+ *     7. w0 = ((P8*X + P9*Y) + P10*Z) + P11 on sample row 0.  INVALID if w0 is zero or not finite; if w0 < 0 every entry of P is negated.
+ *   Residual of a row (fp64, no contraction):  u = ((P0*X + P1*Y) + P2*Z) + P3;  v likewise from P4..7 and w from P8..11;
+ *       du = u - x*w;  dv = v - y*w.  The row is an inlier iff w > 0 && du*du + dv*dv <= t2*(w*w): the squared reprojection distance
+ *     against t^2 with the division multiplied out, inclusive, and the point in front of the camera.
+ *   Round, stop rule, outputs (mask, count, winner) and errors: exactly as for F, with 6 where F has 8; P: n_views x 12, twelve NaN for
+ *     "no model".  A view's result does not depend on the batch it is in.
+ *   Known limit: the DLT is degenerate on coplanar points.  The inlier set is still right there (a plane's points and their images are
+ *     related by a homography, which every P of the degenerate family reproduces), but P is not a pose:
+ *     sfmhip_pose_from_projection reports a huge sv_ratio for it, and the caller takes the pose from elsewhere. */
+int sfmhip_register_views    (sfmhip_ctx*, const double* corr,   int stride, const int32_t* counts,   int n_views, double t, int H, int rounds,
+                              uint64_t seed, int min_inliers, uint8_t* mask,   int32_t* count_out,   double* P /* may be NULL */,
+                              int32_t* winner /* may be NULL */);
+/* the same on device arrays: enqueues only */
+int sfmhip_register_views_dev(sfmhip_ctx*, const double* d_corr, int stride, const int32_t* d_counts, int n_views, double t, int H, int rounds,
+                              uint64_t seed, int min_inliers, uint8_t* d_mask, int32_t* d_count_out, double* d_P /* may be NULL */,
+                              int32_t* d_winner /* may be NULL */);
+/* The pose in a winner of sfmhip_register_views on NORMALISED observations, x = (u - cx)/fx.  Pure host code, no context.
+ * M = P[:, :3] = U S V^T (singular values descending);  R = U V^T, row-major;  t = P[:, 3] / mean(S);  *sv_ratio = S0 / S2 (inf for
+ * S2 = 0).  A true [R|t] scaled by a constant has sv_ratio near 1; the P of coplanar points has a huge one (the measured ranges are in
+ * DESIGN.md 4c), and its R and t mean nothing.  SFMHIP_E_NUMERIC with R and t left alone: a non-finite P or a block of rank below two
+ * (sv_ratio left alone too), or det(U V^T) < 0 (sv_ratio is still written: the P of coplanar points often ends here).  SFMHIP_E_ARG: a
+ * null pointer. */
+int sfmhip_pose_from_projection(const double P[12], double R[9], double t[3], double* sv_ratio);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,7 @@ SYMBOLS = [
     "sfmhip_verify_pairs", "sfmhip_verify_pairs_dev", "sfmhip_verify_matches_dev",
     "sfmhip_verify_pairs_h", "sfmhip_verify_pairs_h_dev",
     "sfmhip_two_view_geometry", "sfmhip_two_view_geometry_dev", "sfmhip_two_view_geometry_matches_dev",
+    "sfmhip_register_views", "sfmhip_register_views_dev", "sfmhip_pose_from_projection",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -185,6 +186,9 @@ def load():
         "sfmhip_two_view_geometry_dev": (i32, [vp, vp, i32, vp, i32, f64, f64, i32, i32, C.c_uint64, i32, f64, vp, vp, vp, vp, vp, vp, vp]),
         "sfmhip_two_view_geometry_matches_dev": (i32, [vp, C.POINTER(vp), i32, vp, i32, vp, vp, i32, vp, f64, f64, i32, i32, C.c_uint64, i32, f64,
                                                        vp, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_register_views": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
+        "sfmhip_register_views_dev": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
+        "sfmhip_pose_from_projection": (i32, [vp, vp, vp, C.POINTER(f64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -551,6 +551,32 @@ class Context:
                                                        int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers), _dptr(d_mask), _dptr(d_count_out),
                                                        _dptr(d_Hm), _dptr(d_winner)))
 
+    # ---------------------------------------------------------------- image registration (absolute pose)
+    def register_views(self, blocks, t, hypotheses=1024, rounds=3, seed=0, min_inliers=6):
+        """(masks, counts int32 n, P n x 3 x 4, winner int32 n): the six-point DLT RANSAC of sfmhip_register_views (where the definition
+        is) on every block of blocks, a sequence of (m_q, 5) arrays of rows (X, Y, Z, x, y), all views in one call.  masks[q]: bool m_q,
+        the rows the view's model accepts; counts[q] = masks[q].sum(), 0 (with NaN P and winner -1) where no model reaches min_inliers.
+        pose_from_projection turns a P on normalised observations into a pose."""
+        rows = [np.ascontiguousarray(b, np.float64).reshape(-1, 5) for b in blocks]
+        n = len(rows)
+        counts = np.array([len(b) for b in rows], np.int32)
+        stride = int(counts.max()) if n else 0
+        corr = np.zeros((n, stride, 5))
+        for q, b in enumerate(rows):
+            corr[q, :len(b)] = b
+        mask = np.zeros((n, stride), np.uint8); cnt = np.zeros(n, np.int32); P = np.full((n, 12), np.nan); win = np.full(n, -1, np.int32)
+        self._check(self.lib.sfmhip_register_views(self.h, corr.ctypes.data, stride, counts.ctypes.data, n, float(t), int(hypotheses), int(rounds),
+                                                   int(seed) & (2 ** 64 - 1), int(min_inliers), mask.ctypes.data, cnt.ctypes.data, P.ctypes.data,
+                                                   win.ctypes.data))
+        return [mask[q, :c].astype(bool) for q, c in enumerate(counts.tolist())], cnt, P.reshape(n, 3, 4), win
+
+    def register_views_dev(self, d_corr, stride, d_counts, n_views, t, d_mask, d_count_out, d_P=0, d_winner=0, hypotheses=1024, rounds=3, seed=0,
+                           min_inliers=6):
+        """the same on device arrays, in the form of verify_pairs_dev (d_corr n_views x stride x 5 float64, d_P n_views x 12); enqueues only"""
+        self._check(self.lib.sfmhip_register_views_dev(self.h, _dptr(d_corr), int(stride), _dptr(d_counts), int(n_views), float(t), int(hypotheses),
+                                                       int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers), _dptr(d_mask), _dptr(d_count_out),
+                                                       _dptr(d_P), _dptr(d_winner)))
+
     def two_view_geometry(self, corr_blocks, t_f, t_h, hypotheses=1024, rounds=3, seed=0, min_inliers=8, hf_ratio=0.8):
         """(kind int32 n, masks, counts int32 n, counts2 int32 n x 2, F n x 3 x 3, Hm n x 3 x 3, winners int32 n x 2): both RANSACs and
         the selection of sfmhip_two_view_geometry.  kind 0: no model, 1: general (masks[q], counts[q] are F's), 2: planar or panoramic
@@ -874,6 +900,69 @@ def two_view_geometry_for_all(K, key_points_for_all, matches_for_all, px=1.0, px
                 print("[Warning]: pair %d: planar or panoramic (H explains %d matches, F %d): its two-view pose is ill-determined." % (i, c2[i, 1], c2[i, 0]))
             out.append(m[masks[i]])
     return out, [(int(kind[i]), int(counts[i]), int(c2[i, 0]), int(c2[i, 1]), F[i], Hm[i]) for i in range(len(blocks))]
+
+
+SV_RATIO_MAX = 2.0           # a P whose left block has S0 / S2 above this is not a pose (coplanar points); the measured ranges: DESIGN.md 4c
+
+
+def pose_from_projection(P):
+    """(ok, R 3 x 3, t 3, sv_ratio) of a winner of register_views on normalised observations (sfmhip_pose_from_projection, host code);
+    ok False with NaN outputs for a non-finite P, a degenerate block or a reflection"""
+    P = np.ascontiguousarray(P, np.float64).reshape(12)
+    R = np.full((3, 3), np.nan); t = np.full(3, np.nan); sv = C.c_double(np.nan)
+    rc = _lib.load().sfmhip_pose_from_projection(P.ctypes.data, R.ctypes.data, t.ctypes.data, C.byref(sv))
+    return rc == _lib.OK, R, t, sv.value
+
+
+def _rvec_of(R):
+    """the angle-axis vector of a rotation matrix away from a half turn (the logarithm of cv::Rodrigues)"""
+    th = np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0))
+    w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return 0.5 * w if th < 1e-12 else th * w / (2.0 * np.sin(th))
+
+
+def _rotmat_of(aa):
+    th = np.linalg.norm(aa)
+    if th < 1e-15:
+        return np.eye(3)
+    w = aa / th
+    Kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
+
+
+def register_views_for_all(K, obj_pts_list, img_pts_list, px=2.0, hypotheses=1024, rounds=3, seed=0, min_inliers=6, sv_ratio_max=SV_RATIO_MAX,
+                           ctx=None):
+    """cv::solvePnPRansac (NViewReconstuct.cpp:1415) for many views in one call: obj_pts_list[q] (m_q, 3) structure points and
+    img_pts_list[q] (m_q, 2) their pixel observations in view q.  The observations are normalised by K, register_views runs at px pixels,
+    the pose comes out of the winning P (pose_from_projection) and is polished on the inliers by the motion-only bundle
+    adjustment: one camera, every point constant, intrinsics fixed.  Returns per view (ok, R 3 x 3, t 3, mask bool m_q, count,
+    sv_ratio); ok is False, with the mask and count still reported, where there is no model, P is no rotation, or sv_ratio exceeds
+    sv_ratio_max (coplanar points: the DLT's P is not a pose there)."""
+    ctx = ctx or default_context()
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    blocks = []
+    for X, uv in zip(obj_pts_list, img_pts_list):
+        X = np.asarray(X, np.float64).reshape(-1, 3); uv = np.asarray(uv, np.float64).reshape(-1, 2)
+        blocks.append(np.column_stack([X, (uv[:, 0] - cx) / fx, (uv[:, 1] - cy) / fy]))
+    if not blocks:
+        return []
+    masks, counts, P, _ = ctx.register_views(blocks, px / (0.5 * (fx + fy)), hypotheses, rounds, seed, min_inliers)
+    out = []
+    for q, b in enumerate(blocks):
+        ok, R, t, sv = (False, np.full((3, 3), np.nan), np.full(3, np.nan), np.nan) if counts[q] == 0 else pose_from_projection(P[q])
+        ok = bool(ok and sv <= sv_ratio_max)
+        if ok:
+            m = masks[q]
+            n = int(m.sum())
+            uv = np.asarray(img_pts_list[q], np.float64).reshape(-1, 2)[m]
+            o = ctx.ba_options(fix_first_camera=0, fix_intrinsics=1)
+            _, ext, _, s = ctx.ba_solve([fx, fy, cx, cy], np.concatenate([_rvec_of(R), t])[None], b[m, :3], np.zeros(n, np.int32),
+                                        np.arange(n, dtype=np.int32), uv, o, cam_const=np.zeros(1, bool), pt_const=np.ones(n, bool))
+            if s["termination"] != 2 and np.isfinite(ext).all():
+                R, t = _rotmat_of(ext[0, :3]), ext[0, 3:].copy()
+        out.append((ok, R, t, masks[q], int(counts[q]), float(sv)))
+    return out
 
 
 def get_matched_points(p1, p2, matches):

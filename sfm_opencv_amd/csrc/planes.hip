@@ -50,6 +50,7 @@ __device__ __forceinline__ bool plane_inlier(double a, double b, double c, doubl
 }
 // what the scoring loop of ransac.hpp needs to know about a plane
 struct PlaneModel {
+    typedef double4 Row;
     static constexpr int NPAR = 4, UNROLL = 8;
     static __device__ __forceinline__ bool inlier(const double (&P)[4], const double4& q, double t) { return plane_inlier(P[0], P[1], P[2], P[3], q.x, q.y, q.z, t); }
 };

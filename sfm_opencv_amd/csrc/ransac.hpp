@@ -3,8 +3,8 @@
 //
 // The shape of the scoring loop.  LANES OWN HYPOTHESES: a workgroup of 256 threads takes 256 hypotheses (blockIdx.x) and a sequence of
 // chunks of SCORE_CHUNK rows (blockIdx.y, then a stride of gridDim.y chunks); a lane keeps its model (2 NPAR VGPRs) and its count in
-// registers; the chunk is staged in LDS as rows of four doubles, and every lane reads the SAME row at the same time: identical addresses
-// are a broadcast, without bank conflicts.  Per row a wave issues the model's residual (contraction is off: it is the prescribed formula),
+// registers; the chunk is staged in LDS as rows of the model's type (M::Row: four doubles, or the padded five of the absolute pose), and
+// every lane reads the SAME row at the same time: identical addresses are a broadcast, without bank conflicts.  Per row a wave issues the model's residual (contraction is off: it is the prescribed formula),
 // a compare and a conditional add, and these VALU instructions are what bounds the kernel (the accounts are with the models).  A wave none
 // of whose lanes has a hypothesis (H = 65: three waves of the second block) only helps with the staging.  Counts: one integer atomicAdd
 // per lane at the very end, so a counter takes at most gridDim.y adds per round, from different workgroups at different times; integer
@@ -12,7 +12,7 @@
 #pragma once
 #include "common.hpp"
 
-#define SCORE_CHUNK 512          // rows staged per pass of the scoring loop (16 KB of LDS)
+#define SCORE_CHUNK 512          // rows staged per pass of the scoring loop (16 KB of LDS for rows of four doubles, 24 KB for rows of six)
 #define SCORE_MAX_WG 2048        // workgroups of a scoring kernel (per pair) at most, 8 per CU of the MI355X; beyond that a workgroup strides over chunks
 
 typedef unsigned long long pu64;
@@ -51,11 +51,11 @@ __device__ __forceinline__ void ransac_sample_distinct(pu64 seed, pu64 g, pu64 m
 
 // The scoring loop of one workgroup (the shape is explained at the top): the number of rows[0 .. m) that this lane's model accepts, added
 // to *counter.  Every thread of the workgroup calls it.  tile: SCORE_CHUNK rows of LDS; model: the lane's M::NPAR parameters, or null for
-// a lane without a hypothesis.  M supplies NPAR, UNROLL (of the row loop) and
-// inlier(const double (&P)[NPAR], const double4& row, double thr).
+// a lane without a hypothesis.  M supplies Row (the type of a staged row), NPAR, UNROLL (of the row loop) and
+// inlier(const double (&P)[NPAR], const Row& row, double thr).
 template <class M>
-__device__ __forceinline__ void ransac_score(double4* tile, const double4* __restrict__ rows, int m, const double* __restrict__ model, double thr,
-                                             int32_t* __restrict__ counter)
+__device__ __forceinline__ void ransac_score(typename M::Row* tile, const typename M::Row* __restrict__ rows, int m, const double* __restrict__ model,
+                                             double thr, int32_t* __restrict__ counter)
 {
     if ((int)blockIdx.y * SCORE_CHUNK >= m) return;                      // uniform over the workgroup; m >= 1 behind it
     const int nchunks = (m - 1) / SCORE_CHUNK + 1;
@@ -66,7 +66,7 @@ __device__ __forceinline__ void ransac_score(double4* tile, const double4* __res
     for (int j = 0; j < M::NPAR; ++j) P[j] = live ? model[j] : NAN;
     int count = 0;
     for (int c = blockIdx.y; c < nchunks; c += gridDim.y) {              // chunk numbers and the rows of a chunk fit an int for every m
-        const double4* chunk = rows + (size_t)c * SCORE_CHUNK;
+        const typename M::Row* chunk = rows + (size_t)c * SCORE_CHUNK;
         const int cnt = m - c * SCORE_CHUNK < SCORE_CHUNK ? m - c * SCORE_CHUNK : SCORE_CHUNK;
         __syncthreads();
 #pragma unroll
@@ -78,7 +78,7 @@ __device__ __forceinline__ void ransac_score(double4* tile, const double4* __res
         if (!wave_live) continue;
 #pragma unroll M::UNROLL
         for (int r = 0; r < cnt; ++r) {
-            const double4 row = tile[r];
+            const typename M::Row row = tile[r];
             count += M::inlier(P, row, thr) ? 1 : 0;
         }
     }

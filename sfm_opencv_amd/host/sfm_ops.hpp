@@ -454,6 +454,83 @@ inline void Rodrigues_vec(const Mat& rvec, Mat& R)
     m[6] = c1 * rx * rz - s * ry;  m[7] = c1 * ry * rz + s * rx;  m[8] = c + c1 * rz * rz;
 }
 
+// ---- image registration (cv::solvePnPRansac, NView:1415) for many views in one call of sfmhip_register_views (where the definition is):
+// obj_pts_list[q] / img_pts_list[q] are the structure points and their pixel observations in view q.  The observations are normalised
+// by K, the threshold is px pixels, the pose comes out of the winning P (sfmhip_pose_from_projection) and is polished on the inliers by
+// the motion-only bundle adjustment: one camera, every point constant, intrinsics fixed.  A view is not ok -- reason says why, the mask
+// and count are still reported -- where no model reaches min_inliers, P is no rotation, or sv_ratio exceeds sv_ratio_max (coplanar
+// points: the DLT's P is not a pose there; the measured ranges are in DESIGN.md 4c).  Returns 0, -1 on error.
+struct RegisteredView { bool ok = false; const char* reason = ""; Mat R, T; std::vector<uint8_t> mask; int count = 0; double sv_ratio = std::nan(""); };
+inline int register_views_for_all(const Mat& K, const std::vector<std::vector<Point3f>>& obj_pts_list, const std::vector<std::vector<Point2f>>& img_pts_list,
+                                  std::vector<RegisteredView>& views, const double px = 2.0, const int hypotheses = 1024, const int rounds = 3,
+                                  const int min_inliers = 6, const uint64_t seed = 0, const double sv_ratio_max = 2.0)
+{
+    const int n = (int)obj_pts_list.size();
+    views.assign((size_t)n, RegisteredView());
+    sfmhip_ctx* ctx = context();
+    if (!ctx || img_pts_list.size() != obj_pts_list.size()) return -1;
+    if (n == 0) return 0;
+    const double fx = K.at<double>(0, 0), fy = K.at<double>(1, 1), cx = K.at<double>(0, 2), cy = K.at<double>(1, 2);
+    size_t stride = 0;
+    for (int q = 0; q < n; ++q) {
+        if (obj_pts_list[(size_t)q].size() != img_pts_list[(size_t)q].size()) return -1;
+        stride = std::max(stride, obj_pts_list[(size_t)q].size());
+    }
+    std::vector<double> corr((size_t)n * stride * 5, 0.0), P((size_t)n * 12);
+    std::vector<int32_t> rows((size_t)n), counts((size_t)n);
+    std::vector<uint8_t> mask((size_t)n * stride, 0);
+    for (int q = 0; q < n; ++q) {
+        const auto& X = obj_pts_list[(size_t)q]; const auto& x = img_pts_list[(size_t)q];
+        rows[(size_t)q] = (int32_t)X.size();
+        double* r = corr.data() + (size_t)q * stride * 5;
+        for (size_t k = 0; k < X.size(); ++k, r += 5) {
+            r[0] = X[k].x; r[1] = X[k].y; r[2] = X[k].z; r[3] = ((double)x[k].x - cx) / fx; r[4] = ((double)x[k].y - cy) / fy;
+        }
+    }
+    if (sfmhip_register_views(ctx, corr.data(), (int)stride, rows.data(), n, px / (0.5 * (fx + fy)), hypotheses, rounds, seed, min_inliers, mask.data(),
+                              counts.data(), P.data(), nullptr) != SFMHIP_OK) {
+        printf("[Err]: register_views_for_all: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    for (int q = 0; q < n; ++q) {
+        RegisteredView& v = views[(size_t)q];
+        const size_t m = (size_t)rows[(size_t)q];
+        v.mask.assign(mask.begin() + (size_t)q * stride, mask.begin() + (size_t)q * stride + m);
+        v.count = counts[(size_t)q];
+        if (v.count == 0) { v.reason = "no model"; continue; }
+        double R[9], t[3];
+        const int rc = sfmhip_pose_from_projection(&P[12 * (size_t)q], R, t, &v.sv_ratio);
+        if (rc == SFMHIP_OK && !(v.sv_ratio <= sv_ratio_max)) { v.reason = "coplanar points"; continue; }
+        if (rc != SFMHIP_OK) { v.reason = v.sv_ratio > sv_ratio_max ? "coplanar points" : "no rotation"; continue; }
+        v.R = Mat(3, 3, CV_64F); v.T = Mat(3, 1, CV_64F);
+        std::copy(R, R + 9, v.R.ptr<double>());
+        for (int a = 0; a < 3; ++a) v.T.at<double>(a) = t[a];
+        v.ok = true;
+        // the refinement: sfmhip_ba_solve_ex over the inliers with the points constant
+        Mat rvec;
+        Rodrigues(v.R, rvec);
+        double K4[4] = { fx, fy, cx, cy }, ext[6] = { rvec.at<double>(0), rvec.at<double>(1), rvec.at<double>(2), t[0], t[1], t[2] };
+        std::vector<double> pts, uv;
+        std::vector<int32_t> oc, op;
+        for (size_t k = 0; k < m; ++k)
+            if (v.mask[k]) {
+                const Point3f& X = obj_pts_list[(size_t)q][k]; const Point2f& x = img_pts_list[(size_t)q][k];
+                op.push_back((int32_t)oc.size()); oc.push_back(0);
+                pts.push_back(X.x); pts.push_back(X.y); pts.push_back(X.z); uv.push_back(x.x); uv.push_back(x.y);
+            }
+        const std::vector<uint8_t> cam_const(1, 0), pt_const(oc.size(), 1);
+        sfm_ba_options o; sfmhip_ba_default_options(&o);
+        o.fix_first_camera = 0; o.fix_intrinsics = 1;
+        sfm_ba_summary s; std::memset(&s, 0, sizeof s);
+        if (sfmhip_ba_solve_ex(ctx, K4, ext, 1, pts.data(), (int)oc.size(), oc.data(), op.data(), uv.data(), (int)oc.size(), cam_const.data(), pt_const.data(),
+                               &o, &s) == SFMHIP_OK && s.termination != SFMHIP_BA_FAILURE && std::isfinite(ext[0] + ext[1] + ext[2] + ext[3] + ext[4] + ext[5])) {
+            for (int a = 0; a < 3; ++a) { rvec.at<double>(a) = ext[a]; v.T.at<double>(a) = ext[3 + a]; }
+            Rodrigues_vec(rvec, v.R);
+        }
+    }
+    return 0;
+}
+
 // ---- bundle adjustment (NView:1162-1244): in place on intrinsic (4x1), extrinsics (6x1 each), structure -----------
 // const_cameras / const_points: indices of blocks held constant (ceres::Problem::SetParameterBlockConstant; camera 0 stays constant
 // as in the reference unless the options say otherwise) -- local / windowed BA, motion-only, structure-only (sfmhip_ba_solve_ex).

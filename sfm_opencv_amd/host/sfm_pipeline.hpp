@@ -247,6 +247,9 @@ struct PipelineOptions {
     int    geometry_h = 1024;              // ... hypotheses per round
     int    geometry_rounds = 3;            // ... rounds
     double geometry_ratio = 0.8;           // ... a pair is planar or panoramic when cH >= ratio * cF
+    double pnp_px = -1.0;                  // >= 0: frame i is registered on the device (register_views_for_all; extension) within this many pixels, the host solvePnPRansac only where that gives no pose
+    int    pnp_h = 1024;                   // ... hypotheses per round
+    int    pnp_rounds = 3;                 // ... rounds
 };
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
@@ -296,8 +299,18 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         if (opt.poses_from_file) { R = f.file_rotations[i + 1]; T = f.file_motions[i + 1]; }
         else {
             if (obj_pts.size() < 4 || img_pts.size() < 4) { printf("[Warning]: too few 3D-2D point pairs for frame %d.\n", i); continue; }
-            if (!solvePnPRansac(obj_pts, img_pts, K, r, T)) { printf("[Warning]: no pose for frame %d.\n", i); continue; }
-            Rodrigues_vec(r, R);
+            bool on_device = false;
+            if (opt.pnp_px >= 0.0) {
+                std::vector<RegisteredView> reg;
+                if (register_views_for_all(K, { obj_pts }, { img_pts }, reg, opt.pnp_px, opt.pnp_h, opt.pnp_rounds) < 0) return -1;
+                on_device = reg[0].ok;
+                if (on_device) { R = reg[0].R; T = reg[0].T; printf("frame %d: registered on device, kept %d of %zu\n", i, reg[0].count, obj_pts.size()); }
+                else printf("frame %d: device pose rejected (%s), host fallback\n", i, reg[0].reason);
+            }
+            if (!on_device) {
+                if (!solvePnPRansac(obj_pts, img_pts, K, r, T)) { printf("[Warning]: no pose for frame %d.\n", i); continue; }
+                Rodrigues_vec(r, R);
+            }
         }
         print_mat("R", R); print_mat("T", T);
         rotations.push_back(R);
@@ -444,7 +457,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]] [--two-view-geometry[=PX[,PXH[,H[,ROUNDS[,RATIO]]]]]]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]] [--two-view-geometry[=PX[,PXH[,H[,ROUNDS[,RATIO]]]]]] [--pnp-device[=PX[,H[,ROUNDS]]]]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -510,6 +523,16 @@ inline int driver_main(int argc, char** argv, bool nview)
             if (v.size() > 2) opt.geometry_h = std::atoi(v[2].c_str());
             if (v.size() > 3) opt.geometry_rounds = std::atoi(v[3].c_str());
             if (v.size() > 4) opt.geometry_ratio = std::atof(v[4].c_str());
+        }
+        else if (a == "--pnp-device") opt.pnp_px = 2.0;
+        else if (a.rfind("--pnp-device=", 0) == 0) {             // PX[,H[,ROUNDS]]: frame i is registered by the six-point DLT RANSAC on the device within PX (2.0) pixels, H (1024) hypotheses in each of ROUNDS (3) rounds, and refined on its inliers; the host solvePnPRansac runs only where that gives no pose
+            opt.pnp_px = std::atof(a.c_str() + 13);
+            const size_t c1 = a.find(',', 13);
+            if (c1 != std::string::npos) {
+                opt.pnp_h = std::atoi(a.c_str() + c1 + 1);
+                const size_t c2 = a.find(',', c1 + 1);
+                if (c2 != std::string::npos) opt.pnp_rounds = std::atoi(a.c_str() + c2 + 1);
+            }
         }
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
         else if (positional++ == 0) opt.out_dir = a;
