@@ -167,7 +167,8 @@ __global__ void fill_kernel(double* __restrict__ p, size_t n, double v)
 // ------------------------------------------------------------------------------------------------
 // host-side problem
 // ------------------------------------------------------------------------------------------------
-enum { SEAM_LIN_IN_BACK = 4, SEAM_INTR_FRONT = 8, SEAM_CAMSTEP_ROLES = 16, SEAM_TREE_BACKWARD = 32, SEAM_BACK_REDUCE = 64, SEAM_ALL = 4 | 8 | 16 | 32 | 64 };
+enum { SEAM_LIN_IN_BACK = 4, SEAM_INTR_FRONT = 8, SEAM_CAMSTEP_ROLES = 16, SEAM_TREE_BACKWARD = 32, SEAM_BACK_REDUCE = 64, SEAM_PIVOT_FOLD = 128,
+       SEAM_ALL = 4 | 8 | 16 | 32 | 64 | 128 };
 struct sfmhip_ba {
     sfmhip_ctx* ctx = nullptr;
     sfm_ba_options o;
@@ -255,7 +256,9 @@ struct sfmhip_ba {
     // Bits 3..6: the one-workgroup reductions off the critical path.  8: the intrinsic block + scalars of the fold (ba_finalize_intr_role)
     // run as a front group of ba_camschur_kernel; 16: ba_camstep_kernel with the gradient maximum in a workgroup of its own and block 0's
     // loads in flight; 32: one backward launch for the tree below the top (chol_tree_backward_kernel); 64: ba_back_reduce_kernel with
-    // its loads in flight.  0 = every piece a launch / a loop of its own.
+    // its loads in flight.  Bit 7 (128): a node's first pivot block factored under its assembly (ba_solver.hpp, SolverPlan::overlap): nodes with
+    // an assembly step (chol_node_forward_kernel's separators, chol_top_kernel) fold that block first and the rest beside wave 0's factorisation.
+    // 0 = every piece a launch / a loop / a phase of its own.
     int seam = SEAM_ALL;
     int* d_tree_path = nullptr; size_t tree_path_cap = 0; bool tree_ok = false;      // per-leaf ancestor lists of the solver plan (bit 5)
     double *d_Vinv2 = nullptr, *d_bp2 = nullptr, *d_WK2 = nullptr, *d_colsq_p2 = nullptr, *d_part_pt2 = nullptr;
@@ -480,6 +483,7 @@ static int enqueue_solve(sfmhip_ba* h)
             pl.damp_diagU = P.diagU; pl.damp_mask = P.posmask; pl.damp_radius = h->damp_radius; pl.damp_min = P.min_diag; pl.damp_max = P.max_diag;
             h->solver_damps = false;
         }
+        pl.overlap = (h->seam & SEAM_PIVOT_FOLD) ? 1 : 0;
         pl.dbg = 0; pl.stamps = nullptr;
 #ifdef SFMHIP_EXPERIMENTS
         // timing experiments (results are garbage with dbg != 0) and per-panel cycle stamps; read once per process
@@ -1551,12 +1555,13 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { sfmhip_ba_destroy(h); ctx->last_error = "upload failed"; return SFMHIP_E_HIP; }
     h->setup_ms[3] = ms_since(t0);
     if (h->o.verbose)
-        printf("[sfmhip_ba] seam %d: the next point pass %s; intrinsic block + scalars %s; gradient maximum %s; backward sweep below the top %s; ba_back_reduce_kernel's loads %s\n", h->seam,
+        printf("[sfmhip_ba] seam %d: the next point pass %s; intrinsic block + scalars %s; gradient maximum %s; backward sweep below the top %s; ba_back_reduce_kernel's loads %s; an assembling node's first pivot block %s\n", h->seam,
                h->d_Vinv2 ? "rides in the back-substitution (ba_back_kernel_lin)" : "is a launch of its own (ba_point_kernel)",
                (h->seam & SEAM_INTR_FRONT) ? "in ba_camschur_kernel's front group (where camera items and pair chunks share that launch)" : "in ba_fold_kernel",
                (h->seam & SEAM_CAMSTEP_ROLES) ? "in a workgroup of its own" : "behind the step in block 0",
                (h->seam & SEAM_TREE_BACKWARD) ? "in one launch (if the plan has parallel separator levels)" : "a launch per level",
-               (h->seam & SEAM_BACK_REDUCE) ? "in flight together" : "trip by trip");
+               (h->seam & SEAM_BACK_REDUCE) ? "in flight together" : "trip by trip",
+               (h->seam & SEAM_PIVOT_FOLD) ? "factored under the rest of the assembly" : "factored after the assembly");
     if (h->o.verbose)
         printf("[sfmhip_ba] create %.2f ms (inputs + observation sort %.2f, orderings %.2f, pair lists %.2f)\n", h->setup_ms[3], h->setup_ms[0],
                h->setup_ms[1] - h->setup_ms[0], h->setup_ms[2] - h->setup_ms[1]);

@@ -262,11 +262,32 @@ struct SolverPlan {
     // and their gradient are zero; Ceres never sees such blocks -- only blocks of added residuals enter the problem, NView:1187-1197 --
     // so they stay where they are instead of making S + D singular as the radius grows); damp_diagU == nullptr: the caller has damped S already
     const double* damp_diagU; const int* damp_mask; double damp_radius, damp_min, damp_max;
+    // nonzero: a node with an assembly step factors its first pivot block UNDER the rest of that assembly (SFMHIP_BA_SEAM bit 7,
+    // see ba.hip); 0: assembly, barrier, reload, factorisation
+    int overlap;
 };
+// The threads that work beside wave 0 while it factors a node's first pivot block (side work of forward_panels' prologue):
+// index in [0, SSIDE_N), or -1 for a thread that takes no part.  Wave 4 shares wave 0's SIMD (the chain runs slower beside a
+// busy neighbour): SSIDE_W4 = 0 leaves it out.  Measured both ways at C4 (profiles/README.md, round 20): no difference to tell.
+#ifndef SSIDE_W4
+#define SSIDE_W4 1
+#endif
+#define SSIDE_N (SSIDE_W4 ? STHREADS - 64 : STHREADS - 128)
+__device__ __forceinline__ int side_thread()
+{
+    const int tid = threadIdx.x;
+    if (tid < 64) return -1;
+    if (SSIDE_W4) return tid - 64;
+    return tid < 256 ? tid - 64 : tid < 320 ? -1 : tid - 128;
+}
 
-template <bool HAS_EXT>
+// pivot_in_lds: the caller has put the first pivot block (assembled and damped) into s.D, without a barrier behind it; `side` is
+// then run by waves 1..7 while wave 0 factors that block -- the rest of the node's assembly.  It must not contain a
+// block barrier and may touch s.B, s.Pair and global memory only (wave_chol32 owns s.D, s.W, s.G and s.Lc).
+template <bool HAS_EXT, class Side>
 __device__ __forceinline__ bool forward_panels(SolverLds& s, double* __restrict__ A, int ld, int k0, int k1, const SolverPlan pl,
-                                               double* __restrict__ rhs, double* __restrict__ extA, int ext_ld, int na, double* __restrict__ extrhs)
+                                               double* __restrict__ rhs, double* __restrict__ extA, int ext_ld, int na, double* __restrict__ extrhs,
+                                               bool pivot_in_lds, Side side)
 {
     // Look-ahead schedule.  Per panel k (entering with L_kk and its inverse in s.D / s.W, every earlier update visible):
     //   1. all waves stage the panel's row blocks (global -> s.B), write L_kk out                          | lds barrier
@@ -311,11 +332,17 @@ __device__ __forceinline__ bool forward_panels(SolverLds& s, double* __restrict_
     // prologue: first pivot block, and the first panel's block-row list
     { const int q0 = prow_start[k0], Rq = prow_start[k0 + 1] - q0; if (tid < Rq) s.Rows3[k0 % 3][tid] = pl.prow[q0 + tid]; }
     if (k0 + 1 < k1) { const int q1 = prow_start[k0 + 1], Rq = prow_start[k0 + 2] - q1; if (tid >= 64 && tid - 64 < Rq) s.Rows3[(k0 + 1) % 3][tid - 64] = pl.prow[q1 + tid - 64]; }
-    for (int r = r0; r < SNB; r += SROWS) s.D[r][c] = A[(size_t)(k0 * SNB + r) * ld + k0 * SNB + c];
-    __syncthreads();
+    if (pivot_in_lds) lds_barrier();
+    else {
+        for (int r = r0; r < SNB; r += SROWS) s.D[r][c] = A[(size_t)(k0 * SNB + r) * ld + k0 * SNB + c];
+        __syncthreads();
+    }
     if (wave == 0 && !(pl.dbg & 1)) ok = wave_chol32(s, lane) && ok;
-    else if (wave > 0) fill_pairs(k0, tid - 64, STHREADS - 64);
-    __syncthreads();
+    else if (wave > 0) {
+        if (pivot_in_lds) side();
+        fill_pairs(k0, tid - 64, STHREADS - 64);
+    }
+    __syncthreads();        // also publishes what the side work stored to global memory: the panels below read it
     double rhs_next = 0.0; bool rhs_in_reg = false;      // wave 4, lanes 0..31: the next panel's right-hand-side block, carried in a register
     for (int k = k0; k < k1; ++k) {
         const int p0 = prow_start[k], R = prow_start[k + 1] - p0;
@@ -654,6 +681,137 @@ __device__ __forceinline__ void fold_node(FoldEnt* __restrict__ sE, const FoldEn
     }
 }
 
+// ---- the first pivot block under the assembly (SolverPlan::overlap) ----------------------------------------------------
+// The same sums as fold_node, split in two: the node's first pivot block alone, by every thread, straight into s.D
+// (fold_pivot), then everything else by the side threads while wave 0 factors that block (fold_rest, the side work of
+// forward_panels).  Destinations are distinct blocks and never a source of one another, so only the order inside one
+// destination's sum matters, and that is the list order in both.
+//
+// All entries of the node staged in sE by one burst (the caller checked e2 - e0 <= SFOLD_LDS).  Returns the staged index of the
+// entry of diagonal block k0 (every diagonal block of the node's own columns has one), -1 if there is none.
+__device__ __forceinline__ int fold_stage(FoldEnt* __restrict__ sE, const FoldEnt* __restrict__ ents, int e0, int e1, int e2, int k0)
+{
+    const int tid = threadIdx.x;
+    const long long* src = (const long long*)(ents + e0);
+    long long* dst = (long long*)sE;
+    for (int i = tid; i < (e2 - e0) * (int)(sizeof(FoldEnt) / 8); i += STHREADS) dst[i] = src[i];
+    lds_barrier();
+    const int lane = tid & 63;          // e1 - e0 <= SFOLD_LDS < 64: a lane per block entry
+    const bool hit = lane < e1 - e0 && sE[lane].diag0 == k0 * SNB;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+    return m ? (int)__builtin_ctzll(m) : -1;
+}
+
+// one 16-byte element pair of a block destination: the state between the requests and the sums
+template <int NSRC>
+struct FoldPair { v2d acc, t[NSRC]; double dmp; int msk; };
+template <int NSRC>
+__device__ __forceinline__ void fold_pair_request(FoldPair<NSRC>& P, const FoldEnt& E, int r, int c, const SolverPlan& pl)
+{
+    P.acc = v2d{ 0.0, 0.0 };
+    if (E.diag0 != -2) P.acc = *(const v2d*)(E.dst + (size_t)r * E.dst_ld + c);
+#pragma unroll
+    for (int q = 0; q < NSRC; ++q)
+        if (q < E.nsrc) P.t[q] = *(const v2d*)(E.src[q] + (size_t)r * E.src_ld[q] + c);
+    P.dmp = 0.0; P.msk = 1;
+    if (E.diag0 >= 0 && pl.damp_diagU && (r & ~1) == c) { P.dmp = pl.damp_diagU[E.diag0 + r]; P.msk = pl.damp_mask[E.diag0 + r] && P.dmp > 0.0; }
+}
+template <int NSRC>
+__device__ __forceinline__ v2d fold_pair_sum(FoldPair<NSRC>& P, const FoldEnt& E, int r, int c, const SolverPlan& pl)
+{
+#pragma unroll
+    for (int q = 0; q < NSRC; ++q)
+        if (q < E.nsrc) P.acc += P.t[q];
+    for (int q = NSRC; q < E.nsrc; ++q) P.acc += *(const v2d*)(E.src[q] + (size_t)r * E.src_ld[q] + c);
+    if (E.diag0 >= 0 && pl.damp_diagU && (r & ~1) == c) {       // this pair holds the diagonal element (r, r)
+        const double add = fmin(fmax(P.dmp, pl.damp_min), pl.damp_max) / pl.damp_radius;
+        if (r & 1) P.acc.y = P.msk ? P.acc.y + add : 1.0; else P.acc.x = P.msk ? P.acc.x + add : 1.0;
+    }
+    *(v2d*)(E.dst + (size_t)r * E.dst_ld + c) = P.acc;
+    return P.acc;
+}
+
+// phase A: all 512 threads, one element pair each, fold the pivot block's entry into S and into s.D (no barrier behind it)
+template <int NSRC>
+__device__ __forceinline__ void fold_pivot(SolverLds& s, const FoldEnt* __restrict__ sE, int pe, const SolverPlan& pl)
+{
+    const int r = threadIdx.x >> 4, c = (threadIdx.x & 15) * 2;
+    const FoldEnt& E = sE[pe];
+    FoldPair<NSRC> P;
+    fold_pair_request(P, E, r, c, pl);
+    const v2d v = fold_pair_sum(P, E, r, c, pl);
+    s.D[r][c] = v.x; s.D[r][c + 1] = v.y;
+}
+
+// phase B, side threads only: every block destination but `pe`, and the right-hand-side pieces.  The (destination, element
+// pair) items are dealt out flat over the side threads, DB per thread and batch with every load of a batch in flight before
+// the first add; the first round of right-hand-side elements is requested with the first batch, as in fold_node.
+template <int DB, int NSRC>
+__device__ __forceinline__ void fold_rest(const FoldEnt* __restrict__ sE, int nb_blk, int cnt, int pe, const SolverPlan& pl)
+{
+    const int t = side_thread();
+    if (t < 0) return;
+    const int items = (nb_blk - 1) * (SNB * SNB / 2), rhs_items = (cnt - nb_blk) * SNB;
+    const bool rhs_mine = t < rhs_items;
+    const int rdi = nb_blk + (t >> 5), re = t & 31;
+    double rv = 0.0, rq[NSRC];
+    if (rhs_mine) {
+        const FoldEnt& E = sE[rdi];
+        if (E.diag0 != -2) rv = E.dst[re];
+#pragma unroll
+        for (int q = 0; q < NSRC; ++q)
+            if (q < E.nsrc) rq[q] = E.src[q][re];
+    }
+    for (int base = 0; base < items || base == 0; base += DB * SSIDE_N) {
+        FoldPair<NSRC> P[DB];
+#pragma unroll
+        for (int u = 0; u < DB; ++u) {
+            const int it = base + u * SSIDE_N + t;
+            if (it < items) {
+                const int d = it >> 9, ep = it & 511;
+                fold_pair_request(P[u], sE[d + (d >= pe ? 1 : 0)], ep >> 4, (ep & 15) * 2, pl);
+            }
+        }
+        if (base == 0 && rhs_mine) {
+            const FoldEnt& E = sE[rdi];
+#pragma unroll
+            for (int q = 0; q < NSRC; ++q)
+                if (q < E.nsrc) rv += rq[q];
+            for (int q = NSRC; q < E.nsrc; ++q) rv += E.src[q][re];
+            E.dst[re] = rv;
+        }
+#pragma unroll
+        for (int u = 0; u < DB; ++u) {
+            const int it = base + u * SSIDE_N + t;
+            if (it < items) {
+                const int d = it >> 9, ep = it & 511;
+                (void)fold_pair_sum(P[u], sE[d + (d >= pe ? 1 : 0)], ep >> 4, (ep & 15) * 2, pl);
+            }
+        }
+    }
+    for (int j = t + SSIDE_N; j < rhs_items; j += SSIDE_N) {       // more right-hand-side elements than side threads
+        const FoldEnt& E = sE[nb_blk + (j >> 5)];
+        double v = E.diag0 != -2 ? E.dst[j & 31] : 0.0;
+        for (int q = 0; q < E.nsrc; ++q) v += E.src[q][j & 31];
+        E.dst[j & 31] = v;
+    }
+}
+
+// Assembly step of a node in front of forward_panels.  With pl.overlap, for a node whose entries fit one staging pass: the entries
+// staged and the first pivot block folded into s.D (phase A); returns the staged index of that block's entry, and the caller hands
+// fold_rest to forward_panels as its side work.  Otherwise the plain fold_node and its barrier; returns -1.
+template <int DB, int NSRC>
+__device__ __forceinline__ int fold_front(SolverLds& s, const FoldEnt* __restrict__ ents, const NodeDesc& nd, const SolverPlan& pl)
+{
+    FoldEnt* sE = (FoldEnt*)&s.B[0][0];         // the entries are staged in s.B (free until the panels start)
+    if (pl.overlap && nd.e2 - nd.e0 <= SFOLD_LDS && nd.k0 < nd.k1) {
+        const int pe = fold_stage(sE, ents, nd.e0, nd.e1, nd.e2, nd.k0);
+        if (pe >= 0) { fold_pivot<NSRC>(s, sE, pe, pl); return pe; }
+    }
+    fold_node<DB, NSRC>(sE, ents, nd.e0, nd.e1, nd.e2, pl);
+    __syncthreads();
+    return -1;
+}
 // single workgroup: whole factorisation + both substitutions (no dissection)
 __global__ __launch_bounds__(STHREADS) void chol_sparse_kernel(double* __restrict__ A, int ld, SolverPlan pl,
                                                                double* __restrict__ rhs, double* __restrict__ y, int* __restrict__ err)
@@ -662,7 +820,7 @@ __global__ __launch_bounds__(STHREADS) void chol_sparse_kernel(double* __restric
     const int tid = threadIdx.x;
     damp_rows(A, ld, pl, 0, pl.nb * SNB);
     __syncthreads();
-    const bool ok = forward_panels<false>(s, A, ld, 0, pl.nb, pl, rhs, nullptr, 0, 0, nullptr);
+    const bool ok = forward_panels<false>(s, A, ld, 0, pl.nb, pl, rhs, nullptr, 0, 0, nullptr, false, [] {});
     if (!ok && tid == 0) *err = 2;
     double* sy = &s.B[0][0];
     const int n = pl.nb * SNB;
@@ -684,13 +842,14 @@ __global__ __launch_bounds__(STHREADS) void chol_node_forward_kernel(double* __r
     if (pl.stamps && threadIdx.x == 0) pl.stamps[(size_t)nd.k0 * 16 + 8] = t_in;
     NSTAMP(9);
     if (threadIdx.x < SAMAX) s.Anc[threadIdx.x] = nd.anc[threadIdx.x];
-    if (nd.e0 == nd.e2) damp_rows(A, ld, pl, nd.k0 * SNB, nd.k1 * SNB);       // a leaf: nothing to assemble, only the damping
-    else fold_node<8, 2>((FoldEnt*)&s.B[0][0], ents, nd.e0, nd.e1, nd.e2, pl);  // two children per separator; the entries are staged in s.B (free until the panels start)
-    __syncthreads();
+    int pe = -1;
+    if (nd.e0 == nd.e2) { damp_rows(A, ld, pl, nd.k0 * SNB, nd.k1 * SNB); __syncthreads(); }       // a leaf: nothing to assemble, only the damping
+    else pe = fold_front<8, 2>(s, ents, nd, pl);         // two children per separator
     NSTAMP(10);
     double* U = ubuf + nd.u_off;
     const int ldu = nd.na * SNB;
-    const bool ok = forward_panels<true>(s, A, ld, nd.k0, nd.k1, pl, rhs, U, ldu, nd.na, U + (size_t)ldu * ldu);
+    const bool ok = forward_panels<true>(s, A, ld, nd.k0, nd.k1, pl, rhs, U, ldu, nd.na, U + (size_t)ldu * ldu, pe >= 0,
+                                         [&] { fold_rest<8, 2>((const FoldEnt*)&s.B[0][0], nd.e1 - nd.e0, nd.e2 - nd.e0, pe, pl); });
     if (!ok && threadIdx.x == 0) *err = 2;
     NSTAMP(11);
 #undef NSTAMP
@@ -705,9 +864,9 @@ __global__ __launch_bounds__(STHREADS) void chol_top_kernel(double* __restrict__
     const int tid = threadIdx.x;
     const NodeDesc nd = nodes[top_node];
     const int t0 = nd.k0 * SNB, ntop = (nd.k1 - nd.k0) * SNB;
-    fold_node<4, 4>((FoldEnt*)&s.B[0][0], ents, nd.e0, nd.e1, nd.e2, pl);       // four children at C4 (up to 8: the nodes of the last parallel level)
-    __syncthreads();
-    const bool ok = forward_panels<false>(s, A, ld, nd.k0, nd.k1, pl, rhs, nullptr, 0, 0, nullptr);
+    const int pe = fold_front<4, 4>(s, ents, nd, pl);       // four children at C4 (up to 8: the nodes of the last parallel level)
+    const bool ok = forward_panels<false>(s, A, ld, nd.k0, nd.k1, pl, rhs, nullptr, 0, 0, nullptr, pe >= 0,
+                                          [&] { fold_rest<4, 4>((const FoldEnt*)&s.B[0][0], nd.e1 - nd.e0, nd.e2 - nd.e0, pe, pl); });
     if (!ok && tid == 0) *err = 2;
     double* sy = &s.B[0][0];
     for (int i = tid; i < ntop; i += STHREADS) sy[t0 + i] = rhs[t0 + i];
