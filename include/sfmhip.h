@@ -387,7 +387,8 @@ int  sfmhip_ba_reduced_system(sfmhip_ba*, double radius, double* S, double* rhs,
  * "blk_chunk", "chunk_desc", "items" (camera-pair lists; int32 except the double pixel arrays), "setup_ms" (4 doubles: host
  * clock of sfmhip_ba_create, cumulative: inputs + observation sort, + orderings, + pair lists, whole call), "solver_plan" (4 int32,
  * valid once an iteration has run: leaves of the dissection (1: none), parallel separator levels, panels of the top node, 1 if the
- * backward sweep below the top is one launch).
+ * backward sweep below the top is one launch), "step_scalars" (9 doubles, what the last LM iteration published to the host:
+ * cost, gradient maximum, model cost change, candidate cost, |dx_p|^2, |x_p|^2, |dx_c|^2, |x_c|^2, error flag).
  * out == NULL: only *n_bytes is set.  Synchronises. */
 int  sfmhip_ba_debug_table(sfmhip_ba*, const char* name, void* out, size_t cap_bytes, size_t* n_bytes);
 /* average device time (ms) per LM iteration of the last sfmhip_ba_iterate call, measured with HIP events on the

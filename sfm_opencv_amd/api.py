@@ -709,7 +709,7 @@ class BAProblem:
         self.ctx._check(self.ctx.lib.sfmhip_ba_reduced_system(self.h, radius, S.ctypes.data, rhs.ctypes.data, C.byref(n), C.byref(cost)))
         return S, rhs, cost.value
 
-    _TABLE_DTYPES = {"ouv": np.float64, "cam_uv": np.float64, "setup_ms": np.float64}
+    _TABLE_DTYPES = {"ouv": np.float64, "cam_uv": np.float64, "setup_ms": np.float64, "step_scalars": np.float64}
 
     def debug_table(self, name):
         """One of the tables sfmhip_ba_create built on the device (sfmhip_ba_debug_table), as a numpy array."""

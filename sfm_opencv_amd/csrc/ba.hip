@@ -1734,6 +1734,14 @@ int sfmhip_ba_debug_table(sfmhip_ba* h, const char* name, void* out, size_t cap_
         if (out && cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
         return SFMHIP_OK;
     }
+    else if (nm == "step_scalars") {
+        // what the last iteration published to the host (ba_loop has consumed it by the time it returns):
+        // [cost, gmax, model cost change, candidate cost, |dx_p|^2, |x_p|^2, |dx_c|^2, |x_c|^2, err]
+        const size_t sz = 9 * sizeof(double);
+        if (n_bytes) *n_bytes = sz;
+        if (out && cap_bytes >= sz) memcpy(out, h->h_scal, sz);
+        return SFMHIP_OK;
+    }
     else if (nm == "setup_ms") { if (n_bytes) *n_bytes = sizeof h->setup_ms; if (out && cap_bytes >= sizeof h->setup_ms) memcpy(out, h->setup_ms, sizeof h->setup_ms); return SFMHIP_OK; }
     else { ctx->last_error = "sfmhip_ba_debug_table: unknown table"; return SFMHIP_E_ARG; }
     if (n_bytes) *n_bytes = bytes;

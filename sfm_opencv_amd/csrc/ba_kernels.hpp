@@ -392,14 +392,17 @@ __device__ __forceinline__ void pt_accumulate(int fixK, const ObsLin& o, PtAcc& 
     a.cost += 0.5 * o.rho0;
     // two chained fma per sum (x*y + z*w + acc would be mul, fma, add)
 #define ACC2(dst, x0, y0, x1, y1) do { dst = fma(x0, y0, dst); dst = fma(x1, y1, dst); } while (0)
+    // EK row 0 is [a 0 c 0] and row 1 is [0 b 0 d] (obs_linearize): only the products without a structural zero are formed (the
+    // others added +-0 to a finite sum).  Slots 17, 20, 22 and 24 of the record stay at the +0 pt_zero gave them.
     if (!fixK) {
-        int s = 16;
+        a.acc[16] = fma(o.EK[0][0], o.EK[0][0], a.acc[16]);
+        a.acc[18] = fma(o.EK[1][1], o.EK[1][1], a.acc[18]);
+        a.acc[19] = fma(o.EK[0][2], o.EK[0][0], a.acc[19]);
+        a.acc[21] = fma(o.EK[0][2], o.EK[0][2], a.acc[21]);
+        a.acc[23] = fma(o.EK[1][3], o.EK[1][1], a.acc[23]);
+        a.acc[25] = fma(o.EK[1][3], o.EK[1][3], a.acc[25]);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) { ACC2(a.acc[s], o.EK[0][i], o.EK[0][j], o.EK[1][i], o.EK[1][j]); ++s; }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ACC2(a.acc[26 + i], o.EK[0][i], o.r[0], o.EK[1][i], o.r[1]);
+        for (int i = 0; i < 4; ++i) a.acc[26 + i] = fma(o.EK[i & 1][i], o.r[i & 1], a.acc[26 + i]);
     }
     ACC2(a.V[0], o.F[0][0], o.F[0][0], o.F[1][0], o.F[1][0]);
     ACC2(a.V[1], o.F[0][1], o.F[0][0], o.F[1][1], o.F[1][0]);
@@ -412,7 +415,7 @@ __device__ __forceinline__ void pt_accumulate(int fixK, const ObsLin& o, PtAcc& 
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) ACC2(a.WK[3 * i + j], o.EK[0][i], o.F[0][j], o.EK[1][i], o.F[1][j]);
+        for (int j = 0; j < 3; ++j) a.WK[3 * i + j] = fma(o.EK[i & 1][i], o.F[i & 1][j], a.WK[3 * i + j]);
 #undef ACC2
 }
 // after the last observation: damping with `radius`, V^-1, and the point's share of the part_pt record.  A constant point
@@ -1080,8 +1083,9 @@ struct BackCam { const double *pre, *t, *pre_c, *t_c, *sc, *y; };     // one cam
 // LIN: also the point pass of the NEXT linearisation, at the candidate (what ba_point_kernel would do one iteration later if
 // the step is accepted), in a loop of its own behind the candidate pass: its gathers are hits by then.  (Inside the candidate
 // pass, sharing the projection, its 36 accumulators on top of that pass's live values spilled 240 registers at three waves per
-// SIMD; the separate loop: 10, outside the loops.)  next_radius damps it; Vi_n / cs_n return V^-1 and the raw column norms,
-// a the sums (pt_store writes them).
+// SIMD; the separate loop: none.)  next_radius damps it; Vi_n / cs_n return V^-1 and the raw column norms, a the sums (pt_store
+// writes them).  a->cost, the sum of rho/2 over the point's observations at the candidate, is the candidate cost: with LIN the
+// candidate pass does not call obs_cost.
 template <bool LIN, bool PTFIX, typename CamAt>
 __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_at, double acc[4], double (*esave)[256][2],
                                               PtAcc* a, double* Vi_n, double* cs_n, double next_radius, int* __restrict__ err_n)
@@ -1107,8 +1111,8 @@ __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_a
         if (free_cam)
 #pragma unroll
             for (int j = 0; j < 6; ++j) { const double yy = rec.y[j]; e0 += o.Ec[0][j] * yy; e1 += o.Ec[1][j] * yy; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { e0 += o.EK[0][j] * yK[j]; e1 += o.EK[1][j] * yK[j]; }
+        // EK row 0 is [a 0 c 0], row 1 is [0 b 0 d]: the products with the structural zeros are left out
+        e0 += o.EK[0][0] * yK[0]; e1 += o.EK[1][1] * yK[1]; e0 += o.EK[0][2] * yK[2]; e1 += o.EK[1][3] * yK[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) t[j] -= o.F[0][j] * e0 + o.F[1][j] * e1;
         if (k - s0 < BACK_ESAVE) { esave[k - s0][tid][0] = e0; esave[k - s0][tid][1] = e1; }
@@ -1139,13 +1143,14 @@ __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_a
             if (free_cam)
 #pragma unroll
                 for (int j = 0; j < 6; ++j) { const double yy = rec.y[j]; m0 -= o.Ec[0][j] * yy; m1 -= o.Ec[1][j] * yy; }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { m0 -= o.EK[0][j] * yK[j]; m1 -= o.EK[1][j] * yK[j]; }
+            m0 -= o.EK[0][0] * yK[0]; m1 -= o.EK[1][1] * yK[1]; m0 -= o.EK[0][2] * yK[2]; m1 -= o.EK[1][3] * yK[3];
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) { m0 -= o.F[0][j] * yp[j]; m1 -= o.F[1][j] * yp[j]; }
         acc[0] -= m0 * (o.r[0] + 0.5 * m0) + m1 * (o.r[1] + 0.5 * m1);
-        acc[1] += obs_cost(P.Kc, rec.pre_c, rec.t_c, Xc, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a);
+        // the candidate cost: with LIN it is the cost the point pass below sums at the same parameters (the same operations on the
+        // same operands as obs_cost, so the same bits: the seam tests compare the two forms)
+        if (!LIN) acc[1] += obs_cost(P.Kc, rec.pre_c, rec.t_c, Xc, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a);
     }
     if (LIN) {
         for (int k = s0; k < s1; ++k) {
@@ -1154,6 +1159,7 @@ __device__ __forceinline__ void ba_back_point(const BADev& P, int p, CamAt cam_a
             obs_linearize(P.Kc, rec.pre_c, rec.t_c, Xc, P.ouv[2 * k], P.ouv[2 * k + 1], P.huber_a, sK, nullptr, sp, oc);
             pt_accumulate(P.fixK, oc, *a);
         }
+        acc[1] = a->cost;
         pt_finish(P, next_radius, sp, *a, Vi_n, cs_n, err_n, pt_fixed<PTFIX>(P, p));
     }
 }
