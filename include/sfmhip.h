@@ -704,6 +704,41 @@ int sfmhip_register_views_dev(sfmhip_ctx*, const double* d_corr, int stride, con
  * null pointer. */
 int sfmhip_pose_from_projection(const double P[12], double R[9], double t[3], double* sv_ratio);
 
+/* ------------------------------------------------------------------------------------------ */
+/* SIFT feature extraction on the device: cv::SIFT::create(N, 3, 0.04, 10)->detect + compute    */
+/* (TwoViewReconstruct.cpp:112, 130-131) inside extract_features (NViewReconstuct.cpp:785-848). */
+/* ------------------------------------------------------------------------------------------ */
+/* The definition is the host extractor of sfm_opencv_amd/host/sfm_features.hpp (sift_detect_and_compute): sigma 1.6, the image doubled
+ * first, 3 layers per octave, contrast 0.04, edge 10.  The contract:
+ *   - the scale space (every Gaussian and DoG level, the number of octaves), the DoG extrema and their refinement (x, y, response, octave,
+ *     layer, row, column) are that code's values bit for bit; `size` may differ from it by one float ulp (one double pow);
+ *   - orientations and descriptors go through the device's exp / atan2 / sin / cos and sum in another order: they agree with the host
+ *     extractor within a tolerance (a fraction of a degree; a descriptor entry or two by one count), not bit for bit; descriptors are
+ *     integer-valued floats in [0, 255], which is what sfmhip_descset_create_l2_dev needs for its exact path;
+ *   - the rows come in the host extractor's order: ascending x, then y, then descending size, then angle, rows equal in all four dropped
+ *     but the first; with max_features > 0 and more rows than that, the max_features strongest by a stable sort on descending response;
+ *   - the result is a function of the image alone: the same bytes for every run.
+ * image: rows x cols x channels (1 = gray, 3 = BGR as cv::imread returns it) bytes, row stride ld bytes (>= cols*channels); rows and cols
+ * at most 16384.
+ * kp: cap key points; desc: cap x 128 float (integer-valued, [0,255]); *n_found: key points found (after de-duplication and the
+ * max_features budget); only the first min(*n_found, cap) rows are written, in the host extractor's order.
+ * The internal lists hold max(cap, 4096, 4*rows*cols / 8) candidates and max(cap, 4096, 4*rows*cols / 32) key points before
+ * de-duplication.  An image that would need more: SFMHIP_E_ARG with a message and nothing written from the host entries, -1 in *d_n_found from the enqueue-only entry; no list is ever cut short silently.
+ * SFMHIP_E_ARG with the outputs left alone: rows or cols < 1 or too large, channels not 1 or 3, ld < cols*channels, cap or max_features
+ * < 0, a null image, a null output that is needed.  An image too small to hold a key point gives 0 key points, not an error. */
+int sfmhip_sift_extract    (sfmhip_ctx*, const uint8_t* img,   int rows, int cols, int channels, size_t ld, int max_features,
+                            sfm_keypoint* kp,   float* desc,   int cap, int32_t* n_found);
+int sfmhip_sift_extract_dev(sfmhip_ctx*, const uint8_t* d_img, int rows, int cols, int channels, size_t ld, int max_features,
+                            sfm_keypoint* d_kp, float* d_desc, int cap, int32_t* d_n_found);   /* enqueue only */
+/* test / diagnostic: one level of the scale space of that image, kind 0 = Gaussian (index 0..5), 1 = DoG (index 0..4); out may be NULL
+ * (sizes only).  *n_oct: octaves built.  SFMHIP_E_ARG also for an octave that is not built (*n_oct is written all the same). */
+int sfmhip_sift_scale_space(sfmhip_ctx*, const uint8_t* img, int rows, int cols, int channels, size_t ld, int octave, int index, int kind,
+                            float* out, int* out_rows, int* out_cols, int* n_oct);
+/* test / diagnostic: the refined extrema before orientation assignment, sorted by (octave, layer, r, c): n x {x, y, size, response} float
+ * + n x {octave, layer, r, c} int32; x, y and size in pixels of the doubled image, layer / r / c where the refinement ended */
+int sfmhip_sift_extrema(sfmhip_ctx*, const uint8_t* img, int rows, int cols, int channels, size_t ld,
+                        float* xysr, int32_t* olrc, int cap, int32_t* n_found);
+
 #ifdef __cplusplus
 }
 #endif

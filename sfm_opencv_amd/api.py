@@ -611,6 +611,75 @@ class Context:
                                                                   float(hf_ratio), _dptr(d_kind), _dptr(d_matches_out), _dptr(d_counts_out),
                                                                   _dptr(d_counts2), _dptr(d_F), _dptr(d_Hm), _dptr(d_winners)))
 
+    # ---------------------------------------------------------------- SIFT on the device
+    @staticmethod
+    def _image(img):
+        """(array, rows, cols, channels, ld bytes) of a uint8 image rows x cols (gray) or rows x cols x 3 (BGR); a padded row stride is
+        kept (the columns must be dense)"""
+        a = np.asarray(img)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
+            raise ValueError("an image is a uint8 array rows x cols or rows x cols x 3")
+        ch = 1 if a.ndim == 2 else a.shape[2]
+        dense = a.strides[1] == ch and (a.ndim == 2 or a.strides[2] == 1) and a.strides[0] >= a.shape[1] * ch
+        if not dense or a.shape[0] == 0 or a.shape[1] == 0:
+            a = np.ascontiguousarray(a)
+        return a, a.shape[0], a.shape[1], ch, (a.strides[0] if a.shape[0] and a.shape[1] else a.shape[1] * ch)
+
+    def sift_extract(self, img, max_features=0, cap=None):
+        """(keypoints[KEYPOINT], descriptors float32 n x 128) of a uint8 image, gray or BGR (sfmhip_sift_extract: the host extractor's
+        SIFT, cv::SIFT::create(max_features, 3, 0.04, 10), on the device).  cap: rows the call may write (default: enough; a smaller
+        one returns the first cap rows)."""
+        a, rows, cols, ch, ld = self._image(img)
+        want = int(cap) if cap is not None else (int(max_features) if max_features > 0 else 8192)
+        while True:
+            kp = np.zeros(max(want, 0), KEYPOINT); desc = np.zeros((max(want, 0), 128), np.float32); n = C.c_int32(0)
+            self._check(self.lib.sfmhip_sift_extract(self.h, a.ctypes.data, rows, cols, ch, ld, int(max_features), kp.ctypes.data, desc.ctypes.data,
+                                                     want, C.byref(n)))
+            if cap is not None or n.value <= want:
+                m = min(n.value, max(want, 0))
+                return kp[:m].copy(), desc[:m].copy()
+            want = n.value
+
+    def sift_extract_dev(self, d_img, d_kp, d_desc, d_n_found, max_features=0, cap=None):
+        """the same on torch CUDA tensors: d_img uint8 rows x cols (x 3), d_kp a uint8 tensor of cap x 28 bytes (KEYPOINT rows), d_desc
+        float32 cap x 128, d_n_found one int32 (-1: an internal list overflowed).  Enqueues on the context's stream, never synchronises."""
+        assert d_img.is_cuda and d_img.dim() in (2, 3) and d_img.stride(-1) == 1
+        rows, cols = d_img.shape[0], d_img.shape[1]
+        ch = 1 if d_img.dim() == 2 else d_img.shape[2]
+        assert d_img.stride(1) == ch
+        cap = d_desc.shape[0] if cap is None else int(cap)
+        self._check(self.lib.sfmhip_sift_extract_dev(self.h, _dptr(d_img), rows, cols, ch, d_img.stride(0), int(max_features), _dptr(d_kp), _dptr(d_desc),
+                                                     cap, _dptr(d_n_found)))
+
+    def sift_scale_space(self, img, octave, index, kind=0):
+        """(level float32 rows x cols, n_oct): Gaussian (kind 0, index 0..5) or DoG (kind 1, index 0..4) level of an octave (test helper)"""
+        a, rows, cols, ch, ld = self._image(img)
+        r, c, no = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.sfmhip_sift_scale_space(self.h, a.ctypes.data, rows, cols, ch, ld, int(octave), int(index), int(kind), None, r, c, no))
+        out = np.empty((r.value, c.value), np.float32)
+        self._check(self.lib.sfmhip_sift_scale_space(self.h, a.ctypes.data, rows, cols, ch, ld, int(octave), int(index), int(kind), out.ctypes.data, r, c, no))
+        return out, no.value
+
+    def sift_octaves(self, img):
+        """number of octaves the scale space of this image has"""
+        a, rows, cols, ch, ld = self._image(img)
+        no = C.c_int(0)
+        self._check(self.lib.sfmhip_sift_scale_space(self.h, a.ctypes.data, rows, cols, ch, ld, 0, 0, 0, None, None, None, no))
+        return no.value
+
+    def sift_extrema(self, img, cap=1 << 16):
+        """(xysr float32 n x 4, olrc int32 n x 4): the refined DoG extrema before orientation assignment, in (octave, layer, r, c) order
+        (test helper)"""
+        a, rows, cols, ch, ld = self._image(img)
+        xysr = np.zeros((cap, 4), np.float32); olrc = np.zeros((cap, 4), np.int32); n = C.c_int32(0)
+        self._check(self.lib.sfmhip_sift_extrema(self.h, a.ctypes.data, rows, cols, ch, ld, xysr.ctypes.data, olrc.ctypes.data, int(cap), C.byref(n)))
+        m = min(n.value, cap)
+        return xysr[:m].copy(), olrc[:m].copy()
+
+    def sift_extract_for_all(self, images, max_features=0):
+        """extract_features' loop (NViewReconstuct.cpp:785-848) on this context: [(keypoints, descriptors)] image by image"""
+        return [self.sift_extract(img, max_features) for img in images]
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
