@@ -723,7 +723,8 @@ int sfmhip_pose_from_projection(const double P[12], double R[9], double t[3], do
  * kp: cap key points; desc: cap x 128 float (integer-valued, [0,255]); *n_found: key points found (after de-duplication and the
  * max_features budget); only the first min(*n_found, cap) rows are written, in the host extractor's order.
  * The internal lists hold max(cap, 4096, 4*rows*cols / 8) candidates and max(cap, 4096, 4*rows*cols / 32) key points before
- * de-duplication.  An image that would need more: SFMHIP_E_ARG with a message and nothing written from the host entries, -1 in *d_n_found from the enqueue-only entry; no list is ever cut short silently.
+ * de-duplication.  An image that would need more: SFMHIP_E_ARG with a message and nothing written from the host entries, -1 in *d_n_found from the enqueue-only entry; no list is ever cut short silently.  (A cap
+ * above rows*cols / 8 enlarges the list.)
  * SFMHIP_E_ARG with the outputs left alone: rows or cols < 1 or too large, channels not 1 or 3, ld < cols*channels, cap or max_features
  * < 0, a null image, a null output that is needed.  An image too small to hold a key point gives 0 key points, not an error. */
 int sfmhip_sift_extract    (sfmhip_ctx*, const uint8_t* img,   int rows, int cols, int channels, size_t ld, int max_features,
@@ -738,6 +739,53 @@ int sfmhip_sift_scale_space(sfmhip_ctx*, const uint8_t* img, int rows, int cols,
  * + n x {octave, layer, r, c} int32; x, y and size in pixels of the doubled image, layer / r / c where the refinement ended */
 int sfmhip_sift_extrema(sfmhip_ctx*, const uint8_t* img, int rows, int cols, int channels, size_t ld,
                         float* xysr, int32_t* olrc, int cap, int32_t* n_found);
+
+/* ------------------------------------------------------------------------------------------ */
+/* AKAZE feature extraction on the device: cv::AKAZE::create()->detectAndCompute, the live     */
+/* extractor of extract_features (NViewReconstuct.cpp:797-812), 61-byte M-LDB rows.            */
+/* ------------------------------------------------------------------------------------------ */
+/* The definition is the host extractor of sfm_opencv_amd/host/sfm_akaze.hpp (akaze_detect_and_compute with Params at its defaults):
+ * 4 octaves x 4 sublevels, soffset 1.6, derivative factor 1.5, threshold 0.001, 70th percentile over 300 bins, pattern size 10.  An
+ * octave o exists while rows >> o >= 80 and cols >> o >= 80.  The contract:
+ *   - every level array (Lt, Lsmooth, Lx, Ly, Ldet) and kcontrast, the raw 3 x 3 maxima, the survivors of both suppression passes and
+ *     their order, the refined x, y, size, response, octave, class_id and the row order (with and without a budget) are that code's
+ *     values bit for bit.  This rests on correctly rounded float division and sqrtf and on contraction being off;
+ *   - angle and the descriptor bits are the only values that pass through atan2f, sinf and cosf of the device maths library: they agree
+ *     with the host extractor within a tolerance (an ulp of the angle; a bit of a few rows in a thousand), not bit for bit;
+ *   - the rows come in the host extractor's order: a stable sort on descending response of the survivors in the order find_extrema
+ *     leaves them; with max_features > 0 the first max_features of them;
+ *   - the result is a function of the image alone: the same bytes for every run.
+ * image: as for sfmhip_sift_extract.  kp: cap key points (size is a diameter, angle in degrees, class_id the level); desc: cap x 61
+ * bytes, dense, bits 486 and 487 clear: what sfmhip_descset_create_hamming2_dev(..., 61, 61, ...) takes.  *n_found: key points found
+ * (after the max_features budget); only the first min(*n_found, cap) rows are written.
+ * The internal list holds max(cap, 4096, rows*cols / 8) raw maxima.  An image that would need more: SFMHIP_E_ARG with a message and
+ * nothing written from the host entries, -1 in *d_n_found from the enqueue-only entry; no list is ever cut short silently.  (A cap
+ * above rows*cols / 8 enlarges the list.)
+ * Device memory: about 130 bytes per pixel for the call (85 for Lt, Lx, Ly, Ldet of the 16 levels, 24 transient, 18 for the lists:
+ * about 150 bytes per row of the list of raw maxima, 190 MB at 10 MP); an allocation that
+ * fails is an error that leaves the context whole.
+ * SFMHIP_E_ARG with the outputs left alone: the argument rules of sfmhip_sift_extract.  An image without a level gives 0 key points,
+ * not an error. */
+int sfmhip_akaze_extract    (sfmhip_ctx*, const uint8_t* img,   int rows, int cols, int channels, size_t ld, int max_features,
+                             sfm_keypoint* kp,   uint8_t* desc,   int cap, int32_t* n_found);
+int sfmhip_akaze_extract_dev(sfmhip_ctx*, const uint8_t* d_img, int rows, int cols, int channels, size_t ld, int max_features,
+                             sfm_keypoint* d_kp, uint8_t* d_desc, int cap, int32_t* d_n_found);   /* enqueue only */
+/* test / diagnostic: one array of level `level` (0 .. 15) of that image's scale space, kind 0 .. 4 = Lt, Lsmooth, Lx, Ly, Ldet; out may
+ * be NULL (sizes only).  *n_levels: levels built; *kcontrast: the contrast factor that level's diffusion used (level 0: k_percentile's
+ * result).  SFMHIP_E_ARG also for a level that is not built (*n_levels is written all the same); with every output but n_levels NULL
+ * the call only counts the levels and succeeds also where there are none. */
+int sfmhip_akaze_scale_space(sfmhip_ctx*, const uint8_t* img, int rows, int cols, int channels, size_t ld, int level, int kind,
+                             float* out, int* out_rows, int* out_cols, int* n_levels, float* kcontrast);
+/* test / diagnostic: the detector's lists, n x {x, y, size, response} float + n x {octave, level} int32.  stage 0: the raw maxima in
+ * scan order (level, y, x); 1: after both suppression passes, in the order of find_extrema's result; 2: after the sub-pixel fit (size
+ * is then the diameter) */
+int sfmhip_akaze_extrema(sfmhip_ctx*, const uint8_t* img, int rows, int cols, int channels, size_t ld, int stage,
+                         float* xysr, int32_t* ol, int cap, int32_t* n_found);
+/* test / diagnostic: the suppression of find_extrema alone on a caller's list of n x {x, y, response} with levels 0 .. 15 that do not
+ * decrease along the list (anything else: SFMHIP_E_ARG); the order within a level is the caller's, size is the level's
+ * (1.6f * powf(2, sublevel / 4.f + octave) * 1.5f).  kept: the indices of the survivors in the order of find_extrema's result (room for
+ * n), *n_kept their number. */
+int sfmhip_akaze_suppress(sfmhip_ctx*, const float* xyr, const int32_t* level, int n, int32_t* kept, int32_t* n_kept);
 
 #ifdef __cplusplus
 }

@@ -680,6 +680,74 @@ class Context:
         """extract_features' loop (NViewReconstuct.cpp:785-848) on this context: [(keypoints, descriptors)] image by image"""
         return [self.sift_extract(img, max_features) for img in images]
 
+    # ---------------------------------------------------------------- AKAZE on the device
+    def akaze_extract(self, img, max_features=0, cap=None):
+        """(keypoints[KEYPOINT], descriptors uint8 n x 61) of a uint8 image, gray or BGR (sfmhip_akaze_extract: the host extractor's
+        AKAZE, cv::AKAZE::create(), on the device).  cap: rows the call may write (default: enough; a smaller one returns the first
+        cap rows)."""
+        a, rows, cols, ch, ld = self._image(img)
+        want = int(cap) if cap is not None else (int(max_features) if max_features > 0 else 8192)
+        while True:
+            kp = np.zeros(max(want, 0), KEYPOINT); desc = np.zeros((max(want, 0), 61), np.uint8); n = C.c_int32(0)
+            self._check(self.lib.sfmhip_akaze_extract(self.h, a.ctypes.data, rows, cols, ch, ld, int(max_features), kp.ctypes.data, desc.ctypes.data,
+                                                      want, C.byref(n)))
+            if cap is not None or n.value <= want:
+                m = min(n.value, max(want, 0))
+                return kp[:m].copy(), desc[:m].copy()
+            want = n.value
+
+    def akaze_extract_dev(self, d_img, d_kp, d_desc, d_n_found, max_features=0, cap=None):
+        """the same on torch CUDA tensors: d_img uint8 rows x cols (x 3), d_kp a uint8 tensor of cap x 28 bytes (KEYPOINT rows), d_desc
+        uint8 cap x 61 (dense), d_n_found one int32 (-1: the list of raw maxima overflowed).  Enqueues on the context's stream, never
+        synchronises."""
+        assert d_img.is_cuda and d_img.dim() in (2, 3) and d_img.stride(-1) == 1
+        rows, cols = d_img.shape[0], d_img.shape[1]
+        ch = 1 if d_img.dim() == 2 else d_img.shape[2]
+        assert d_img.stride(1) == ch and d_desc.is_contiguous() and d_desc.shape[1] == 61
+        cap = d_desc.shape[0] if cap is None else int(cap)
+        self._check(self.lib.sfmhip_akaze_extract_dev(self.h, _dptr(d_img), rows, cols, ch, d_img.stride(0), int(max_features), _dptr(d_kp), _dptr(d_desc),
+                                                      cap, _dptr(d_n_found)))
+
+    def akaze_levels(self, img):
+        """number of levels the scale space of this image has (0: an octave needs 80 rows and 80 columns)"""
+        a, rows, cols, ch, ld = self._image(img)
+        nl = C.c_int(0)
+        self._check(self.lib.sfmhip_akaze_scale_space(self.h, a.ctypes.data, rows, cols, ch, ld, 0, 0, None, None, None, nl, None))
+        return nl.value
+
+    def akaze_scale_space(self, img, level, kind=0):
+        """(array float32 rows x cols, n_levels, kcontrast): Lt, Lsmooth, Lx, Ly or Ldet (kind 0 .. 4) of a level (test helper)"""
+        a, rows, cols, ch, ld = self._image(img)
+        r, c, nl, kc = C.c_int(0), C.c_int(0), C.c_int(0), C.c_float(0)
+        self._check(self.lib.sfmhip_akaze_scale_space(self.h, a.ctypes.data, rows, cols, ch, ld, int(level), int(kind), None, r, c, nl, None))
+        out = np.empty((r.value, c.value), np.float32)
+        self._check(self.lib.sfmhip_akaze_scale_space(self.h, a.ctypes.data, rows, cols, ch, ld, int(level), int(kind), out.ctypes.data, r, c, nl, kc))
+        return out, nl.value, np.float32(kc.value)
+
+    def akaze_extrema(self, img, stage=2, cap=1 << 16):
+        """(xysr float32 n x 4, ol int32 n x 2 = octave, level): the raw maxima in scan order (stage 0), the survivors of the suppression
+        (1) or of the sub-pixel fit (2), in the host's order (test helper)"""
+        a, rows, cols, ch, ld = self._image(img)
+        xysr = np.zeros((cap, 4), np.float32); ol = np.zeros((cap, 2), np.int32); n = C.c_int32(0)
+        self._check(self.lib.sfmhip_akaze_extrema(self.h, a.ctypes.data, rows, cols, ch, ld, int(stage), xysr.ctypes.data, ol.ctypes.data, int(cap), C.byref(n)))
+        m = min(n.value, cap)
+        return xysr[:m].copy(), ol[:m].copy()
+
+    def akaze_suppress(self, xyr, level):
+        """indices (int32) of the candidates {x, y, response} (n x 3) with levels `level` (0 .. 15, not decreasing) that both passes of the
+        host's find_extrema keep, in its order (test helper)"""
+        xyr = np.ascontiguousarray(xyr, np.float32).reshape(-1, 3)
+        level = np.ascontiguousarray(level, np.int32).reshape(-1)
+        if len(level) != len(xyr):
+            raise ValueError("one level per candidate")
+        kept = np.zeros(max(len(xyr), 1), np.int32); n = C.c_int32(0)
+        self._check(self.lib.sfmhip_akaze_suppress(self.h, xyr.ctypes.data, level.ctypes.data, len(xyr), kept.ctypes.data, C.byref(n)))
+        return kept[:n.value].copy()
+
+    def akaze_extract_for_all(self, images, max_features=0):
+        """extract_features' loop (NViewReconstuct.cpp:785-848) with its live extractor on this context: [(keypoints, descriptors)]"""
+        return [self.akaze_extract(img, max_features) for img in images]
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)

@@ -425,9 +425,35 @@ inline bool sift_detect_and_compute_device(const Image& img, std::vector<KeyPoin
 #include "sfm_akaze.hpp"
 namespace sfm {
 
+// The AKAZE above on the device (sfmhip_akaze_extract, csrc/akaze.hip): scale space, detector, suppression and refined key points are
+// sfm_akaze.hpp's values bit for bit, angles and descriptor bits agree within the device maths library's rounding.  The host still reads
+// the image (and samples the colours); one call per image on the process's context.  false: no device, or the call failed (printed).
+inline bool akaze_detect_and_compute_device(const Image& img, std::vector<KeyPoint>& key_points, Mat& descriptors, int max_features = 0)
+{
+    key_points.clear(); descriptors = Mat(0, 61, CV_8U);
+    sfmhip_ctx* ctx = context();
+    if (!ctx || img.empty()) return false;
+    int cap = max_features > 0 ? max_features : 8192;
+    for (;;) {
+        key_points.assign((size_t)cap, KeyPoint());
+        descriptors = Mat(cap, 61, CV_8U);
+        int32_t n = 0;
+        const int rc = sfmhip_akaze_extract(ctx, img.data.data(), img.rows, img.cols, img.channels, (size_t)img.cols * img.channels, max_features,
+                                            reinterpret_cast<sfm_keypoint*>(key_points.data()), descriptors.ptr<uint8_t>(), cap, &n);
+        if (rc != SFMHIP_OK) { printf("[Err]: akaze_detect_and_compute_device: %s\n", sfmhip_last_error(ctx)); key_points.clear(); descriptors = Mat(0, 61, CV_8U); return false; }
+        if (n <= cap) {
+            key_points.resize((size_t)n);
+            descriptors.rows = n; descriptors.buf.resize((size_t)n * 61);
+            return true;
+        }
+        cap = n;                                            // more key points than rows offered: once more with room for all
+    }
+}
+
 // which extractor extract_features runs: the reference's live one is AKAZE (NView:797), its commented twin SIFT (NView:798, TwoView:112)
-// EXTRACT_SIFT_DEVICE: the SIFT above on the device, image after image on the process's context (created before the first image)
-enum Extractor { EXTRACT_SIFT = 0, EXTRACT_AKAZE = 1, EXTRACT_SIFT_DEVICE = 2 };
+// EXTRACT_SIFT_DEVICE / EXTRACT_AKAZE_DEVICE: the same extractors on the device, image after image on the process's context (created
+// before the first image)
+enum Extractor { EXTRACT_SIFT = 0, EXTRACT_AKAZE = 1, EXTRACT_SIFT_DEVICE = 2, EXTRACT_AKAZE_DEVICE = 3 };
 
 inline void extract_features(std::vector<std::string>& image_names, std::vector<std::vector<KeyPoint>>& key_points_for_all,
                              std::vector<Mat>& descriptor_for_all, std::vector<std::vector<Vec3b>>& colors_for_all, int max_features = 0,
@@ -440,14 +466,16 @@ inline void extract_features(std::vector<std::string>& image_names, std::vector<
     std::vector<std::vector<KeyPoint>> kps((size_t)n); std::vector<Mat> descs((size_t)n); std::vector<std::vector<Vec3b>> cols((size_t)n);
     std::vector<int> state((size_t)n, 0);           // 0: unreadable, 1: too few key points, 2: kept
     std::vector<std::string> warnings((size_t)n);
-    if (extractor == EXTRACT_SIFT_DEVICE && !context()) return;          // no GPU: said by context(), and there is no quiet host path behind it
-#pragma omp parallel for schedule(dynamic, 1) if (extractor != EXTRACT_SIFT_DEVICE)
+    const bool on_device = extractor == EXTRACT_SIFT_DEVICE || extractor == EXTRACT_AKAZE_DEVICE;
+    if (on_device && !context()) return;                                // no GPU: said by context(), and there is no quiet host path behind it
+#pragma omp parallel for schedule(dynamic, 1) if (!on_device)
     for (int k = 0; k < n; ++k) {
         const Image img = imread(image_names[(size_t)k]);
         if (img.empty()) continue;
         std::vector<KeyPoint>& key_points = kps[(size_t)k]; Mat& descriptor = descs[(size_t)k];
         if (extractor == EXTRACT_AKAZE) akaze_detect_and_compute(img, key_points, descriptor, max_features);
         else if (extractor == EXTRACT_SIFT_DEVICE) { if (!sift_detect_and_compute_device(img, key_points, descriptor, max_features)) continue; }
+        else if (extractor == EXTRACT_AKAZE_DEVICE) { if (!akaze_detect_and_compute_device(img, key_points, descriptor, max_features)) continue; }
         else sift_detect_and_compute(img, key_points, descriptor, P);
         state[(size_t)k] = 1;
         if (key_points.size() <= 10) continue;
