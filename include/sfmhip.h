@@ -787,6 +787,37 @@ int sfmhip_akaze_extrema(sfmhip_ctx*, const uint8_t* img, int rows, int cols, in
  * n), *n_kept their number. */
 int sfmhip_akaze_suppress(sfmhip_ctx*, const float* xyr, const int32_t* level, int n, int32_t* kept, int32_t* n_kept);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Baseline JPEG decoding on the device: the cv::imread of extract_features                    */
+/* (NViewReconstuct.cpp:801, TwoViewReconstruct.cpp:116), entropy stage to BGR pixels.         */
+/* ------------------------------------------------------------------------------------------ */
+/* The definition is the host decoder of sfm_opencv_amd/host/sfm_jpeg.hpp (decode_jpeg: libjpeg's islow IDCT, fancy 2:1 and 2:1 x 2:1
+ * chroma filters, 16-bit fixed-point YCbCr tables), which the library includes.  The contract:
+ *   - for every input the verdict equals decode_jpeg's, and on acceptance every byte equals its output (all of it is integer
+ *     arithmetic); the one exception is a file of 2 GiB or more, which is refused here;
+ *   - the result is a function of the file bytes alone, for every `entropy` value and every run.
+ * bytes: the n bytes of the file.  img: rows x cols x channels bytes (sizes from sfmhip_jpeg_info), row stride ld bytes (>= cols*channels;
+ * bytes of a row past cols*channels are not touched): BGR as cv::imread returns it, or gray -- the layout sfmhip_sift_extract_dev /
+ * sfmhip_akaze_extract_dev take.
+ * entropy: where the Huffman stage runs.  1 = on the host (decode_scan of that header; the coefficients are uploaded), 2 = on the device,
+ * one lane per restart interval (the DC predictors are reset at every RSTn, so intervals are independent; a file without DRI is one
+ * interval: legal, a single lane, slow), 0 = automatic: the device for a file with a restart interval and at least 48 intervals (the
+ * measured break-even against the host stage, profiles/r18_time_jpeg.log).  The
+ * inverse DCT, the chroma filters and the colour conversion always run on the device.
+ * Refusal is SFMHIP_E_ARG with a message in sfmhip_last_error: whatever decode_jpeg refuses (progressive, arithmetic, 12-bit, CMYK or
+ * RGB-coded files, damaged headers, fewer restart markers than intervals, a corrupt entropy-coded stream), a null pointer,
+ * ld < cols*channels, entropy outside 0 .. 2.  sfmhip_jpeg_decode then writes nothing to img.
+ * sfmhip_jpeg_decode_dev enqueues on the context's stream and never synchronises; `bytes` has been consumed when it returns.  It refuses
+ * on the host what the headers show (and, with the host entropy stage, a corrupt stream).  For a corrupt stream found by the device
+ * entropy stage it leaves a nonzero *d_status (bit 0: DC category > 11, 1: DC predictor outside 16 bits, 2: run past coefficient 63, 3:
+ * AC category > 10) and the image contents are then unspecified; *d_status is 0 otherwise.  No byte outside the file's scan is read,
+ * whatever the stream holds.
+ * sfmhip_jpeg_info: host only, no context; what the headers say.  n_intervals = ceil(MCUs / restart_interval), 1 without DRI.
+ * SFMHIP_E_ARG (no message) for a null pointer or headers the decoder refuses. */
+int sfmhip_jpeg_info      (const uint8_t* bytes, size_t n, int* rows, int* cols, int* channels, int* restart_interval, int* n_intervals);
+int sfmhip_jpeg_decode    (sfmhip_ctx*, const uint8_t* bytes, size_t n, int entropy, uint8_t* img,   size_t ld);
+int sfmhip_jpeg_decode_dev(sfmhip_ctx*, const uint8_t* bytes, size_t n, int entropy, uint8_t* d_img, size_t ld, int32_t* d_status);   /* enqueue only */
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,7 @@ SYMBOLS = [
     "sfmhip_register_views", "sfmhip_register_views_dev", "sfmhip_pose_from_projection",
     "sfmhip_sift_extract", "sfmhip_sift_extract_dev", "sfmhip_sift_scale_space", "sfmhip_sift_extrema",
     "sfmhip_akaze_extract", "sfmhip_akaze_extract_dev", "sfmhip_akaze_scale_space", "sfmhip_akaze_extrema", "sfmhip_akaze_suppress",
+    "sfmhip_jpeg_info", "sfmhip_jpeg_decode", "sfmhip_jpeg_decode_dev",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -200,6 +201,9 @@ def load():
         "sfmhip_akaze_scale_space": (i32, [vp, vp, i32, i32, i32, sz, i32, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float)]),
         "sfmhip_akaze_extrema": (i32, [vp, vp, i32, i32, i32, sz, i32, vp, vp, i32, C.POINTER(C.c_int32)]),
         "sfmhip_akaze_suppress": (i32, [vp, vp, vp, i32, vp, C.POINTER(C.c_int32)]),
+        "sfmhip_jpeg_info": (i32, [vp, sz, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "sfmhip_jpeg_decode": (i32, [vp, vp, sz, i32, vp, sz]),
+        "sfmhip_jpeg_decode_dev": (i32, [vp, vp, sz, i32, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -748,11 +748,55 @@ class Context:
         """extract_features' loop (NViewReconstuct.cpp:785-848) with its live extractor on this context: [(keypoints, descriptors)]"""
         return [self.akaze_extract(img, max_features) for img in images]
 
+    # ---------------------------------------------------------------- baseline JPEG on the device
+    def jpeg_decode(self, data, entropy=0):
+        """uint8 rows x cols (gray) or rows x cols x 3 (BGR, as cv::imread returns it) of a baseline JPEG file's bytes (bytes or a uint8
+        array): sfmhip_jpeg_decode, the host decoder's pixels byte for byte.  entropy: 0 automatic, 1 Huffman stage on the host, 2 on
+        the device.  SfmHipError for a file the decoder refuses."""
+        buf = _jpeg_bytes(data)
+        rows, cols, ch, _, _ = jpeg_info(buf)
+        out = np.empty((rows, cols) if ch == 1 else (rows, cols, 3), np.uint8)
+        self._check(self.lib.sfmhip_jpeg_decode(self.h, buf.ctypes.data, buf.size, int(entropy), out.ctypes.data, cols * ch))
+        return out
+
+    def jpeg_decode_dev(self, data, entropy=0):
+        """(image, status): the same into a new torch uint8 CUDA tensor, and one int32 that is non-zero when the device entropy stage met
+        a corrupt stream (the image is then unspecified).  Enqueues on the context's stream, never synchronises: this is the image
+        sift_extract_dev / akaze_extract_dev take."""
+        import torch
+        buf = _jpeg_bytes(data)
+        rows, cols, ch, _, _ = jpeg_info(buf)
+        dev = torch.device("cuda", self.device)
+        img = torch.empty((rows, cols) if ch == 1 else (rows, cols, 3), dtype=torch.uint8, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        self._check(self.lib.sfmhip_jpeg_decode_dev(self.h, buf.ctypes.data, buf.size, int(entropy), _dptr(img), cols * ch, _dptr(status)))
+        return img, status
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
         self._check(self.lib.sfmhip_points_fallback_count(self.h, C.byref(c)))
         return c.value
+
+
+def _jpeg_bytes(data):
+    """a contiguous uint8 array over a file's bytes (bytes / bytearray / memoryview, or a uint8 array)"""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8:
+            raise ValueError("a JPEG file is bytes or a uint8 array")
+        return np.ascontiguousarray(data).reshape(-1)
+    return np.frombuffer(data, np.uint8)
+
+
+def jpeg_info(data):
+    """(rows, cols, channels, restart_interval, n_intervals) from the headers of a baseline JPEG file's bytes (sfmhip_jpeg_info: host
+    only, no context).  SfmHipError for a file the decoder refuses."""
+    buf = _jpeg_bytes(data)
+    v = [C.c_int(0) for _ in range(5)]
+    rc = _lib.load().sfmhip_jpeg_info(buf.ctypes.data if buf.size else None, buf.size, *[C.byref(x) for x in v])
+    if rc != 0:
+        raise SfmHipError(f"libsfmhip error {rc}: not a baseline JPEG the decoder supports, or damaged headers")
+    return tuple(x.value for x in v)
 
 
 def _const_mask(m, n):

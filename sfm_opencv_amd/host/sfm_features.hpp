@@ -36,7 +36,9 @@ struct Image {
 };
 
 // baseline JPEG (sfm_jpeg.hpp: the pixels libjpeg / cv::imread produce) or binary PPM (P6, RGB -> stored BGR) / PGM (P5), maxval 255
-inline Image imread(const std::string& path)
+// jpeg_on_device: a JPEG file is decoded by sfmhip_jpeg_decode on the process's context (the same bytes; a refused file is an
+// unreadable image, as on the host)
+inline Image imread(const std::string& path, bool jpeg_on_device = false)
 {
     Image img;
     std::ifstream f(path, std::ios::binary);
@@ -46,7 +48,16 @@ inline Image imread(const std::string& path)
         std::vector<uint8_t> bytes((size_t)f.tellg());
         f.seekg(0);
         f.read((char*)bytes.data(), (std::streamsize)bytes.size());
-        if (!f || !jpeg::decode_jpeg(bytes.data(), bytes.size(), img.rows, img.cols, img.channels, img.data)) return Image();
+        if (!f) return Image();
+        if (jpeg_on_device) {
+            sfmhip_ctx* ctx = context();
+            int ri = 0, ni = 0;
+            if (!ctx || sfmhip_jpeg_info(bytes.data(), bytes.size(), &img.rows, &img.cols, &img.channels, &ri, &ni) != SFMHIP_OK) return Image();
+            img.data.resize((size_t)img.rows * img.cols * img.channels);
+            if (sfmhip_jpeg_decode(ctx, bytes.data(), bytes.size(), 0, img.data.data(), (size_t)img.cols * img.channels) != SFMHIP_OK) return Image();
+            return img;
+        }
+        if (!jpeg::decode_jpeg(bytes.data(), bytes.size(), img.rows, img.cols, img.channels, img.data)) return Image();
         return img;
     }
     f.clear(); f.seekg(0);
@@ -457,7 +468,7 @@ enum Extractor { EXTRACT_SIFT = 0, EXTRACT_AKAZE = 1, EXTRACT_SIFT_DEVICE = 2, E
 
 inline void extract_features(std::vector<std::string>& image_names, std::vector<std::vector<KeyPoint>>& key_points_for_all,
                              std::vector<Mat>& descriptor_for_all, std::vector<std::vector<Vec3b>>& colors_for_all, int max_features = 0,
-                             Extractor extractor = EXTRACT_SIFT)
+                             Extractor extractor = EXTRACT_SIFT, bool jpeg_device = false)
 {
     key_points_for_all.clear(); descriptor_for_all.clear(); colors_for_all.clear();
     sift::Params P; P.nfeatures = max_features;
@@ -470,7 +481,7 @@ inline void extract_features(std::vector<std::string>& image_names, std::vector<
     if (on_device && !context()) return;                                // no GPU: said by context(), and there is no quiet host path behind it
 #pragma omp parallel for schedule(dynamic, 1) if (!on_device)
     for (int k = 0; k < n; ++k) {
-        const Image img = imread(image_names[(size_t)k]);
+        const Image img = imread(image_names[(size_t)k], on_device && jpeg_device);
         if (img.empty()) continue;
         std::vector<KeyPoint>& key_points = kps[(size_t)k]; Mat& descriptor = descs[(size_t)k];
         if (extractor == EXTRACT_AKAZE) akaze_detect_and_compute(img, key_points, descriptor, max_features);

@@ -11,11 +11,22 @@
 // Supported: SOF0 / SOF1 (Huffman, 8-bit), 1 or 3 components, sampling factors 1..2 (other ratios: sample replication), DRI /
 // RSTn, 8- and 16-bit quantisation tables.  Not supported (decode_jpeg returns false): progressive (SOF2), arithmetic coding,
 // 12-bit, CMYK / Adobe-transform files.
+//
+// decode_jpeg is parse_headers (the file's Frame) + decode_scan (the entropy-coded scan, handing each block's quantised coefficients
+// to a sink) with a sink that dequantises and runs the inverse DCT.  The device decoder (csrc/jpeg.hip, sfmhip_jpeg_decode) includes
+// this file for the same parser, the same scan decoder with a sink that stores the coefficients, the 1-D pass of the inverse DCT
+// (idct_1d, host and device) and the colour tables: there is one of each in the tree.
 #pragma once
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
+
+#if defined(__HIPCC__)
+#define SFM_JPEG_HD __host__ __device__
+#else
+#define SFM_JPEG_HD
+#endif
 
 namespace sfm {
 namespace jpeg {
@@ -93,54 +104,49 @@ inline int extend(int v, int s) { return s == 0 ? 0 : (v < (1 << (s - 1)) ? v - 
 static const uint8_t kZigzag[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                                      35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
 
-inline uint8_t clamp_sample(int v) { v += 128; return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
+SFM_JPEG_HD inline uint8_t clamp_sample(int v) { v += 128; return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
+SFM_JPEG_HD inline int descale(long long x, int n) { return (int)((x + (1ll << (n - 1))) >> n); }
 
-// jpeg_idct_islow [3P, libjpeg jidctint.c]: Loeffler-Ligtenberg-Moschytz, CONST_BITS = 13, PASS1_BITS = 2; `coef` already dequantised
-inline void idct_islow(const int* coef, uint8_t* out, int stride)
+// One 1-D pass of jpeg_idct_islow [3P, libjpeg jidctint.c]: Loeffler-Ligtenberg-Moschytz, CONST_BITS = 13; i0..i7: the eight inputs
+// of a column or row, o[0..7]: the eight sums before descaling.  64-bit throughout, so that 16-bit quantisers cannot overflow it.
+// Host and device (csrc/jpeg.hip) share this text: the device pixels are the host's by construction.
+SFM_JPEG_HD inline void idct_1d(long long i0, long long i1, long long i2, long long i3, long long i4, long long i5, long long i6, long long i7, long long* o)
 {
     const int C0298 = 2446, C0390 = 3196, C0541 = 4433, C0765 = 6270, C0899 = 7373, C1175 = 9633, C1501 = 12299, C1847 = 15137,
               C1961 = 16069, C2053 = 16819, C2562 = 20995, C3072 = 25172;
+    long long z2 = i2, z3 = i6;
+    long long z1 = (z2 + z3) * C0541;
+    long long tmp2 = z1 + z3 * (-C1847), tmp3 = z1 + z2 * C0765;
+    long long tmp0 = (i0 + i4) * 8192, tmp1 = (i0 - i4) * 8192;
+    const long long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = i7; tmp1 = i5; tmp2 = i3; tmp3 = i1;
+    z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2; long long z4 = tmp1 + tmp3;
+    const long long z5 = (z3 + z4) * C1175;
+    tmp0 *= C0298; tmp1 *= C2053; tmp2 *= C3072; tmp3 *= C1501;
+    z1 *= -C0899; z2 *= -C2562; z3 *= -C1961; z4 *= -C0390;
+    z3 += z5; z4 += z5;
+    tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
+    o[0] = tmp10 + tmp3; o[7] = tmp10 - tmp3;
+    o[1] = tmp11 + tmp2; o[6] = tmp11 - tmp2;
+    o[2] = tmp12 + tmp1; o[5] = tmp12 - tmp1;
+    o[3] = tmp13 + tmp0; o[4] = tmp13 - tmp0;
+}
+
+// jpeg_idct_islow: column pass (PASS1_BITS = 2: descale by 11), row pass (descale by 18); `coef` already dequantised
+inline void idct_islow(const int* coef, uint8_t* out, int stride)
+{
     int ws[64];
-    auto descale = [](long long x, int n) { return (int)((x + (1ll << (n - 1))) >> n); };
+    long long o[8];
     for (int c = 0; c < 8; ++c) {
         const int* in = coef + c;
-        long long z2 = in[16], z3 = in[48];
-        long long z1 = (z2 + z3) * C0541;
-        long long tmp2 = z1 + z3 * (-C1847), tmp3 = z1 + z2 * C0765;
-        z2 = in[0]; z3 = in[32];
-        long long tmp0 = (z2 + z3) * 8192, tmp1 = (z2 - z3) * 8192;
-        const long long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = in[56]; tmp1 = in[40]; tmp2 = in[24]; tmp3 = in[8];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2; long long z4 = tmp1 + tmp3;
-        const long long z5 = (z3 + z4) * C1175;
-        tmp0 *= C0298; tmp1 *= C2053; tmp2 *= C3072; tmp3 *= C1501;
-        z1 *= -C0899; z2 *= -C2562; z3 *= -C1961; z4 *= -C0390;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        ws[c] = descale(tmp10 + tmp3, 11); ws[56 + c] = descale(tmp10 - tmp3, 11);
-        ws[8 + c] = descale(tmp11 + tmp2, 11); ws[48 + c] = descale(tmp11 - tmp2, 11);
-        ws[16 + c] = descale(tmp12 + tmp1, 11); ws[40 + c] = descale(tmp12 - tmp1, 11);
-        ws[24 + c] = descale(tmp13 + tmp0, 11); ws[32 + c] = descale(tmp13 - tmp0, 11);
+        idct_1d(in[0], in[8], in[16], in[24], in[32], in[40], in[48], in[56], o);
+        for (int r = 0; r < 8; ++r) ws[8 * r + c] = descale(o[r], 11);
     }
     for (int r = 0; r < 8; ++r) {
         const int* w = ws + 8 * r;
-        long long z2 = w[2], z3 = w[6];
-        long long z1 = (z2 + z3) * C0541;
-        long long tmp2 = z1 + z3 * (-C1847), tmp3 = z1 + z2 * C0765;
-        long long tmp0 = ((long long)w[0] + w[4]) * 8192, tmp1 = ((long long)w[0] - w[4]) * 8192;
-        const long long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = w[7]; tmp1 = w[5]; tmp2 = w[3]; tmp3 = w[1];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2; long long z4 = tmp1 + tmp3;
-        const long long z5 = (z3 + z4) * C1175;
-        tmp0 *= C0298; tmp1 *= C2053; tmp2 *= C3072; tmp3 *= C1501;
-        z1 *= -C0899; z2 *= -C2562; z3 *= -C1961; z4 *= -C0390;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        uint8_t* o = out + (size_t)r * stride;
-        o[0] = clamp_sample(descale(tmp10 + tmp3, 18)); o[7] = clamp_sample(descale(tmp10 - tmp3, 18));
-        o[1] = clamp_sample(descale(tmp11 + tmp2, 18)); o[6] = clamp_sample(descale(tmp11 - tmp2, 18));
-        o[2] = clamp_sample(descale(tmp12 + tmp1, 18)); o[5] = clamp_sample(descale(tmp12 - tmp1, 18));
-        o[3] = clamp_sample(descale(tmp13 + tmp0, 18)); o[4] = clamp_sample(descale(tmp13 - tmp0, 18));
+        idct_1d(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], o);
+        uint8_t* q = out + (size_t)r * stride;
+        for (int c = 0; c < 8; ++c) q[c] = clamp_sample(descale(o[c], 18));
     }
 }
 
@@ -194,14 +200,41 @@ inline void upsample(const Component& c, int hmax, int vmax, int W, int H, std::
     }
 }
 
-// out: rows x cols x channels (3 = BGR as cv::imread returns it, 1 = gray); false on anything unsupported or corrupt
-inline bool decode_jpeg(const uint8_t* d, size_t n, int& rows, int& cols, int& channels, std::vector<uint8_t>& out)
+// ycc_rgb_convert [3P, libjpeg jdcolor.c]: the 16-bit fixed-point tables (every entry fits 32 bits; the device decoder takes them
+// from here, because fix() rounds a double product)
+inline void ycc_tables(int* cr_r, int* cb_b, long* cr_g, long* cb_g)
+{
+    auto fix = [](double x) { return (long)(x * 65536.0 + 0.5); };
+    for (int k = 0; k < 256; ++k) {
+        const long x = k - 128;
+        cr_r[k] = (int)((fix(1.40200) * x + 32768) >> 16);
+        cb_b[k] = (int)((fix(1.77200) * x + 32768) >> 16);
+        cr_g[k] = -fix(0.71414) * x;
+        cb_g[k] = -fix(0.34414) * x + 32768;
+    }
+}
+
+// what the headers of a file say: filled by parse_headers, read by decode_scan and by the device decoder (csrc/jpeg.hip)
+struct Frame {
+    int W = 0, H = 0;
+    int hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
+    int restart = 0;                    // MCUs per restart interval, 0 = none
+    std::vector<Component> comp;        // sampling, tq / td / ta, true and padded plane sizes; the planes themselves stay empty
+    uint16_t qt[4][64]; bool qt_ok[4] = { false, false, false, false };      // natural order
+    Huff hdc[4], hac[4];
+    size_t scan = 0;                    // offset of the first entropy-coded byte
+    long long mcus() const { return (long long)mcux * mcuy; }
+    long long intervals() const { return restart ? (mcus() + restart - 1) / restart : 1; }
+};
+
+// false on anything unsupported or damaged in the headers
+inline bool parse_headers(const uint8_t* d, size_t n, Frame& fr)
 {
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return false;
-    uint16_t qt[4][64]; bool qt_ok[4] = { false, false, false, false };
-    Huff hdc[4], hac[4];
-    std::vector<Component> comp;
-    int W = 0, H = 0, restart = 0, adobe_transform = -1;
+    uint16_t (&qt)[4][64] = fr.qt; bool (&qt_ok)[4] = fr.qt_ok;
+    Huff (&hdc)[4] = fr.hdc; Huff (&hac)[4] = fr.hac;
+    std::vector<Component>& comp = fr.comp;
+    int& W = fr.W; int& H = fr.H; int& restart = fr.restart; int adobe_transform = -1;
     size_t i = 2;
     while (i + 4 <= n) {
         if (d[i] != 0xFF) return false;
@@ -267,20 +300,35 @@ inline bool decode_jpeg(const uint8_t* d, size_t n, int& rows, int& cols, int& c
     }
     if (comp.empty() || i >= n) return false;
     if (comp.size() == 3 && adobe_transform == 0) return false;         // RGB-coded file
-    int hmax = 1, vmax = 1;
+    int& hmax = fr.hmax; int& vmax = fr.vmax;
+    hmax = vmax = 1;
     for (auto& c : comp) {
         if (c.h < 1 || c.h > 4 || c.v < 1 || c.v > 4 || c.tq > 3 || !qt_ok[c.tq] || c.td > 3 || c.ta > 3 || !hdc[c.td].present || !hac[c.ta].present) return false;
         hmax = c.h > hmax ? c.h : hmax; vmax = c.v > vmax ? c.v : vmax;
     }
     if (comp.size() == 1) { comp[0].h = comp[0].v = 1; hmax = vmax = 1; }       // a single-component scan is not interleaved
     for (auto& c : comp) if (hmax % c.h || vmax % c.v) return false;
-    const int mcux = (W + 8 * hmax - 1) / (8 * hmax), mcuy = (H + 8 * vmax - 1) / (8 * vmax);
+    const int mcux = fr.mcux = (W + 8 * hmax - 1) / (8 * hmax), mcuy = fr.mcuy = (H + 8 * vmax - 1) / (8 * vmax);
     for (auto& c : comp) {
         c.w = (W * c.h + hmax - 1) / hmax; c.hgt = (H * c.v + vmax - 1) / vmax;
         c.pw = mcux * 8 * c.h; c.ph = mcuy * 8 * c.v;
-        c.plane.assign((size_t)c.pw * c.ph, 0);
+        c.pred = 0;
     }
-    BitReader br; br.p = d + i; br.end = d + n;
+    fr.scan = i;
+    return true;
+}
+
+// The one scan of a baseline file: Huffman decoding, DC prediction, restart handling.  sink(component index, block row, block column,
+// coef): the 64 QUANTISED coefficients of a block in natural order, before dequantisation.  false on a corrupt stream (blocks decoded
+// before it have reached the sink).
+template <class Sink>
+inline bool decode_scan(const uint8_t* d, size_t n, Frame& fr, Sink&& sink)
+{
+    std::vector<Component>& comp = fr.comp;
+    const Huff (&hdc)[4] = fr.hdc; const Huff (&hac)[4] = fr.hac;
+    const int restart = fr.restart, mcux = fr.mcux, mcuy = fr.mcuy;
+    for (auto& c : comp) c.pred = 0;
+    BitReader br; br.p = d + fr.scan; br.end = d + n;
     int coef[64];
     int until_restart = restart;
     for (int my = 0; my < mcuy; ++my)
@@ -295,30 +343,50 @@ inline bool decode_jpeg(const uint8_t* d, size_t n, int& rows, int& cols, int& c
                 for (auto& c : comp) c.pred = 0;
                 until_restart = restart;
             }
-            for (auto& c : comp)
+            for (size_t ci = 0; ci < comp.size(); ++ci) {
+                Component& c = comp[ci];
                 for (int by = 0; by < c.v; ++by)
                     for (int bx = 0; bx < c.h; ++bx) {
                         memset(coef, 0, sizeof coef);
-                        const uint16_t* q = qt[c.tq];
                         int s = decode_symbol(br, hdc[c.td]);
                         if (s > 11) return false;                 // DC difference category of 8-bit data: 0..11 (ITU T.81 F.1.2.1)
                         c.pred += extend(br.get(s), s);
                         if (c.pred < -32768 || c.pred > 32767) return false;      // outside what any encoder of 8-bit samples emits
-                        coef[0] = c.pred * q[0];
+                        coef[0] = c.pred;
                         for (int k = 1; k < 64;) {
                             const int rs = decode_symbol(br, hac[c.ta]);
                             const int r = rs >> 4; s = rs & 15;
                             if (s == 0) { if (r == 15) { k += 16; continue; } break; }
                             k += r;
                             if (k > 63 || s > 10) return false;       // AC category of 8-bit data: 1..10
-                            const int z = kZigzag[k];
-                            coef[z] = extend(br.get(s), s) * q[z];
+                            coef[kZigzag[k]] = extend(br.get(s), s);
                             ++k;
                         }
-                        idct_islow(coef, &c.plane[(size_t)((my * c.v + by) * 8) * c.pw + (mx * c.h + bx) * 8], c.pw);
+                        sink((int)ci, my * c.v + by, mx * c.h + bx, (const int*)coef);
                     }
+            }
             if (restart) --until_restart;
         }
+    return true;
+}
+
+// out: rows x cols x channels (3 = BGR as cv::imread returns it, 1 = gray); false on anything unsupported or corrupt
+inline bool decode_jpeg(const uint8_t* d, size_t n, int& rows, int& cols, int& channels, std::vector<uint8_t>& out)
+{
+    Frame fr;
+    if (!parse_headers(d, n, fr)) return false;
+    std::vector<Component>& comp = fr.comp;
+    const int W = fr.W, H = fr.H, hmax = fr.hmax, vmax = fr.vmax;
+    for (auto& c : comp) c.plane.assign((size_t)c.pw * c.ph, 0);
+    // the sink of the pixel path: dequantise (an int product: the categories bound it), inverse DCT into the component's plane
+    const bool ok = decode_scan(d, n, fr, [&](int ci, int brow, int bcol, const int* qc) {
+        Component& c = comp[(size_t)ci];
+        const uint16_t* q = fr.qt[c.tq];
+        int coef[64];
+        for (int z = 0; z < 64; ++z) coef[z] = qc[z] * q[z];
+        idct_islow(coef, &c.plane[(size_t)(brow * 8) * c.pw + bcol * 8], c.pw);
+    });
+    if (!ok) return false;
     rows = H; cols = W;
     if (comp.size() == 1) {
         channels = 1;
@@ -329,16 +397,8 @@ inline bool decode_jpeg(const uint8_t* d, size_t n, int& rows, int& cols, int& c
     channels = 3;
     std::vector<uint8_t> full[3];
     for (int c = 0; c < 3; ++c) upsample(comp[c], hmax, vmax, W, H, full[c]);
-    // ycc_rgb_convert [3P, libjpeg jdcolor.c]: 16-bit fixed-point tables
     int cr_r[256], cb_b[256]; long cr_g[256], cb_g[256];
-    auto fix = [](double x) { return (long)(x * 65536.0 + 0.5); };
-    for (int k = 0; k < 256; ++k) {
-        const long x = k - 128;
-        cr_r[k] = (int)((fix(1.40200) * x + 32768) >> 16);
-        cb_b[k] = (int)((fix(1.77200) * x + 32768) >> 16);
-        cr_g[k] = -fix(0.71414) * x;
-        cb_g[k] = -fix(0.34414) * x + 32768;
-    }
+    ycc_tables(cr_r, cb_b, cr_g, cb_g);
     auto lim = [](int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); };
     out.resize((size_t)W * H * 3);
     for (size_t p = 0; p < (size_t)W * H; ++p) {

@@ -229,6 +229,7 @@ struct PipelineOptions {
     bool akaze = false;                    // directory input: AKAZE + M-LDB rows (the reference's live extractor, NView:797) or SIFT (its commented twin,
                                            // TwoView:112).  driver_main sets the default per program: NViewReconstruct AKAZE, TwoViewReconstruct SIFT
     bool sift_device = false;              // directory input with SIFT: the extractor runs on the device (EXTRACT_SIFT_DEVICE); the host one is the default
+    bool jpeg_device = false;              // with a device extractor: .jpg files are decoded on the device too (sfmhip_jpeg_decode), the same pixels
     bool akaze_device = false;             // directory input with AKAZE: the extractor runs on the device (EXTRACT_AKAZE_DEVICE); the host one is the default
     double refine_px = 0.0;                // > 0: after BA, refine_structure(max_px) + a second BA (extension, not reference behaviour)
     bool cross_check = false;              // mutual nearest neighbours only, after the ratio test (extension, not reference behaviour)
@@ -459,7 +460,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--sift-device] [--akaze-device] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]] [--two-view-geometry[=PX[,PXH[,H[,ROUNDS[,RATIO]]]]]] [--pnp-device[=PX[,H[,ROUNDS]]]]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--sift-device] [--akaze-device] [--jpeg-device] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]] [--two-view-geometry[=PX[,PXH[,H[,ROUNDS[,RATIO]]]]]] [--pnp-device[=PX[,H[,ROUNDS]]]]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -482,6 +483,7 @@ inline int driver_main(int argc, char** argv, bool nview)
         else if (a == "--sift") opt.akaze = false;
         else if (a == "--sift-device") opt.sift_device = true;   // with SIFT selected: extract on the device (sfmhip_sift_extract), not on the host threads
         else if (a == "--akaze-device") opt.akaze_device = true; // with AKAZE selected: extract on the device (sfmhip_akaze_extract)
+        else if (a == "--jpeg-device") opt.jpeg_device = true;   // with the extractor on the device: decode .jpg files there too (sfmhip_jpeg_decode)
         else if (a.rfind("--max-features=", 0) == 0) opt.max_features = std::atoi(a.c_str() + 15);
         else if (a == "--cross-check") opt.cross_check = true;
         else if (a == "--refine") opt.refine_px = 4.0;
@@ -541,6 +543,10 @@ inline int driver_main(int argc, char** argv, bool nview)
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
         else if (positional++ == 0) opt.out_dir = a;
     }
+    if (opt.jpeg_device && !(opt.akaze ? opt.akaze_device : opt.sift_device)) {     // it would create a context only to decode
+        printf("[Err]: --jpeg-device needs the extractor on the device (--sift --sift-device, or --akaze --akaze-device).\n");
+        return 1;
+    }
     if (opt.verify_px >= 0.0 && opt.geometry_px >= 0.0) { printf("[Err]: --verify-matches and --two-view-geometry exclude each other.\n"); return 1; }
     Features f;
     if (is_directory(argv[1])) {
@@ -552,7 +558,7 @@ inline int driver_main(int argc, char** argv, bool nview)
         if (n_files == 0) n_files = get_files_format(argv[1], ".pgm", img_names);
         printf("Total %d image files.\n", n_files);
         f.K = load_K(argv[1]);
-        extract_features(img_names, f.key_points_for_all, f.descriptor_for_all, f.colors_for_all, opt.max_features, opt.akaze ? (opt.akaze_device ? EXTRACT_AKAZE_DEVICE : EXTRACT_AKAZE) : (opt.sift_device ? EXTRACT_SIFT_DEVICE : EXTRACT_SIFT));
+        extract_features(img_names, f.key_points_for_all, f.descriptor_for_all, f.colors_for_all, opt.max_features, opt.akaze ? (opt.akaze_device ? EXTRACT_AKAZE_DEVICE : EXTRACT_AKAZE) : (opt.sift_device ? EXTRACT_SIFT_DEVICE : EXTRACT_SIFT), opt.jpeg_device);
         f.file_rotations.assign(f.key_points_for_all.size(), Mat()); f.file_motions.assign(f.key_points_for_all.size(), Mat());
         if (!opt.save_features.empty() && !write_features(opt.save_features, f)) printf("[Warning]: cannot write %s\n", opt.save_features.c_str());
     } else {
