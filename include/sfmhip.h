@@ -705,6 +705,86 @@ int sfmhip_register_views_dev(sfmhip_ctx*, const double* d_corr, int stride, con
 int sfmhip_pose_from_projection(const double P[12], double R[9], double t[3], double* sv_ratio);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Two-view relative pose: for every pair of a batch the winning F of sfmhip_verify_pairs or    */
+/* sfmhip_two_view_geometry on K-NORMALISED rows becomes a refined (R, t) with its re-taken     */
+/* inlier set, its cheirality and parallax counts and the quality of the decomposition (what    */
+/* the reference does on the host for its first pair: cv::recoverPose behind findEssentialMat,  */
+/* NView:1048).  Again the definition.  The decomposition, the vote and every per-row decision  */
+/* are prescribed fp64 operation by operation (no contraction, division and sqrt correctly      */
+/* rounded).  The refinement is prescribed as an algorithm, and its sums are reduced in a fixed */
+/* order without floating-point atomics: a pair's doubles are the same bits in every run and in */
+/* every batch the pair is in.  They are NOT promised bit for bit against another               */
+/* implementation of the same algorithm (the order of the sums is the library's).               */
+/* ------------------------------------------------------------------------------------------ */
+/*   Input: corr, stride, counts: the blocks of sfmhip_verify_pairs, rows (x1, y1, x2, y2) normalised by K, x = (u - cx)/fx.  mask_in:
+ *     n_pairs x stride uint8 as sfmhip_verify_pairs or sfmhip_two_view_geometry leave it, or NULL.  F: n_pairs x 9, the epipolar model on
+ *     those rows, row-major (x2' F x1 = 0).
+ *   Parameters: t finite and >= 0, the threshold of the Sampson test, t2 = t*t; 0 <= rounds <= 8; 0 <= iters <= 50; max_depth finite and
+ *     >= 0, in baselines (0: no bound; cv::recoverPose uses 50); min_angle finite, 0 <= min_angle <= pi/2, in radians,
+ *     cos2 = cos(min_angle)^2 computed once on the host (c = cos(min_angle) of libm, cos2 = c*c).
+ *   Lists: L0 = the rows below counts[q] with four finite values.  U = the rows of L0 whose mask_in byte is non-zero, or all of L0 if
+ *     mask_in is NULL.  n_used = |U|.
+ *   1. Decomposition.  F = u diag(s) v^T by one-sided Jacobi rotations (Hestenes) on the columns of F, the iteration of
+ *     sfmhip_pose_from_projection: W = F, V = I; at most 60 sweeps over the column pairs (p,q) = (0,1), (0,2), (1,2); per pair
+ *     a = sum_i W[i][p]^2, b = sum_i W[i][q]^2, c = sum_i W[i][p]*W[i][q], each summed from 0 in ascending i; the pair is skipped if
+ *     c == 0 or |c| <= 1e-16*sqrt(a*b); else zeta = (b - a)/(2*c), tn = sign(zeta) / (|zeta| + sqrt(1 + zeta*zeta)) with sign(0) = +1,
+ *     cs = 1/sqrt(1 + tn*tn), sn = cs*tn, and in W and in V: (col p, col q) <- (cs*p - sn*q, sn*p + cs*q); a sweep that rotates nothing
+ *     ends the iteration.  S_j = sqrt(W0j*W0j + W1j*W1j + W2j*W2j) (left to right); the columns are put in descending order of S by the
+ *     exchange sort ord = (0,1,2), for a = 0..1, b = a+1..2: if S[ord[b]] > S[ord[a]] swap ord[a], ord[b];  s_j = S[ord[j]],
+ *     u[:,j] = W[:,ord[j]] / s_j (zero if s_j is not > 0), v[:,j] = V[:,ord[j]];  where s2 is not > 1e-15*s0 the third left vector is
+ *     sign(det v) * (u[:,0] x u[:,1]).  det m = m00*(m11*m22 - m21*m12) - m10*(m01*m22 - m21*m02) + m20*(m01*m12 - m11*m02).
+ *     If det u < 0 every entry of u is negated; v likewise.  With W of cv::recoverPose, Ra = u W v^T and Rb = u W^T v^T:
+ *       Ra[i][j] = (u[i][0]*v[j][1] - u[i][1]*v[j][0]) + u[i][2]*v[j][2];   Rb[i][j] = (u[i][1]*v[j][0] - u[i][0]*v[j][1]) + u[i][2]*v[j][2];
+ *     tc = u[:,2].  Candidates k = 0..3 in cv::recoverPose's order: (Ra, tc), (Rb, tc), (Ra, -tc), (Rb, -tc).  s0, s1, s2 are reported:
+ *     s1/s0 and s2/s0 say how far F is from an essential matrix (1 and 0 for one).
+ *   2. The per-row test under a pose (R, t), with nothing divided and every decision on the computed values:
+ *       p0 = (R0*x1 + R1*y1) + R2;  p1 = (R3*x1 + R4*y1) + R5;  p2 = (R6*x1 + R7*y1) + R8           (p = R a, a = (x1, y1, 1), b = (x2, y2, 1))
+ *       aa = (p0*p0 + p1*p1) + p2*p2;  bb = (x2*x2 + y2*y2) + 1;  ab = (p0*x2 + p1*y2) + p2;
+ *       at = (p0*t0 + p1*t1) + p2*t2;  bt = (x2*t0 + y2*t1) + t2;
+ *       D = aa*bb - ab*ab;  n1 = ab*bt - at*bb;  n2 = aa*bt - ab*at.
+ *     n1 / D and n2 / D are the depths in camera 1 and 2, in baselines, of the least-squares meeting point of the two rays.
+ *     IN FRONT: D > 0 && n1 > 0 && n2 > 0, and, when max_depth > 0, n1 < max_depth*D && n2 < max_depth*D.
+ *     PARALLAX at least min_angle: in front, and ab <= 0 || ab*ab <= cos2*(aa*bb).
+ *   3. Vote.  n4[k] = the rows of U in front under candidate k.  cand = the k with the largest n4, the smallest k among equals.
+ *   No pose (status 0): F not finite; n_used < 8; s1 not > 0 or s0 not finite; no candidate has a row in front.  Then pose is twelve NaN,
+ *     info is zero except cand = -1 and n_used, quality is five NaN and the pair's mask_out row is zero.
+ *   4. Refinement: `rounds` rounds of at most `iters` Levenberg-Marquardt iterations (rounds = 0 or iters = 0: none; the voted candidate
+ *     is returned).  Cost: the sum over a set of rows of r^2, r = e / sqrt(d + 1e-300) with e and d of the sfmhip_verify_pairs residual
+ *     under E = [t]x R:  E[j] = t1*R[6+j] - t2*R[3+j];  E[3+j] = t2*R[j] - t0*R[6+j];  E[6+j] = t0*R[3+j] - t1*R[j]  (j = 0..2).
+ *     Five parameters d: R <- exp([d0..2]x) R (Rodrigues; below an angle of 1e-9 the series 1 - th^2/6, 1/2 - th^2/24) and
+ *     t <- (t + d3*b1 + d4*b2) normalised, b1 = (t x e_k) normalised with k the first smallest of |t0|, |t1|, |t2| as the host
+ *     refine_motion picks it, b2 = t x b1.  The Jacobian is analytic: dE/dd_k = [t]x [e_k]x R for k < 3, [b1]x R and [b2]x R; with
+ *     l = E a, m = E^T b and dl, dm, de the same under dE:  dr = de/sqrt(d) - r*(l0*dl0 + l1*dl1 + m0*dm0 + m1*dm1)/d.
+ *     A round starts with lambda = 1e-3.  An iteration forms A = J^T J, g = J^T r and then tries up to eight times: solve
+ *     (A + lambda*diag(A + 1e-12)) d = -g by Cholesky (not positive definite: lambda *= 10, next try); the step is accepted iff its cost
+ *     is < the current cost, then lambda = max(0.3*lambda, 1e-9), and the round ends if the gain was <= 1e-12 * the cost before; a
+ *     rejected step: lambda *= 10.  An iteration without an accepted step ends the round.
+ *     The set of round 0 is U.  The set of round p >= 1 is the rows of L0 that pass the sfmhip_verify_pairs test e*e <= t2*d under the
+ *     current E; fewer than 8 rows end the refinement with the pose as it stands.  (Round 0 uses the caller's set because the
+ *     decomposition of an exact eight-row fit can explain far fewer rows than F itself.)
+ *   5. Outputs per pair.  pose (n_pairs x 12): R row-major, then the unit t; x2 ~ R x1 + t.
+ *     info (n_pairs x 10 int32): status, cand, n4[0..3], n_used, n_inl, n_front, n_angle.  n_inl: the rows of L0 that pass the Sampson
+ *     test under the final E; n_front: those of them in front under the final pose; n_angle: those of them with the parallax.
+ *     quality (n_pairs x 5): s0, s1, s2, then the cost of the last round's set at that round's start and end (no round: the cost of U
+ *     under the voted candidate, twice).
+ *     mask_out (n_pairs x stride uint8): bit 0 the final Sampson inlier, bit 1 in front, bit 2 the parallax: 0, 1, 3 or 7; rows
+ *     outside L0 are 0.  info and mask_out are functions of the returned pose's bits by 2. and the Sampson test.
+ *   SFMHIP_E_ARG with the outputs left alone: t, max_depth or min_angle non-finite or negative, min_angle > pi/2, rounds or iters out of
+ *     range, a negative stride or n_pairs, a null required pointer.  n_pairs == 0: OK, no pointer touched.
+ *   Known limit: a pair of kind 2 of sfmhip_two_view_geometry (planar or panoramic) has no determined F, and this call computes whatever
+ *     its F implies.  Callers skip such pairs; a pose from the homography is not provided. */
+int sfmhip_relative_pose    (sfmhip_ctx*, const double* corr,   int stride, const int32_t* counts,   int n_pairs,
+                             const uint8_t* mask_in /* may be NULL: every row */,   const double* F,   double t, int rounds, int iters,
+                             double max_depth, double min_angle, double* pose,   int32_t* info,   double* quality /* may be NULL */,
+                             uint8_t* mask_out /* may be NULL */);
+/* the same on device arrays: one kernel launch for the batch (one workgroup per pair), enqueued on the context's stream; never
+ * synchronises.  The outputs may not overlap the inputs. */
+int sfmhip_relative_pose_dev(sfmhip_ctx*, const double* d_corr, int stride, const int32_t* d_counts, int n_pairs,
+                             const uint8_t* d_mask_in /* may be NULL */, const double* d_F, double t, int rounds, int iters,
+                             double max_depth, double min_angle, double* d_pose, int32_t* d_info, double* d_quality /* may be NULL */,
+                             uint8_t* d_mask_out /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------ */
 /* SIFT feature extraction on the device: cv::SIFT::create(N, 3, 0.04, 10)->detect + compute    */
 /* (TwoViewReconstruct.cpp:112, 130-131) inside extract_features (NViewReconstuct.cpp:785-848). */
 /* ------------------------------------------------------------------------------------------ */

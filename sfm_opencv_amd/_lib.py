@@ -72,6 +72,7 @@ SYMBOLS = [
     "sfmhip_verify_pairs_h", "sfmhip_verify_pairs_h_dev",
     "sfmhip_two_view_geometry", "sfmhip_two_view_geometry_dev", "sfmhip_two_view_geometry_matches_dev",
     "sfmhip_register_views", "sfmhip_register_views_dev", "sfmhip_pose_from_projection",
+    "sfmhip_relative_pose", "sfmhip_relative_pose_dev",
     "sfmhip_sift_extract", "sfmhip_sift_extract_dev", "sfmhip_sift_scale_space", "sfmhip_sift_extrema",
     "sfmhip_akaze_extract", "sfmhip_akaze_extract_dev", "sfmhip_akaze_scale_space", "sfmhip_akaze_extrema", "sfmhip_akaze_suppress",
     "sfmhip_jpeg_info", "sfmhip_jpeg_decode", "sfmhip_jpeg_decode_dev",
@@ -192,6 +193,8 @@ def load():
         "sfmhip_register_views": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
         "sfmhip_register_views_dev": (i32, [vp, vp, i32, vp, i32, f64, i32, i32, C.c_uint64, i32, vp, vp, vp, vp]),
         "sfmhip_pose_from_projection": (i32, [vp, vp, vp, C.POINTER(f64)]),
+        "sfmhip_relative_pose": (i32, [vp, vp, i32, vp, i32, vp, vp, f64, i32, i32, f64, f64, vp, vp, vp, vp]),
+        "sfmhip_relative_pose_dev": (i32, [vp, vp, i32, vp, i32, vp, vp, f64, i32, i32, f64, f64, vp, vp, vp, vp]),
         "sfmhip_sift_extract": (i32, [vp, vp, i32, i32, i32, sz, i32, vp, vp, i32, C.POINTER(C.c_int32)]),
         "sfmhip_sift_extract_dev": (i32, [vp, vp, i32, i32, i32, sz, i32, vp, vp, i32, vp]),
         "sfmhip_sift_scale_space": (i32, [vp, vp, i32, i32, i32, sz, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),

@@ -551,6 +551,39 @@ class Context:
                                                        int(rounds), int(seed) & (2 ** 64 - 1), int(min_inliers), _dptr(d_mask), _dptr(d_count_out),
                                                        _dptr(d_Hm), _dptr(d_winner)))
 
+    # ---------------------------------------------------------------- two-view relative pose
+    def relative_pose(self, blocks, masks, F, t, rounds=3, iters=10, max_depth=50.0, min_angle_deg=2.0):
+        """(pose n x 12, info int32 n x 10, quality n x 5, masks_out): the relative pose of sfmhip_relative_pose (where the definition
+        is) for every block of blocks, a sequence of (m_q, 4) arrays of rows (x1, y1, x2, y2) NORMALISED by K, all pairs in one call.
+        masks: per pair the bool / uint8 inlier mask of verify_pairs or two_view_geometry, or None for every row; F: n x 3 x 3, the
+        epipolar model on those rows; t: the Sampson threshold.  pose[q] = R row-major then the unit t (NaN without a pose);
+        info[q] = status, cand, n4[0..3], n_used, n_inl, n_front, n_angle; quality[q] = s0, s1, s2, cost before and after the last
+        round; masks_out[q]: uint8 m_q, bit 0 the final Sampson inlier, bit 1 in front of both cameras, bit 2 the parallax."""
+        corr, counts, n, stride = self._corr_blocks(blocks)
+        F = np.ascontiguousarray(F, np.float64).reshape(n, 9)
+        mask_in = None
+        if masks is not None:
+            mask_in = np.zeros((n, stride), np.uint8)
+            for q, m in enumerate(masks):
+                m = np.asarray(m).reshape(-1)
+                if len(m) != counts[q]:
+                    raise ValueError(f"mask {q} has {len(m)} entries for {counts[q]} rows")
+                mask_in[q, :len(m)] = m != 0
+        pose = np.full((n, 12), np.nan); info = np.zeros((n, 10), np.int32); quality = np.full((n, 5), np.nan); mask = np.zeros((n, stride), np.uint8)
+        self._check(self.lib.sfmhip_relative_pose(self.h, corr.ctypes.data, stride, counts.ctypes.data, n, mask_in.ctypes.data if mask_in is not None else None,
+                                                  F.ctypes.data, float(t), int(rounds), int(iters), float(max_depth), float(np.radians(min_angle_deg)),
+                                                  pose.ctypes.data, info.ctypes.data, quality.ctypes.data, mask.ctypes.data))
+        return pose, info, quality, [mask[q, :c].copy() for q, c in enumerate(counts.tolist())]
+
+    def relative_pose_dev(self, d_corr, stride, d_counts, n_pairs, d_mask_in, d_F, t, d_pose, d_info, d_quality=0, d_mask_out=0, rounds=3, iters=10,
+                          max_depth=50.0, min_angle_deg=2.0):
+        """the same on device arrays (torch tensors or integer addresses; 0 for d_mask_in: every row, for d_quality / d_mask_out: not
+        wanted): d_corr n_pairs x stride x 4 float64, d_mask_in / d_mask_out n_pairs x stride uint8, d_F n_pairs x 9, d_pose n_pairs x 12,
+        d_info int32 n_pairs x 10, d_quality n_pairs x 5; one kernel launch on the context's stream, never synchronises"""
+        self._check(self.lib.sfmhip_relative_pose_dev(self.h, _dptr(d_corr), int(stride), _dptr(d_counts), int(n_pairs), _dptr(d_mask_in), _dptr(d_F),
+                                                      float(t), int(rounds), int(iters), float(max_depth), float(np.radians(min_angle_deg)),
+                                                      _dptr(d_pose), _dptr(d_info), _dptr(d_quality), _dptr(d_mask_out)))
+
     # ---------------------------------------------------------------- image registration (absolute pose)
     def register_views(self, blocks, t, hypotheses=1024, rounds=3, seed=0, min_inliers=6):
         """(masks, counts int32 n, P n x 3 x 4, winner int32 n): the six-point DLT RANSAC of sfmhip_register_views (where the definition
@@ -1081,6 +1114,53 @@ def two_view_geometry_for_all(K, key_points_for_all, matches_for_all, px=1.0, px
                 print("[Warning]: pair %d: planar or panoramic (H explains %d matches, F %d): its two-view pose is ill-determined." % (i, c2[i, 1], c2[i, 0]))
             out.append(m[masks[i]])
     return out, [(int(kind[i]), int(counts[i]), int(c2[i, 0]), int(c2[i, 1]), F[i], Hm[i]) for i in range(len(blocks))]
+
+
+POSE_MIN_INLIERS = 15        # find_transform's gates (NViewReconstuct.cpp:1041, 1056): more inliers than this,
+POSE_MIN_FRONT = 0.7         # and at least this share of them in front of both cameras
+
+
+def _normalised_blocks(K, key_points_for_all, matches_for_all):
+    """per consecutive pair the rows (x1, y1, x2, y2) of its matches normalised by K"""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    blocks = []
+    for i, m in enumerate(matches_for_all):
+        a, b = key_points_for_all[i], key_points_for_all[i + 1]
+        q, t = m["queryIdx"], m["trainIdx"]
+        blocks.append(np.stack([(a["x"][q].astype(np.float64) - cx) / fx, (a["y"][q].astype(np.float64) - cy) / fy,
+                                (b["x"][t].astype(np.float64) - cx) / fx, (b["y"][t].astype(np.float64) - cy) / fy], 1).reshape(-1, 4))
+    return blocks, 0.5 * (fx + fy)
+
+
+def relative_pose_for_all(K, key_points_for_all, matches_for_all, px=1.0, px_h=2.0, hypotheses=1024, rounds=3, seed=0, min_inliers=15, hf_ratio=0.8,
+                          pose_rounds=3, pose_iters=10, max_depth=50.0, min_angle_deg=2.0, ctx=None):
+    """find_transform (NViewReconstuct.cpp:1022-1060) for every consecutive pair of the chain on the device: two_view_geometry (F and
+    homography RANSAC, the selection) and then relative_pose on the pairs of kind 1, with F's inlier mask and F.  Returns per pair a dict:
+    ok, R (3 x 3) and t (unit 3; NaN without a pose), kind (0, 1, 2 of sfmhip_two_view_geometry), counts (dict: n_used, n_inl, n_front,
+    n_angle, cand, n4), sv (s0, s1, s2 of F) and kept (bool per match: the final inliers in front of both cameras, bit 1 of mask_out).
+    ok applies find_transform's own gates, more than 15 inliers and n_front / n_inl >= 0.7, and requires kind 1; a pair of kind 0 or 2 is
+    reported without a pose (a pose from the homography is not provided)."""
+    ctx = ctx or default_context()
+    blocks, f = _normalised_blocks(K, key_points_for_all, matches_for_all)
+    if not blocks:
+        return []
+    kind, masks, _, _, F, _, _ = ctx.two_view_geometry(blocks, px / f, px_h / f, hypotheses, rounds, seed, min_inliers, hf_ratio)
+    general = [q for q in range(len(blocks)) if kind[q] == 1]
+    out = [dict(ok=False, R=np.full((3, 3), np.nan), t=np.full(3, np.nan), kind=int(kind[q]), counts=dict(n_used=0, n_inl=0, n_front=0, n_angle=0, cand=-1, n4=[0] * 4),
+                sv=np.full(3, np.nan), kept=np.zeros(len(blocks[q]), bool)) for q in range(len(blocks))]
+    if general:
+        pose, info, quality, mo = ctx.relative_pose([blocks[q] for q in general], [masks[q] for q in general], F[general], px / f, pose_rounds, pose_iters,
+                                                    max_depth, min_angle_deg)
+        for j, q in enumerate(general):
+            o, i = out[q], info[j]
+            o["counts"] = dict(n_used=int(i[6]), n_inl=int(i[7]), n_front=int(i[8]), n_angle=int(i[9]), cand=int(i[1]), n4=[int(x) for x in i[2:6]])
+            o["sv"] = quality[j, :3].copy()
+            if i[0] == 1:
+                o["R"] = pose[j, :9].reshape(3, 3).copy(); o["t"] = pose[j, 9:].copy()
+                o["kept"] = (mo[j] & 2) != 0
+                o["ok"] = bool(i[7] > POSE_MIN_INLIERS and i[8] >= POSE_MIN_FRONT * i[7])
+    return out
 
 
 SV_RATIO_MAX = 2.0           # a P whose left block has S0 / S2 above this is not a pose (coplanar points); the measured ranges: DESIGN.md 4c

@@ -41,6 +41,8 @@
 #include "common.hpp"
 #pragma clang fp contract(off)
 #include "ransac.hpp"
+#include "svd3.hpp"
+#include "twoview_rows.hpp"               // THE residual test of F and the clamp of a block's count, shared with relpose.hip
 
 #define HYP_THREADS 64           // hypotheses per workgroup of twoview_hyp_kernel
 #define TWOVIEW_H_MAX 65536
@@ -59,19 +61,6 @@ struct TwoViewState {
 };
 template <class M> __device__ __forceinline__ bool round_dead(const TwoViewState* s) { return s->stop || s->m < M::SAMPLE; }
 
-// THE residual test: scoring, list building and the mask all call this, so the length of a list and the sum of a mask row equal the
-// model's count by construction.  False for a NaN F (an invalid hypothesis).
-__device__ __forceinline__ bool twoview_inlier(const double (&F)[9], double x1, double y1, double x2, double y2, double t2)
-{
-    const double l0 = (F[0] * x1 + F[1] * y1) + F[2];
-    const double l1 = (F[3] * x1 + F[4] * y1) + F[5];
-    const double l2 = (F[6] * x1 + F[7] * y1) + F[8];
-    const double m0 = (F[0] * x2 + F[3] * y2) + F[6];
-    const double m1 = (F[1] * x2 + F[4] * y2) + F[7];
-    const double e = (x2 * l0 + y2 * l1) + l2;
-    const double d = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
-    return e * e <= t2 * d;
-}
 // THE transfer test of the homography model, under the same rule: the squared forward transfer distance against t^2 with the division by
 // w^2 multiplied out.  False for a NaN H.
 __device__ __forceinline__ bool homography_inlier(const double (&Hm)[9], double x1, double y1, double x2, double y2, double t2)
@@ -162,7 +151,6 @@ template <> struct RowIO<PoseRow> {
     static __device__ __forceinline__ PoseRow load(const double* p) { return PoseRow{ p[0], p[1], p[2], p[3], p[4], 0.0 }; }
     static __device__ __forceinline__ bool finite(const PoseRow& r) { return isfinite(r.X) && isfinite(r.Y) && isfinite(r.Z) && isfinite(r.x) && isfinite(r.y); }
 };
-__device__ __forceinline__ int clamp_count(int c, int stride) { return c < 0 ? 0 : (c > stride ? stride : c); }
 
 // ordered compaction inside a workgroup of 256 threads: the number of flagged threads below this one, and how many there are in all.
 // Every thread of the workgroup calls it; sw: four ints of LDS.
@@ -816,53 +804,19 @@ int sfmhip_register_views(sfmhip_ctx* ctx, const double* corr, int stride, const
                          GeomOut{ mask, count_out, P, winner, nullptr, nullptr, nullptr, nullptr, nullptr });
 }
 
-// Pure host code: the SVD of the left 3 x 3 block by one-sided Jacobi rotations (Hestenes), which finds the small singular value of a
-// planar DLT to its own precision where an eigen-solver on M^T M would square the ratio away.
+// Pure host code: the SVD of the left 3 x 3 block by the one-sided Jacobi rotations of svd3.hpp (Hestenes), which find the small singular
+// value of a planar DLT to its own precision where an eigen-solver on M^T M would square the ratio away.
 int sfmhip_pose_from_projection(const double P[12], double R[9], double t[3], double* sv_ratio)
 {
     if (!P || !R || !t || !sv_ratio) return SFMHIP_E_ARG;
     for (int j = 0; j < 12; ++j)
         if (!std::isfinite(P[j])) return SFMHIP_E_NUMERIC;
-    double U[3][3], V[3][3] = { { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 } };
+    double M[3][3], u[3][3], v[3][3], S[3];                             // columns in descending order of the singular values
     for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) U[i][j] = P[4 * i + j];
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double a = 0, b = 0, c = 0;
-                for (int i = 0; i < 3; ++i) { a += U[i][p] * U[i][p]; b += U[i][q] * U[i][q]; c += U[i][p] * U[i][q]; }
-                if (c == 0.0 || std::fabs(c) <= 1e-16 * std::sqrt(a * b)) continue;
-                rotated = true;
-                const double zeta = (b - a) / (2.0 * c);
-                const double tn = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / std::sqrt(1.0 + tn * tn), sn = cs * tn;
-                for (int i = 0; i < 3; ++i) {
-                    const double up = U[i][p], uq = U[i][q], vp = V[i][p], vq = V[i][q];
-                    U[i][p] = cs * up - sn * uq; U[i][q] = sn * up + cs * uq;
-                    V[i][p] = cs * vp - sn * vq; V[i][q] = sn * vp + cs * vq;
-                }
-            }
-        if (!rotated) break;
-    }
-    double S[3];
-    int ord[3] = { 0, 1, 2 };
-    for (int j = 0; j < 3; ++j) S[j] = std::sqrt(U[0][j] * U[0][j] + U[1][j] * U[1][j] + U[2][j] * U[2][j]);
-    for (int a = 0; a < 2; ++a)
-        for (int b = a + 1; b < 3; ++b)
-            if (S[ord[b]] > S[ord[a]]) std::swap(ord[a], ord[b]);
-    const double s0 = S[ord[0]], s1 = S[ord[1]], s2 = S[ord[2]];
+        for (int j = 0; j < 3; ++j) M[i][j] = P[4 * i + j];
+    svd3::jacobi(M, u, v, S);
+    const double s0 = S[0], s1 = S[1], s2 = S[2];
     if (!(s0 > 0.0) || !(s1 > 0.0) || !std::isfinite(s0)) return SFMHIP_E_NUMERIC;                     // rank below two: no rotation to speak of
-    double u[3][3], v[3][3];                                            // columns in descending order of the singular values
-    for (int j = 0; j < 3; ++j)
-        for (int i = 0; i < 3; ++i) { u[i][j] = S[ord[j]] > 0.0 ? U[i][ord[j]] / S[ord[j]] : 0.0; v[i][j] = V[i][ord[j]]; }
-    if (!(s2 > 1e-15 * s0)) {                                           // rank two: the third left vector completes the other two
-        const double sgn = (v[0][0] * (v[1][1] * v[2][2] - v[2][1] * v[1][2]) - v[1][0] * (v[0][1] * v[2][2] - v[2][1] * v[0][2]) +
-                            v[2][0] * (v[0][1] * v[1][2] - v[1][1] * v[0][2])) < 0 ? -1.0 : 1.0;
-        u[0][2] = sgn * (u[1][0] * u[2][1] - u[2][0] * u[1][1]);
-        u[1][2] = sgn * (u[2][0] * u[0][1] - u[0][0] * u[2][1]);
-        u[2][2] = sgn * (u[0][0] * u[1][1] - u[1][0] * u[0][1]);
-    }
     double Rm[9];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) Rm[3 * i + j] = (u[i][0] * v[j][0] + u[i][1] * v[j][1]) + u[i][2] * v[j][2];

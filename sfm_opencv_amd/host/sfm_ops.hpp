@@ -307,6 +307,86 @@ inline int two_view_geometry_for_all(const Mat& K, const std::vector<std::vector
     return 0;
 }
 
+// ---- find_transform (NView:1022-1060) for every consecutive pair on the device: two_view_geometry_for_all as above (the lists are
+// filtered in the same way, kind / counts / counts2 mean the same), and then sfmhip_relative_pose (where the definition is) on the pairs of
+// kind 1 with F's inlier mask and F, both calls over all pairs at once.  poses[i]: ok applies find_transform's own gates (more than 15
+// inliers, n_front / n_inl >= 0.7) and requires kind 1; a pair of kind 0 or 2 is reported without a pose (reason says why).  kept is a
+// flag per match of the list AS IT CAME IN, set for the final inliers in front of both cameras (bit 1 of mask_out), and matches those
+// elements in their order: the re-taken set is usually larger than the RANSAC's.  Returns 0, -1 on error.
+struct RelativePose {
+    bool ok = false; const char* reason = ""; int kind = 0; Mat R, T;
+    int cand = -1, n4[4] = { 0, 0, 0, 0 }, n_used = 0, n_inl = 0, n_front = 0, n_angle = 0;
+    double sv[3] = { std::nan(""), std::nan(""), std::nan("") };
+    std::vector<uint8_t> kept; std::vector<DMatch> matches;
+};
+inline int relative_pose_for_all(const Mat& K, const std::vector<std::vector<KeyPoint>>& key_points_for_all,
+                                 std::vector<std::vector<DMatch>>& matches_for_all, std::vector<int32_t>& kind, std::vector<int32_t>& counts,
+                                 std::vector<int32_t>& counts2, std::vector<RelativePose>& poses, const double px = 1.0, const double px_h = 2.0,
+                                 const int hypotheses = 1024, const int rounds = 3, const double hf_ratio = 0.8, const int min_inliers = 15,
+                                 const uint64_t seed = 0, const int pose_rounds = 3, const int pose_iters = 10, const double max_depth = 50.0,
+                                 const double min_angle_deg = 2.0)
+{
+    const int n_pairs = (int)matches_for_all.size();
+    kind.assign((size_t)n_pairs, 0); counts.assign((size_t)n_pairs, 0); counts2.assign((size_t)n_pairs * 2, 0);
+    poses.assign((size_t)n_pairs, RelativePose());
+    sfmhip_ctx* ctx = context();
+    if (!ctx || (int)key_points_for_all.size() < n_pairs + 1) return -1;
+    if (n_pairs == 0) return 0;
+    const double f = 0.5 * (K.at<double>(0, 0) + K.at<double>(1, 1));
+    size_t stride = 0;
+    std::vector<double> corr, F((size_t)n_pairs * 9), pose((size_t)n_pairs * 12), quality((size_t)n_pairs * 5);
+    std::vector<int32_t> rows, info((size_t)n_pairs * 10);
+    pair_rows_for_all(K, key_points_for_all, matches_for_all, corr, rows, stride);
+    std::vector<uint8_t> mask((size_t)n_pairs * stride, 0), mask_out((size_t)n_pairs * stride, 0);
+    if (sfmhip_two_view_geometry(ctx, corr.data(), (int)stride, rows.data(), n_pairs, px / f, px_h / f, hypotheses, rounds, seed, min_inliers, hf_ratio,
+                                 kind.data(), mask.data(), counts.data(), counts2.data(), F.data(), nullptr, nullptr) != SFMHIP_OK) {
+        printf("[Err]: relative_pose_for_all: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    // a pair of another kind gets no pose: without rows it ends with status 0
+    std::vector<int32_t> pose_rows(rows);
+    for (int i = 0; i < n_pairs; ++i)
+        if (kind[(size_t)i] != 1) pose_rows[(size_t)i] = 0;
+    if (sfmhip_relative_pose(ctx, corr.data(), (int)stride, pose_rows.data(), n_pairs, mask.data(), F.data(), px / f, pose_rounds, pose_iters, max_depth,
+                             min_angle_deg * 3.14159265358979323846 / 180.0, pose.data(), info.data(), quality.data(), mask_out.data()) != SFMHIP_OK) {
+        printf("[Err]: relative_pose_for_all: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    for (int i = 0; i < n_pairs; ++i) {
+        auto& m = matches_for_all[(size_t)i];
+        RelativePose& p = poses[(size_t)i];
+        const int32_t* in = &info[10 * (size_t)i];
+        p.kind = kind[(size_t)i];
+        p.kept.assign(m.size(), 0);
+        if (p.kind != 1) p.reason = p.kind == 2 ? "planar or panoramic" : "no two-view model";
+        else {
+            p.cand = in[1]; p.n_used = in[6]; p.n_inl = in[7]; p.n_front = in[8]; p.n_angle = in[9];
+            for (int k = 0; k < 4; ++k) p.n4[k] = in[2 + k];
+            for (int k = 0; k < 3; ++k) p.sv[k] = quality[5 * (size_t)i + k];
+            if (in[0] != 1) p.reason = "no candidate has a match in front";
+            else {
+                p.R = Mat(3, 3, CV_64F); p.T = Mat(3, 1, CV_64F);
+                std::copy(&pose[12 * (size_t)i], &pose[12 * (size_t)i] + 9, p.R.ptr<double>());
+                std::copy(&pose[12 * (size_t)i] + 9, &pose[12 * (size_t)i] + 12, p.T.ptr<double>());
+                for (size_t k = 0; k < m.size(); ++k)
+                    if (mask_out[(size_t)i * stride + k] & 2) { p.kept[k] = 1; p.matches.push_back(m[k]); }
+                if (p.n_inl <= 15) p.reason = "15 inliers or fewer";
+                else if ((double)p.n_front < 0.7 * (double)p.n_inl) p.reason = "fewer than 0.7 of the inliers in front";
+                else p.ok = true;
+            }
+        }
+        if (kind[(size_t)i] == 0) {
+            printf("[Warning]: pair %d: no two-view model with %d matches, the %zu matches are kept as they are.\n", i, min_inliers, m.size());
+            continue;
+        }
+        if (kind[(size_t)i] == 2)
+            printf("[Warning]: pair %d: planar or panoramic (H explains %d matches, F %d): its two-view pose is ill-determined.\n", i,
+                   (int)counts2[2 * (size_t)i + 1], (int)counts2[2 * (size_t)i]);
+        keep_masked(m, mask.data() + (size_t)i * stride);
+    }
+    return 0;
+}
+
 inline void get_matched_points(const std::vector<KeyPoint>& p1, const std::vector<KeyPoint>& p2, const std::vector<DMatch> matches,
                                std::vector<Point2f>& out_p1, std::vector<Point2f>& out_p2)
 {

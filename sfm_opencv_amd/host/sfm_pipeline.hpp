@@ -253,7 +253,17 @@ struct PipelineOptions {
     double pnp_px = -1.0;                  // >= 0: frame i is registered on the device (register_views_for_all; extension) within this many pixels, the host solvePnPRansac only where that gives no pose
     int    pnp_h = 1024;                   // ... hypotheses per round
     int    pnp_rounds = 3;                 // ... rounds
+    int    pose_rounds = -1;               // >= 0: with geometry_px, the pose of the first pair comes from the device (relative_pose_for_all; extension): rounds of its refinement; find_transform only where that gives no usable pose
+    int    pose_iters = 10;                // ... Levenberg-Marquardt iterations per round
 };
+
+// the first pair's pose from relative_pose_for_all, or the message that find_transform runs instead; true: p holds a usable pose
+inline bool device_pose_or_fallback(const RelativePose& p, const size_t n_matches)
+{
+    if (p.ok) printf("pair 0: pose on device, kept %zu of %zu, %d in front, %d with parallax\n", p.matches.size(), n_matches, p.n_front, p.n_angle);
+    else printf("pair 0: device pose rejected (%s), host fallback\n", p.reason);
+    return p.ok;
+}
 
 // main() of NViewReconstuct.cpp from "match_features_for_all" on (NView:1369-1517)
 inline int run_nview(Features& f, const PipelineOptions& opt)
@@ -263,6 +273,7 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
     std::vector<std::vector<DMatch>> matches_for_all;
     match_features_for_all(f.descriptor_for_all, matches_for_all, opt.cross_check);
     if (matches_for_all.empty()) { printf("[Err]: fewer than two usable images.\n"); return -1; }
+    const size_t first_pair_size = matches_for_all[0].size();
     if (opt.verify_px >= 0.0) {
         // 15: the gate find_transform puts on the inliers of findEssentialMat (NView:1042)
         std::vector<size_t> before;
@@ -271,12 +282,17 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
         if (verify_matches_for_all(K, kpts_for_all, matches_for_all, kept, opt.verify_px, opt.verify_h, opt.verify_rounds, 15) < 0) return -1;
         for (size_t i = 0; i < before.size(); ++i) printf("pair %zu: verified %d of %zu\n", i, (int)kept[i], before[i]);
     }
+    std::vector<RelativePose> device_poses;
     if (opt.geometry_px >= 0.0) {
         std::vector<size_t> before;
         for (const auto& m : matches_for_all) before.push_back(m.size());
         std::vector<int32_t> kind, kept, both;
-        if (two_view_geometry_for_all(K, kpts_for_all, matches_for_all, kind, kept, both, opt.geometry_px, opt.geometry_px_h, opt.geometry_h,
-                                      opt.geometry_rounds, opt.geometry_ratio, 15) < 0) return -1;
+        if (opt.pose_rounds >= 0) {
+            if (relative_pose_for_all(K, kpts_for_all, matches_for_all, kind, kept, both, device_poses, opt.geometry_px, opt.geometry_px_h, opt.geometry_h,
+                                      opt.geometry_rounds, opt.geometry_ratio, 15, 0, opt.pose_rounds, opt.pose_iters) < 0) return -1;
+        }
+        else if (two_view_geometry_for_all(K, kpts_for_all, matches_for_all, kind, kept, both, opt.geometry_px, opt.geometry_px_h, opt.geometry_h,
+                                           opt.geometry_rounds, opt.geometry_ratio, 15) < 0) return -1;
         static const char* const names[3] = { "none", "general", "planar-or-panoramic" };
         for (size_t i = 0; i < before.size(); ++i)
             printf("pair %zu: geometry %s, kept %d of %zu (F %d, H %d)\n", i, names[kind[i]], (int)kept[i], before[i], (int)both[2 * i], (int)both[2 * i + 1]);
@@ -288,8 +304,13 @@ inline int run_nview(Features& f, const PipelineOptions& opt)
     std::vector<Mat> rotations, translations;
 
     printf("\nConstruct from the first two frames...\n");
-    const int ret = init_structure(K, kpts_for_all, colors_for_all, matches_for_all, pts3d, inds_2d_to_3d, colors, rotations, translations,
-                                   opt.poses_from_file ? &f.file_rotations[1] : nullptr, opt.poses_from_file ? &f.file_motions[1] : nullptr);
+    const Mat *first_R = opt.poses_from_file ? &f.file_rotations[1] : nullptr, *first_T = opt.poses_from_file ? &f.file_motions[1] : nullptr;
+    if (!opt.poses_from_file && !device_poses.empty() && device_pose_or_fallback(device_poses[0], first_pair_size)) {
+        // the pose and the kept matches of the first pair come from the device call; init_structure keeps every match it is given
+        matches_for_all[0] = device_poses[0].matches;
+        first_R = &device_poses[0].R; first_T = &device_poses[0].T;
+    }
+    const int ret = init_structure(K, kpts_for_all, colors_for_all, matches_for_all, pts3d, inds_2d_to_3d, colors, rotations, translations, first_R, first_T);
     if (ret < 0) return ret;
     if (opt.poses_from_file) { rotations[0] = f.file_rotations[0]; translations[0] = f.file_motions[0]; }
 
@@ -442,9 +463,21 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
     std::vector<uint8_t> mv;
     if (opt.poses_from_file) { R = f.file_rotations[1]; T = f.file_motions[1]; mv.assign(p1.size(), 1); }
     else {
-        find_transform(f.K, p1, p2, R, T, mask);
-        if (R.empty() || T.empty()) { printf("[Err]: no transform between the two frames.\n"); return -1; }
-        mv = mask_vector(mask);
+        bool on_device = false;
+        if (opt.geometry_px >= 0.0 && opt.pose_rounds >= 0) {
+            std::vector<std::vector<DMatch>> chain = { matches };
+            std::vector<int32_t> kind, kept, both;
+            std::vector<RelativePose> poses;
+            if (relative_pose_for_all(f.K, f.key_points_for_all, chain, kind, kept, both, poses, opt.geometry_px, opt.geometry_px_h, opt.geometry_h,
+                                      opt.geometry_rounds, opt.geometry_ratio, 15, 0, opt.pose_rounds, opt.pose_iters) < 0) return -1;
+            on_device = device_pose_or_fallback(poses[0], matches.size());
+            if (on_device) { R = poses[0].R; T = poses[0].T; mv = poses[0].kept; }
+        }
+        if (!on_device) {
+            find_transform(f.K, p1, p2, R, T, mask);
+            if (R.empty() || T.empty()) { printf("[Err]: no transform between the two frames.\n"); return -1; }
+            mv = mask_vector(mask);
+        }
     }
     Mat structure;                                           // 4 x N, homogeneous
     maskout_2d_pts_pair(mv, p1, p2);
@@ -460,7 +493,7 @@ inline int run_twoview(Features& f, const PipelineOptions& opt)
 inline int driver_main(int argc, char** argv, bool nview)
 {
     if (argc < 2 || std::string(argv[1]).empty()) {
-        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--sift-device] [--akaze-device] [--jpeg-device] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]] [--two-view-geometry[=PX[,PXH[,H[,ROUNDS[,RATIO]]]]]] [--pnp-device[=PX[,H[,ROUNDS]]]]\n", argv[0]);
+        printf("[Warning]: empty dataset path.\nusage: %s <image directory (.jpg | .ppm | .pgm, K.txt beside them) | features file> [output dir = ../Viewer] [--poses-from-file] [--write-back-poses] [--quiet] [--akaze | --sift] [--sift-device] [--akaze-device] [--jpeg-device] [--gpus=DEV,DEV,...] [--max-features=N] [--save-features=FILE] [--features-only] [--refine[=PX]] [--cross-check] [--filter-outliers[=RATIO]] [--radius-outliers=R[,MIN]] [--largest-cluster=R[,MIN_POINTS]] [--voxel-size=H] [--planes=T[,MAX[,MIN_INLIERS]]] [--verify-matches[=PX[,H[,ROUNDS]]]] [--two-view-geometry[=PX[,PXH[,H[,ROUNDS[,RATIO]]]]]] [--pnp-device[=PX[,H[,ROUNDS]]]] [--pose-device[=ROUNDS[,ITERS]]]\n", argv[0]);
         return 0;
     }
     PipelineOptions opt;
@@ -540,6 +573,12 @@ inline int driver_main(int argc, char** argv, bool nview)
                 if (c2 != std::string::npos) opt.pnp_rounds = std::atoi(a.c_str() + c2 + 1);
             }
         }
+        else if (a == "--pose-device") opt.pose_rounds = 3;
+        else if (a.rfind("--pose-device=", 0) == 0) {            // ROUNDS[,ITERS]: with --two-view-geometry, the pose of the first pair is decomposed from its F, voted and refined on the device in ROUNDS (3) rounds of at most ITERS (10) iterations; find_transform runs only where that gives no usable pose
+            opt.pose_rounds = std::atoi(a.c_str() + 14);
+            const size_t c1 = a.find(',', 14);
+            if (c1 != std::string::npos) opt.pose_iters = std::atoi(a.c_str() + c1 + 1);
+        }
         else if (a.rfind("--save-features=", 0) == 0) opt.save_features = a.substr(16);
         else if (positional++ == 0) opt.out_dir = a;
     }
@@ -547,6 +586,8 @@ inline int driver_main(int argc, char** argv, bool nview)
         printf("[Err]: --jpeg-device needs the extractor on the device (--sift --sift-device, or --akaze --akaze-device).\n");
         return 1;
     }
+    if (opt.pose_rounds >= 0 && opt.geometry_px < 0.0) { printf("[Err]: --pose-device needs --two-view-geometry: the pose is taken from that call's F and inliers.\n"); return 1; }
+    if (opt.pose_rounds > 8 || opt.pose_iters < 0 || opt.pose_iters > 50) { printf("[Err]: --pose-device=ROUNDS[,ITERS]: ROUNDS 0..8, ITERS 0..50.\n"); return 1; }
     if (opt.verify_px >= 0.0 && opt.geometry_px >= 0.0) { printf("[Err]: --verify-matches and --two-view-geometry exclude each other.\n"); return 1; }
     Features f;
     if (is_directory(argv[1])) {
