@@ -898,6 +898,91 @@ int sfmhip_jpeg_info      (const uint8_t* bytes, size_t n, int* rows, int* cols,
 int sfmhip_jpeg_decode    (sfmhip_ctx*, const uint8_t* bytes, size_t n, int entropy, uint8_t* img,   size_t ld);
 int sfmhip_jpeg_decode_dev(sfmhip_ctx*, const uint8_t* bytes, size_t n, int entropy, uint8_t* d_img, size_t ld, int32_t* d_status);   /* enqueue only */
 
+/* ------------------------------------------------------------------------------------------ */
+/* Dense depth: plane-sweep stereo of calibrated images, a consistency check between the depth  */
+/* maps of neighbouring views, and the kept pixels as coloured world points (what colmap does   */
+/* in patch_match_stereo + stereo_fusion and OpenMVG leaves to OpenMVS; no reference            */
+/* counterpart, the reference stops at the sparse cloud).  Again the definition.  Everything    */
+/* expensive is integer arithmetic: the samples are fixed-point integers and the window sums    */
+/* are exact, so no result depends on the order of a sum and an implementation may tile, sum    */
+/* separably or keep running sums and still give these bits.  The float and double operations   */
+/* are prescribed one by one (no contraction, division and sqrt correctly rounded).  A result   */
+/* is a function of its inputs alone: the same bytes for every run and every launch geometry.   */
+/* ------------------------------------------------------------------------------------------ */
+/* Geometry (host only, no context).  Poses are the bundle adjustment's: ext6 = (angle-axis w, t), world to camera, x_cam = R(w) X + t
+ *   (NView:151-183), one shared K4 = (fx, fy, cx, cy).  For the reference view r and each source s of n_src (0 .. 8):
+ *     Rrel = R_s R_r^T,  trel = t_s - Rrel t_r            (n_src x 9 row-major, n_src x 3, double):  x_s = Rrel x_r + trel
+ *     A = K Rrel K^-1,   b = K trel                        (n_src x 9, n_src x 3), computed in double and rounded to float
+ *     Rinv = R_r^T,      c = -R_r^T t_r                    (X_world = Rinv x_r + c)
+ *   A reference pixel (u, v) at inverse depth w is seen in s at the pixel ~ A (u, v, 1)^T + w b.  Any output may be NULL.
+ *   SFMHIP_E_ARG with the outputs left alone: a null K4 or ext6_ref, n_src out of range, a null ext6_src with n_src > 0, a K4 that
+ *   is not finite or has a zero focal length.  The other entries take these arrays, not poses. */
+int sfmhip_sweep_geometry(const double K4[4], const double ext6_ref[6], const double* ext6_src, int n_src, float* A, float* b,
+                          double* Rrel, double* trel, double Rinv[9], double c[3]);
+
+/* Stage 1, the plane sweep.
+ *   Input: the reference image and n_src (1 .. 8) source images, all rows x cols x channels bytes (channels 1 = gray, 3 = BGR), row
+ *     stride ld bytes (>= cols*channels; bytes of a row past cols*channels change nothing), rows and cols at most 16384; src: n_src
+ *     pointers.  A, b: n_src x 9 and n_src x 3 float from the geometry call -- HOST arrays in both forms, they travel as launch
+ *     arguments.  D planes, 2 <= D <= 4096; wmin < wmax, inverse depths, positive and finite; the window radius r, 0 <= r <= 5;
+ *     min_sources >= 1; min_score (not NaN).
+ *   Gray: g = (1868*B + 9617*G + 4899*R + 8192) >> 14 for BGR, the byte itself for gray.
+ *   Planes, fronto-parallel in the reference camera: in double step = (wmax - wmin)/(D - 1), w_k = wmin + k*step; wf_k = (float)w_k.
+ *   Warp of the reference pixel (u, v) (as floats) into source s at plane k, in float and in this order, i = 0 .. 2:
+ *       q_i = (A[3i]*u + A[3i+1]*v) + (A[3i+2] + wf_k*b[i]);   sx = q_0/q_2;   sy = q_1/q_2.
+ *     The pixel is GOOD when q_2 > 0 && sx >= 0 && sy >= 0 && sx < cols-1 && sy < rows-1 (a NaN is not good).
+ *   Sample: x0 = floor(sx), fx = (int)floor((sx - x0)*32) (both float operations are exact), y0 and fy likewise;
+ *       smp = (g[y0][x0]*(32-fx)*(32-fy) + g[y0][x0+1]*fx*(32-fy) + g[y0+1][x0]*(32-fx)*fy + g[y0+1][x0+1]*fx*fy + 32) >> 6,
+ *     an integer in [0, 4080], sixteen times a gray value.  The reference's value at a pixel is 16*g.
+ *   Score of source s at (u, v, k): over the (2r+1)^2 pixels of the window around (u, v), n = (2r+1)^2, the exact integer sums Sr, Srr
+ *     (reference values and their squares), Sw, Sww (samples), Srw (products); in 64-bit integers vr = n*Srr - Sr*Sr,
+ *     vw = n*Sww - Sw*Sw, cov = n*Srw - Sr*Sw.  The source COUNTS when the window lies inside the image, every pixel of it is good,
+ *     vr > 0 and vw > 0; its score is then the double (double)cov / sqrt((double)vr * (double)vw).  (r = 0: vr = 0, nothing counts.)
+ *   Score of plane k: SCORED when at least min_sources sources count; c_k = (the sum of their scores from 0.0 in ascending s) / (their
+ *     number as a double).  The winner is the scored k with the largest c_k, the smallest k among equals.
+ *   No scored plane, or a winner with c_k < min_score: plane = -1, score = depth = NaN.
+ *   Sub-plane fit: where 0 < k < D-1, both neighbours are scored and den = (c_{k-1} - 2.0*c_k) + c_{k+1} < 0:
+ *       w = w_k + ((0.5*(c_{k-1} - c_{k+1})) / den) * step,   else w = w_k;   depth = (float)(1.0/w),  score = (float)c_k.
+ *   Output per pixel, rows x cols dense: plane int32, score float, depth float.
+ *   SFMHIP_E_ARG with the outputs left alone: a null pointer (an entry of src included), a size, D, r, n_src or min_sources out of range,
+ *     channels not 1 or 3, ld < cols*channels, wmin or wmax not positive and finite, wmin >= wmax, a NaN min_score.  An image smaller
+ *     than the window is not an error: every pixel is -1.
+ *   Device memory: (n_src + 1) * rows * cols bytes of gray planes from the context's block cache. */
+int sfmhip_plane_sweep    (sfmhip_ctx*, const uint8_t* ref,   const uint8_t* const* src,   int n_src, int rows, int cols, int channels, size_t ld,
+                           const float* A, const float* b, int D, double wmin, double wmax, int r, int min_sources, double min_score,
+                           int32_t* plane,   float* score,   float* depth);
+/* the same on resident images (src: a HOST array of n_src device pointers), enqueued on the context's stream; never synchronises */
+int sfmhip_plane_sweep_dev(sfmhip_ctx*, const uint8_t* d_ref, const uint8_t* const* d_src, int n_src, int rows, int cols, int channels, size_t ld,
+                           const float* A, const float* b, int D, double wmin, double wmax, int r, int min_sources, double min_score,
+                           int32_t* d_plane, float* d_score, float* d_depth);
+
+/* Stage 2, consistency.  depth: the depth map of a view (rows x cols float, NaN = none); depth_src: n_src (1 .. 8) pointers to the depth
+ *   maps of other views of the same size, each swept with that view as its reference; K4, Rrel, trel (host arrays in both forms) from
+ *   the geometry call with this view as the reference; rel_tol finite and >= 0; min_consistent >= 0.
+ *   For a pixel (u, v) with a finite depth d and every source s, in double and in this order:
+ *       X0 = ((u - cx)/fx)*d;  X1 = ((v - cy)/fy)*d;  X2 = d;      Y_i = ((R[3i]*X0 + R[3i+1]*X1) + R[3i+2]*X2) + t[i]   (R = Rrel, t = trel of s)
+ *       Y_2 > 0;   pu = floor(((fx*Y_0)/Y_2 + cx) + 0.5),  pv = floor(((fy*Y_1)/Y_2 + cy) + 0.5),  0 <= pu < cols and 0 <= pv < rows;
+ *       d_s = depth_s[pv][pu] finite;   |d_s - Y_2| <= rel_tol*Y_2.
+ *   count (uint8): the sources that pass all of it (0 for a pixel without a depth); keep (uint8, 0 / 1): the depth is finite and
+ *   count >= min_consistent.  Either output may be NULL, not both.  SFMHIP_E_ARG with the outputs left alone: a null input, sizes or
+ *   n_src out of range, rel_tol negative or not finite, min_consistent < 0. */
+int sfmhip_depth_consistency    (sfmhip_ctx*, const float* depth,   const float* const* depth_src,   int n_src, int rows, int cols, const double K4[4],
+                                 const double* Rrel, const double* trel, double rel_tol, int min_consistent, uint8_t* count,   uint8_t* keep);
+int sfmhip_depth_consistency_dev(sfmhip_ctx*, const float* d_depth, const float* const* d_depth_src, int n_src, int rows, int cols, const double K4[4],
+                                 const double* Rrel, const double* trel, double rel_tol, int min_consistent, uint8_t* d_count, uint8_t* d_keep);   /* enqueue only */
+
+/* Stage 3, export.  The pixels whose keep byte is non-zero, in row-major order (a prefix sum places them; no atomic decides an order):
+ *       xyz_i = ((Rinv[3i]*X0 + Rinv[3i+1]*X1) + Rinv[3i+2]*X2) + c[i]   with X of stage 2, in double: world points, n x 3 double, what
+ *   sfmhip_voxel_downsample, sfmhip_estimate_normals and the .ply writer take; bgr (n x 3 bytes): the pixel of img (as the images of stage
+ *   1; gray is replicated).  *n_found: the full count; only the first min(*n_found, cap) rows are written, nothing past them is touched.
+ *   xyz or bgr may be NULL (img too when bgr is).  K4, Rinv, c: host arrays in both forms.  The _dev form writes *d_n_found on the device.
+ *   SFMHIP_E_ARG with the outputs left alone: a null depth, keep, K4, Rinv, c or n_found, sizes out of range, channels not 1 or 3,
+ *   ld < cols*channels, cap < 0, bgr without img, cap > 0 with neither xyz nor bgr. */
+int sfmhip_depth_to_points    (sfmhip_ctx*, const float* depth,   const uint8_t* keep,   const uint8_t* img,   int rows, int cols, int channels, size_t ld,
+                               const double K4[4], const double Rinv[9], const double c[3], double* xyz,   uint8_t* bgr,   int cap, int32_t* n_found);
+int sfmhip_depth_to_points_dev(sfmhip_ctx*, const float* d_depth, const uint8_t* d_keep, const uint8_t* d_img, int rows, int cols, int channels, size_t ld,
+                               const double K4[4], const double Rinv[9], const double c[3], double* d_xyz, uint8_t* d_bgr, int cap, int32_t* d_n_found);   /* enqueue only */
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,8 @@ SYMBOLS = [
     "sfmhip_sift_extract", "sfmhip_sift_extract_dev", "sfmhip_sift_scale_space", "sfmhip_sift_extrema",
     "sfmhip_akaze_extract", "sfmhip_akaze_extract_dev", "sfmhip_akaze_scale_space", "sfmhip_akaze_extrema", "sfmhip_akaze_suppress",
     "sfmhip_jpeg_info", "sfmhip_jpeg_decode", "sfmhip_jpeg_decode_dev",
+    "sfmhip_sweep_geometry", "sfmhip_plane_sweep", "sfmhip_plane_sweep_dev", "sfmhip_depth_consistency", "sfmhip_depth_consistency_dev",
+    "sfmhip_depth_to_points", "sfmhip_depth_to_points_dev",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -207,6 +209,13 @@ def load():
         "sfmhip_jpeg_info": (i32, [vp, sz, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "sfmhip_jpeg_decode": (i32, [vp, vp, sz, i32, vp, sz]),
         "sfmhip_jpeg_decode_dev": (i32, [vp, vp, sz, i32, vp, sz, vp]),
+        "sfmhip_sweep_geometry": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_plane_sweep": (i32, [vp, vp, C.POINTER(vp), i32, i32, i32, i32, sz, vp, vp, i32, f64, f64, i32, i32, f64, vp, vp, vp]),
+        "sfmhip_plane_sweep_dev": (i32, [vp, vp, C.POINTER(vp), i32, i32, i32, i32, sz, vp, vp, i32, f64, f64, i32, i32, f64, vp, vp, vp]),
+        "sfmhip_depth_consistency": (i32, [vp, vp, C.POINTER(vp), i32, i32, i32, vp, vp, vp, f64, i32, vp, vp]),
+        "sfmhip_depth_consistency_dev": (i32, [vp, vp, C.POINTER(vp), i32, i32, i32, vp, vp, vp, f64, i32, vp, vp]),
+        "sfmhip_depth_to_points": (i32, [vp, vp, vp, vp, i32, i32, i32, sz, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int32)]),
+        "sfmhip_depth_to_points_dev": (i32, [vp, vp, vp, vp, i32, i32, i32, sz, vp, vp, vp, vp, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -805,6 +805,79 @@ class Context:
         self._check(self.lib.sfmhip_jpeg_decode_dev(self.h, buf.ctypes.data, buf.size, int(entropy), _dptr(img), cols * ch, _dptr(status)))
         return img, status
 
+    # ---------------------------------------------------------------- dense depth (sfmhip_plane_sweep and what follows it)
+    def sweep_geometry(self, K4, ext_ref, ext_src):
+        """(A float32 n x 9, b float32 n x 3, Rrel n x 9, trel n x 3, Rinv 9, c 3) of sfmhip_sweep_geometry: what the three dense stages
+        take instead of poses.  ext: the bundle adjustment's (angle-axis, t) rows; host only"""
+        return sweep_geometry(K4, ext_ref, ext_src)
+
+    def plane_sweep(self, ref, srcs, A, b, planes, wmin, wmax, radius=2, min_sources=1, min_score=0.0):
+        """(plane int32, score float32, depth float32), each rows x cols: sfmhip_plane_sweep (where the definition is) of the reference
+        image against the source images (uint8 rows x cols or rows x cols x 3 BGR; rows of a padded buffer may be passed as a view)"""
+        imgs, ptrs, rows, cols, ch, ld = _dense_images([ref] + list(srcs))
+        n = len(imgs) - 1
+        A = np.ascontiguousarray(A, np.float32).reshape(n, 9); b = np.ascontiguousarray(b, np.float32).reshape(n, 3)
+        plane = np.empty((rows, cols), np.int32); score = np.empty((rows, cols), np.float32); depth = np.empty((rows, cols), np.float32)
+        src = (C.c_void_p * max(n, 1))(*ptrs[1:])
+        self._check(self.lib.sfmhip_plane_sweep(self.h, ptrs[0], src, n, rows, cols, ch, ld, A.ctypes.data, b.ctypes.data, int(planes), float(wmin), float(wmax),
+                                                int(radius), int(min_sources), float(min_score), plane.ctypes.data, score.ctypes.data, depth.ctypes.data))
+        return plane, score, depth
+
+    def plane_sweep_dev(self, d_ref, d_srcs, rows, cols, channels, ld, A, b, planes, wmin, wmax, radius, min_sources, min_score, d_plane, d_score, d_depth):
+        """the same on resident images (torch CUDA tensors or device addresses; A and b stay host arrays): enqueues on the context's
+        stream, never synchronises"""
+        n = len(d_srcs)
+        A = np.ascontiguousarray(A, np.float32).reshape(n, 9); b = np.ascontiguousarray(b, np.float32).reshape(n, 3)
+        src = (C.c_void_p * max(n, 1))(*[_dptr(x) for x in d_srcs])
+        self._check(self.lib.sfmhip_plane_sweep_dev(self.h, _dptr(d_ref), src, n, int(rows), int(cols), int(channels), int(ld), A.ctypes.data, b.ctypes.data,
+                                                    int(planes), float(wmin), float(wmax), int(radius), int(min_sources), float(min_score), _dptr(d_plane),
+                                                    _dptr(d_score), _dptr(d_depth)))
+
+    def depth_consistency(self, depth, depth_srcs, K4, Rrel, trel, rel_tol=0.01, min_consistent=1):
+        """(count uint8, keep uint8), each rows x cols: sfmhip_depth_consistency of a view's depth map against those of its sources"""
+        maps = [np.ascontiguousarray(d, np.float32) for d in [depth] + list(depth_srcs)]
+        rows, cols = maps[0].shape
+        if any(m.shape != (rows, cols) for m in maps):
+            raise ValueError("the depth maps differ in size")
+        n = len(maps) - 1
+        K4 = np.ascontiguousarray(K4, np.float64).reshape(4); Rrel = np.ascontiguousarray(Rrel, np.float64).reshape(n, 9)
+        trel = np.ascontiguousarray(trel, np.float64).reshape(n, 3)
+        count = np.empty((rows, cols), np.uint8); keep = np.empty((rows, cols), np.uint8)
+        src = (C.c_void_p * max(n, 1))(*[m.ctypes.data for m in maps[1:]])
+        self._check(self.lib.sfmhip_depth_consistency(self.h, maps[0].ctypes.data, src, n, rows, cols, K4.ctypes.data, Rrel.ctypes.data, trel.ctypes.data,
+                                                      float(rel_tol), int(min_consistent), count.ctypes.data, keep.ctypes.data))
+        return count, keep
+
+    def depth_consistency_dev(self, d_depth, d_depth_srcs, rows, cols, K4, Rrel, trel, rel_tol, min_consistent, d_count, d_keep):
+        """the same on resident depth maps (K4, Rrel, trel stay host arrays): enqueues only"""
+        n = len(d_depth_srcs)
+        K4 = np.ascontiguousarray(K4, np.float64).reshape(4); Rrel = np.ascontiguousarray(Rrel, np.float64).reshape(n, 9)
+        trel = np.ascontiguousarray(trel, np.float64).reshape(n, 3)
+        src = (C.c_void_p * max(n, 1))(*[_dptr(x) for x in d_depth_srcs])
+        self._check(self.lib.sfmhip_depth_consistency_dev(self.h, _dptr(d_depth), src, n, int(rows), int(cols), K4.ctypes.data, Rrel.ctypes.data, trel.ctypes.data,
+                                                          float(rel_tol), int(min_consistent), _dptr(d_count), _dptr(d_keep)))
+
+    def depth_to_points(self, depth, keep, img, K4, Rinv, c, cap=None):
+        """(xyz m x 3 float64, bgr m x 3 uint8, n_found): the kept pixels as world points with their colours, in row-major order
+        (sfmhip_depth_to_points); m = min(n_found, cap), cap = every pixel unless given"""
+        depth = np.ascontiguousarray(depth, np.float32); keep = np.ascontiguousarray(keep, np.uint8)
+        (im,), (ptr,), rows, cols, ch, ld = _dense_images([img])
+        if depth.shape != (rows, cols) or keep.shape != (rows, cols):
+            raise ValueError("depth, keep and the image differ in size")
+        cap = rows * cols if cap is None else int(cap)
+        K4 = np.ascontiguousarray(K4, np.float64).reshape(4); Rinv = np.ascontiguousarray(Rinv, np.float64).reshape(9); c = np.ascontiguousarray(c, np.float64).reshape(3)
+        xyz = np.empty((max(cap, 1), 3), np.float64); bgr = np.empty((max(cap, 1), 3), np.uint8); n = C.c_int32(0)
+        self._check(self.lib.sfmhip_depth_to_points(self.h, depth.ctypes.data, keep.ctypes.data, ptr, rows, cols, ch, ld, K4.ctypes.data, Rinv.ctypes.data,
+                                                    c.ctypes.data, xyz.ctypes.data, bgr.ctypes.data, cap, C.byref(n)))
+        m = min(n.value, cap)
+        return xyz[:m].copy(), bgr[:m].copy(), n.value
+
+    def depth_to_points_dev(self, d_depth, d_keep, d_img, rows, cols, channels, ld, K4, Rinv, c, d_xyz, d_bgr, cap, d_n_found):
+        """the same on resident arrays (K4, Rinv, c stay host arrays); the int32 at d_n_found receives the full count: enqueues only"""
+        K4 = np.ascontiguousarray(K4, np.float64).reshape(4); Rinv = np.ascontiguousarray(Rinv, np.float64).reshape(9); c = np.ascontiguousarray(c, np.float64).reshape(3)
+        self._check(self.lib.sfmhip_depth_to_points_dev(self.h, _dptr(d_depth), _dptr(d_keep), _dptr(d_img), int(rows), int(cols), int(channels), int(ld),
+                                                        K4.ctypes.data, Rinv.ctypes.data, c.ctypes.data, _dptr(d_xyz), _dptr(d_bgr), int(cap), _dptr(d_n_found)))
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
@@ -1300,3 +1373,123 @@ def refine_structure(intrinsic, extrinsics, obs_cam, obs_pt, obs_uv, structure, 
     keep &= ok[op]
     K2, ext2, pts2, s = ctx.ba_solve(K4, ext, new_pts[ids], oc[keep], remap[op[keep]].astype(np.int32), uv[keep], opts)
     return K2, ext2, pts2, ids, keep, s
+
+
+# ---------------------------------------------------------------------------------------------------- dense depth
+def _dense_images(images):
+    """(arrays, addresses, rows, cols, channels, ld) of uint8 images of one size for the dense entries: an image whose pixels are
+    contiguous inside its rows is passed where it lies with its row stride (a view of a padded buffer), anything else as a dense copy"""
+    arrs = [np.asarray(im) for im in images]
+    shape = arrs[0].shape
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3) or any(a.shape != shape or a.dtype != np.uint8 for a in arrs):
+        raise ValueError("images are uint8 arrays of one size, rows x cols or rows x cols x 3")
+    rows, cols = shape[:2]
+    ch = 1 if len(shape) == 2 else 3
+
+    def in_place(a):
+        return a.strides[-1] == 1 and (ch == 1 or a.strides[1] == 3) and a.strides[0] >= cols * ch
+    if not (all(in_place(a) for a in arrs) and len({a.strides[0] for a in arrs}) == 1):
+        arrs = [np.ascontiguousarray(a) for a in arrs]
+    return arrs, [a.ctypes.data for a in arrs], rows, cols, ch, arrs[0].strides[0]
+
+
+def sweep_geometry(K4, ext_ref, ext_src):
+    """sfmhip_sweep_geometry (host only, no context): (A, b, Rrel, trel, Rinv, c)"""
+    K4 = np.ascontiguousarray(K4, np.float64).reshape(4); ext_ref = np.ascontiguousarray(ext_ref, np.float64).reshape(6)
+    ext_src = np.ascontiguousarray(ext_src, np.float64).reshape(-1, 6)
+    n = ext_src.shape[0]
+    A = np.zeros((n, 9), np.float32); b = np.zeros((n, 3), np.float32); Rrel = np.zeros((n, 9)); trel = np.zeros((n, 3)); Rinv = np.zeros(9); c = np.zeros(3)
+    rc = _lib.load().sfmhip_sweep_geometry(K4.ctypes.data, ext_ref.ctypes.data, ext_src.ctypes.data, n, A.ctypes.data, b.ctypes.data, Rrel.ctypes.data,
+                                           trel.ctypes.data, Rinv.ctypes.data, c.ctypes.data)
+    if rc != 0:
+        raise SfmHipError(f"sfmhip_sweep_geometry: error {rc}")
+    return A, b, Rrel, trel, Rinv, c
+
+
+def dense_sources(ext, n_src):
+    """for every view the n_src other views with the nearest camera centres, nearest first (equal distances: the lower index)"""
+    ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)
+    cen = np.array([sweep_geometry((1.0, 1.0, 0.0, 0.0), e, np.zeros((0, 6)))[5] for e in ext])
+    out = []
+    for i in range(len(ext)):
+        d = np.sqrt(((cen - cen[i]) ** 2).sum(1)); d[i] = np.inf
+        out.append([int(j) for j in np.argsort(d, kind="stable")[:n_src]])
+    return out
+
+
+def dense_depth_range(sparse_pts, ext6):
+    """[wmin, wmax] of a view from the depths z > 0 of the sparse points in it: the inverses of their 98th and 2nd percentile, the
+    interval then widened by a quarter of its length at both ends (the lower end no lower than half the 98th percentile's inverse)"""
+    _, _, _, _, Rinv, c = sweep_geometry((1.0, 1.0, 0.0, 0.0), ext6, np.zeros((0, 6)))
+    P = np.ascontiguousarray(sparse_pts, np.float64).reshape(-1, 3)
+    z = ((P[:, 0] - c[0]) * Rinv[2] + (P[:, 1] - c[1]) * Rinv[5]) + (P[:, 2] - c[2]) * Rinv[8]
+    z = z[np.isfinite(z) & (z > 0)]
+    if z.size < 2:
+        raise ValueError("fewer than two sparse points in front of a view: give wmin and wmax")
+    zlo, zhi = np.percentile(z, [2.0, 98.0])
+    wlo, whi = 1.0 / zhi, 1.0 / zlo
+    span = whi - wlo
+    if not span > 0:
+        span = 0.5 * wlo
+    return max(wlo - 0.25 * span, 0.5 * wlo), whi + 0.25 * span
+
+
+def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, radius=2, wmin=None, wmax=None, min_sources=1, min_score=0.5, rel_tol=0.01,
+                        min_consistent=None, voxel=0.0, ctx=None):
+    """The dense step after the bundle adjustment: every view is swept against the n_src views with the nearest camera centres
+    (sfmhip_plane_sweep_dev), its depth map is checked against theirs (sfmhip_depth_consistency_dev), the kept pixels become coloured
+    world points (sfmhip_depth_to_points_dev), and the views' points are concatenated in view order.  images: uint8 arrays (or torch
+    CUDA tensors) of one size, gray or BGR; K4 and ext: the bundle adjustment's intrinsics and (angle-axis, t) rows.  The inverse-depth
+    range of a view comes from sparse_pts (dense_depth_range) unless wmin and wmax are given.  min_consistent: min(2, n_src) unless
+    given.  voxel > 0: the cloud is replaced by one centroid per voxel (voxel_downsample; a voxel's colour is the rounded mean of its
+    points' per channel).  The images, depth maps and masks stay on the device between the stages.  Returns (xyz n x 3 float64, bgr n x 3 uint8)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)
+        n_img = len(images)
+        if n_img != len(ext) or n_img < 2:
+            raise ValueError("one pose per image, at least two images")
+        n_src = min(int(n_src), n_img - 1)
+        if min_consistent is None:
+            min_consistent = min(2, n_src)
+        dev = torch.device("cuda", ctx.device)
+        d_img = [im.to(dev).contiguous() if hasattr(im, "data_ptr") else torch.from_numpy(np.ascontiguousarray(im)).to(dev) for im in images]
+        rows, cols = d_img[0].shape[:2]
+        ch = 1 if d_img[0].dim() == 2 else 3
+        if any(t.shape != d_img[0].shape or t.dtype != torch.uint8 for t in d_img) or (ch == 3 and d_img[0].shape[2] != 3):
+            raise ValueError("images are uint8 arrays of one size, rows x cols or rows x cols x 3")
+        torch.cuda.synchronize(dev)                      # the uploads ran on torch's stream, the stages run on the context's
+        sources = dense_sources(ext, n_src)
+        geo = [sweep_geometry(K4, ext[i], ext[sources[i]]) for i in range(n_img)]
+        npx = rows * cols
+        d_depth = [torch.empty(npx, dtype=torch.float32, device=dev) for _ in range(n_img)]
+        d_plane = torch.empty(npx, dtype=torch.int32, device=dev); d_score = torch.empty(npx, dtype=torch.float32, device=dev)
+        for i in range(n_img):
+            lo, hi = (wmin, wmax) if wmin is not None and wmax is not None else dense_depth_range(sparse_pts, ext[i])
+            ctx.plane_sweep_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius, min_sources,
+                                min_score, d_plane, d_score, d_depth[i])
+        d_keep = torch.empty(npx, dtype=torch.uint8, device=dev)
+        d_xyz = torch.empty((npx, 3), dtype=torch.float64, device=dev); d_bgr = torch.empty((npx, 3), dtype=torch.uint8, device=dev)
+        d_n = torch.empty(1, dtype=torch.int32, device=dev)
+        xyz, bgr = [], []
+        for i in range(n_img):
+            _, _, Rrel, trel, Rinv, c = geo[i]
+            ctx.depth_consistency_dev(d_depth[i], [d_depth[j] for j in sources[i]], rows, cols, K4, Rrel, trel, rel_tol, min_consistent, None, d_keep)
+            ctx.depth_to_points_dev(d_depth[i], d_keep, d_img[i], rows, cols, ch, cols * ch, K4, Rinv, c, d_xyz, d_bgr, npx, d_n)
+            ctx.synchronize()
+            m = int(d_n.item())
+            xyz.append(d_xyz[:m].cpu().numpy()); bgr.append(d_bgr[:m].cpu().numpy())
+        xyz = np.concatenate(xyz); bgr = np.concatenate(bgr)
+        if voxel and voxel > 0 and len(xyz):
+            cen, counts, voxel_of, _ = ctx.voxel_downsample(xyz, voxel)
+            total = np.zeros((len(cen), 3), np.int64)
+            ok = voxel_of >= 0
+            np.add.at(total, voxel_of[ok], bgr[ok].astype(np.int64))
+            cnt = counts.astype(np.int64)[:, None]
+            xyz, bgr = cen, ((2 * total + cnt) // (2 * cnt)).astype(np.uint8)
+        return xyz, bgr
+    finally:
+        if own:
+            ctx.close()

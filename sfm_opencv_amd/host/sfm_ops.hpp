@@ -5,6 +5,7 @@
 // mirrors of the OpenCV types, implemented over the C-ABI of libsfmhip.so (include/sfmhip.h).  A maintainer of the
 // reference keeps his cv:: types and uses the shims shown in INTEGRATION.md; code without OpenCV uses this header.
 #pragma once
+#include <algorithm>
 #include <cassert>
 #include <cmath>
 #include <cstdint>
@@ -786,6 +787,121 @@ inline int voxel_downsample(const std::vector<Point3d>& pts3d, const std::vector
             for (int ch = 0; ch < 3; ++ch) out_colors[v][ch] = (unsigned char)((2 * sum[(size_t)v * 3 + ch] + counts[v]) / (2 * (long long)counts[v]));
     }
     return nv;
+}
+
+// ---- dense cloud (extension; sfmhip_plane_sweep, sfmhip_depth_consistency, sfmhip_depth_to_points) -- the dense step after the bundle
+// adjustment, the mirror of api.dense_cloud_for_all: every view is swept against the n_src views with the nearest camera centres (equal
+// distances: the lower index), its depth map is checked against theirs, the kept pixels become coloured world points, the views' points
+// follow each other in view order; voxel > 0: voxel_downsample on the result.  images: rows x cols x channels bytes each, dense.
+// intrinsic: 4 x 1 (fx, fy, cx, cy); extrinsics: 6 x 1 (angle-axis, t) per view, as bundle_adjustment leaves them.  The inverse-depth
+// range of a view is [wmin, wmax] where wmin < wmax are given, else dense_depth_range of the sparse points.  Returns the number of
+// points, -1 on error.
+struct DenseOptions {
+    int n_src = 2, planes = 64, radius = 2, min_sources = 1;
+    double wmin = 0.0, wmax = 0.0, min_score = 0.5, rel_tol = 0.01;
+    int min_consistent = -1;               // < 0: min(2, n_src)
+    double voxel = 0.0;
+};
+// numpy.percentile(z, q) with its default linear interpolation, z sorted ascending
+inline double dense_percentile(const std::vector<double>& z, const double q)
+{
+    const double pos = q / 100.0 * (double)(z.size() - 1);
+    const size_t lo = (size_t)std::floor(pos), hi = std::min(lo + 1, z.size() - 1);
+    const double t = pos - (double)lo, a = z[lo], b = z[hi];
+    return t >= 0.5 ? b - (b - a) * (1.0 - t) : a + (b - a) * t;
+}
+// the inverses of the 98th and 2nd percentile of the sparse points' depths z > 0 in the view, the interval widened by a quarter of its
+// length at both ends (the lower end no lower than half the 98th percentile's inverse); false with fewer than two points in front
+inline bool dense_depth_range(const std::vector<Point3d>& sparse_pts, const double ext6[6], double& wmin, double& wmax)
+{
+    const double K1[4] = { 1.0, 1.0, 0.0, 0.0 };
+    double Rinv[9], c[3];
+    if (sfmhip_sweep_geometry(K1, ext6, nullptr, 0, nullptr, nullptr, nullptr, nullptr, Rinv, c) != SFMHIP_OK) return false;
+    std::vector<double> z;
+    for (const Point3d& p : sparse_pts) {
+        const double v = ((p.x - c[0]) * Rinv[2] + (p.y - c[1]) * Rinv[5]) + (p.z - c[2]) * Rinv[8];
+        if (std::isfinite(v) && v > 0.0) z.push_back(v);
+    }
+    if (z.size() < 2) return false;
+    std::sort(z.begin(), z.end());
+    const double wlo = 1.0 / dense_percentile(z, 98.0), whi = 1.0 / dense_percentile(z, 2.0);
+    double span = whi - wlo;
+    if (!(span > 0.0)) span = 0.5 * wlo;
+    wmin = std::max(wlo - 0.25 * span, 0.5 * wlo);
+    wmax = whi + 0.25 * span;
+    return true;
+}
+inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const int rows, const int cols, const int channels, const Mat& intrinsic,
+                               const std::vector<Mat>& extrinsics, const std::vector<Point3d>& sparse_pts, const DenseOptions& opt,
+                               std::vector<Point3d>& out_pts, std::vector<Vec3b>& out_colors)
+{
+    sfmhip_ctx* ctx = context();
+    out_pts.clear(); out_colors.clear();
+    const int n_img = (int)images.size();
+    if (!ctx || n_img < 2 || extrinsics.size() != images.size() || rows < 1 || cols < 1) return -1;
+    const int n_src = std::min(opt.n_src, n_img - 1), min_consistent = opt.min_consistent < 0 ? std::min(2, n_src) : opt.min_consistent;
+    if (n_src < 1 || n_src > 8) return -1;
+    const double* K4 = intrinsic.ptr<double>();
+    const double K1[4] = { 1.0, 1.0, 0.0, 0.0 };
+    const size_t npx = (size_t)rows * cols, ld = (size_t)cols * channels;
+    // the sources of every view: the nearest camera centres
+    std::vector<double> cen((size_t)n_img * 3);
+    for (int i = 0; i < n_img; ++i)
+        if (sfmhip_sweep_geometry(K1, extrinsics[i].ptr<double>(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &cen[3 * (size_t)i]) != SFMHIP_OK) return -1;
+    std::vector<std::vector<int>> sources(n_img);
+    for (int i = 0; i < n_img; ++i) {
+        std::vector<std::pair<double, int>> d;
+        for (int j = 0; j < n_img; ++j) {
+            if (j == i) continue;
+            const double dx = cen[3 * j] - cen[3 * i], dy = cen[3 * j + 1] - cen[3 * i + 1], dz = cen[3 * j + 2] - cen[3 * i + 2];
+            d.emplace_back(std::sqrt((dx * dx + dy * dy) + dz * dz), j);
+        }
+        std::stable_sort(d.begin(), d.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
+        for (int k = 0; k < n_src; ++k) sources[i].push_back(d[k].second);
+    }
+    struct Geo { float A[72], b[24]; double Rrel[72], trel[24], Rinv[9], c[3]; };
+    std::vector<Geo> geo(n_img);
+    std::vector<std::vector<float>> depth(n_img, std::vector<float>(npx));
+    std::vector<int32_t> plane(npx);
+    std::vector<float> score(npx);
+    for (int i = 0; i < n_img; ++i) {
+        double e[48];
+        const uint8_t* src[8];
+        for (int k = 0; k < n_src; ++k) { std::memcpy(e + 6 * k, extrinsics[sources[i][k]].ptr<double>(), 6 * sizeof(double)); src[k] = images[sources[i][k]]; }
+        Geo& g = geo[i];
+        if (sfmhip_sweep_geometry(K4, extrinsics[i].ptr<double>(), e, n_src, g.A, g.b, g.Rrel, g.trel, g.Rinv, g.c) != SFMHIP_OK) return -1;
+        double wmin = opt.wmin, wmax = opt.wmax;
+        if (!(wmin < wmax) && !dense_depth_range(sparse_pts, extrinsics[i].ptr<double>(), wmin, wmax)) {
+            printf("[Err]: dense_cloud_for_all: no depth range for view %d\n", i);
+            return -1;
+        }
+        if (sfmhip_plane_sweep(ctx, images[i], src, n_src, rows, cols, channels, ld, g.A, g.b, opt.planes, wmin, wmax, opt.radius, opt.min_sources, opt.min_score,
+                               plane.data(), score.data(), depth[i].data()) != SFMHIP_OK) {
+            printf("[Err]: dense_cloud_for_all: %s\n", sfmhip_last_error(ctx));
+            return -1;
+        }
+    }
+    std::vector<uint8_t> keep(npx);
+    std::vector<Point3d> xyz(npx);
+    std::vector<Vec3b> bgr(npx);
+    std::vector<Point3d> pts;
+    std::vector<Vec3b> cols_out;
+    for (int i = 0; i < n_img; ++i) {
+        const float* ds[8];
+        for (int k = 0; k < n_src; ++k) ds[k] = depth[sources[i][k]].data();
+        const Geo& g = geo[i];
+        int32_t n = 0;
+        if (sfmhip_depth_consistency(ctx, depth[i].data(), ds, n_src, rows, cols, K4, g.Rrel, g.trel, opt.rel_tol, min_consistent, nullptr, keep.data()) != SFMHIP_OK ||
+            sfmhip_depth_to_points(ctx, depth[i].data(), keep.data(), images[i], rows, cols, channels, ld, K4, g.Rinv, g.c, &xyz[0].x, &bgr[0].v[0], (int)npx, &n) != SFMHIP_OK) {
+            printf("[Err]: dense_cloud_for_all: %s\n", sfmhip_last_error(ctx));
+            return -1;
+        }
+        pts.insert(pts.end(), xyz.begin(), xyz.begin() + n);
+        cols_out.insert(cols_out.end(), bgr.begin(), bgr.begin() + n);
+    }
+    if (opt.voxel > 0.0 && !pts.empty()) return voxel_downsample(pts, cols_out, opt.voxel, out_pts, out_colors);
+    out_pts.swap(pts); out_colors.swap(cols_out);
+    return (int)out_pts.size();
 }
 
 // ---- outputs (NView:186-338) ------------------------------------------------------------------------------------
