@@ -983,6 +983,48 @@ int sfmhip_depth_to_points    (sfmhip_ctx*, const float* depth,   const uint8_t*
 int sfmhip_depth_to_points_dev(sfmhip_ctx*, const float* d_depth, const uint8_t* d_keep, const uint8_t* d_img, int rows, int cols, int channels, size_t ld,
                                const double K4[4], const double Rinv[9], const double c[3], double* d_xyz, uint8_t* d_bgr, int cap, int32_t* d_n_found);   /* enqueue only */
 
+/* Stage 1 regularised: semi-global aggregation (Hirschmueller 2008) of the sweep's cost volume, a second path from the images to a depth
+ * map that stages 2 and 3 take as it is.  After one quantisation of the plane score everything is unsigned integer arithmetic.
+ *   Cost volume.  Everything up to the plane score c_k is the plane sweep's definition, unchanged (gray, planes, warp, sample, window
+ *     sums, the mean over the counting sources, min_sources).  For a scored plane, in double and in this order:
+ *       t = (1.0 - c_k)*cost_scale;   q = floor(t + 0.5);   C = q < 0 ? 0 : q > 65534 ? 65534 : (uint16)q.
+ *     A plane that is not scored has C = 65535.  Layout: rows x cols x D uint16, plane fastest.  2 <= D <= 256; cost_scale positive and
+ *     finite.  (The scores of a textured scene crowd just below 1: choose cost_scale so that their differences survive, e.g. 262144.)
+ *   Aggregation.  The directions (dy, dx) in this order -- paths = 4: (0,1), (0,-1), (1,0), (-1,0); paths = 8: these, then (1,1), (-1,-1),
+ *     (1,-1), (-1,1).  For a direction r and a pixel p: if p - r lies outside the image, L_r(p,k) = C(p,k); otherwise, with
+ *     m = min_j L_r(p-r,j),
+ *       L_r(p,k) = C(p,k) + min(L_r(p-r,k), L_r(p-r,k-1) + P1 [k > 0], L_r(p-r,k+1) + P1 [k < D-1], m + P2) - m.
+ *     S(p,k) is the sum of L_r(p,k) over the directions.  All values are unsigned 32-bit integers; with 0 <= P1 <= P2 <= 65535,
+ *     L <= C + P2 and S cannot overflow.  The value 65535 takes part like any other cost (an unseen plane is unlikely, not forbidden);
+ *     a pixel with no scored plane passes its neighbours' costs through.
+ *   Winner.  Among the k with C(p,k) != 65535 the smallest S wins, the smallest k among equals.  If there is none, or C(p,k) > max_cost
+ *     (0 .. 65535): plane = -1, cost = 65535, sum = 0, depth = NaN.  Sub-plane fit: where 0 < k < D-1, neither neighbour's C is 65535 and
+ *     den = ((double)S_{k-1} - 2.0*(double)S_k) + (double)S_{k+1} > 0:
+ *       w = w_k + ((0.5*((double)S_{k-1} - (double)S_{k+1}))/den)*step,   else w = w_k;   depth = (float)(1.0/w),
+ *     w_k and step as in the sweep.  Output per pixel: plane int32, cost uint16 (the winner's C), sum uint32 (its S), depth float.
+ *   sweep_costs takes the plane sweep's arguments up to min_sources, then cost_scale, and writes the volume.  sgm_depth takes a volume and
+ *     writes the four outputs, any of which may be NULL but not all, and S (rows x cols x D uint32) where S is not NULL (a test's output:
+ *     a production caller passes NULL).  plane_sweep_sgm does both; its volumes are temporaries from the context's block cache
+ *     (6 * rows * cols * D bytes), so nothing of size D crosses the bus.  The _dev forms enqueue on the context's stream and never
+ *     synchronise.
+ *   SFMHIP_E_ARG with the outputs left alone: whatever the plane sweep refuses (min_score apart), D > 256, a cost_scale that is not
+ *     positive and finite, a null volume, sizes out of range, wmin or wmax not positive and finite, wmin >= wmax, P1 < 0, P1 > P2,
+ *     P2 > 65535, paths not 4 or 8, max_cost outside 0 .. 65535, every output of sgm_depth NULL, a NULL output of plane_sweep_sgm. */
+int sfmhip_sweep_costs    (sfmhip_ctx*, const uint8_t* ref,   const uint8_t* const* src,   int n_src, int rows, int cols, int channels, size_t ld,
+                           const float* A, const float* b, int D, double wmin, double wmax, int r, int min_sources, double cost_scale, uint16_t* cost);
+int sfmhip_sweep_costs_dev(sfmhip_ctx*, const uint8_t* d_ref, const uint8_t* const* d_src, int n_src, int rows, int cols, int channels, size_t ld,
+                           const float* A, const float* b, int D, double wmin, double wmax, int r, int min_sources, double cost_scale, uint16_t* d_cost);
+int sfmhip_sgm_depth    (sfmhip_ctx*, const uint16_t* cost,   int rows, int cols, int D, double wmin, double wmax, int P1, int P2, int paths, int max_cost,
+                         int32_t* plane,   uint16_t* win_cost,   uint32_t* sum,   float* depth,   uint32_t* S);
+int sfmhip_sgm_depth_dev(sfmhip_ctx*, const uint16_t* d_cost, int rows, int cols, int D, double wmin, double wmax, int P1, int P2, int paths, int max_cost,
+                         int32_t* d_plane, uint16_t* d_win_cost, uint32_t* d_sum, float* d_depth, uint32_t* d_S);
+int sfmhip_plane_sweep_sgm    (sfmhip_ctx*, const uint8_t* ref,   const uint8_t* const* src,   int n_src, int rows, int cols, int channels, size_t ld,
+                               const float* A, const float* b, int D, double wmin, double wmax, int r, int min_sources, double cost_scale,
+                               int P1, int P2, int paths, int max_cost, int32_t* plane,   uint16_t* win_cost,   float* depth);
+int sfmhip_plane_sweep_sgm_dev(sfmhip_ctx*, const uint8_t* d_ref, const uint8_t* const* d_src, int n_src, int rows, int cols, int channels, size_t ld,
+                               const float* A, const float* b, int D, double wmin, double wmax, int r, int min_sources, double cost_scale,
+                               int P1, int P2, int paths, int max_cost, int32_t* d_plane, uint16_t* d_win_cost, float* d_depth);
+
 #ifdef __cplusplus
 }
 #endif

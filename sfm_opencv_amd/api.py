@@ -878,6 +878,66 @@ class Context:
         self._check(self.lib.sfmhip_depth_to_points_dev(self.h, _dptr(d_depth), _dptr(d_keep), _dptr(d_img), int(rows), int(cols), int(channels), int(ld),
                                                         K4.ctypes.data, Rinv.ctypes.data, c.ctypes.data, _dptr(d_xyz), _dptr(d_bgr), int(cap), _dptr(d_n_found)))
 
+    # ---------------------------------------------------------------- semi-global aggregation of the sweep's costs (sfmhip_sgm_depth)
+    def sweep_costs(self, ref, srcs, A, b, planes, wmin, wmax, radius=2, min_sources=1, cost_scale=262144.0):
+        """rows x cols x planes uint16: sfmhip_sweep_costs, the sweep's plane scores as costs (65535 = not scored)"""
+        imgs, ptrs, rows, cols, ch, ld = _dense_images([ref] + list(srcs))
+        n = len(imgs) - 1
+        A = np.ascontiguousarray(A, np.float32).reshape(n, 9); b = np.ascontiguousarray(b, np.float32).reshape(n, 3)
+        cost = np.empty((rows, cols, max(int(planes), 1)), np.uint16)
+        src = (C.c_void_p * max(n, 1))(*ptrs[1:])
+        self._check(self.lib.sfmhip_sweep_costs(self.h, ptrs[0], src, n, rows, cols, ch, ld, A.ctypes.data, b.ctypes.data, int(planes), float(wmin), float(wmax),
+                                                int(radius), int(min_sources), float(cost_scale), cost.ctypes.data))
+        return cost
+
+    def sweep_costs_dev(self, d_ref, d_srcs, rows, cols, channels, ld, A, b, planes, wmin, wmax, radius, min_sources, cost_scale, d_cost):
+        """the same on resident images into a resident volume (A and b stay host arrays): enqueues only"""
+        n = len(d_srcs)
+        A = np.ascontiguousarray(A, np.float32).reshape(n, 9); b = np.ascontiguousarray(b, np.float32).reshape(n, 3)
+        src = (C.c_void_p * max(n, 1))(*[_dptr(x) for x in d_srcs])
+        self._check(self.lib.sfmhip_sweep_costs_dev(self.h, _dptr(d_ref), src, n, int(rows), int(cols), int(channels), int(ld), A.ctypes.data, b.ctypes.data,
+                                                    int(planes), float(wmin), float(wmax), int(radius), int(min_sources), float(cost_scale), _dptr(d_cost)))
+
+    def sgm_depth(self, cost, wmin, wmax, P1, P2, paths=8, max_cost=65535, return_sums=False):
+        """(plane int32, cost uint16, sum uint32, depth float32), each rows x cols: sfmhip_sgm_depth of a rows x cols x planes uint16 cost
+        volume; return_sums: also S (rows x cols x planes uint32), the aggregated volume"""
+        cost = np.ascontiguousarray(cost, np.uint16)
+        rows, cols, D = cost.shape
+        plane = np.empty((rows, cols), np.int32); wc = np.empty((rows, cols), np.uint16); ssum = np.empty((rows, cols), np.uint32)
+        depth = np.empty((rows, cols), np.float32)
+        S = np.empty((rows, cols, D), np.uint32) if return_sums else None
+        self._check(self.lib.sfmhip_sgm_depth(self.h, cost.ctypes.data, rows, cols, D, float(wmin), float(wmax), int(P1), int(P2), int(paths), int(max_cost),
+                                              plane.ctypes.data, wc.ctypes.data, ssum.ctypes.data, depth.ctypes.data, S.ctypes.data if return_sums else None))
+        return (plane, wc, ssum, depth, S) if return_sums else (plane, wc, ssum, depth)
+
+    def sgm_depth_dev(self, d_cost, rows, cols, planes, wmin, wmax, P1, P2, paths, max_cost, d_plane, d_win_cost, d_sum, d_depth, d_S=None):
+        """the same on a resident volume; any output may be None but not all of the first four: enqueues only"""
+        self._check(self.lib.sfmhip_sgm_depth_dev(self.h, _dptr(d_cost), int(rows), int(cols), int(planes), float(wmin), float(wmax), int(P1), int(P2), int(paths),
+                                                  int(max_cost), _dptr(d_plane), _dptr(d_win_cost), _dptr(d_sum), _dptr(d_depth), _dptr(d_S)))
+
+    def plane_sweep_sgm(self, ref, srcs, A, b, planes, wmin, wmax, radius=2, min_sources=1, cost_scale=262144.0, P1=512, P2=4096, paths=8, max_cost=65535):
+        """(plane int32, cost uint16, depth float32), each rows x cols: sfmhip_plane_sweep_sgm, the sweep's costs aggregated along 4 or 8
+        directions before the winner is taken; the volumes stay on the device"""
+        imgs, ptrs, rows, cols, ch, ld = _dense_images([ref] + list(srcs))
+        n = len(imgs) - 1
+        A = np.ascontiguousarray(A, np.float32).reshape(n, 9); b = np.ascontiguousarray(b, np.float32).reshape(n, 3)
+        plane = np.empty((rows, cols), np.int32); wc = np.empty((rows, cols), np.uint16); depth = np.empty((rows, cols), np.float32)
+        src = (C.c_void_p * max(n, 1))(*ptrs[1:])
+        self._check(self.lib.sfmhip_plane_sweep_sgm(self.h, ptrs[0], src, n, rows, cols, ch, ld, A.ctypes.data, b.ctypes.data, int(planes), float(wmin), float(wmax),
+                                                    int(radius), int(min_sources), float(cost_scale), int(P1), int(P2), int(paths), int(max_cost), plane.ctypes.data,
+                                                    wc.ctypes.data, depth.ctypes.data))
+        return plane, wc, depth
+
+    def plane_sweep_sgm_dev(self, d_ref, d_srcs, rows, cols, channels, ld, A, b, planes, wmin, wmax, radius, min_sources, cost_scale, P1, P2, paths, max_cost,
+                            d_plane, d_win_cost, d_depth):
+        """the same on resident images: enqueues only"""
+        n = len(d_srcs)
+        A = np.ascontiguousarray(A, np.float32).reshape(n, 9); b = np.ascontiguousarray(b, np.float32).reshape(n, 3)
+        src = (C.c_void_p * max(n, 1))(*[_dptr(x) for x in d_srcs])
+        self._check(self.lib.sfmhip_plane_sweep_sgm_dev(self.h, _dptr(d_ref), src, n, int(rows), int(cols), int(channels), int(ld), A.ctypes.data, b.ctypes.data,
+                                                        int(planes), float(wmin), float(wmax), int(radius), int(min_sources), float(cost_scale), int(P1), int(P2),
+                                                        int(paths), int(max_cost), _dptr(d_plane), _dptr(d_win_cost), _dptr(d_depth)))
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
@@ -1435,14 +1495,16 @@ def dense_depth_range(sparse_pts, ext6):
 
 
 def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, radius=2, wmin=None, wmax=None, min_sources=1, min_score=0.5, rel_tol=0.01,
-                        min_consistent=None, voxel=0.0, ctx=None):
+                        min_consistent=None, voxel=0.0, ctx=None, sgm=None):
     """The dense step after the bundle adjustment: every view is swept against the n_src views with the nearest camera centres
     (sfmhip_plane_sweep_dev), its depth map is checked against theirs (sfmhip_depth_consistency_dev), the kept pixels become coloured
     world points (sfmhip_depth_to_points_dev), and the views' points are concatenated in view order.  images: uint8 arrays (or torch
     CUDA tensors) of one size, gray or BGR; K4 and ext: the bundle adjustment's intrinsics and (angle-axis, t) rows.  The inverse-depth
     range of a view comes from sparse_pts (dense_depth_range) unless wmin and wmax are given.  min_consistent: min(2, n_src) unless
     given.  voxel > 0: the cloud is replaced by one centroid per voxel (voxel_downsample; a voxel's colour is the rounded mean of its
-    points' per channel).  The images, depth maps and masks stay on the device between the stages.  Returns (xyz n x 3 float64, bgr n x 3 uint8)."""
+    points' per channel).  sgm = (cost_scale, P1, P2, paths, max_cost): the sweep's costs are aggregated along 4 or 8 directions before
+    the winner is taken (sfmhip_plane_sweep_sgm_dev; at most 256 planes, min_score is not used); None: the winner per pixel.  The
+    images, depth maps and masks stay on the device between the stages.  Returns (xyz n x 3 float64, bgr n x 3 uint8)."""
     import torch
     own = ctx is None
     ctx = ctx or Context(0)
@@ -1466,8 +1528,14 @@ def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, ra
         npx = rows * cols
         d_depth = [torch.empty(npx, dtype=torch.float32, device=dev) for _ in range(n_img)]
         d_plane = torch.empty(npx, dtype=torch.int32, device=dev); d_score = torch.empty(npx, dtype=torch.float32, device=dev)
+        d_cost = torch.empty(npx if sgm is not None else 0, dtype=torch.int16, device=dev)       # the winners' 16-bit costs
         for i in range(n_img):
             lo, hi = (wmin, wmax) if wmin is not None and wmax is not None else dense_depth_range(sparse_pts, ext[i])
+            if sgm is not None:
+                cost_scale, P1, P2, paths, max_cost = sgm
+                ctx.plane_sweep_sgm_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius,
+                                        min_sources, cost_scale, P1, P2, paths, max_cost, d_plane, d_cost, d_depth[i])
+                continue
             ctx.plane_sweep_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius, min_sources,
                                 min_score, d_plane, d_score, d_depth[i])
         d_keep = torch.empty(npx, dtype=torch.uint8, device=dev)

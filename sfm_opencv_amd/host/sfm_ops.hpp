@@ -801,6 +801,11 @@ struct DenseOptions {
     double wmin = 0.0, wmax = 0.0, min_score = 0.5, rel_tol = 0.01;
     int min_consistent = -1;               // < 0: min(2, n_src)
     double voxel = 0.0;
+    // semi-global aggregation of the sweep's costs before the winner is taken (sfmhip_plane_sweep_sgm; at most 256 planes, min_score is
+    // not used); off: the winner per pixel
+    bool sgm = false;
+    double sgm_cost_scale = 262144.0;
+    int sgm_P1 = 512, sgm_P2 = 4096, sgm_paths = 8, sgm_max_cost = 65535;
 };
 // numpy.percentile(z, q) with its default linear interpolation, z sorted ascending
 inline double dense_percentile(const std::vector<double>& z, const double q)
@@ -864,6 +869,7 @@ inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const 
     std::vector<std::vector<float>> depth(n_img, std::vector<float>(npx));
     std::vector<int32_t> plane(npx);
     std::vector<float> score(npx);
+    std::vector<uint16_t> win_cost(opt.sgm ? npx : 0);
     for (int i = 0; i < n_img; ++i) {
         double e[48];
         const uint8_t* src[8];
@@ -875,8 +881,12 @@ inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const 
             printf("[Err]: dense_cloud_for_all: no depth range for view %d\n", i);
             return -1;
         }
-        if (sfmhip_plane_sweep(ctx, images[i], src, n_src, rows, cols, channels, ld, g.A, g.b, opt.planes, wmin, wmax, opt.radius, opt.min_sources, opt.min_score,
-                               plane.data(), score.data(), depth[i].data()) != SFMHIP_OK) {
+        const int rc = opt.sgm ? sfmhip_plane_sweep_sgm(ctx, images[i], src, n_src, rows, cols, channels, ld, g.A, g.b, opt.planes, wmin, wmax, opt.radius, opt.min_sources,
+                                                        opt.sgm_cost_scale, opt.sgm_P1, opt.sgm_P2, opt.sgm_paths, opt.sgm_max_cost, plane.data(), win_cost.data(),
+                                                        depth[i].data())
+                               : sfmhip_plane_sweep(ctx, images[i], src, n_src, rows, cols, channels, ld, g.A, g.b, opt.planes, wmin, wmax, opt.radius, opt.min_sources,
+                                                    opt.min_score, plane.data(), score.data(), depth[i].data());
+        if (rc != SFMHIP_OK) {
             printf("[Err]: dense_cloud_for_all: %s\n", sfmhip_last_error(ctx));
             return -1;
         }
