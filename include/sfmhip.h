@@ -1025,6 +1025,85 @@ int sfmhip_plane_sweep_sgm_dev(sfmhip_ctx*, const uint8_t* d_ref, const uint8_t*
                                const float* A, const float* b, int D, double wmin, double wmax, int r, int min_sources, double cost_scale,
                                int P1, int P2, int paths, int max_cost, int32_t* d_plane, uint16_t* d_win_cost, float* d_depth);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Dense mesh: truncated signed distance fusion of the depth maps into a voxel volume and      */
+/* marching tetrahedra on it (what Open3D's ScalableTSDFVolume, or colmap's stereo_fusion with  */
+/* a mesher behind it, give; no reference counterpart).  Again the definition.  The volume is   */
+/* integer sums, a voxel is owned by one thread and a mesh edge by one voxel: no result depends */
+/* on the order of a sum, on the launch geometry or on how the views are split over calls.      */
+/* ------------------------------------------------------------------------------------------ */
+/* Volume: dims = (nx, ny, nz) voxels, every n_a >= 1 and nx*ny*nz <= 2^28; the voxel (i, j, k) has the linear index
+ *     lin = (k*ny + j)*nx + i  (x fastest) and the centre  X_a = origin[a] + ((double)idx_a + 0.5)*voxel,  idx = (i, j, k);
+ *   origin: 3 finite doubles; voxel > 0 and finite.  The caller owns int32 dsum[nvox], int32 wsum[nvox] and, for colour,
+ *   uint32 csum[nvox][3] (B, G, R), and zeroes them before the first call.  dims, origin, K4, R, t and the arrays of pointers are HOST
+ *   arrays in both forms.
+ *
+ * Integration.  n_views (1 .. 8) views per call: depth[v] rows x cols float (NaN or infinite = none), rows and cols at most 16384;
+ *   keep (the array, or any entry of it, may be NULL): rows x cols bytes, the consistency stage's map; img (NULL exactly when csum is
+ *   NULL; then no entry may be NULL): the images of stage 1 of the dense path with their channels (1 or 3) and row stride ld (both
+ *   are read only with img); K4 = (fx, fy, cx, cy); per view R (9 doubles, world to camera, row-major) and t (3 doubles): R is n_views x 9,
+ *   t is n_views x 3.  trunc > 0 and finite.
+ *   For every voxel and every view of the call, in double and in this order (no contraction):
+ *       Y_i = ((R[3i]*X_0 + R[3i+1]*X_1) + R[3i+2]*X_2) + t[i];       Y_2 > 0;
+ *       pu = floor(((fx*Y_0)/Y_2 + cx) + 0.5),  pv = floor(((fy*Y_1)/Y_2 + cy) + 0.5),  0 <= pu < cols and 0 <= pv < rows;
+ *       d = depth[pv][pu] finite, and keep[pv][pu] != 0 where the view has a keep map;
+ *       s = (double)d - Y_2;    s >= -trunc    (else the voxel is hidden behind the surface and the view does not count);
+ *       q = (int)floor(((s > trunc ? trunc : s)/trunc)*32767.0 + 0.5);
+ *       dsum += q;  wsum += 1;  csum[c] += the pixel's B, G, R (a gray pixel three times).
+ *   A call ADDS to the volume.  The sums are integers: the views {0 .. n} in one call, in several calls or in another order give the same
+ *   bytes.  |q| <= 32767, so dsum holds 65,535 counted views per voxel; staying below that is the caller's business.
+ *   SFMHIP_E_ARG with the volume left alone: a null dims, origin, depth (or entry of it), K4, R, t, dsum or wsum; one of img and csum
+ *   without the other, a null entry of img; dims, rows, cols or n_views out of range; with img, channels not 1 or 3 or ld < cols*channels;
+ *   origin not finite; voxel or trunc not positive and finite.
+ *   Device memory: none in the _dev form; the host form holds the volume, the maps and the images in the context's block cache. */
+int sfmhip_tsdf_integrate    (sfmhip_ctx*, const int dims[3], const double origin[3], double voxel, double trunc, const float* const* depth,
+                              const uint8_t* const* keep,   const uint8_t* const* img,   int n_views, int rows, int cols, int channels, size_t ld,
+                              const double K4[4], const double* R, const double* t, int32_t* dsum,   int32_t* wsum,   uint32_t* csum);
+/* the same on resident maps, images and volume (depth, keep, img: HOST arrays of device pointers), enqueued on the context's stream;
+ * never synchronises */
+int sfmhip_tsdf_integrate_dev(sfmhip_ctx*, const int dims[3], const double origin[3], double voxel, double trunc, const float* const* d_depth,
+                              const uint8_t* const* d_keep, const uint8_t* const* d_img, int n_views, int rows, int cols, int channels, size_t ld,
+                              const double K4[4], const double* R, const double* t, int32_t* d_dsum, int32_t* d_wsum, uint32_t* d_csum);
+
+/* Extraction: marching tetrahedra on the Kuhn split of every cell.
+ *   A voxel is VALID when wsum >= min_weight (min_weight >= 1) and INSIDE when dsum < 0 (dsum == 0 is outside): a sign test on integers.
+ *   Cells: the (nx-1)(ny-1)(nz-1) cubes between eight neighbouring voxel centres, numbered by their lowest corner in x-fastest order.  A
+ *   cell is PROCESSED when its 8 corners are valid.  A volume with a dimension of 1 has no cells: the mesh is empty, which is no error.
+ *   The corner (dx, dy, dz) of a cell has the code dx + 2*dy + 4*dz.  The tetrahedra of a cell, in this order, with their parity sigma (the
+ *   sign of det[c1-c0, c2-c0, c3-c0]):
+ *       0: (0,1,3,7) +1    1: (0,1,5,7) -1    2: (0,2,3,7) -1    3: (0,2,6,7) +1    4: (0,4,5,7) +1    5: (0,4,6,7) -1
+ *   -- the six monotone paths from corner 0 to corner 7; the same split in every cell, so the diagonals of a face shared by two cells
+ *   agree.  Every edge of a tetrahedron joins a voxel v to v + d, d in {0,1}^3 and not zero; its id is 7*lin(v) + (code(d) - 1).
+ *   Vertices: one per edge that joins an inside and an outside voxel and belongs to at least one processed cell, numbered by ascending
+ *   edge id.  With a = v and b = v + d (a is the end with the smaller lin), in this order:
+ *       num = (int64)dsum_a*wsum_b;   den = num - (int64)dsum_b*wsum_a   (never zero on such an edge);   s = (double)num/(double)den;
+ *       p_c = Xa_c + s*(Xb_c - Xa_c)                                     (X: the voxel centres above);
+ *       colour, per channel: m_v = (2*csum_v + wsum_v)/(2*wsum_v) (integers, 64 bits), then
+ *                            (uint8)floor(((double)m_a + s*((double)m_b - (double)m_a)) + 0.5).
+ *   Triangles: by ascending cell, then tetrahedron 0 .. 5, then triangle 0 .. 1.  In a tetrahedron with the corner positions 0 .. 3,
+ *   E(x,y) is the vertex on the edge between the positions x and y, and par(k,l,m,n) the sign of that permutation of (0,1,2,3) times sigma.
+ *       one inside corner at position k, the others l < m < n:   (E(k,l), E(k,m), E(k,n)) when par(k,l,m,n) > 0, else (E(k,l), E(k,n), E(k,m));
+ *       three inside (the outside one at k):                     that triangle reversed, i.e. the other of the two;
+ *       two inside k < l, outside m < n, Q = (E(k,m), E(k,n), E(l,n), E(l,m)):
+ *                                                                (Q0,Q1,Q2), (Q0,Q2,Q3) when par(k,l,m,n) > 0, else (Q0,Q2,Q1), (Q0,Q3,Q2).
+ *   With these rules the normal (p1-p0) x (p2-p0) of every triangle points from the inside corners to the outside ones, and the mesh is
+ *   an oriented manifold wherever the volume is observed.  A triangle of zero area (an s of exactly 0) is kept: dropping it would open
+ *   the surface.
+ *   Output: xyz (n_vertices x 3 double), bgr (n_vertices x 3 bytes; NULL allowed, and required NULL when csum is NULL), tri (n_triangles x 3
+ *   int32 vertex numbers).  *n_vertices and *n_triangles always receive the full counts; only the first min(count, cap) rows of xyz / bgr
+ *   (vertex_cap) and of tri (triangle_cap) are written and nothing past them is touched, so a call with both caps 0 sizes the arrays of
+ *   a second one.  xyz or tri may be NULL (it is then not written).  The _dev form writes the two counts on the device.
+ *   SFMHIP_E_ARG with the outputs left alone: a null dims, origin, dsum, wsum, n_vertices or n_triangles; dims out of range; origin not
+ *   finite, voxel not positive and finite; min_weight < 1; a negative cap; bgr without csum.
+ *   Device memory: 13 bytes per voxel (corner signs 4, edge mask 1, vertex and triangle numbers 4 + 4) and the scans' tile sums from the
+ *   context's block cache; the host form also holds the volume and the capped outputs there. */
+int sfmhip_tsdf_mesh    (sfmhip_ctx*, const int dims[3], const double origin[3], double voxel, const int32_t* dsum,   const int32_t* wsum,
+                         const uint32_t* csum,   int min_weight, double* xyz,   uint8_t* bgr,   int vertex_cap, int32_t* tri,   int triangle_cap,
+                         int32_t* n_vertices,   int32_t* n_triangles);
+int sfmhip_tsdf_mesh_dev(sfmhip_ctx*, const int dims[3], const double origin[3], double voxel, const int32_t* d_dsum, const int32_t* d_wsum,
+                         const uint32_t* d_csum, int min_weight, double* d_xyz, uint8_t* d_bgr, int vertex_cap, int32_t* d_tri, int triangle_cap,
+                         int32_t* d_n_vertices, int32_t* d_n_triangles);   /* enqueue only */
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,7 @@ SYMBOLS = [
     "sfmhip_sweep_geometry", "sfmhip_plane_sweep", "sfmhip_plane_sweep_dev", "sfmhip_depth_consistency", "sfmhip_depth_consistency_dev",
     "sfmhip_depth_to_points", "sfmhip_depth_to_points_dev",
     "sfmhip_sweep_costs", "sfmhip_sweep_costs_dev", "sfmhip_sgm_depth", "sfmhip_sgm_depth_dev", "sfmhip_plane_sweep_sgm", "sfmhip_plane_sweep_sgm_dev",
+    "sfmhip_tsdf_integrate", "sfmhip_tsdf_integrate_dev", "sfmhip_tsdf_mesh", "sfmhip_tsdf_mesh_dev",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -223,6 +224,10 @@ def load():
         "sfmhip_sgm_depth_dev": (i32, [vp, vp, i32, i32, i32, f64, f64, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "sfmhip_plane_sweep_sgm": (i32, [vp, vp, C.POINTER(vp), i32, i32, i32, i32, sz, vp, vp, i32, f64, f64, i32, i32, f64, i32, i32, i32, i32, vp, vp, vp]),
         "sfmhip_plane_sweep_sgm_dev": (i32, [vp, vp, C.POINTER(vp), i32, i32, i32, i32, sz, vp, vp, i32, f64, f64, i32, i32, f64, i32, i32, i32, i32, vp, vp, vp]),
+        "sfmhip_tsdf_integrate": (i32, [vp, vp, vp, f64, f64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, sz, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_tsdf_integrate_dev": (i32, [vp, vp, vp, f64, f64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, sz, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_tsdf_mesh": (i32, [vp, vp, vp, f64, vp, vp, vp, i32, vp, vp, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "sfmhip_tsdf_mesh_dev": (i32, [vp, vp, vp, f64, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -878,6 +878,78 @@ class Context:
         self._check(self.lib.sfmhip_depth_to_points_dev(self.h, _dptr(d_depth), _dptr(d_keep), _dptr(d_img), int(rows), int(cols), int(channels), int(ld),
                                                         K4.ctypes.data, Rinv.ctypes.data, c.ctypes.data, _dptr(d_xyz), _dptr(d_bgr), int(cap), _dptr(d_n_found)))
 
+    # ---------------------------------------------------------------- dense mesh (sfmhip_tsdf_integrate, sfmhip_tsdf_mesh)
+    def tsdf_integrate(self, dims, origin, voxel, trunc, depths, keeps, images, K4, R, t, dsum, wsum, csum=None):
+        """sfmhip_tsdf_integrate: adds up to 8 views to the caller's volume IN PLACE (dsum, wsum: contiguous int32 arrays of nx*ny*nz
+        entries, x fastest; csum: uint32 nvox x 3 with images, None without).  depths: float32 rows x cols maps; keeps: None, or a list
+        of uint8 maps / None per view; images: None, or the views' uint8 images (gray or BGR); R (n x 9, world to camera), t (n x 3)"""
+        n = len(depths)
+        maps = [np.ascontiguousarray(d, np.float32) for d in depths]
+        rows, cols = maps[0].shape
+        kp = [None if keeps is None or k is None else np.ascontiguousarray(k, np.uint8) for k in (keeps if keeps is not None else [None] * n)]
+        if any(m.shape != (rows, cols) for m in maps) or len(kp) != n or any(k is not None and k.shape != (rows, cols) for k in kp):
+            raise ValueError("the depth and keep maps differ in size or number")
+        ch, ld, img_p = 1, cols, None
+        if images is not None:
+            ims, ptrs, irows, icols, ch, ld = _dense_images(images)
+            if (irows, icols) != (rows, cols) or len(ims) != n:
+                raise ValueError("the images and the depth maps differ in size or number")
+            img_p = (C.c_void_p * n)(*ptrs)
+        _tsdf_volume_ok(dims, dsum, wsum, csum)
+        dims_a, origin_a, K4, R, t = _tsdf_host_args(dims, origin, K4, R, t, n)
+        depth_p = (C.c_void_p * n)(*[m.ctypes.data for m in maps])
+        keep_p = None if keeps is None else (C.c_void_p * n)(*[None if k is None else k.ctypes.data for k in kp])
+        self._check(self.lib.sfmhip_tsdf_integrate(self.h, dims_a.ctypes.data, origin_a.ctypes.data, float(voxel), float(trunc), depth_p, keep_p, img_p, n, rows, cols, ch, ld,
+                                                   K4.ctypes.data, R.ctypes.data, t.ctypes.data, dsum.ctypes.data, wsum.ctypes.data,
+                                                   None if csum is None else csum.ctypes.data))
+
+    def tsdf_integrate_dev(self, dims, origin, voxel, trunc, d_depths, d_keeps, d_images, rows, cols, channels, ld, K4, R, t, d_dsum, d_wsum, d_csum):
+        """the same on resident maps, images and volume (torch CUDA tensors or device addresses; d_keeps, or entries of it, and d_images /
+        d_csum may be None): enqueues on the context's stream, never synchronises"""
+        n = len(d_depths)
+        dims_a, origin_a, K4, R, t = _tsdf_host_args(dims, origin, K4, R, t, n)
+        depth_p = (C.c_void_p * n)(*[_dptr(x) for x in d_depths])
+        keep_p = None if d_keeps is None else (C.c_void_p * n)(*[None if k is None else _dptr(k) for k in d_keeps])
+        img_p = None if d_images is None else (C.c_void_p * n)(*[_dptr(x) for x in d_images])
+        self._check(self.lib.sfmhip_tsdf_integrate_dev(self.h, dims_a.ctypes.data, origin_a.ctypes.data, float(voxel), float(trunc), depth_p, keep_p, img_p, n, int(rows),
+                                                       int(cols), int(channels), int(ld), K4.ctypes.data, R.ctypes.data, t.ctypes.data, _dptr(d_dsum), _dptr(d_wsum),
+                                                       None if d_csum is None else _dptr(d_csum)))
+
+    def tsdf_mesh(self, dims, origin, voxel, dsum, wsum, csum=None, min_weight=1, vertex_cap=None, triangle_cap=None):
+        """(xyz m x 3 float64, bgr m x 3 uint8 or None without csum, tri k x 3 int32, n_vertices, n_triangles): sfmhip_tsdf_mesh, marching
+        tetrahedra on the volume.  Without caps the call is made twice, the first time with caps of 0 for the counts; with caps,
+        m = min(n_vertices, vertex_cap) and k = min(n_triangles, triangle_cap)"""
+        dsum = np.ascontiguousarray(dsum, np.int32); wsum = np.ascontiguousarray(wsum, np.int32)
+        csum = None if csum is None else np.ascontiguousarray(csum, np.uint32)
+        _tsdf_volume_ok(dims, dsum, wsum, csum)
+        dims_a, origin_a, *_ = _tsdf_host_args(dims, origin, np.zeros(4), np.zeros(9), np.zeros(3), 1)
+        nv, nt = C.c_int32(0), C.c_int32(0)
+
+        def call(xyz, bgr, vcap, tri, tcap):
+            self._check(self.lib.sfmhip_tsdf_mesh(self.h, dims_a.ctypes.data, origin_a.ctypes.data, float(voxel), dsum.ctypes.data, wsum.ctypes.data,
+                                                  None if csum is None else csum.ctypes.data, int(min_weight), None if xyz is None else xyz.ctypes.data,
+                                                  None if bgr is None else bgr.ctypes.data, vcap, None if tri is None else tri.ctypes.data, tcap, C.byref(nv), C.byref(nt)))
+        if vertex_cap is None or triangle_cap is None:
+            call(None, None, 0, None, 0)
+            vertex_cap = nv.value if vertex_cap is None else int(vertex_cap)
+            triangle_cap = nt.value if triangle_cap is None else int(triangle_cap)
+        vcap, tcap = int(vertex_cap), int(triangle_cap)
+        xyz = np.empty((max(vcap, 1), 3), np.float64); tri = np.empty((max(tcap, 1), 3), np.int32)
+        bgr = None if csum is None else np.empty((max(vcap, 1), 3), np.uint8)
+        call(xyz, bgr, vcap, tri, tcap)
+        m, k = min(nv.value, vcap), min(nt.value, tcap)
+        return xyz[:m].copy(), None if bgr is None else bgr[:m].copy(), tri[:k].copy(), nv.value, nt.value
+
+    def tsdf_mesh_dev(self, dims, origin, voxel, d_dsum, d_wsum, d_csum, min_weight, d_xyz, d_bgr, vertex_cap, d_tri, triangle_cap, d_n_vertices, d_n_triangles):
+        """the same on a resident volume into resident arrays (any of d_csum, d_xyz, d_bgr, d_tri may be None); the int32s at d_n_vertices and
+        d_n_triangles receive the full counts: enqueues only"""
+        dims_a, origin_a, *_ = _tsdf_host_args(dims, origin, np.zeros(4), np.zeros(9), np.zeros(3), 1)
+
+        def p(x):
+            return None if x is None else _dptr(x)
+        self._check(self.lib.sfmhip_tsdf_mesh_dev(self.h, dims_a.ctypes.data, origin_a.ctypes.data, float(voxel), _dptr(d_dsum), _dptr(d_wsum), p(d_csum), int(min_weight),
+                                                  p(d_xyz), p(d_bgr), int(vertex_cap), p(d_tri), int(triangle_cap), _dptr(d_n_vertices), _dptr(d_n_triangles)))
+
     # ---------------------------------------------------------------- semi-global aggregation of the sweep's costs (sfmhip_sgm_depth)
     def sweep_costs(self, ref, srcs, A, b, planes, wmin, wmax, radius=2, min_sources=1, cost_scale=262144.0):
         """rows x cols x planes uint16: sfmhip_sweep_costs, the sweep's plane scores as costs (65535 = not scored)"""
@@ -1494,6 +1566,44 @@ def dense_depth_range(sparse_pts, ext6):
     return max(wlo - 0.25 * span, 0.5 * wlo), whi + 0.25 * span
 
 
+def _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax, min_sources, min_score, min_consistent, sgm):
+    """what dense_cloud_for_all and dense_mesh_for_all share: the images on the device, every view's sources and geometry arrays, and its
+    depth map (plane sweep, or its semi-global form), all enqueued on the context's stream.  Returns (device, d_img, rows, cols, channels,
+    sources, geometry, d_depth, min_consistent, scratch); the caller holds on to `scratch`, the sweeps' other outputs, until it has
+    synchronised the context: the sweeps may still be writing them."""
+    import torch
+    ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)
+    n_img = len(images)
+    if n_img != len(ext) or n_img < 2:
+        raise ValueError("one pose per image, at least two images")
+    n_src = min(int(n_src), n_img - 1)
+    if min_consistent is None:
+        min_consistent = min(2, n_src)
+    dev = torch.device("cuda", ctx.device)
+    d_img = [im.to(dev).contiguous() if hasattr(im, "data_ptr") else torch.from_numpy(np.ascontiguousarray(im)).to(dev) for im in images]
+    rows, cols = d_img[0].shape[:2]
+    ch = 1 if d_img[0].dim() == 2 else 3
+    if any(t.shape != d_img[0].shape or t.dtype != torch.uint8 for t in d_img) or (ch == 3 and d_img[0].shape[2] != 3):
+        raise ValueError("images are uint8 arrays of one size, rows x cols or rows x cols x 3")
+    torch.cuda.synchronize(dev)                      # the uploads ran on torch's stream, the stages run on the context's
+    sources = dense_sources(ext, n_src)
+    geo = [sweep_geometry(K4, ext[i], ext[sources[i]]) for i in range(n_img)]
+    npx = rows * cols
+    d_depth = [torch.empty(npx, dtype=torch.float32, device=dev) for _ in range(n_img)]
+    d_plane = torch.empty(npx, dtype=torch.int32, device=dev); d_score = torch.empty(npx, dtype=torch.float32, device=dev)
+    d_cost = torch.empty(npx if sgm is not None else 0, dtype=torch.int16, device=dev)       # the winners' 16-bit costs
+    for i in range(n_img):
+        lo, hi = (wmin, wmax) if wmin is not None and wmax is not None else dense_depth_range(sparse_pts, ext[i])
+        if sgm is not None:
+            cost_scale, P1, P2, paths, max_cost = sgm
+            ctx.plane_sweep_sgm_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius,
+                                    min_sources, cost_scale, P1, P2, paths, max_cost, d_plane, d_cost, d_depth[i])
+            continue
+        ctx.plane_sweep_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius, min_sources,
+                            min_score, d_plane, d_score, d_depth[i])
+    return dev, d_img, rows, cols, ch, sources, geo, d_depth, min_consistent, (d_plane, d_score, d_cost)
+
+
 def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, radius=2, wmin=None, wmax=None, min_sources=1, min_score=0.5, rel_tol=0.01,
                         min_consistent=None, voxel=0.0, ctx=None, sgm=None):
     """The dense step after the bundle adjustment: every view is swept against the n_src views with the nearest camera centres
@@ -1509,35 +1619,9 @@ def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, ra
     own = ctx is None
     ctx = ctx or Context(0)
     try:
-        ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)
-        n_img = len(images)
-        if n_img != len(ext) or n_img < 2:
-            raise ValueError("one pose per image, at least two images")
-        n_src = min(int(n_src), n_img - 1)
-        if min_consistent is None:
-            min_consistent = min(2, n_src)
-        dev = torch.device("cuda", ctx.device)
-        d_img = [im.to(dev).contiguous() if hasattr(im, "data_ptr") else torch.from_numpy(np.ascontiguousarray(im)).to(dev) for im in images]
-        rows, cols = d_img[0].shape[:2]
-        ch = 1 if d_img[0].dim() == 2 else 3
-        if any(t.shape != d_img[0].shape or t.dtype != torch.uint8 for t in d_img) or (ch == 3 and d_img[0].shape[2] != 3):
-            raise ValueError("images are uint8 arrays of one size, rows x cols or rows x cols x 3")
-        torch.cuda.synchronize(dev)                      # the uploads ran on torch's stream, the stages run on the context's
-        sources = dense_sources(ext, n_src)
-        geo = [sweep_geometry(K4, ext[i], ext[sources[i]]) for i in range(n_img)]
-        npx = rows * cols
-        d_depth = [torch.empty(npx, dtype=torch.float32, device=dev) for _ in range(n_img)]
-        d_plane = torch.empty(npx, dtype=torch.int32, device=dev); d_score = torch.empty(npx, dtype=torch.float32, device=dev)
-        d_cost = torch.empty(npx if sgm is not None else 0, dtype=torch.int16, device=dev)       # the winners' 16-bit costs
-        for i in range(n_img):
-            lo, hi = (wmin, wmax) if wmin is not None and wmax is not None else dense_depth_range(sparse_pts, ext[i])
-            if sgm is not None:
-                cost_scale, P1, P2, paths, max_cost = sgm
-                ctx.plane_sweep_sgm_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius,
-                                        min_sources, cost_scale, P1, P2, paths, max_cost, d_plane, d_cost, d_depth[i])
-                continue
-            ctx.plane_sweep_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius, min_sources,
-                                min_score, d_plane, d_score, d_depth[i])
+        dev, d_img, rows, cols, ch, sources, geo, d_depth, min_consistent, scratch = _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax,
+                                                                                                         min_sources, min_score, min_consistent, sgm)
+        n_img, npx = len(d_img), rows * cols
         d_keep = torch.empty(npx, dtype=torch.uint8, device=dev)
         d_xyz = torch.empty((npx, 3), dtype=torch.float64, device=dev); d_bgr = torch.empty((npx, 3), dtype=torch.uint8, device=dev)
         d_n = torch.empty(1, dtype=torch.int32, device=dev)
@@ -1558,6 +1642,84 @@ def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, ra
             cnt = counts.astype(np.int64)[:, None]
             xyz, bgr = cen, ((2 * total + cnt) // (2 * cnt)).astype(np.uint8)
         return xyz, bgr
+    finally:
+        if own:
+            ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------- dense mesh
+def _tsdf_volume_ok(dims, dsum, wsum, csum):
+    nvox = int(dims[0]) * int(dims[1]) * int(dims[2])
+    for a, dt, shape in ((dsum, np.int32, (nvox,)), (wsum, np.int32, (nvox,)), (csum, np.uint32, (nvox, 3))):
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == int(np.prod(shape))):
+            raise ValueError("the volume is contiguous arrays: dsum, wsum int32 of nx*ny*nz entries, csum uint32 of three per voxel")
+
+
+def _tsdf_host_args(dims, origin, K4, R, t, n):
+    return (np.ascontiguousarray(dims, np.int32).reshape(3), np.ascontiguousarray(origin, np.float64).reshape(3), np.ascontiguousarray(K4, np.float64).reshape(4),
+            np.ascontiguousarray(R, np.float64).reshape(n, 9), np.ascontiguousarray(t, np.float64).reshape(n, 3))
+
+
+def tsdf_bounds(sparse_pts, voxels=128, margin=0.1):
+    """(dims, origin, voxel) of a volume around the sparse cloud: per axis the 2nd and 98th percentile of the finite points, the interval
+    widened by `margin` of its length at both ends; the voxel is the longest side over `voxels`, and the other axes take as many voxels as
+    cover their side (at least 2), centred on it"""
+    P = np.ascontiguousarray(sparse_pts, np.float64).reshape(-1, 3)
+    P = P[np.isfinite(P).all(1)]
+    if len(P) < 2:
+        raise ValueError("fewer than two finite sparse points: give the volume")
+    lo, hi = np.percentile(P, 2.0, axis=0), np.percentile(P, 98.0, axis=0)
+    span = hi - lo
+    lo, hi = lo - float(margin) * span, hi + float(margin) * span
+    side = hi - lo
+    if not side.max() > 0:
+        raise ValueError("the sparse points do not span a volume")
+    voxel = float(side.max()) / int(voxels)
+    dims = np.maximum(np.ceil(side / voxel - 1e-9).astype(np.int64), 2)
+    origin = 0.5 * (lo + hi) - 0.5 * dims * voxel
+    return tuple(int(d) for d in dims), tuple(float(o) for o in origin), voxel
+
+
+def dense_mesh_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, radius=2, wmin=None, wmax=None, min_sources=1, min_score=0.5, rel_tol=0.01,
+                       min_consistent=None, ctx=None, voxels=128, trunc_voxels=4, min_weight=2, sgm=None, volume=None):
+    """The dense surface after the bundle adjustment: the depth maps and keep masks of dense_cloud_for_all's chain (same arguments, same
+    meaning) stay on the device, all views are fused into one truncated signed distance volume 8 per call (sfmhip_tsdf_integrate_dev) and
+    the volume is meshed by marching tetrahedra (sfmhip_tsdf_mesh_dev, once for the counts and once into arrays of that size).  The
+    volume is volume = (dims, origin, voxel) or tsdf_bounds(sparse_pts, voxels); the truncation distance trunc_voxels voxels; a voxel
+    counts with min_weight views.  Returns (xyz n x 3 float64, bgr n x 3 uint8, tri m x 3 int32)."""
+    import torch
+    own = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        dev, d_img, rows, cols, ch, sources, geo, d_depth, min_consistent, scratch = _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax,
+                                                                                                         min_sources, min_score, min_consistent, sgm)
+        n_img, npx = len(d_img), rows * cols
+        dims, origin, voxel = volume if volume is not None else tsdf_bounds(sparse_pts, voxels)
+        nvox = int(dims[0]) * int(dims[1]) * int(dims[2])
+        d_keep = [torch.empty(npx, dtype=torch.uint8, device=dev) for _ in range(n_img)]
+        for i in range(n_img):
+            ctx.depth_consistency_dev(d_depth[i], [d_depth[j] for j in sources[i]], rows, cols, K4, geo[i][2], geo[i][3], rel_tol, min_consistent, None, d_keep[i])
+        ctx.synchronize()                                # the volume is zeroed on torch's stream
+        d_dsum = torch.zeros(nvox, dtype=torch.int32, device=dev); d_wsum = torch.zeros(nvox, dtype=torch.int32, device=dev)
+        d_csum = torch.zeros((nvox, 3), dtype=torch.int32, device=dev)
+        d_n = torch.zeros(2, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        # world to camera of every view: Rinv = R^T and c = -R^T t from the geometry call
+        R = np.array([np.asarray(g[4]).reshape(3, 3).T.ravel() for g in geo])
+        t = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)[:, 3:]
+        for i0 in range(0, n_img, 8):
+            sl = slice(i0, min(i0 + 8, n_img))
+            ctx.tsdf_integrate_dev(dims, origin, voxel, trunc_voxels * voxel, d_depth[sl], d_keep[sl], d_img[sl], rows, cols, ch, cols * ch, K4, R[sl], t[sl],
+                                   d_dsum, d_wsum, d_csum)
+        ctx.tsdf_mesh_dev(dims, origin, voxel, d_dsum, d_wsum, d_csum, min_weight, None, None, 0, None, 0, d_n[0:1], d_n[1:2])
+        ctx.synchronize()
+        nv, nt = (int(x) for x in d_n.cpu().numpy())
+        d_xyz = torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev); d_bgr = torch.empty((max(nv, 1), 3), dtype=torch.uint8, device=dev)
+        d_tri = torch.empty((max(nt, 1), 3), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.tsdf_mesh_dev(dims, origin, voxel, d_dsum, d_wsum, d_csum, min_weight, d_xyz, d_bgr, nv, d_tri, nt, d_n[0:1], d_n[1:2])
+        ctx.synchronize()
+        return d_xyz[:nv].cpu().numpy(), d_bgr[:nv].cpu().numpy(), d_tri[:nt].cpu().numpy()
     finally:
         if own:
             ctx.close()

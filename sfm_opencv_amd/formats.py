@@ -17,6 +17,7 @@ _WRAP = 71      # cv::FileStorage wrap margin [3P]
 
 PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                        ("r", "u1"), ("g", "u1"), ("b", "u1")])
+PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
 def _dtoa(v):
@@ -207,3 +208,41 @@ def read_ply_binary(path):
             break
     n = int(re.search(rb"element vertex (\d+)", raw[:end]).group(1))
     return np.frombuffer(raw[end:end + n * PLY_VERTEX.itemsize], PLY_VERTEX).copy()
+
+
+def mesh_ply_bytes(xyz, bgr, tri):
+    """a triangle mesh as a binary little-endian .ply: the vertex element of write_ply_binary (float32 x y z, the normals -- zero: the
+    mesher estimates none --, uchar red green blue from the (b, g, r) rows), then `element face` with `property list uchar int
+    vertex_indices`, three int32 per face.  bgr None: white."""
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3); tri = np.asarray(tri, np.int32).reshape(-1, 3)
+    bgr = np.full((len(xyz), 3), 255, np.uint8) if bgr is None else np.asarray(bgr, np.uint8).reshape(-1, 3)
+    if len(bgr) != len(xyz) or (len(tri) and (tri.min() < 0 or tri.max() >= len(xyz))):
+        raise ValueError("one colour per vertex, and faces that index the vertices")
+    v = np.zeros(len(xyz), PLY_VERTEX)
+    v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    v["b"], v["g"], v["r"] = bgr[:, 0], bgr[:, 1], bgr[:, 2]
+    f = np.zeros(len(tri), PLY_FACE)
+    f["n"] = 3; f["v"] = tri
+    hdr = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v),
+           "property float x", "property float y", "property float z",
+           "property float nx", "property float ny", "property float nz",
+           "property uchar red", "property uchar green", "property uchar blue",
+           "element face %d" % len(f), "property list uchar int vertex_indices", "end_header"]
+    return ("\n".join(hdr) + "\n").encode("ascii") + v.tobytes() + f.tobytes()
+
+
+def write_mesh_ply(path, xyz, bgr, tri):
+    with open(path, "wb") as f:
+        f.write(mesh_ply_bytes(xyz, bgr, tri))
+
+
+def read_mesh_ply(path):
+    """(xyz n x 3 float32, bgr n x 3 uint8, tri m x 3 int32) of a file write_mesh_ply wrote"""
+    raw = open(path, "rb").read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    n = int(re.search(rb"element vertex (\d+)", raw[:end]).group(1)); m = int(re.search(rb"element face (\d+)", raw[:end]).group(1))
+    v = np.frombuffer(raw, PLY_VERTEX, n, end)
+    f = np.frombuffer(raw, PLY_FACE, m, end + n * PLY_VERTEX.itemsize)
+    if len(raw) != end + n * PLY_VERTEX.itemsize + m * PLY_FACE.itemsize or (m and (f["n"] != 3).any()):
+        raise ValueError("not a triangle mesh of write_mesh_ply")
+    return np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["b"], v["g"], v["r"]], 1), f["v"].copy()

@@ -806,6 +806,12 @@ struct DenseOptions {
     bool sgm = false;
     double sgm_cost_scale = 262144.0;
     int sgm_P1 = 512, sgm_P2 = 4096, sgm_paths = 8, sgm_max_cost = 65535;
+    // the mesh (dense_mesh_for_all): the volume is (mesh_dims, mesh_origin, mesh_voxel) where mesh_voxel > 0, else tsdf_bounds of the sparse
+    // points with mesh_voxels voxels along its longest side; truncation at mesh_trunc_voxels voxels; a voxel counts with mesh_min_weight views
+    int mesh_voxels = 128, mesh_min_weight = 2;
+    double mesh_trunc_voxels = 4.0, mesh_margin = 0.1;
+    int mesh_dims[3] = { 0, 0, 0 };
+    double mesh_origin[3] = { 0.0, 0.0, 0.0 }, mesh_voxel = 0.0;
 };
 // numpy.percentile(z, q) with its default linear interpolation, z sorted ascending
 inline double dense_percentile(const std::vector<double>& z, const double q)
@@ -836,24 +842,25 @@ inline bool dense_depth_range(const std::vector<Point3d>& sparse_pts, const doub
     wmax = whi + 0.25 * span;
     return true;
 }
-inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const int rows, const int cols, const int channels, const Mat& intrinsic,
-                               const std::vector<Mat>& extrinsics, const std::vector<Point3d>& sparse_pts, const DenseOptions& opt,
-                               std::vector<Point3d>& out_pts, std::vector<Vec3b>& out_colors)
+struct DenseGeo { float A[72], b[24]; double Rrel[72], trel[24], Rinv[9], c[3]; };
+// what dense_cloud_for_all and dense_mesh_for_all share: the sources of every view (the nearest camera centres), its geometry arrays and
+// its depth map (the plane sweep, or its semi-global form); false on error, with the message printed under the caller's name
+inline bool dense_depth_maps(sfmhip_ctx* ctx, const char* who, const std::vector<const uint8_t*>& images, const int rows, const int cols, const int channels,
+                             const Mat& intrinsic, const std::vector<Mat>& extrinsics, const std::vector<Point3d>& sparse_pts, const DenseOptions& opt, int& n_src,
+                             std::vector<std::vector<int>>& sources, std::vector<DenseGeo>& geo, std::vector<std::vector<float>>& depth)
 {
-    sfmhip_ctx* ctx = context();
-    out_pts.clear(); out_colors.clear();
     const int n_img = (int)images.size();
-    if (!ctx || n_img < 2 || extrinsics.size() != images.size() || rows < 1 || cols < 1) return -1;
-    const int n_src = std::min(opt.n_src, n_img - 1), min_consistent = opt.min_consistent < 0 ? std::min(2, n_src) : opt.min_consistent;
-    if (n_src < 1 || n_src > 8) return -1;
+    if (!ctx || n_img < 2 || extrinsics.size() != images.size() || rows < 1 || cols < 1) return false;
+    n_src = std::min(opt.n_src, n_img - 1);
+    if (n_src < 1 || n_src > 8) return false;
     const double* K4 = intrinsic.ptr<double>();
     const double K1[4] = { 1.0, 1.0, 0.0, 0.0 };
     const size_t npx = (size_t)rows * cols, ld = (size_t)cols * channels;
     // the sources of every view: the nearest camera centres
     std::vector<double> cen((size_t)n_img * 3);
     for (int i = 0; i < n_img; ++i)
-        if (sfmhip_sweep_geometry(K1, extrinsics[i].ptr<double>(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &cen[3 * (size_t)i]) != SFMHIP_OK) return -1;
-    std::vector<std::vector<int>> sources(n_img);
+        if (sfmhip_sweep_geometry(K1, extrinsics[i].ptr<double>(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &cen[3 * (size_t)i]) != SFMHIP_OK) return false;
+    sources.assign(n_img, std::vector<int>());
     for (int i = 0; i < n_img; ++i) {
         std::vector<std::pair<double, int>> d;
         for (int j = 0; j < n_img; ++j) {
@@ -864,9 +871,8 @@ inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const 
         std::stable_sort(d.begin(), d.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
         for (int k = 0; k < n_src; ++k) sources[i].push_back(d[k].second);
     }
-    struct Geo { float A[72], b[24]; double Rrel[72], trel[24], Rinv[9], c[3]; };
-    std::vector<Geo> geo(n_img);
-    std::vector<std::vector<float>> depth(n_img, std::vector<float>(npx));
+    geo.assign(n_img, DenseGeo());
+    depth.assign(n_img, std::vector<float>(npx));
     std::vector<int32_t> plane(npx);
     std::vector<float> score(npx);
     std::vector<uint16_t> win_cost(opt.sgm ? npx : 0);
@@ -874,12 +880,12 @@ inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const 
         double e[48];
         const uint8_t* src[8];
         for (int k = 0; k < n_src; ++k) { std::memcpy(e + 6 * k, extrinsics[sources[i][k]].ptr<double>(), 6 * sizeof(double)); src[k] = images[sources[i][k]]; }
-        Geo& g = geo[i];
-        if (sfmhip_sweep_geometry(K4, extrinsics[i].ptr<double>(), e, n_src, g.A, g.b, g.Rrel, g.trel, g.Rinv, g.c) != SFMHIP_OK) return -1;
+        DenseGeo& g = geo[i];
+        if (sfmhip_sweep_geometry(K4, extrinsics[i].ptr<double>(), e, n_src, g.A, g.b, g.Rrel, g.trel, g.Rinv, g.c) != SFMHIP_OK) return false;
         double wmin = opt.wmin, wmax = opt.wmax;
         if (!(wmin < wmax) && !dense_depth_range(sparse_pts, extrinsics[i].ptr<double>(), wmin, wmax)) {
-            printf("[Err]: dense_cloud_for_all: no depth range for view %d\n", i);
-            return -1;
+            printf("[Err]: %s: no depth range for view %d\n", who, i);
+            return false;
         }
         const int rc = opt.sgm ? sfmhip_plane_sweep_sgm(ctx, images[i], src, n_src, rows, cols, channels, ld, g.A, g.b, opt.planes, wmin, wmax, opt.radius, opt.min_sources,
                                                         opt.sgm_cost_scale, opt.sgm_P1, opt.sgm_P2, opt.sgm_paths, opt.sgm_max_cost, plane.data(), win_cost.data(),
@@ -887,10 +893,26 @@ inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const 
                                : sfmhip_plane_sweep(ctx, images[i], src, n_src, rows, cols, channels, ld, g.A, g.b, opt.planes, wmin, wmax, opt.radius, opt.min_sources,
                                                     opt.min_score, plane.data(), score.data(), depth[i].data());
         if (rc != SFMHIP_OK) {
-            printf("[Err]: dense_cloud_for_all: %s\n", sfmhip_last_error(ctx));
-            return -1;
+            printf("[Err]: %s: %s\n", who, sfmhip_last_error(ctx));
+            return false;
         }
     }
+    return true;
+}
+inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const int rows, const int cols, const int channels, const Mat& intrinsic,
+                               const std::vector<Mat>& extrinsics, const std::vector<Point3d>& sparse_pts, const DenseOptions& opt,
+                               std::vector<Point3d>& out_pts, std::vector<Vec3b>& out_colors)
+{
+    sfmhip_ctx* ctx = context();
+    out_pts.clear(); out_colors.clear();
+    int n_src = 0;
+    std::vector<std::vector<int>> sources;
+    std::vector<DenseGeo> geo;
+    std::vector<std::vector<float>> depth;
+    if (!dense_depth_maps(ctx, "dense_cloud_for_all", images, rows, cols, channels, intrinsic, extrinsics, sparse_pts, opt, n_src, sources, geo, depth)) return -1;
+    const int n_img = (int)images.size(), min_consistent = opt.min_consistent < 0 ? std::min(2, n_src) : opt.min_consistent;
+    const double* K4 = intrinsic.ptr<double>();
+    const size_t npx = (size_t)rows * cols, ld = (size_t)cols * channels;
     std::vector<uint8_t> keep(npx);
     std::vector<Point3d> xyz(npx);
     std::vector<Vec3b> bgr(npx);
@@ -899,7 +921,7 @@ inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const 
     for (int i = 0; i < n_img; ++i) {
         const float* ds[8];
         for (int k = 0; k < n_src; ++k) ds[k] = depth[sources[i][k]].data();
-        const Geo& g = geo[i];
+        const DenseGeo& g = geo[i];
         int32_t n = 0;
         if (sfmhip_depth_consistency(ctx, depth[i].data(), ds, n_src, rows, cols, K4, g.Rrel, g.trel, opt.rel_tol, min_consistent, nullptr, keep.data()) != SFMHIP_OK ||
             sfmhip_depth_to_points(ctx, depth[i].data(), keep.data(), images[i], rows, cols, channels, ld, K4, g.Rinv, g.c, &xyz[0].x, &bgr[0].v[0], (int)npx, &n) != SFMHIP_OK) {
@@ -912,6 +934,97 @@ inline int dense_cloud_for_all(const std::vector<const uint8_t*>& images, const 
     if (opt.voxel > 0.0 && !pts.empty()) return voxel_downsample(pts, cols_out, opt.voxel, out_pts, out_colors);
     out_pts.swap(pts); out_colors.swap(cols_out);
     return (int)out_pts.size();
+}
+
+// ---- dense mesh (extension; sfmhip_tsdf_integrate, sfmhip_tsdf_mesh), the mirror of api.tsdf_bounds and api.dense_mesh_for_all
+// (dims, origin, voxel) of a volume around the sparse cloud: per axis the 2nd and 98th percentile of the finite points, widened by `margin`
+// of the interval at both ends; the voxel is the longest side over `voxels`, the other axes take the voxels that cover their side (at
+// least 2), centred on it; false with fewer than two finite points or a cloud without extent
+inline bool tsdf_bounds(const std::vector<Point3d>& sparse_pts, const int voxels, const double margin, int dims[3], double origin[3], double& voxel)
+{
+    std::vector<double> ax[3];
+    for (const Point3d& p : sparse_pts)
+        if (std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z)) { ax[0].push_back(p.x); ax[1].push_back(p.y); ax[2].push_back(p.z); }
+    if (ax[0].size() < 2 || voxels < 1) return false;
+    double lo[3], hi[3], side = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        std::sort(ax[a].begin(), ax[a].end());
+        const double l = dense_percentile(ax[a], 2.0), h = dense_percentile(ax[a], 98.0), span = h - l;
+        lo[a] = l - margin * span; hi[a] = h + margin * span;
+        side = std::max(side, hi[a] - lo[a]);
+    }
+    if (!(side > 0.0)) return false;
+    voxel = side / (double)voxels;
+    for (int a = 0; a < 3; ++a) {
+        dims[a] = std::max((int)std::ceil((hi[a] - lo[a]) / voxel - 1e-9), 2);
+        origin[a] = 0.5 * (lo[a] + hi[a]) - 0.5 * (double)dims[a] * voxel;
+    }
+    return true;
+}
+// The dense surface after the bundle adjustment: dense_cloud_for_all's depth maps and keep masks (same arguments), every view fused into
+// one truncated signed distance volume, 8 views per call, and the volume meshed by marching tetrahedra (once for the counts, once into
+// arrays of that size).  out_tris: three vertex numbers per triangle.  Returns the number of triangles, -1 on error.
+inline int dense_mesh_for_all(const std::vector<const uint8_t*>& images, const int rows, const int cols, const int channels, const Mat& intrinsic,
+                              const std::vector<Mat>& extrinsics, const std::vector<Point3d>& sparse_pts, const DenseOptions& opt,
+                              std::vector<Point3d>& out_pts, std::vector<Vec3b>& out_colors, std::vector<int32_t>& out_tris)
+{
+    sfmhip_ctx* ctx = context();
+    out_pts.clear(); out_colors.clear(); out_tris.clear();
+    int n_src = 0;
+    std::vector<std::vector<int>> sources;
+    std::vector<DenseGeo> geo;
+    std::vector<std::vector<float>> depth;
+    if (!dense_depth_maps(ctx, "dense_mesh_for_all", images, rows, cols, channels, intrinsic, extrinsics, sparse_pts, opt, n_src, sources, geo, depth)) return -1;
+    const int n_img = (int)images.size(), min_consistent = opt.min_consistent < 0 ? std::min(2, n_src) : opt.min_consistent;
+    const double* K4 = intrinsic.ptr<double>();
+    const size_t npx = (size_t)rows * cols, ld = (size_t)cols * channels;
+    int dims[3] = { opt.mesh_dims[0], opt.mesh_dims[1], opt.mesh_dims[2] };
+    double origin[3] = { opt.mesh_origin[0], opt.mesh_origin[1], opt.mesh_origin[2] }, voxel = opt.mesh_voxel;
+    if (!(voxel > 0.0) && !tsdf_bounds(sparse_pts, opt.mesh_voxels, opt.mesh_margin, dims, origin, voxel)) {
+        printf("[Err]: dense_mesh_for_all: no volume\n");
+        return -1;
+    }
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || (double)dims[0] * dims[1] * dims[2] > 268435456.0) return -1;
+    std::vector<std::vector<uint8_t>> keep(n_img, std::vector<uint8_t>(npx));
+    std::vector<double> R((size_t)n_img * 9), t((size_t)n_img * 3);
+    for (int i = 0; i < n_img; ++i) {
+        const float* ds[8];
+        for (int k = 0; k < n_src; ++k) ds[k] = depth[sources[i][k]].data();
+        const DenseGeo& g = geo[i];
+        if (sfmhip_depth_consistency(ctx, depth[i].data(), ds, n_src, rows, cols, K4, g.Rrel, g.trel, opt.rel_tol, min_consistent, nullptr, keep[i].data()) != SFMHIP_OK) {
+            printf("[Err]: dense_mesh_for_all: %s\n", sfmhip_last_error(ctx));
+            return -1;
+        }
+        for (int r = 0; r < 3; ++r)                                      // world to camera: the transpose of Rinv, and the pose's t
+            for (int c = 0; c < 3; ++c) R[9 * (size_t)i + 3 * r + c] = g.Rinv[3 * c + r];
+        std::memcpy(&t[3 * (size_t)i], extrinsics[i].ptr<double>() + 3, 3 * sizeof(double));
+    }
+    const size_t nvox = (size_t)dims[0] * dims[1] * dims[2];
+    std::vector<int32_t> dsum(nvox, 0), wsum(nvox, 0);
+    std::vector<uint32_t> csum(nvox * 3, 0);
+    for (int i0 = 0; i0 < n_img; i0 += 8) {
+        const int n = std::min(8, n_img - i0);
+        const float* dp[8]; const uint8_t* kp[8]; const uint8_t* ip[8];
+        for (int k = 0; k < n; ++k) { dp[k] = depth[i0 + k].data(); kp[k] = keep[i0 + k].data(); ip[k] = images[i0 + k]; }
+        if (sfmhip_tsdf_integrate(ctx, dims, origin, voxel, opt.mesh_trunc_voxels * voxel, dp, kp, ip, n, rows, cols, channels, ld, K4, &R[9 * (size_t)i0], &t[3 * (size_t)i0],
+                                  dsum.data(), wsum.data(), csum.data()) != SFMHIP_OK) {
+            printf("[Err]: dense_mesh_for_all: %s\n", sfmhip_last_error(ctx));
+            return -1;
+        }
+    }
+    int32_t nv = 0, nt = 0;
+    if (sfmhip_tsdf_mesh(ctx, dims, origin, voxel, dsum.data(), wsum.data(), csum.data(), opt.mesh_min_weight, nullptr, nullptr, 0, nullptr, 0, &nv, &nt) != SFMHIP_OK) {
+        printf("[Err]: dense_mesh_for_all: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    out_pts.resize(nv); out_colors.resize(nv); out_tris.resize((size_t)nt * 3);
+    if (nv > 0 && nt > 0 &&
+        sfmhip_tsdf_mesh(ctx, dims, origin, voxel, dsum.data(), wsum.data(), csum.data(), opt.mesh_min_weight, &out_pts[0].x, &out_colors[0].v[0], nv, out_tris.data(), nt, &nv,
+                         &nt) != SFMHIP_OK) {
+        printf("[Err]: dense_mesh_for_all: %s\n", sfmhip_last_error(ctx));
+        return -1;
+    }
+    return nt;
 }
 
 // ---- outputs (NView:186-338) ------------------------------------------------------------------------------------
@@ -1067,6 +1180,25 @@ inline void write_ply_binary(const std::string& path, const std::vector<Pt3DPly>
         f.write((const char*)&p.nx, 4); f.write((const char*)&p.ny, 4); f.write((const char*)&p.nz, 4);
         f.write((const char*)&p.r, 1); f.write((const char*)&p.g, 1); f.write((const char*)&p.b, 1);
     }
+}
+
+// a triangle mesh as a binary little-endian .ply: write_ply_binary's vertex element (the normals zero: the mesher estimates none; the
+// colours (b, g, r) rows written red, green, blue), then `element face` with a uchar count of 3 and three int32 per face
+inline void write_mesh_ply(const std::string& path, const std::vector<Point3d>& pts, const std::vector<Vec3b>& colors, const std::vector<int32_t>& tris)
+{
+    assert(pts.size() == colors.size() && tris.size() % 3 == 0);
+    std::ofstream f(path, std::ios::out | std::ios::binary);
+    assert(f.is_open());
+    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << pts.size() << "\nproperty float x\nproperty float y\nproperty float z\n"
+         "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+         "element face " << tris.size() / 3 << "\nproperty list uchar int vertex_indices\nend_header\n";
+    for (size_t i = 0; i < pts.size(); ++i) {
+        const float v[6] = { (float)pts[i].x, (float)pts[i].y, (float)pts[i].z, 0.0f, 0.0f, 0.0f };
+        const uint8_t rgb[3] = { colors[i][2], colors[i][1], colors[i][0] };
+        f.write((const char*)v, 24); f.write((const char*)rgb, 3);
+    }
+    const uint8_t three = 3;
+    for (size_t i = 0; i < tris.size(); i += 3) { f.write((const char*)&three, 1); f.write((const char*)&tris[i], 12); }
 }
 
 }  // namespace sfm
