@@ -648,8 +648,11 @@ static int build_solver_plan(sfmhip_ba* h)
     ChainArgs chain_args;
     memset(&chain_args, 0, sizeof chain_args);
     bool chain_ok = false;
-    // Not with constant blocks under an all-reduce hook: the chain solver reads entries of S above the diagonal, which the packed
-    // all-reduce message does not carry (first finding; unmasked problems keep the selection they had).
+    // Not with constant blocks under an all-reduce hook (first finding).  That gate dates from when the chain solver read
+    // the camera x intrinsics coupling above the diagonal, which the packed all-reduce message does not carry; it now takes nothing
+    // from above the block diagonal (the poisoned solve of tests/host/chain_emu_test.cpp holds it to that), and unmasked problems under
+    // a hook take it (tests/test_ba_hook_solvers_gpu.py).  Masked ones keep the selection they had:
+    // test_resident_shards_agree_when_only_one_holds_constant_points asserts it, and lifting the gate is a change of its own.
     if (h->o.solver == 0 && !h->force_dense && ncf >= 12 && ncf <= 640 && !(h->masked && h->ar_fn)) {
         const int npad_nat = std::max(NB, round_up(6 * ncf + (h->fixK ? 0 : 4), NB));
         chain_ok = npad_nat <= h->npad_max && chain_plan(chain_args, ncf, w, h->fixK ? 0 : 4, npad_nat, npad_nat, 0, -1, 0, (size_t)160 << 10);

@@ -28,6 +28,11 @@
 //
 // Everything is summed in a fixed order: results are run-to-run identical.
 //
+// Only the lower block triangle of S counts: no entry (i, j) whose 32x32 block lies above the block diagonal (j / 32 > i / 32)
+// may influence the result, because the packed multi-rank message (ba_pack_kernel) carries none of them -- under an all-reduce
+// hook they hold the rank's local partial sum.  The camera x intrinsics coupling is therefore read from the intrinsics' rows.
+// tests/host/chain_emu_test.cpp holds the solver to this: it repeats every solve with NaN in those entries.
+//
 // The file compiles twice: with hipcc for gfx950, and with g++ -DCHAIN_HOST_EMU against a fiber emulation of a workgroup
 // (tests/host/chain_emu_test.cpp) that runs the same index arithmetic on the CPU -- the solver is mostly index
 // bookkeeping, and a GPU round trip costs minutes.
@@ -373,7 +378,7 @@ CH_DEV bool ch_step(const ChainArgs& A, const ChFront& F, const unsigned short* 
 // j = lane & 7), r < 6:
 //   v[0..3]   row r of the camera x columns j + 8 t of [earlier cameras | itself]: S[6 n + r][6 (n - ne) + c]; its own block damped,
 //             kept where block row >= block column
-//   v[4]      border rows K_j / rhs (j <= nk) x its column r:  S[6 n + r][koff + j] / rhs[6 n + r]
+//   v[4]      border rows K_j / rhs (j <= nk) x its column r:  S[koff + j][6 n + r] / rhs[6 n + r]
 //   v[5]      diagU of the lane's diagonal element (-1: none): the damping is applied when the value is stored
 //   v[6..8]   LA rows j + 8 t x its column r (only while the window is first filled; zero afterwards: the slot's previous
 //             occupant left fill there)
@@ -407,7 +412,7 @@ CH_DEV void ch_cam_load(const ChainArgs& A, const ChLeafGeo& g, int n, int ne, b
         }
     }
     v[4] = 0.0;
-    if (act && !is_ra && j <= A.nk) v[4] = j < A.nk ? row[A.koff + j] : A.rhs[6 * n + r];
+    if (act && !is_ra && j <= A.nk) v[4] = j < A.nk ? A.S[(size_t)(A.koff + j) * A.ld + 6 * n + r] : A.rhs[6 * n + r];
     // the diagonal element this lane holds (column 6 ne + r of its row) is damped when it is stored: nothing here waits for a load
     v[5] = -1.0;
     if (act && !is_ra && A.diagU && ((6 * ne + r) & 7) == j) v[5] = A.diagU[6 * n + r];
@@ -494,7 +499,7 @@ CH_DEV void ch_stage_load(const ChainArgs& A, const unsigned short* pairs, int n
             St.v[u] = v; St.d[u] = base + 9 * blk + k;
         } else if (e < n1 + n2) {
             const int qq = e - n1, kt = qq / (6 * w), c = qq - 6 * w * kt, br = A.nbd + kt;
-            if (kt < A.nk) St.v[u] = A.S[(size_t)(6 * own_lo + c) * A.ld + A.koff + kt];
+            if (kt < A.nk) St.v[u] = A.S[(size_t)(A.koff + kt) * A.ld + 6 * own_lo + c];
             else if (kt == A.nk) St.v[u] = A.rhs[6 * own_lo + c];
             St.d[u] = base + WW + 9 * ((br / 3) * RB + c / 3) + 3 * (br % 3) + c % 3;
         } else if (l == A.m) {

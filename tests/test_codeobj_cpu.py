@@ -72,3 +72,17 @@ def test_hot_kernels_have_no_scratch_and_fit_their_occupancy(tmp_path):
             assert k["vgpr"] + k["agpr"] <= regs, (name, k)
     for name, k in find("knn2_hamming2_fp4_kernelILi8"):
         assert 48 * 1024 < k["lds"] <= 80 * 1024, (name, k)     # two staged buffers; one 8-wave workgroup per CU
+
+    # The chain solver's two kernels (csrc/ba_chain.hpp): latency-bound, every spilled value would sit on the chain each camera
+    # waits for.  The bound is what the commit before the mirrored reads of S compiled to for gfx950: scratch and spilled registers
+    # equal to it, and the register count inside the same occupancy bucket (chain_sub_kernel: eight waves per workgroup, two per
+    # SIMD, 256 registers; chain_top_kernel: sixteen waves, four per SIMD, 128 registers).
+    #        (name fragment,      scratch bytes, spilled registers, registers of the bucket)     measured there: VGPR + AGPR / scratch / spills
+    chain = [("chain_sub_kernel", 0, 0, 256),                                                  # 215 + 0 / 0 / 0
+             ("chain_top_kernel", 0, 0, 128)]                                                  # 118 + 0 / 0 / 0
+    for sub, scratch, spills, regs in chain:
+        hits = find(sub)
+        assert len(hits) == 1, hits
+        for name, k in hits:
+            assert k["scratch"] == scratch and (k["spill"] or 0) == spills, (name, k)
+            assert k["vgpr"] + k["agpr"] <= regs, (name, k)
