@@ -1104,6 +1104,73 @@ int sfmhip_tsdf_mesh_dev(sfmhip_ctx*, const int dims[3], const double origin[3],
                          const uint32_t* d_csum, int min_weight, double* d_xyz, uint8_t* d_bgr, int vertex_cap, int32_t* d_tri, int triangle_cap,
                          int32_t* d_n_vertices, int32_t* d_n_triangles);   /* enqueue only */
 
+/* ---- Mesh clean-up (extension; not in the reference): connected components and their filter, vertex clustering, vertex normals, Laplacian /
+ * Taubin smoothing of an indexed triangle mesh such as sfmhip_tsdf_mesh produces.  What follows is the definition; every output is a
+ * function of the input alone, the same bits for every run and launch geometry.
+ *   Common rules, for every call below:
+ *   - A mesh is xyz (nv x 3 double), optionally bgr (nv x 3 bytes; NULL: no colours, bgr_out is then not written) and tri (nt x 3 int32).
+ *     0 <= nv <= 2^30, 0 <= nt <= 2^28; nv == 0 or nt == 0 is no error (an array of no rows may be NULL).
+ *   - A triangle is VALID when its three indices lie in [0, nv); repeated indices are allowed.  An invalid triangle takes part in nothing
+ *     and is dropped wherever triangles are written.  A vertex is REFERENCED when a valid triangle names it.
+ *   - Every entry point has a host form, which copies in and out, keeps its temporaries in the context's block cache and returns counts
+ *     through int*, and a _dev form, which works on resident arrays, writes its counts to device int32s, only enqueues on the context's
+ *     stream and never synchronises.
+ *   - Outputs may not alias inputs.  Argument errors return SFMHIP_E_ARG with the outputs left alone.  A failed allocation is an error
+ *     (SFMHIP_E_HIP), the outputs are left alone and the next call works.
+ *
+ * Components.  Two valid triangles are connected when they share a VERTEX index (Open3D's cluster_connected_triangles asks for a shared
+ * edge; the two agree on a manifold mesh, and differ where two surfaces touch in a point, which this definition joins).  A component is
+ * a class of the transitive closure; components are numbered 0 .. C-1 in ascending order of their smallest vertex index.
+ * tri_label[t]: the triangle's component, -1 for an invalid triangle; vertex_label[v] (may be NULL): the component of the triangles that
+ * name v, -1 for an unreferenced vertex; sizes[c] (capacity nt, may be NULL): the number of triangles of component c.  The host form
+ * writes the first C entries of sizes; the _dev form writes all nt, zero from C on.  The components come from a lock-free union-find (one
+ * thread per triangle unites v0 with v1 and with v2); should its retry cap ever be hit, the _dev form reports n_components = -1 and the
+ * host form returns SFMHIP_E_NUMERIC, as sfmhip_cluster_dbscan does. */
+int sfmhip_mesh_components    (sfmhip_ctx*, int nv, const int32_t* tri,   int nt, int32_t* tri_label,   int32_t* vertex_label,   int* n_components,
+                               int32_t* sizes);
+int sfmhip_mesh_components_dev(sfmhip_ctx*, int nv, const int32_t* d_tri, int nt, int32_t* d_tri_label, int32_t* d_vertex_label, int32_t* d_n_components,
+                               int32_t* d_sizes);
+/* Component filter.  min_triangles >= 1, keep_largest 0 or 1.  Component c is kept iff sizes[c] >= min_triangles and, with keep_largest, c is
+ * the component with the most triangles (the smallest number among equals); the winner is decided on the device.  Kept triangles keep their
+ * order.  Kept vertices are those a kept triangle names: they stay in ascending old index and are renumbered by a prefix sum;
+ * vertex_map (nv, may be NULL) is old -> new, -1 for a dropped vertex.  xyz_out / bgr_out have capacity nv rows and tri_out nt rows; only the
+ * first *nv_out / *nt_out rows are written.  min_triangles = 1, keep_largest = 0 is the plain "drop invalid triangles and unreferenced
+ * vertices".  A hit retry cap: both counts -1 on the device, SFMHIP_E_NUMERIC from the host form. */
+int sfmhip_mesh_filter_components    (sfmhip_ctx*, const double* xyz,   const uint8_t* bgr,   int nv, const int32_t* tri,   int nt, int min_triangles, int keep_largest,
+                                      double* xyz_out,   uint8_t* bgr_out,   int32_t* tri_out,   int32_t* vertex_map,   int* nv_out,       int* nt_out);
+int sfmhip_mesh_filter_components_dev(sfmhip_ctx*, const double* d_xyz, const uint8_t* d_bgr, int nv, const int32_t* d_tri, int nt, int min_triangles, int keep_largest,
+                                      double* d_xyz_out, uint8_t* d_bgr_out, int32_t* d_tri_out, int32_t* d_vertex_map, int32_t* d_nv_out, int32_t* d_nt_out);
+/* Simplification by vertex clustering (Open3D's simplify_vertex_clustering with average contraction).  voxel finite and > 0.
+ *   - Clusters and their centroids are exactly sfmhip_voxel_downsample on the referenced vertices: an unreferenced vertex takes no part (it
+ *     enters that call as a row of NaN), and neither does a referenced vertex with a non-finite coordinate.
+ *   - A cluster's colour, per channel, is (2*sum + count) / (2*count) over its vertices in 64-bit integers.
+ *   - A triangle maps through the clusters.  It is dropped when it is invalid, when one of its vertices has no cluster, or when two of
+ *     its mapped indices are equal.  The others are rotated cyclically so that the smallest index comes first -- the orientation stays, so
+ *     (a,b,c) and (a,c,b) stay distinct --, and the output is the DISTINCT triples in ascending lexicographic order.
+ *   - Clusters that no output triangle names are removed and the rest renumbered in ascending order (monotone: order and rotation stay).
+ *   - vertex_map (nv, may be NULL): input vertex -> output vertex, or -1.  Capacities as for the filter.
+ *   - At most 2^21 cells along an axis, as in sfmhip_voxel_downsample: beyond that the _dev form reports nv_out = -1 (nt_out = 0, the
+ *     arrays unspecified) and the host form returns SFMHIP_E_ARG with its outputs left alone.
+ * Nothing about manifoldness is promised: clustering can fold a thin surface onto itself. */
+int sfmhip_mesh_simplify    (sfmhip_ctx*, const double* xyz,   const uint8_t* bgr,   int nv, const int32_t* tri,   int nt, double voxel,
+                             double* xyz_out,   uint8_t* bgr_out,   int32_t* tri_out,   int32_t* vertex_map,   int* nv_out,       int* nt_out);
+int sfmhip_mesh_simplify_dev(sfmhip_ctx*, const double* d_xyz, const uint8_t* d_bgr, int nv, const int32_t* d_tri, int nt, double voxel,
+                             double* d_xyz_out, uint8_t* d_bgr_out, int32_t* d_tri_out, int32_t* d_vertex_map, int32_t* d_nv_out, int32_t* d_nt_out);
+/* Area-weighted vertex normals (normals: nv x 3 double).  For a valid triangle, without contraction: e1 = p1 - p0 and e2 = p2 - p0 component by
+ * component, N = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x).  S_v starts from +0.0 and adds N_t for every corner that names v, in
+ * ascending (t, corner).  l = sqrt((Sx*Sx + Sy*Sy) + Sz*Sz).  The normal is S / l per component when l > 0 and l is finite, else three zeros:
+ * an unreferenced vertex, cancellation, NaN, overflow. */
+int sfmhip_mesh_vertex_normals    (sfmhip_ctx*, const double* xyz,   int nv, const int32_t* tri,   int nt, double* normals);
+int sfmhip_mesh_vertex_normals_dev(sfmhip_ctx*, const double* d_xyz, int nv, const int32_t* d_tri, int nt, double* d_normals);
+/* Laplacian (mu == 0) or Taubin smoothing (Open3D's filter_smooth_laplacian / filter_smooth_taubin, whose defaults are lambda 0.5, mu -0.53).
+ * The neighbours of v are the distinct w != v that share a valid triangle with v, in ascending order w0 < w1 < ...  A step with factor f
+ * reads only the previous iterate: with deg > 0 neighbours m_c = (((+0.0 + x_w0) + x_w1) + ...) / (double)deg and out_c = p_c + f*(m_c - p_c);
+ * with none the vertex does not move.  mu == 0: `iterations` steps with lambda; else `iterations` pairs of steps, lambda then mu.
+ * 0 <= iterations <= 1000, zero iterations is a copy; lambda and mu finite.  Colours do not move.  There is NO boundary pinning: the rim of
+ * an open surface shrinks like everything else. */
+int sfmhip_mesh_smooth    (sfmhip_ctx*, const double* xyz,   int nv, const int32_t* tri,   int nt, int iterations, double lambda, double mu, double* xyz_out);
+int sfmhip_mesh_smooth_dev(sfmhip_ctx*, const double* d_xyz, int nv, const int32_t* d_tri, int nt, int iterations, double lambda, double mu, double* d_xyz_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,9 @@ SYMBOLS = [
     "sfmhip_depth_to_points", "sfmhip_depth_to_points_dev",
     "sfmhip_sweep_costs", "sfmhip_sweep_costs_dev", "sfmhip_sgm_depth", "sfmhip_sgm_depth_dev", "sfmhip_plane_sweep_sgm", "sfmhip_plane_sweep_sgm_dev",
     "sfmhip_tsdf_integrate", "sfmhip_tsdf_integrate_dev", "sfmhip_tsdf_mesh", "sfmhip_tsdf_mesh_dev",
+    "sfmhip_mesh_components", "sfmhip_mesh_components_dev", "sfmhip_mesh_filter_components", "sfmhip_mesh_filter_components_dev",
+    "sfmhip_mesh_simplify", "sfmhip_mesh_simplify_dev", "sfmhip_mesh_vertex_normals", "sfmhip_mesh_vertex_normals_dev",
+    "sfmhip_mesh_smooth", "sfmhip_mesh_smooth_dev",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -228,6 +231,16 @@ def load():
         "sfmhip_tsdf_integrate_dev": (i32, [vp, vp, vp, f64, f64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, sz, vp, vp, vp, vp, vp, vp]),
         "sfmhip_tsdf_mesh": (i32, [vp, vp, vp, f64, vp, vp, vp, i32, vp, vp, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "sfmhip_tsdf_mesh_dev": (i32, [vp, vp, vp, f64, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp]),
+        "sfmhip_mesh_components": (i32, [vp, i32, vp, i32, vp, vp, C.POINTER(i32), vp]),
+        "sfmhip_mesh_components_dev": (i32, [vp, i32, vp, i32, vp, vp, vp, vp]),
+        "sfmhip_mesh_filter_components": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+        "sfmhip_mesh_filter_components_dev": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_mesh_simplify": (i32, [vp, vp, vp, i32, vp, i32, f64, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+        "sfmhip_mesh_simplify_dev": (i32, [vp, vp, vp, i32, vp, i32, f64, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_mesh_vertex_normals": (i32, [vp, vp, i32, vp, i32, vp]),
+        "sfmhip_mesh_vertex_normals_dev": (i32, [vp, vp, i32, vp, i32, vp]),
+        "sfmhip_mesh_smooth": (i32, [vp, vp, i32, vp, i32, i32, f64, f64, vp]),
+        "sfmhip_mesh_smooth_dev": (i32, [vp, vp, i32, vp, i32, i32, f64, f64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

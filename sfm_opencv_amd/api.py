@@ -950,6 +950,85 @@ class Context:
         self._check(self.lib.sfmhip_tsdf_mesh_dev(self.h, dims_a.ctypes.data, origin_a.ctypes.data, float(voxel), _dptr(d_dsum), _dptr(d_wsum), p(d_csum), int(min_weight),
                                                   p(d_xyz), p(d_bgr), int(vertex_cap), p(d_tri), int(triangle_cap), _dptr(d_n_vertices), _dptr(d_n_triangles)))
 
+    # ---------------------------------------------------------------- mesh clean-up (sfmhip_mesh_*)
+    @staticmethod
+    def _mesh_arrays(xyz, bgr, tri):
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3); tri = np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+        if bgr is not None:
+            bgr = np.ascontiguousarray(bgr, np.uint8).reshape(-1, 3)
+            if len(bgr) != len(xyz):
+                raise ValueError("one colour per vertex")
+        return xyz, bgr, tri
+
+    def mesh_components(self, nv, tri):
+        """(tri_label int32 nt, vertex_label int32 nv, sizes int32 C): the connected components of a triangle mesh, two triangles connected
+        when they share a vertex, numbered by their smallest vertex (sfmhip_mesh_components); -1 for an invalid triangle and for an
+        unreferenced vertex"""
+        tri = np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+        nv, nt = int(nv), len(tri)
+        tl = np.full(nt, -1, np.int32); vl = np.full(nv, -1, np.int32); sizes = np.zeros(nt, np.int32); m = C.c_int(0)
+        self._check(self.lib.sfmhip_mesh_components(self.h, nv, tri.ctypes.data, nt, tl.ctypes.data, vl.ctypes.data, C.byref(m), sizes.ctypes.data))
+        return tl, vl, sizes[:m.value].copy()
+
+    def mesh_components_dev(self, nv, d_tri, nt, d_tri_label, d_vertex_label, d_n_components, d_sizes=None):
+        """the same on resident arrays (d_vertex_label / d_sizes may be None); d_sizes holds nt entries, zero from the number of components
+        on: enqueues only"""
+        self._check(self.lib.sfmhip_mesh_components_dev(self.h, int(nv), _dptr(d_tri), int(nt), _dptr(d_tri_label), _dptr(d_vertex_label), _dptr(d_n_components),
+                                                        _dptr(d_sizes)))
+
+    def _mesh_rebuild(self, fn, xyz, bgr, tri, *params):
+        xyz, bgr, tri = self._mesh_arrays(xyz, bgr, tri)
+        nv, nt = len(xyz), len(tri)
+        xo = np.empty((nv, 3), np.float64); bo = None if bgr is None else np.empty((nv, 3), np.uint8); to = np.empty((nt, 3), np.int32)
+        vmap = np.full(nv, -1, np.int32); m, k = C.c_int(0), C.c_int(0)
+        self._check(fn(self.h, xyz.ctypes.data, None if bgr is None else bgr.ctypes.data, nv, tri.ctypes.data, nt, *params, xo.ctypes.data,
+                       None if bo is None else bo.ctypes.data, to.ctypes.data, vmap.ctypes.data, C.byref(m), C.byref(k)))
+        return xo[:m.value].copy(), None if bo is None else bo[:m.value].copy(), to[:k.value].copy(), vmap
+
+    def mesh_filter_components(self, xyz, bgr, tri, min_triangles=1, keep_largest=False):
+        """(xyz, bgr or None, tri, vertex_map): the components with at least min_triangles triangles, or of those only the largest (the
+        smallest number among equals); the kept triangles in their order, the vertices they name in theirs (sfmhip_mesh_filter_components).
+        The defaults drop invalid triangles and unreferenced vertices and nothing else."""
+        return self._mesh_rebuild(self.lib.sfmhip_mesh_filter_components, xyz, bgr, tri, int(min_triangles), int(bool(keep_largest)))
+
+    def mesh_filter_components_dev(self, d_xyz, d_bgr, nv, d_tri, nt, min_triangles, keep_largest, d_xyz_out, d_bgr_out, d_tri_out, d_vertex_map, d_nv_out, d_nt_out):
+        """the same on resident arrays (d_bgr with d_bgr_out, and d_vertex_map, may be None); outputs of nv / nt rows, the int32s at d_nv_out /
+        d_nt_out receive the counts: enqueues only"""
+        self._check(self.lib.sfmhip_mesh_filter_components_dev(self.h, _dptr(d_xyz), _dptr(d_bgr), int(nv), _dptr(d_tri), int(nt), int(min_triangles),
+                                                               int(bool(keep_largest)), _dptr(d_xyz_out), _dptr(d_bgr_out), _dptr(d_tri_out), _dptr(d_vertex_map),
+                                                               _dptr(d_nv_out), _dptr(d_nt_out)))
+
+    def mesh_simplify(self, xyz, bgr, tri, voxel):
+        """(xyz, bgr or None, tri, vertex_map): vertex clustering on cells of edge `voxel` -- the centroids of sfmhip_voxel_downsample over
+        the referenced vertices, the distinct non-degenerate triangles between them in ascending order (sfmhip_mesh_simplify)"""
+        return self._mesh_rebuild(self.lib.sfmhip_mesh_simplify, xyz, bgr, tri, float(voxel))
+
+    def mesh_simplify_dev(self, d_xyz, d_bgr, nv, d_tri, nt, voxel, d_xyz_out, d_bgr_out, d_tri_out, d_vertex_map, d_nv_out, d_nt_out):
+        """the same on resident arrays; the int32 at d_nv_out becomes -1 where the cell is too small for the mesh's extent: enqueues only"""
+        self._check(self.lib.sfmhip_mesh_simplify_dev(self.h, _dptr(d_xyz), _dptr(d_bgr), int(nv), _dptr(d_tri), int(nt), float(voxel), _dptr(d_xyz_out), _dptr(d_bgr_out),
+                                                      _dptr(d_tri_out), _dptr(d_vertex_map), _dptr(d_nv_out), _dptr(d_nt_out)))
+
+    def mesh_vertex_normals(self, xyz, tri):
+        """nv x 3 float64: area-weighted unit normals, zeros where there is none (sfmhip_mesh_vertex_normals)"""
+        xyz, _, tri = self._mesh_arrays(xyz, None, tri)
+        out = np.zeros((len(xyz), 3), np.float64)
+        self._check(self.lib.sfmhip_mesh_vertex_normals(self.h, xyz.ctypes.data, len(xyz), tri.ctypes.data, len(tri), out.ctypes.data))
+        return out
+
+    def mesh_vertex_normals_dev(self, d_xyz, nv, d_tri, nt, d_normals):
+        self._check(self.lib.sfmhip_mesh_vertex_normals_dev(self.h, _dptr(d_xyz), int(nv), _dptr(d_tri), int(nt), _dptr(d_normals)))
+
+    def mesh_smooth(self, xyz, tri, iterations=10, lam=0.5, mu=-0.53):
+        """nv x 3 float64: `iterations` Taubin pairs of steps (lam, then mu), or Laplacian steps with lam where mu == 0
+        (sfmhip_mesh_smooth); no boundary pinning"""
+        xyz, _, tri = self._mesh_arrays(xyz, None, tri)
+        out = np.empty((len(xyz), 3), np.float64)
+        self._check(self.lib.sfmhip_mesh_smooth(self.h, xyz.ctypes.data, len(xyz), tri.ctypes.data, len(tri), int(iterations), float(lam), float(mu), out.ctypes.data))
+        return out
+
+    def mesh_smooth_dev(self, d_xyz, nv, d_tri, nt, iterations, lam, mu, d_xyz_out):
+        self._check(self.lib.sfmhip_mesh_smooth_dev(self.h, _dptr(d_xyz), int(nv), _dptr(d_tri), int(nt), int(iterations), float(lam), float(mu), _dptr(d_xyz_out)))
+
     # ---------------------------------------------------------------- semi-global aggregation of the sweep's costs (sfmhip_sgm_depth)
     def sweep_costs(self, ref, srcs, A, b, planes, wmin, wmax, radius=2, min_sources=1, cost_scale=262144.0):
         """rows x cols x planes uint16: sfmhip_sweep_costs, the sweep's plane scores as costs (65535 = not scored)"""
@@ -1681,12 +1760,17 @@ def tsdf_bounds(sparse_pts, voxels=128, margin=0.1):
 
 
 def dense_mesh_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, radius=2, wmin=None, wmax=None, min_sources=1, min_score=0.5, rel_tol=0.01,
-                       min_consistent=None, ctx=None, voxels=128, trunc_voxels=4, min_weight=2, sgm=None, volume=None):
+                       min_consistent=None, ctx=None, voxels=128, trunc_voxels=4, min_weight=2, sgm=None, volume=None, min_component=None, keep_largest=False,
+                       simplify_voxels=None, smooth=None, normals=False):
     """The dense surface after the bundle adjustment: the depth maps and keep masks of dense_cloud_for_all's chain (same arguments, same
     meaning) stay on the device, all views are fused into one truncated signed distance volume 8 per call (sfmhip_tsdf_integrate_dev) and
     the volume is meshed by marching tetrahedra (sfmhip_tsdf_mesh_dev, once for the counts and once into arrays of that size).  The
     volume is volume = (dims, origin, voxel) or tsdf_bounds(sparse_pts, voxels); the truncation distance trunc_voxels voxels; a voxel
-    counts with min_weight views.  Returns (xyz n x 3 float64, bgr n x 3 uint8, tri m x 3 int32)."""
+    counts with min_weight views.  Returns (xyz n x 3 float64, bgr n x 3 uint8, tri m x 3 int32).
+    The clean-up of the resident mesh, every step off by default and run in this order: min_component / keep_largest (the components with
+    at least that many triangles / only the largest: sfmhip_mesh_filter_components_dev), simplify_voxels (vertex clustering on cells of that
+    many voxels: sfmhip_mesh_simplify_dev), smooth = (iterations, lambda, mu) (sfmhip_mesh_smooth_dev), normals (a fourth array, n x 3
+    float64: sfmhip_mesh_vertex_normals_dev)."""
     import torch
     own = ctx is None
     ctx = ctx or Context(0)
@@ -1719,7 +1803,37 @@ def dense_mesh_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, rad
         torch.cuda.synchronize(dev)
         ctx.tsdf_mesh_dev(dims, origin, voxel, d_dsum, d_wsum, d_csum, min_weight, d_xyz, d_bgr, nv, d_tri, nt, d_n[0:1], d_n[1:2])
         ctx.synchronize()
-        return d_xyz[:nv].cpu().numpy(), d_bgr[:nv].cpu().numpy(), d_tri[:nt].cpu().numpy()
+
+        def rebuilt(call, *params):
+            """a call that writes a new mesh: the arrays it filled and their counts"""
+            o_xyz = torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev); o_bgr = torch.empty((max(nv, 1), 3), dtype=torch.uint8, device=dev)
+            o_tri = torch.empty((max(nt, 1), 3), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            call(d_xyz, d_bgr, nv, d_tri, nt, *params, o_xyz, o_bgr, o_tri, None, d_n[0:1], d_n[1:2])
+            ctx.synchronize()
+            mv, mt = (int(x) for x in d_n.cpu().numpy())
+            if mv < 0:
+                raise SfmHipError("dense_mesh_for_all: the mesh clean-up failed (a cluster cell too small for the mesh's extent, or the union-find's retry cap)")
+            return o_xyz, o_bgr, o_tri, mv, mt
+        if min_component is not None or keep_largest:
+            d_xyz, d_bgr, d_tri, nv, nt = rebuilt(ctx.mesh_filter_components_dev, 1 if min_component is None else int(min_component), bool(keep_largest))
+        if simplify_voxels is not None:
+            d_xyz, d_bgr, d_tri, nv, nt = rebuilt(ctx.mesh_simplify_dev, float(simplify_voxels) * voxel)
+        if smooth is not None:
+            iterations, lam, mu = smooth
+            o_xyz = torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)
+            ctx.mesh_smooth_dev(d_xyz, nv, d_tri, nt, iterations, lam, mu, o_xyz)
+            ctx.synchronize()
+            d_xyz = o_xyz
+        out = (d_xyz[:nv].cpu().numpy(), d_bgr[:nv].cpu().numpy(), d_tri[:nt].cpu().numpy())
+        if normals:
+            d_nrm = torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)
+            ctx.mesh_vertex_normals_dev(d_xyz, nv, d_tri, nt, d_nrm)
+            ctx.synchronize()
+            out += (d_nrm[:nv].cpu().numpy(),)
+        return out
     finally:
         if own:
             ctx.close()

@@ -163,6 +163,10 @@ void sfm_enqueue_scan_u32(hipStream_t st, unsigned* data, size_t n, unsigned* bs
 // either may be null; method: SFMHIP_POINTS_*.  Enqueues on the context's stream, never synchronises.  The grid leaves the number of
 // queries it handed to its brute-force pass in ctx->d_points_fallback.
 int sfm_points_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, int K, int method, int32_t* d_idx, double* d_dist);
+// points.hip: the voxel-grid down-sampling of sfmhip_voxel_downsample_dev on a device cloud of n >= 1 points (mesh.hip clusters the
+// vertices of a mesh with it); d_counts / d_voxel_of may be null.  Enqueues on the context's stream, never synchronises.
+int sfm_voxel_downsample_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double voxel, double* d_centroids, int32_t* d_counts, int32_t* d_voxel_of,
+                                 int32_t* d_n_voxels);
 // normals.hip: plane fit on the K neighbours listed in d_idx (n x K, -1 = none), the fit of normals_kernel
 int sfm_normals_from_knn_enqueue(sfmhip_ctx* ctx, const double* d_pts, const int32_t* d_idx, int n, int K, double* d_normals);
 // the method SFMHIP_POINTS_AUTO stands for at n points

@@ -210,10 +210,14 @@ def read_ply_binary(path):
     return np.frombuffer(raw[end:end + n * PLY_VERTEX.itemsize], PLY_VERTEX).copy()
 
 
-def mesh_ply_bytes(xyz, bgr, tri):
-    """a triangle mesh as a binary little-endian .ply: the vertex element of write_ply_binary (float32 x y z, the normals -- zero: the
-    mesher estimates none --, uchar red green blue from the (b, g, r) rows), then `element face` with `property list uchar int
-    vertex_indices`, three int32 per face.  bgr None: white."""
+MESH_NORMALS_COMMENT = "comment normals area-weighted per vertex"
+
+
+def mesh_ply_bytes(xyz, bgr, tri, normals=None):
+    """a triangle mesh as a binary little-endian .ply: the vertex element of write_ply_binary (float32 x y z, then nx ny nz, uchar red green
+    blue from the (b, g, r) rows), then `element face` with `property list uchar int vertex_indices`, three int32 per face.  bgr None:
+    white.  Without normals the nx ny nz fields are zero and the file is what it has always been; with normals (n x 3) they hold them
+    as float32 and the header carries the line MESH_NORMALS_COMMENT, by which read_mesh_ply tells the two apart."""
     xyz = np.asarray(xyz, np.float64).reshape(-1, 3); tri = np.asarray(tri, np.int32).reshape(-1, 3)
     bgr = np.full((len(xyz), 3), 255, np.uint8) if bgr is None else np.asarray(bgr, np.uint8).reshape(-1, 3)
     if len(bgr) != len(xyz) or (len(tri) and (tri.min() < 0 or tri.max() >= len(xyz))):
@@ -221,9 +225,15 @@ def mesh_ply_bytes(xyz, bgr, tri):
     v = np.zeros(len(xyz), PLY_VERTEX)
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     v["b"], v["g"], v["r"] = bgr[:, 0], bgr[:, 1], bgr[:, 2]
+    if normals is not None:
+        normals = np.asarray(normals, np.float64).reshape(-1, 3)
+        if len(normals) != len(xyz):
+            raise ValueError("one normal per vertex")
+        v["nx"], v["ny"], v["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     f = np.zeros(len(tri), PLY_FACE)
     f["n"] = 3; f["v"] = tri
-    hdr = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v),
+    hdr = ["ply", "format binary_little_endian 1.0"] + ([MESH_NORMALS_COMMENT] if normals is not None else []) + [
+           "element vertex %d" % len(v),
            "property float x", "property float y", "property float z",
            "property float nx", "property float ny", "property float nz",
            "property uchar red", "property uchar green", "property uchar blue",
@@ -231,13 +241,14 @@ def mesh_ply_bytes(xyz, bgr, tri):
     return ("\n".join(hdr) + "\n").encode("ascii") + v.tobytes() + f.tobytes()
 
 
-def write_mesh_ply(path, xyz, bgr, tri):
+def write_mesh_ply(path, xyz, bgr, tri, normals=None):
     with open(path, "wb") as f:
-        f.write(mesh_ply_bytes(xyz, bgr, tri))
+        f.write(mesh_ply_bytes(xyz, bgr, tri, normals))
 
 
 def read_mesh_ply(path):
-    """(xyz n x 3 float32, bgr n x 3 uint8, tri m x 3 int32) of a file write_mesh_ply wrote"""
+    """(xyz n x 3 float32, bgr n x 3 uint8, tri m x 3 int32) of a file write_mesh_ply wrote, and a fourth array (normals n x 3 float32) for
+    a file that was written with normals"""
     raw = open(path, "rb").read()
     end = raw.index(b"end_header\n") + len(b"end_header\n")
     n = int(re.search(rb"element vertex (\d+)", raw[:end]).group(1)); m = int(re.search(rb"element face (\d+)", raw[:end]).group(1))
@@ -245,4 +256,7 @@ def read_mesh_ply(path):
     f = np.frombuffer(raw, PLY_FACE, m, end + n * PLY_VERTEX.itemsize)
     if len(raw) != end + n * PLY_VERTEX.itemsize + m * PLY_FACE.itemsize or (m and (f["n"] != 3).any()):
         raise ValueError("not a triangle mesh of write_mesh_ply")
-    return np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["b"], v["g"], v["r"]], 1), f["v"].copy()
+    out = (np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["b"], v["g"], v["r"]], 1), f["v"].copy())
+    if (MESH_NORMALS_COMMENT + "\n").encode("ascii") in raw[:end]:
+        out += (np.stack([v["nx"], v["ny"], v["nz"]], 1),)
+    return out

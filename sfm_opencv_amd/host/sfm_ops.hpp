@@ -812,6 +812,15 @@ struct DenseOptions {
     double mesh_trunc_voxels = 4.0, mesh_margin = 0.1;
     int mesh_dims[3] = { 0, 0, 0 };
     double mesh_origin[3] = { 0.0, 0.0, 0.0 }, mesh_voxel = 0.0;
+    // the clean-up of the mesh (clean_mesh), every step off by default and run in this order: the components with at least
+    // mesh_min_component triangles (0: off) / only the largest; vertex clustering on cells of mesh_simplify_voxels voxels (0: off);
+    // mesh_smooth_iterations Taubin pairs of steps (lambda, then mu), Laplacian steps where mu == 0 (0: off); vertex normals
+    int mesh_min_component = 0;
+    bool mesh_keep_largest = false;
+    double mesh_simplify_voxels = 0.0;
+    int mesh_smooth_iterations = 0;
+    double mesh_smooth_lambda = 0.5, mesh_smooth_mu = -0.53;
+    bool mesh_normals = false;
 };
 // numpy.percentile(z, q) with its default linear interpolation, z sorted ascending
 inline double dense_percentile(const std::vector<double>& z, const double q)
@@ -961,12 +970,60 @@ inline bool tsdf_bounds(const std::vector<Point3d>& sparse_pts, const int voxels
     }
     return true;
 }
+// The clean-up of a triangle mesh in place, the mirror of the five sfmhip_mesh_* calls in the order api.dense_mesh_for_all runs them:
+// min_component >= 1 or keep_largest: sfmhip_mesh_filter_components; cell > 0: sfmhip_mesh_simplify on cells of that edge; iterations > 0:
+// sfmhip_mesh_smooth; normals != nullptr: sfmhip_mesh_vertex_normals into it.  Returns the number of triangles, -1 on error.
+inline int clean_mesh(std::vector<Point3d>& pts, std::vector<Vec3b>& colors, std::vector<int32_t>& tris, const int min_component, const bool keep_largest,
+                      const double cell, const int iterations, const double lambda, const double mu, std::vector<Point3d>* normals)
+{
+    sfmhip_ctx* ctx = context();
+    if (pts.size() != colors.size() || tris.size() % 3 != 0) return -1;
+    auto fail = [&]() { printf("[Err]: clean_mesh: %s\n", sfmhip_last_error(ctx)); return -1; };
+    // a call that writes a new mesh into arrays of the old one's size
+    auto rebuilt = [&](auto&& call) {
+        const int nv = (int)pts.size(), nt = (int)(tris.size() / 3);
+        std::vector<Point3d> p2(nv); std::vector<Vec3b> c2(nv); std::vector<int32_t> t2((size_t)nt * 3);
+        int mv = 0, mt = 0;
+        if (call(nv ? &pts[0].x : nullptr, nv ? &colors[0].v[0] : nullptr, nv, tris.data(), nt, nv ? &p2[0].x : nullptr, nv ? &c2[0].v[0] : nullptr, t2.data(), &mv, &mt) !=
+            SFMHIP_OK)
+            return false;
+        p2.resize(mv); c2.resize(mv); t2.resize((size_t)mt * 3);
+        pts.swap(p2); colors.swap(c2); tris.swap(t2);
+        return true;
+    };
+    if (min_component >= 1 || keep_largest) {
+        if (!rebuilt([&](const double* x, const uint8_t* c, int nv, const int32_t* t, int nt, double* xo, uint8_t* co, int32_t* to, int* mv, int* mt) {
+                return sfmhip_mesh_filter_components(ctx, x, c, nv, t, nt, std::max(min_component, 1), keep_largest ? 1 : 0, xo, co, to, nullptr, mv, mt);
+            }))
+            return fail();
+    }
+    if (cell > 0.0) {
+        if (!rebuilt([&](const double* x, const uint8_t* c, int nv, const int32_t* t, int nt, double* xo, uint8_t* co, int32_t* to, int* mv, int* mt) {
+                return sfmhip_mesh_simplify(ctx, x, c, nv, t, nt, cell, xo, co, to, nullptr, mv, mt);
+            }))
+            return fail();
+    }
+    const int nv = (int)pts.size(), nt = (int)(tris.size() / 3);
+    if (iterations > 0 && nv > 0) {
+        std::vector<Point3d> p2(nv);
+        if (sfmhip_mesh_smooth(ctx, &pts[0].x, nv, tris.data(), nt, iterations, lambda, mu, &p2[0].x) != SFMHIP_OK) return fail();
+        pts.swap(p2);
+    }
+    if (normals) {
+        normals->assign(nv, Point3d());
+        if (nv > 0 && sfmhip_mesh_vertex_normals(ctx, &pts[0].x, nv, tris.data(), nt, &(*normals)[0].x) != SFMHIP_OK) return fail();
+    }
+    return nt;
+}
+
 // The dense surface after the bundle adjustment: dense_cloud_for_all's depth maps and keep masks (same arguments), every view fused into
 // one truncated signed distance volume, 8 views per call, and the volume meshed by marching tetrahedra (once for the counts, once into
-// arrays of that size).  out_tris: three vertex numbers per triangle.  Returns the number of triangles, -1 on error.
+// arrays of that size), then cleaned up as the mesh_* options say (clean_mesh; out_normals is filled where opt.mesh_normals is set and it is
+// given).  out_tris: three vertex numbers per triangle.  Returns the number of triangles, -1 on error.
 inline int dense_mesh_for_all(const std::vector<const uint8_t*>& images, const int rows, const int cols, const int channels, const Mat& intrinsic,
                               const std::vector<Mat>& extrinsics, const std::vector<Point3d>& sparse_pts, const DenseOptions& opt,
-                              std::vector<Point3d>& out_pts, std::vector<Vec3b>& out_colors, std::vector<int32_t>& out_tris)
+                              std::vector<Point3d>& out_pts, std::vector<Vec3b>& out_colors, std::vector<int32_t>& out_tris,
+                              std::vector<Point3d>* out_normals = nullptr)
 {
     sfmhip_ctx* ctx = context();
     out_pts.clear(); out_colors.clear(); out_tris.clear();
@@ -1024,6 +1081,10 @@ inline int dense_mesh_for_all(const std::vector<const uint8_t*>& images, const i
         printf("[Err]: dense_mesh_for_all: %s\n", sfmhip_last_error(ctx));
         return -1;
     }
+    const bool want_normals = opt.mesh_normals && out_normals;
+    if (opt.mesh_min_component >= 1 || opt.mesh_keep_largest || opt.mesh_simplify_voxels > 0.0 || opt.mesh_smooth_iterations > 0 || want_normals)
+        return clean_mesh(out_pts, out_colors, out_tris, opt.mesh_min_component, opt.mesh_keep_largest, opt.mesh_simplify_voxels * voxel, opt.mesh_smooth_iterations,
+                          opt.mesh_smooth_lambda, opt.mesh_smooth_mu, want_normals ? out_normals : nullptr);
     return nt;
 }
 
@@ -1182,18 +1243,23 @@ inline void write_ply_binary(const std::string& path, const std::vector<Pt3DPly>
     }
 }
 
-// a triangle mesh as a binary little-endian .ply: write_ply_binary's vertex element (the normals zero: the mesher estimates none; the
-// colours (b, g, r) rows written red, green, blue), then `element face` with a uchar count of 3 and three int32 per face
-inline void write_mesh_ply(const std::string& path, const std::vector<Point3d>& pts, const std::vector<Vec3b>& colors, const std::vector<int32_t>& tris)
+// a triangle mesh as a binary little-endian .ply: write_ply_binary's vertex element (the colours (b, g, r) rows written red, green, blue),
+// then `element face` with a uchar count of 3 and three int32 per face.  Without normals the nx ny nz fields are zero and the file is
+// what it has always been; with them (one per vertex) they are written as floats and the header carries a comment line that says so
+// (formats.MESH_NORMALS_COMMENT in the Python writer, which this mirrors byte for byte)
+inline void write_mesh_ply(const std::string& path, const std::vector<Point3d>& pts, const std::vector<Vec3b>& colors, const std::vector<int32_t>& tris,
+                           const std::vector<Point3d>* normals = nullptr)
 {
-    assert(pts.size() == colors.size() && tris.size() % 3 == 0);
+    assert(pts.size() == colors.size() && tris.size() % 3 == 0 && (!normals || normals->size() == pts.size()));
     std::ofstream f(path, std::ios::out | std::ios::binary);
     assert(f.is_open());
-    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << pts.size() << "\nproperty float x\nproperty float y\nproperty float z\n"
+    f << "ply\nformat binary_little_endian 1.0\n" << (normals ? "comment normals area-weighted per vertex\n" : "") << "element vertex " << pts.size()
+      << "\nproperty float x\nproperty float y\nproperty float z\n"
          "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
          "element face " << tris.size() / 3 << "\nproperty list uchar int vertex_indices\nend_header\n";
     for (size_t i = 0; i < pts.size(); ++i) {
-        const float v[6] = { (float)pts[i].x, (float)pts[i].y, (float)pts[i].z, 0.0f, 0.0f, 0.0f };
+        const float v[6] = { (float)pts[i].x, (float)pts[i].y, (float)pts[i].z, normals ? (float)(*normals)[i].x : 0.0f, normals ? (float)(*normals)[i].y : 0.0f,
+                             normals ? (float)(*normals)[i].z : 0.0f };
         const uint8_t rgb[3] = { colors[i][2], colors[i][1], colors[i][0] };
         f.write((const char*)v, 24); f.write((const char*)rgb, 3);
     }
