@@ -10,7 +10,7 @@ median and min .. max.  The input is the mesh of experiments/time_tsdf.py: 8 vie
   --trace DIR / --stats DIR   the kernels of each call, from a kernel trace of its own:
                   rocprofv3 --kernel-trace --output-format csv -d DIR -- python experiments/time_mesh.py --trace DIR
                   python experiments/time_mesh.py --stats DIR
-              per call: the time in the radix sort's and the scan's kernels (ba_setup.hpp) and in each kernel of mesh.hip / points.hip.
+              per call: the time in the radix sort's and the scan's kernels (sortscan.hip) and in each kernel of mesh.hip / points.hip.
 
     python experiments/time_mesh.py [--runs 5] [--sizes 128,256]
 """
@@ -214,7 +214,7 @@ def run_stats(a):
             assert per * p["calls"] == len(seg), (name, len(seg), p["calls"])
             tot = {}
             for i in seg[per:]:
-                key = "radix sort (setup_rs_*)" if "setup_rs" in names[i] else "scans (setup_scan_*)" if "setup_scan" in names[i] else names[i]
+                key = "radix sort (sfm_sort_*)" if "sfm_sort_" in names[i] else "scans (sfm_scan_*)" if "sfm_scan_" in names[i] else names[i]
                 tot[key] = tot.get(key, 0.0) + (int(rows[i]["End_Timestamp"]) - int(rows[i]["Start_Timestamp"])) / 1e6 / (p["calls"] - 1)
             total = sum(tot.values())
             print(f"    {name}: {per} launches, {total:.3f} ms in kernels")

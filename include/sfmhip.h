@@ -369,6 +369,15 @@ int  sfmhip_match_pairs_multi_ex(sfmhip_ctx* const* ctxs, int n_ctx, int kind, c
                                  double ratio, float floor_, float mult, int flags, sfm_dmatch* matches, int max_per_pair, int32_t* counts);
 /* test hook: the next n device allocations of the context fail (SFMHIP_E_HIP) -- what an out-of-memory device looks like to its callers */
 int  sfmhip_debug_fail_allocations(sfmhip_ctx*, int n);
+/* test hooks: the two device primitives under every list of the library (csrc/sortscan.hpp), on host arrays.
+ * sfmhip_debug_sort_pairs: the stable radix sort of n (64-bit key, 32-bit value) pairs; vals NULL: the values are 0 .. n - 1.  It moves
+ * 8 bits per pass and makes at least one pass, so the order is that of the low 8 * max(1, ceil(bits / 8)) bits of the keys (not of the
+ * low `bits` bits), equal ones in their input order; the keys come back whole.  0 <= bits <= 64.
+ * sfmhip_debug_scan_u32: out[i] = in[0] + .. + in[i - 1] modulo 2^32; *total64_out (may be NULL) = the sum of all n, exact only while every
+ * tile of 4096 counters and every group of 256 consecutive tile totals sums below 2^32 (32-bit partial sums under a 64-bit carry), 0 at n = 0.
+ * Both: n < 2^31, no output may overlap an input or the other output (SFMHIP_E_ARG), one block of the cache, the stream drained on return. */
+int  sfmhip_debug_sort_pairs(sfmhip_ctx*, const uint64_t* keys, const uint32_t* vals_or_null, size_t n, int bits, uint64_t* keys_out, uint32_t* vals_out);
+int  sfmhip_debug_scan_u32(sfmhip_ctx*, const uint32_t* in, size_t n, uint32_t* out, uint64_t* total64_out);
 /* run the LM loop to termination */
 int  sfmhip_ba_run(sfmhip_ba*, sfm_ba_summary* summary);
 /* run exactly n_iter LM iterations (tolerance checks disabled); state carries over between calls */

@@ -118,6 +118,23 @@ class Context:
         """release the device blocks the context keeps from destroyed BA problems (sfmhip_trim)"""
         self._check(self.lib.sfmhip_trim(self.h))
 
+    def debug_sort_pairs(self, keys, vals=None, bits=64):
+        """(keys, values) after the library's stable radix sort of uint64 keys with uint32 values (None: the element index), ordered by
+        the low 8 * max(1, ceil(bits / 8)) bits of the keys (sfmhip_debug_sort_pairs, test helper)"""
+        k = np.ascontiguousarray(keys, np.uint64)
+        v = None if vals is None else np.ascontiguousarray(vals, np.uint32)
+        ko = np.empty(k.size, np.uint64); vo = np.empty(k.size, np.uint32)
+        self._check(self.lib.sfmhip_debug_sort_pairs(self.h, k.ctypes.data, None if v is None else v.ctypes.data, k.size, int(bits),
+                                                     ko.ctypes.data, vo.ctypes.data))
+        return ko, vo
+
+    def debug_scan_u32(self, counters):
+        """(exclusive prefix sums modulo 2^32 as uint32, the 64-bit total) of uint32 counters (sfmhip_debug_scan_u32, test helper)"""
+        a = np.ascontiguousarray(counters, np.uint32)
+        out = np.empty(a.size, np.uint32); total = C.c_uint64(0xffffffffffffffff)
+        self._check(self.lib.sfmhip_debug_scan_u32(self.h, a.ctypes.data, a.size, out.ctypes.data, C.byref(total)))
+        return out, total.value
+
     def set_kernel_timing(self, enable=True):
         """bracket every kNN launch sequence with HIP events (sfmhip_set_kernel_timing)"""
         self._check(self.lib.sfmhip_set_kernel_timing(self.h, 1 if enable else 0))

@@ -49,6 +49,7 @@
 // pixels, 64201 on 10 MP), and the flag below is what stands behind the estimate.  A list that
 // would overflow raises a flag: the host entries return SFMHIP_E_ARG with a message, the enqueue-only entry leaves -1 in *d_n_found.
 #include "common.hpp"
+#include "sortscan.hpp"
 #pragma clang fp contract(off)
 #include <cmath>
 
@@ -845,32 +846,27 @@ static int akaze_enqueue_scale_space(sfmhip_ctx* ctx, const AkPlan& P, const AkA
     return SFMHIP_OK;
 }
 
-// the lists of one carve: candidates, suppression state, survivors, sort areas (K rows each)
+// the lists of one carve: candidates, suppression state, survivors (K rows each), the sort of K keys and the K + 1 flags of the fit
 struct AkLists {
     AkCand *raw, *cand; int *slot, *pend, *victim; AkFit* fit; pu32* list;
-    pu64* k[2]; pu32* v[2]; pu32 *hist, *bsum, *flag, *scan;
-    size_t o_raw, o_cand, o_slot, o_pend, o_victim, o_fit, o_list, o_k[2], o_v[2], o_hist, o_bsum, o_flag, o_scan;
+    SfmSort keys; SfmScan flags;
+    size_t o_raw, o_cand, o_slot, o_pend, o_victim, o_fit, o_list;
     void carve(SfmCarve& c, size_t K)
     {
         o_raw = c(K * sizeof(AkCand)); o_cand = c(K * sizeof(AkCand)); o_slot = c(K * 4); o_pend = c(K * 4); o_victim = c(K * 4);
         o_fit = c(K * sizeof(AkFit)); o_list = c(K * 4);
-        for (int i = 0; i < 2; ++i) { o_k[i] = c(K * 8); o_v[i] = c(K * 4); }
-        o_hist = c(sfm_radix_sort_hist_words(K) * 4); o_bsum = c(sfm_radix_sort_bsum_words(K) * 4);
-        o_flag = c((K + 1) * 4); o_scan = c(sfm_scan_bsum_words(K + 1) * 4);
+        keys.carve(c, K); flags.carve(c, K + 1);
     }
     void bind(char* w)
     {
         raw = (AkCand*)(w + o_raw); cand = (AkCand*)(w + o_cand); slot = (int*)(w + o_slot); pend = (int*)(w + o_pend); victim = (int*)(w + o_victim);
         fit = (AkFit*)(w + o_fit); list = (pu32*)(w + o_list);
-        for (int i = 0; i < 2; ++i) { k[i] = (pu64*)(w + o_k[i]); v[i] = (pu32*)(w + o_v[i]); }
-        hist = (pu32*)(w + o_hist); bsum = (pu32*)(w + o_bsum); flag = (pu32*)(w + o_flag); scan = (pu32*)(w + o_scan);
+        keys.bind(w); flags.bind(w);
     }
-    // one stable sort of the keys in k[0] (values: v[0], or the row index); returns the side that holds the result
-    int sort(hipStream_t st, size_t K, int bits, bool identity) { return sfm_enqueue_radix_sort(st, k[0], k[1], v[0], v[1], hist, bsum, K, bits, identity); }
 };
 
 // both passes of find_extrema on the sorted list S.cand (its length in cnt->n_raw): afterwards the survivors' indices are in
-// S.v[returned side] in aux order, their number in cnt->n_kept
+// S.keys.v[returned side] in aux order, their number in cnt->n_kept
 static int akaze_enqueue_suppress(hipStream_t st, AkLists& S, size_t K, AkCounters* cnt, const AkTab* tab, int ysorted)
 {
     const int kb = ceil_div((int)K, 256), rb = std::min(kb, 2048);
@@ -880,12 +876,12 @@ static int akaze_enqueue_suppress(hipStream_t st, AkLists& S, size_t K, AkCounte
         hipLaunchKernelGGL(akaze_suppress_publish_kernel, dim3(rb), dim3(256), 0, st, (pu32)K, (const AkCounters*)cnt, S.slot, S.pend, (const int*)S.victim, r);
     }
     hipLaunchKernelGGL(akaze_suppress_kernel, dim3(1), dim3(1024), 0, st, (const AkCand*)S.cand, (pu32)K, cnt, tab, ysorted, S.slot, S.pend, S.victim);
-    hipLaunchKernelGGL(akaze_suppress2_kernel, dim3(kb), dim3(256), 0, st, (const AkCand*)S.cand, (pu32)K, cnt, tab, ysorted, (const int*)S.slot, S.k[0]);
-    return S.sort(st, K, 32, true);
+    hipLaunchKernelGGL(akaze_suppress2_kernel, dim3(kb), dim3(256), 0, st, (const AkCand*)S.cand, (pu32)K, cnt, tab, ysorted, (const int*)S.slot, S.keys.k[0]);
+    return S.keys.sort(st, K, 0, 32, true);
 }
 
 // find_extrema + subpixel: stage 0 stops after the ordered raw maxima, 1 after the suppression, 2 after the fit (S.list: the rows of S.fit that
-// hold, in aux order; cnt->n_fit of them).  *order_side: the side of S.v with the survivors of stage 1
+// hold, in aux order; cnt->n_fit of them).  *order_side: the side of S.keys.v with the survivors of stage 1
 static void akaze_enqueue_detect(sfmhip_ctx* ctx, const AkPlan& P, const AkAreas& A, AkLists& S, int stage, int* order_side)
 {
     hipStream_t st = ctx->stream;
@@ -898,18 +894,18 @@ static void akaze_enqueue_detect(sfmhip_ctx* ctx, const AkPlan& P, const AkAreas
         hipLaunchKernelGGL(akaze_maxima_kernel, akaze_grid(H - 2 * b, W - 2 * b), dim3(256), 0, st, (const float*)(A.lev + T.off[i] + 3 * (size_t)H * W), H, W, b, i,
                            (float)(1 << T.octave[i]), S.raw, (pu32)K, A.cnt);
     }
-    hipLaunchKernelGGL(akaze_key_kernel, dim3(kb), dim3(256), 0, st, (const AkCand*)S.raw, (pu32)K, (const AkCounters*)A.cnt, S.k[0]);
-    int side = S.sort(st, K, 32, true);
-    hipLaunchKernelGGL(akaze_gather_kernel, dim3(kb), dim3(256), 0, st, (const AkCand*)S.raw, (const pu32*)S.v[side], (pu32)K, (const AkCounters*)A.cnt, S.cand);
+    hipLaunchKernelGGL(akaze_key_kernel, dim3(kb), dim3(256), 0, st, (const AkCand*)S.raw, (pu32)K, (const AkCounters*)A.cnt, S.keys.k[0]);
+    int side = S.keys.sort(st, K, 0, 32, true);
+    hipLaunchKernelGGL(akaze_gather_kernel, dim3(kb), dim3(256), 0, st, (const AkCand*)S.raw, (const pu32*)S.keys.v[side], (pu32)K, (const AkCounters*)A.cnt, S.cand);
     *order_side = 0;
     if (stage < 1) return;
     side = akaze_enqueue_suppress(st, S, K, A.cnt, A.tab, 1);
     *order_side = side;
     if (stage < 2) return;
-    hipLaunchKernelGGL(akaze_subpixel_kernel, dim3(kb1), dim3(256), 0, st, (const AkCand*)S.cand, (const pu32*)S.v[side], (pu32)K, (const AkCounters*)A.cnt,
-                       (const AkTab*)A.tab, (const float*)A.lev, S.fit, S.flag);
-    sfm_enqueue_scan_u32(st, S.flag, K + 1, S.scan);
-    hipLaunchKernelGGL(akaze_compact_kernel, dim3(kb), dim3(256), 0, st, (const pu32*)S.flag, (pu32)K, A.cnt, S.list);
+    hipLaunchKernelGGL(akaze_subpixel_kernel, dim3(kb1), dim3(256), 0, st, (const AkCand*)S.cand, (const pu32*)S.keys.v[side], (pu32)K, (const AkCounters*)A.cnt,
+                       (const AkTab*)A.tab, (const float*)A.lev, S.fit, S.flags.data);
+    S.flags.scan(st, K + 1);
+    hipLaunchKernelGGL(akaze_compact_kernel, dim3(kb), dim3(256), 0, st, (const pu32*)S.flags.data, (pu32)K, A.cnt, S.list);
 }
 
 // everything behind sfmhip_akaze_extract_dev
@@ -938,13 +934,13 @@ static int akaze_enqueue(sfmhip_ctx* ctx, const uint8_t* d_img, int rows, int co
     akaze_enqueue_detect(ctx, P, A, S, 2, &side);
     // std::stable_sort on descending response over the rows that passed the fit, in aux order
     const int kb = ceil_div((int)K, 256);
-    hipLaunchKernelGGL(akaze_resp_key_kernel, dim3(kb), dim3(256), 0, st, (const AkFit*)S.fit, (const pu32*)S.list, (pu32)K, (const AkCounters*)A.cnt, S.k[0]);
-    SFM_HIP_TRY(ctx, hipMemcpyAsync(S.v[0], S.list, K * 4, hipMemcpyDeviceToDevice, st));
-    side = S.sort(st, K, 32, false);
+    hipLaunchKernelGGL(akaze_resp_key_kernel, dim3(kb), dim3(256), 0, st, (const AkFit*)S.fit, (const pu32*)S.list, (pu32)K, (const AkCounters*)A.cnt, S.keys.k[0]);
+    SFM_HIP_TRY(ctx, hipMemcpyAsync(S.keys.v[0], S.list, K * 4, hipMemcpyDeviceToDevice, st));
+    side = S.keys.sort(st, K, 0, 32, false);
     hipLaunchKernelGGL(akaze_count_kernel, dim3(1), dim3(1), 0, st, (const AkCounters*)A.cnt, max_features, d_n_found);
     if (cap > 0) {
         const int db = (int)std::min<size_t>(ceil_div(cap, 4), (size_t)ctx->num_cus * 16);
-        hipLaunchKernelGGL(akaze_describe_kernel, dim3(db), dim3(256), 0, st, (const AkTab*)A.tab, (const float*)A.lev, (const AkFit*)S.fit, (const pu32*)S.v[side],
+        hipLaunchKernelGGL(akaze_describe_kernel, dim3(db), dim3(256), 0, st, (const AkTab*)A.tab, (const float*)A.lev, (const AkFit*)S.fit, (const pu32*)S.keys.v[side],
                            (const int32_t*)d_n_found, cap, d_kp, d_desc);
     }
     SFM_HIP_TRY(ctx, hipGetLastError());
@@ -1069,7 +1065,7 @@ int sfmhip_akaze_extrema(sfmhip_ctx* ctx, const uint8_t* img, int rows, int cols
     if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
     int side = 0;
     akaze_enqueue_detect(ctx, P, A, S, stage, &side);
-    hipLaunchKernelGGL(akaze_stage_out_kernel, dim3(ceil_div((int)K, 256)), dim3(256), 0, st, stage, (const AkCand*)S.cand, (const pu32*)S.v[side], (const AkFit*)S.fit,
+    hipLaunchKernelGGL(akaze_stage_out_kernel, dim3(ceil_div((int)K, 256)), dim3(256), 0, st, stage, (const AkCand*)S.cand, (const pu32*)S.keys.v[side], (const AkFit*)S.fit,
                        (const pu32*)S.list, (pu32)K, (const AkCounters*)A.cnt, (const AkTab*)A.tab, cap, (float*)(w + o_xysr), (int32_t*)(w + o_ol), (int32_t*)(w + o_n));
     hipError_t e = hipGetLastError();
     int32_t n = 0;
@@ -1119,7 +1115,7 @@ int sfmhip_akaze_suppress(sfmhip_ctx* ctx, const float* xyr, const int32_t* leve
     const int kb = ceil_div(n, 256);
     hipLaunchKernelGGL(akaze_pack_kernel, dim3(kb), dim3(256), 0, st, (const float*)(w + o_xyr), (const int32_t*)(w + o_lvl), (pu32)n, cnt, S.cand);
     const int side = akaze_enqueue_suppress(st, S, K, cnt, (const AkTab*)(w + o_tab), 0);
-    hipLaunchKernelGGL(akaze_kept_out_kernel, dim3(kb), dim3(256), 0, st, (const pu32*)S.v[side], (pu32)K, (const AkCounters*)cnt, (int32_t*)(w + o_kept), (int32_t*)(w + o_n));
+    hipLaunchKernelGGL(akaze_kept_out_kernel, dim3(kb), dim3(256), 0, st, (const pu32*)S.keys.v[side], (pu32)K, (const AkCounters*)cnt, (int32_t*)(w + o_kept), (int32_t*)(w + o_n));
     if (e == hipSuccess) e = hipGetLastError();
     int32_t m = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&m, w + o_n, sizeof m, hipMemcpyDeviceToHost, st);

@@ -1212,8 +1212,10 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     su64 *obsK[2], *ptK[2]; su32 *obsV[2], *ptV[2], *st_pt, *hist, *bsum; int* d_flags; su64* d_total;
     for (int i = 0; i < 2; ++i) { TRY_RC(T.get(&obsK[i], (size_t)nobs)); TRY_RC(T.get(&obsV[i], (size_t)nobs)); TRY_RC(T.get(&ptK[i], (size_t)np)); TRY_RC(T.get(&ptV[i], (size_t)np)); }
     TRY_RC(T.get(&st_pt, (size_t)np + 1));
-    TRY_RC(T.get(&hist, 256 * setup_rs_tiles(nmax) + 1)); TRY_RC(T.get(&bsum, setup_scan_tiles(std::max(256 * setup_rs_tiles(nmax), nmax + 1)) + 1));
+    // one pair of scratch areas for every sort and every scan of this phase
+    TRY_RC(T.get(&hist, SfmSort::hist_words(nmax) + 1)); TRY_RC(T.get(&bsum, std::max(SfmSort::bsum_words(nmax), SfmScan::bsum_words(nmax + 1)) + 1));
     TRY_RC(T.get(&d_flags, 4)); TRY_RC(T.get(&d_total, 2));
+    const SfmSort obsS = SfmSort::of(obsK[0], obsK[1], obsV[0], obsV[1], hist, bsum), ptS = SfmSort::of(ptK[0], ptK[1], ptV[0], ptV[1], hist, bsum);
     SFM_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int), st));
     stamp("tables + temporaries");
     const int cb = std::max(1, setup_bit_width((su64)nc - 1)), pb = std::max(1, setup_bit_width((su64)std::max(np, 1) - 1));
@@ -1222,8 +1224,7 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     int ro = 0;
     if (nobs) {
         hipLaunchKernelGGL(setup_obs_key_kernel, dim3(gobs), dim3(256), 0, st, (const int*)d_rc, (const int*)d_rp, nobs, nc, np, cb, obsK[0], d_flags);
-        SetupSortBufs B = { { obsK[0], obsK[1] }, { obsV[0], obsV[1] }, hist, bsum };
-        ro = setup_radix_sort(st, B, (size_t)nobs, cb + pb, true);
+        ro = obsS.sort(st, (size_t)nobs, 0, cb + pb, true);
     }
     // first observation of every point in the sorted list (no counters, no atomics: the run boundaries of the sorted keys), longest track
     hipLaunchKernelGGL(setup_starts_kernel, dim3((unsigned)ceil_div(nobs + 1, 256)), dim3(256), 0, st, (const su64*)obsK[ro], (size_t)nobs, cb, (su64)np, st_pt);
@@ -1244,17 +1245,16 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     // ---- points by camera list: LSD over groups of list positions, last group first
     {
         const int mmax = std::max(flags[1], 1), b = std::max(1, setup_bit_width((su64)nc)), G = 64 / b, groups = ceil_div(mmax, G);
-        su64* K[2] = { ptK[0], ptK[1] }; su32* V[2] = { ptV[0], ptV[1] };
+        int rp = 0;
         for (int g = groups - 1; g >= 0 && np > 0; --g) {
             const int j0 = g * G, npos = std::min(G, mmax - j0);
-            hipLaunchKernelGGL(setup_ptkey_kernel, dim3(gpt), dim3(256), 0, st, g == groups - 1 ? (const su32*)nullptr : (const su32*)V[0], np, (const su32*)st_pt,
-                               (const su64*)obsK[ro], (1ull << cb) - 1ull, j0, npos, b, K[0]);
-            SetupSortBufs B = { { K[0], K[1] }, { V[0], V[1] }, hist, bsum };
-            if (setup_radix_sort(st, B, (size_t)np, npos * b, g == groups - 1)) { std::swap(K[0], K[1]); std::swap(V[0], V[1]); }
+            hipLaunchKernelGGL(setup_ptkey_kernel, dim3(gpt), dim3(256), 0, st, g == groups - 1 ? (const su32*)nullptr : (const su32*)ptV[rp], np, (const su32*)st_pt,
+                               (const su64*)obsK[ro], (1ull << cb) - 1ull, j0, npos, b, ptK[rp]);
+            rp = ptS.sort(st, (size_t)np, rp, npos * b, g == groups - 1);
         }
         SFM_HIP_TRY(ctx, hipMemsetAsync(h->d_pt_start, 0, ((size_t)np + 1) * sizeof(int), st));
-        if (np) hipLaunchKernelGGL(setup_slot_kernel, dim3(gpt), dim3(256), 0, st, (const su32*)V[0], np, (const su32*)st_pt, h->d_slot, (su32*)h->d_pt_start);
-        setup_enqueue_scan(st, (su32*)h->d_pt_start, (size_t)np + 1, bsum, nullptr);
+        if (np) hipLaunchKernelGGL(setup_slot_kernel, dim3(gpt), dim3(256), 0, st, (const su32*)ptV[rp], np, (const su32*)st_pt, h->d_slot, (su32*)h->d_pt_start);
+        sfm_enqueue_scan(st, (su32*)h->d_pt_start, (size_t)np + 1, bsum);
     }
     if (pt_const && np) {           // constant points: the caller's flags into slot order
         unsigned char* d_flags_in = nullptr;
@@ -1267,10 +1267,9 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     if (nobs) {
         hipLaunchKernelGGL(setup_fill_obs_kernel, dim3(gobs), dim3(256), 0, st, (const su64*)obsK[ro], (const su32*)obsV[ro], nobs, cb, (const su32*)st_pt, (const int*)h->d_slot,
                            (const int*)h->d_pt_start, (const double2*)d_ruv, h->d_ocam, h->d_opt, (double2*)h->d_ouv, obsK[ro ^ 1]);
-        SetupSortBufs B = { { obsK[ro ^ 1], obsK[ro] }, { obsV[ro ^ 1], obsV[ro] }, hist, bsum };
-        const int r = setup_radix_sort(st, B, (size_t)nobs, cb, true);
-        hipLaunchKernelGGL(setup_starts_kernel, dim3((unsigned)ceil_div(nobs + 1, 256)), dim3(256), 0, st, (const su64*)B.k[r], (size_t)nobs, 0, (su64)nc, (su32*)h->d_cam_start);
-        hipLaunchKernelGGL(setup_cam_copy_kernel, dim3(gobs), dim3(256), 0, st, (const su32*)B.v[r], nobs, (const int*)h->d_opt, (const double2*)h->d_ouv, h->d_cam_pt,
+        const int r = obsS.sort(st, (size_t)nobs, ro ^ 1, cb, true);
+        hipLaunchKernelGGL(setup_starts_kernel, dim3((unsigned)ceil_div(nobs + 1, 256)), dim3(256), 0, st, (const su64*)obsK[r], (size_t)nobs, 0, (su64)nc, (su32*)h->d_cam_start);
+        hipLaunchKernelGGL(setup_cam_copy_kernel, dim3(gobs), dim3(256), 0, st, (const su32*)obsV[r], nobs, (const int*)h->d_opt, (const double2*)h->d_ouv, h->d_cam_pt,
                            (double2*)h->d_cam_uv);
     }
     if (np) {
@@ -1287,7 +1286,7 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     SFM_HIP_TRY(ctx, hipMemsetAsync(npair, 0, ((size_t)np + 1) * sizeof(su32), st));
     SFM_HIP_TRY(ctx, hipMemsetAsync(d_total + 1, 0, sizeof(su64), st));
     if (np) hipLaunchKernelGGL(setup_pair_count_kernel, dim3(gpt), dim3(256), 0, st, (const int*)h->d_pt_start, (const int*)h->d_ocam, np, h->nfix, (const unsigned char*)h->d_ptfix, npair, d_total + 1);
-    setup_enqueue_scan(st, npair, (size_t)np + 1, bsum, d_total);
+    sfm_enqueue_scan(st, npair, (size_t)np + 1, bsum, d_total);
     su64 total_pairs = 0;
     std::vector<int> cam_start((size_t)nc + 1);
     SFM_HIP_TRY(ctx, hipMemcpyAsync(&total_pairs, d_total + 1, sizeof(su64), hipMemcpyDeviceToHost, st));      // the count kernel's own 64-bit sum: the scan's counters may have wrapped
@@ -1307,16 +1306,15 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
         su64 *pK[2], *blk_key = nullptr; su32 *pV[2], *flag = nullptr, *hist2 = nullptr, *bsum2 = nullptr, *blk_first = nullptr; int2* raw = nullptr;
         for (int i = 0; i < 2; ++i) { TRY_RC(T.get(&pK[i], npairs)); TRY_RC(T.get(&pV[i], npairs)); }
         TRY_RC(T.get(&raw, npairs)); TRY_RC(T.get(&flag, npairs + 1));
-        TRY_RC(T.get(&hist2, 256 * setup_rs_tiles(npairs) + 1)); TRY_RC(T.get(&bsum2, setup_scan_tiles(std::max(256 * setup_rs_tiles(npairs), npairs + 1)) + 1));
+        TRY_RC(T.get(&hist2, SfmSort::hist_words(npairs) + 1)); TRY_RC(T.get(&bsum2, std::max(SfmSort::bsum_words(npairs), SfmScan::bsum_words(npairs + 1)) + 1));
         hipLaunchKernelGGL(setup_pair_gen_kernel, dim3(gobs), dim3(256), 0, st, (const int*)h->d_pt_start, (const int*)h->d_ocam, (const int*)h->d_opt, nobs, h->nfix, (const unsigned char*)h->d_ptfix, nc,
                            (const su32*)npair, pK[0], raw);
         stamp("pair generation");
-        SetupSortBufs B = { { pK[0], pK[1] }, { pV[0], pV[1] }, hist2, bsum2 };
-        const int r = setup_radix_sort(st, B, npairs, setup_bit_width((su64)nc * (su64)nc - 1), true);
+        const int r = SfmSort::of(pK[0], pK[1], pV[0], pV[1], hist2, bsum2).sort(st, npairs, 0, setup_bit_width((su64)nc * (su64)nc - 1), true);
         stamp("pair sort");
         const unsigned gpair = (unsigned)((npairs + 1 + 255) / 256);
-        hipLaunchKernelGGL(setup_flag_kernel, dim3(gpair), dim3(256), 0, st, (const su64*)pK[r], npairs, flag);
-        setup_enqueue_scan(st, flag, npairs + 1, bsum2, d_total);
+        sfm_enqueue_run_heads(st, pK[r], npairs, ~0ull, flag);       // a key is two camera numbers: never all ones
+        sfm_enqueue_scan(st, flag, npairs + 1, bsum2, d_total);
         su64 nblk64 = 0;
         SFM_HIP_TRY(ctx, hipMemcpyAsync(&nblk64, d_total, sizeof(su64), hipMemcpyDeviceToHost, st));
         TRY_RC(dalloc(h, &h->d_items, npairs));
@@ -1796,18 +1794,3 @@ int sfmhip_ba_solve_ex(sfmhip_ctx* ctx, double* K4, double* ext6, int n_cam, dou
 }
 
 }  // extern "C"
-
-// The stable radix sort of ba_setup.hpp for the other translation units of the library (points.hip bins a cloud with it).  The kernels of
-// that header have external linkage, so it stays included here only and these two functions are its door (common.hpp declares them).
-size_t sfm_radix_sort_hist_words(size_t n) { return (size_t)256 * setup_rs_tiles(n); }
-size_t sfm_radix_sort_bsum_words(size_t n) { return setup_scan_tiles((size_t)256 * setup_rs_tiles(n)); }
-int sfm_enqueue_radix_sort(hipStream_t st, unsigned long long* k0, unsigned long long* k1, unsigned* v0, unsigned* v1, unsigned* hist, unsigned* bsum,
-                           size_t n, int bits, bool identity_vals)
-{
-    SetupSortBufs B;
-    B.k[0] = k0; B.k[1] = k1; B.v[0] = v0; B.v[1] = v1; B.hist = hist; B.bsum = bsum;
-    return setup_radix_sort(st, B, n, bits, identity_vals);
-}
-// ... and its exclusive prefix sum of 32-bit counters, in place (points.hip numbers the voxels of a cloud with it)
-size_t sfm_scan_bsum_words(size_t n) { return setup_scan_tiles(n); }
-void sfm_enqueue_scan_u32(hipStream_t st, unsigned* data, size_t n, unsigned* bsum) { setup_enqueue_scan(st, data, n, bsum, nullptr); }

@@ -1,4 +1,4 @@
-// ba_setup.hpp -- construction of a bundle-adjustment problem ON THE DEVICE (included by ba.hip only).
+// ba_setup.hpp -- construction of a bundle-adjustment problem ON THE DEVICE (included by ba.hip only: its kernels have external linkage).
 //
 // bundle_adjustment() of the reference is ONE call that builds the ceres::Problem and solves it
 // (NViewReconstuct.cpp:1169-1224), and the "Time (s)" it prints covers both (NView:1239).  What has to be built here
@@ -14,189 +14,15 @@
 // The resulting tables are identical, entry by entry, to the ones the host code produced (tests/test_ba_setup_gpu.py
 // restates the orderings in numpy), so the iteration results stay bit-identical.
 //
-// Everything here is HBM-bound integer work on a few hundred MB at most; the kernels are plain coalesced passes, the
-// only structured one is the radix scatter (per-wave match-any ranking, so that the sort is stable).
+// Everything here is HBM-bound integer work on a few hundred MB at most, in plain coalesced passes: the key, starts, slot, fill,
+// pair, items and crange kernels.  The sorts, the scans and the run heads between them are the library's own (sortscan.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "sortscan.hpp"
 
 typedef unsigned long long su64;
 typedef unsigned int su32;
-
-// ------------------------------------------------------------------------------------------------
-// exclusive prefix sum of 32-bit counters, in place: tile scan -> scan of the tile totals -> add
-// ------------------------------------------------------------------------------------------------
-#define SCAN_ITEMS 16
-#define SCAN_TILE (256 * SCAN_ITEMS)
-
-__device__ __forceinline__ su32 setup_wave_incl_scan(su32 v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const su32 t = __shfl_up(v, off); if (lane >= off) v += t; }
-    return v;
-}
-
-// 256 threads: exclusive prefix of v over the workgroup, the workgroup's total in *total
-__device__ __forceinline__ su32 setup_block_excl_scan(su32 v, su32* total, su32* sm)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const su32 incl = setup_wave_incl_scan(v, lane);
-    if (lane == 63) sm[wave] = incl;
-    __syncthreads();
-    su32 wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const su32 s = sm[w]; if (w < wave) wbase += s; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return wbase + incl - v;
-}
-
-__global__ __launch_bounds__(256) void setup_scan_tile_kernel(su32* __restrict__ data, size_t n, su32* __restrict__ bsum)
-{
-    __shared__ su32 sm[4];
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    su32 x[SCAN_ITEMS], sum = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) { x[j] = base + j < n ? data[base + j] : 0u; sum += x[j]; }
-    su32 tot;
-    su32 run = setup_block_excl_scan(sum, &tot, sm);
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) { if (base + j < n) data[base + j] = run; run += x[j]; }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// one workgroup: exclusive scan of the tile totals (64-bit carry: *total64 tells the caller whether 32 bits sufficed)
-__global__ __launch_bounds__(256) void setup_scan_top_kernel(su32* __restrict__ bsum, int nb, su64* __restrict__ total64)
-{
-    __shared__ su32 sm[4];
-    su64 carry = 0;
-    for (int base = 0; base < nb; base += 256) {
-        const int i = base + threadIdx.x;
-        const su32 v = i < nb ? bsum[i] : 0u;
-        su32 tot;
-        const su32 ex = setup_block_excl_scan(v, &tot, sm);
-        if (i < nb) bsum[i] = (su32)(carry + ex);
-        carry += tot;
-    }
-    if (threadIdx.x == 0 && total64) *total64 = carry;
-}
-
-__global__ __launch_bounds__(256) void setup_scan_add_kernel(su32* __restrict__ data, size_t n, const su32* __restrict__ bsum)
-{
-    const su32 add = bsum[blockIdx.x];
-    const size_t base = (size_t)blockIdx.x * SCAN_TILE;
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) { const size_t i = base + (size_t)j * 256 + threadIdx.x; if (i < n) data[i] += add; }
-}
-
-static inline size_t setup_scan_tiles(size_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
-
-// data[0..n) -> exclusive prefix sums; bsum: scratch of setup_scan_tiles(n) counters; total64 (device, may be null) = the sum
-static inline void setup_enqueue_scan(hipStream_t st, su32* data, size_t n, su32* bsum, su64* total64)
-{
-    if (n == 0) { if (total64) (void)hipMemsetAsync(total64, 0, sizeof(su64), st); return; }
-    const int nb = (int)setup_scan_tiles(n);
-    hipLaunchKernelGGL(setup_scan_tile_kernel, dim3(nb), dim3(256), 0, st, data, n, bsum);
-    hipLaunchKernelGGL(setup_scan_top_kernel, dim3(1), dim3(256), 0, st, bsum, nb, total64);
-    hipLaunchKernelGGL(setup_scan_add_kernel, dim3(nb), dim3(256), 0, st, data, n, (const su32*)bsum);
-}
-
-// ------------------------------------------------------------------------------------------------
-// stable LSD radix sort of (64-bit key, 32-bit value) pairs, 8 bits per pass
-//   tile = 4 waves x RS_ROUNDS x 64 consecutive elements; a wave owns a contiguous piece of the tile and walks it 64
-//   elements at a time, ranking equal digits with a match-any over eight ballots, so equal keys keep their order.
-// ------------------------------------------------------------------------------------------------
-#define RS_ROUNDS 16
-#define RS_TILE (256 * RS_ROUNDS)
-
-__global__ __launch_bounds__(256) void setup_rs_hist_kernel(const su64* __restrict__ keys, size_t n, int shift, su32* __restrict__ hist, int nblocks)
-{
-    __shared__ su32 cnt[256];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t base = (size_t)blockIdx.x * RS_TILE;
-#pragma unroll 4
-    for (int r = 0; r < RS_ROUNDS; ++r) {
-        const size_t i = base + (size_t)r * 256 + threadIdx.x;
-        if (i < n) atomicAdd(&cnt[(su32)(keys[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * nblocks + blockIdx.x] = cnt[threadIdx.x];      // digit-major: one scan over the whole table gives the offsets
-}
-
-__global__ __launch_bounds__(256) void setup_rs_scatter_kernel(const su64* __restrict__ kin, const su32* __restrict__ vin, su64* __restrict__ kout,
-                                                               su32* __restrict__ vout, size_t n, int shift, const su32* __restrict__ off, int nblocks)
-{
-    __shared__ su32 wcnt[4][256];
-    __shared__ su32 wbase[4][256];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0;
-    __syncthreads();
-    const size_t w0 = (size_t)blockIdx.x * RS_TILE + (size_t)wave * (64 * RS_ROUNDS);
-    su64 k[RS_ROUNDS]; su32 v[RS_ROUNDS], rk[RS_ROUNDS];
-    const su64 lt = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int r = 0; r < RS_ROUNDS; ++r) {
-        const size_t i = w0 + (size_t)r * 64 + lane;
-        const bool valid = i < n;
-        k[r] = valid ? kin[i] : 0ull;
-        v[r] = valid ? (vin ? vin[i] : (su32)i) : 0u;
-        const su32 d = (su32)(k[r] >> shift) & 255u;
-        su64 m = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) { const bool bit = (d >> b) & 1u; const su64 bal = __ballot(bit); m &= bit ? bal : ~bal; }
-        rk[r] = 0;
-        if (valid) {
-            // every lane of the group reads the wave's running count of this digit, then the group's last lane advances it
-            // (one wave, program order: the read of all lanes precedes the write)
-            const su32 prev = wcnt[wave][d];
-            rk[r] = prev + (su32)__popcll(m & lt);
-            if ((m >> lane) == 1ull) wcnt[wave][d] = prev + (su32)__popcll(m);
-        }
-    }
-    __syncthreads();
-    {
-        su32 run = off[(size_t)tid * nblocks + blockIdx.x];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { wbase[w][tid] = run; run += wcnt[w][tid]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ROUNDS; ++r) {
-        const size_t i = w0 + (size_t)r * 64 + lane;
-        if (i < n) {
-            const su32 d = (su32)(k[r] >> shift) & 255u;
-            const size_t pos = (size_t)wbase[wave][d] + rk[r];
-            kout[pos] = k[r]; vout[pos] = v[r];
-        }
-    }
-}
-
-struct SetupSortBufs {
-    su64* k[2]; su32* v[2];     // ping-pong; the input keys are in k[0]
-    su32* hist; su32* bsum;     // 256 * tiles counters; setup_scan_tiles(256 * tiles) counters
-};
-static inline size_t setup_rs_tiles(size_t n) { return (n + RS_TILE - 1) / RS_TILE; }
-
-// Sorts by the low `bits` bits of the keys.  Values: v[0], or the element index where identity_vals.  Returns the index
-// (0 / 1) of the buffers that hold the result.
-static inline int setup_radix_sort(hipStream_t st, const SetupSortBufs& B, size_t n, int bits, bool identity_vals)
-{
-    if (n == 0) return 0;
-    const int passes = bits <= 0 ? 1 : (bits + 7) / 8;
-    const int nblocks = (int)setup_rs_tiles(n);
-    int cur = 0;
-    for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(setup_rs_hist_kernel, dim3(nblocks), dim3(256), 0, st, (const su64*)B.k[cur], n, 8 * p, B.hist, nblocks);
-        setup_enqueue_scan(st, B.hist, (size_t)256 * nblocks, B.bsum, nullptr);
-        hipLaunchKernelGGL(setup_rs_scatter_kernel, dim3(nblocks), dim3(256), 0, st, (const su64*)B.k[cur],
-                           (p == 0 && identity_vals) ? (const su32*)nullptr : (const su32*)B.v[cur], B.k[cur ^ 1], B.v[cur ^ 1], n, 8 * p,
-                           (const su32*)B.hist, nblocks);
-        cur ^= 1;
-    }
-    return cur;
-}
 
 // ------------------------------------------------------------------------------------------------
 // the set-up passes
@@ -371,13 +197,7 @@ __global__ __launch_bounds__(256) void setup_slot_flags_kernel(const unsigned ch
     if (p < np) flags_slot[slot[p]] = flags[p] ? 1 : 0;
 }
 
-// run starts of the sorted pair keys: flag -> (scan) -> compaction
-__global__ __launch_bounds__(256) void setup_flag_kernel(const su64* __restrict__ keys, size_t n, su32* __restrict__ flag)
-{
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t > n) return;
-    flag[t] = (t < n && (t == 0 || keys[t] != keys[t - 1])) ? 1u : 0u;       // n + 1 entries: the scan leaves the count in flag[n]
-}
+// run starts of the sorted pair keys: run heads -> (scan) -> compaction
 __global__ __launch_bounds__(256) void setup_compact_kernel(const su64* __restrict__ keys, const su32* __restrict__ rank, size_t n, su64* __restrict__ blk_key,
                                                             su32* __restrict__ blk_first)
 {

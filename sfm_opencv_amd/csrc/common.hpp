@@ -147,18 +147,6 @@ void sfm_pool_trim(sfmhip_ctx* ctx);
 // rccl.hip: communicators cached for sets of contexts go when one of their contexts does
 void sfm_rccl_forget_ctx(sfmhip_ctx* ctx);
 
-// ba.hip: the stable LSD radix sort of ba_setup.hpp on (64-bit key, 32-bit value) pairs, for the other translation units.  Keys in k0,
-// values in v0 (or the element index where identity_vals); k1 / v1: ping-pong buffers of n entries; hist / bsum: scratch of
-// sfm_radix_sort_hist_words(n) / sfm_radix_sort_bsum_words(n) 32-bit words.  Sorts by the low `bits` bits, enqueues only, returns the
-// index (0 / 1) of the buffers that hold the result.
-size_t sfm_radix_sort_hist_words(size_t n);
-size_t sfm_radix_sort_bsum_words(size_t n);
-int sfm_enqueue_radix_sort(hipStream_t st, unsigned long long* k0, unsigned long long* k1, unsigned* v0, unsigned* v1, unsigned* hist, unsigned* bsum,
-                           size_t n, int bits, bool identity_vals);
-// ba.hip: the exclusive prefix sum of the same header, in place over data[0 .. n); bsum: scratch of sfm_scan_bsum_words(n) words
-size_t sfm_scan_bsum_words(size_t n);
-void sfm_enqueue_scan_u32(hipStream_t st, unsigned* data, size_t n, unsigned* bsum);
-
 // points.hip: K nearest other points of every point of a device cloud (n x 3 double) into d_idx (n x K int32) / d_dist (n x K double),
 // either may be null; method: SFMHIP_POINTS_*.  Enqueues on the context's stream, never synchronises.  The grid leaves the number of
 // queries it handed to its brute-force pass in ctx->d_points_fallback.

@@ -21,9 +21,10 @@
 //   sgm_winner_kernel     a wave per pixel: the first smallest sum among the scored planes, the sub-plane fit
 //   consistency_kernel    one thread per pixel, fp64
 //   points_count_kernel / points_write_kernel   the kept pixels of 256 consecutive pixels are counted per workgroup, the counts go through
-//                         the exclusive scan of ba_setup.hpp, and the second kernel ranks the pixels inside a workgroup by ballots: the
+//                         the exclusive scan of sortscan.hpp, and the second kernel ranks the pixels inside a workgroup by ballots: the
 //                         rows come out in row-major order without an atomic.
 #include "common.hpp"
+#include "sortscan.hpp"
 #include <cmath>
 #pragma clang fp contract(off)
 
@@ -757,18 +758,19 @@ static int points_enqueue(sfmhip_ctx* ctx, const float* d_depth, const uint8_t* 
 {
     const size_t npx = (size_t)rows * cols, nb = (npx + 255) / 256;
     SfmCarve carve;
-    const size_t o_cnt = carve((nb + 1) * 4), o_scan = carve(sfm_scan_bsum_words(nb + 1) * 4);
+    SfmScan C(carve, nb + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
-    unsigned* counts = (unsigned*)(w + o_cnt);
+    C.bind(w);
+    unsigned* counts = C.data;
     PointsParams P;
     P.fx = K4[0]; P.fy = K4[1]; P.cx = K4[2]; P.cy = K4[3];
     std::memcpy(P.Rinv, Rinv, sizeof(P.Rinv));
     std::memcpy(P.c, c, sizeof(P.c));
     hipLaunchKernelGGL(points_count_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, d_keep, npx, (unsigned)nb, counts);
-    sfm_enqueue_scan_u32(ctx->stream, counts, nb + 1, (unsigned*)(w + o_scan));
+    C.scan(ctx->stream, nb + 1);
     hipLaunchKernelGGL(points_write_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, d_depth, d_keep, d_img, rows, cols, channels, ld, P, (const unsigned*)counts,
                        (unsigned)nb, d_xyz, d_bgr, cap, d_n_found);
     SFM_HIP_TRY(ctx, hipGetLastError());

@@ -17,11 +17,12 @@
 //                mesh_colour_kernel, mesh_simplify_emit_kernel
 //   normals      mesh_tri_normal_kernel (N_t and the three corner records) -- sort by vertex -- mesh_run_start_kernel,
 //                mesh_vertex_normal_kernel (a gather of 24-byte rows N_t in ascending (t, corner))
-//   smooth       mesh_pair_key_kernel (six directed pairs per triangle) -- sort -- mesh_pair_head_kernel -- scan -- mesh_csr_kernel,
+//   smooth       mesh_pair_key_kernel (six directed pairs per triangle) -- sort -- run heads -- scan -- mesh_csr_kernel,
 //                then per step mesh_smooth_step_kernel (a gather of 24-byte rows x_w in ascending w)
 // The two gather kernels read rows at random; the vertex numbering of sfmhip_tsdf_mesh (by edge id, x fastest) keeps a vertex's
 // neighbours within a few volume rows of it, which is what makes those reads hit in L2.  Nothing here re-orders vertices.
 #include "common.hpp"
+#include "sortscan.hpp"
 #include "unionfind.hpp"
 #include <cmath>
 #pragma clang fp contract(off)
@@ -121,17 +122,19 @@ static int components_enqueue(sfmhip_ctx* ctx, int nv, const int32_t* d_tri, int
     hipStream_t st = ctx->stream;
     const size_t NV = (size_t)nv, NT = (size_t)nt;
     SfmCarve carve;
-    const size_t o_err = carve(sizeof(pu32)), o_ref = carve(NV), o_par = carve(NV * 4), o_flag = carve((NV + 1) * 4), o_scan = carve(sfm_scan_bsum_words(NV + 1) * 4);
+    const size_t o_err = carve(sizeof(pu32)), o_ref = carve(NV), o_par = carve(NV * 4);
+    SfmScan F(carve, NV + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
-    pu32 *err = (pu32*)(w + o_err), *parent = (pu32*)(w + o_par), *flag = (pu32*)(w + o_flag);
+    F.bind(w);
+    pu32 *err = (pu32*)(w + o_err), *parent = (pu32*)(w + o_par), *flag = F.data;
     uint8_t* ref = (uint8_t*)(w + o_ref);
     hipLaunchKernelGGL(mesh_cc_init_kernel, mesh_grid(NV), dim3(256), 0, st, nv, parent, ref, err);
     hipLaunchKernelGGL(mesh_cc_link_kernel, mesh_grid(NT), dim3(256), 0, st, d_tri, nt, nv, parent, ref, err);
     hipLaunchKernelGGL(mesh_cc_flatten_kernel, mesh_grid(NV + 1), dim3(256), 0, st, (const uint8_t*)ref, nv, parent, flag);
-    sfm_enqueue_scan_u32(st, flag, NV + 1, (pu32*)(w + o_scan));
+    F.scan(st, NV + 1);
     hipLaunchKernelGGL(mesh_cc_label_kernel, mesh_grid(std::max(NV, NT)), dim3(256), 0, st, d_tri, nt, nv, (const uint8_t*)ref, (const pu32*)parent, (const pu32*)flag,
                        (const pu32*)err, d_tri_label, d_vertex_label, d_ncomp);
     SFM_HIP_TRY(ctx, hipGetLastError());
@@ -214,22 +217,23 @@ static int filter_enqueue(sfmhip_ctx* ctx, const double* d_xyz, const uint8_t* d
     hipStream_t st = ctx->stream;
     const size_t NV = (size_t)nv, NT = (size_t)nt, big = std::max(NV, NT);
     SfmCarve carve;
-    const size_t o_head = carve(2 * sizeof(int32_t)), o_lab = carve(NT * 4), o_size = carve(NT * 4), o_tf = carve((NT + 1) * 4), o_vf = carve((NV + 1) * 4),
-                 o_scan = carve(sfm_scan_bsum_words(big + 1) * 4);
+    const size_t o_head = carve(2 * sizeof(int32_t)), o_lab = carve(NT * 4), o_size = carve(NT * 4);
+    SfmScan TF(carve, NT + 1), VF(carve, NV + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    TF.bind(w); VF.bind(w);
     int32_t *head = (int32_t*)(w + o_head), *lab = (int32_t*)(w + o_lab), *sizes = (int32_t*)(w + o_size);
-    pu32 *tf = (pu32*)(w + o_tf), *vf = (pu32*)(w + o_vf), *scan = (pu32*)(w + o_scan);
+    pu32 *tf = TF.data, *vf = VF.data;
     rc = components_enqueue(ctx, nv, d_tri, nt, lab, nullptr, head, sizes);
     if (rc != SFMHIP_OK) return rc;
     if (keep_largest) hipLaunchKernelGGL(mesh_largest_kernel, dim3(1), dim3(256), 0, st, (const int32_t*)sizes, (const int32_t*)head, head + 1);
     SFM_HIP_TRY(ctx, hipMemsetAsync(vf, 0, (NV + 1) * 4, st));
     hipLaunchKernelGGL(mesh_keep_kernel, mesh_grid(NT + 1), dim3(256), 0, st, d_tri, nt, (const int32_t*)lab, (const int32_t*)sizes, (const int32_t*)(head + 1), min_triangles,
                        keep_largest, tf, vf);
-    sfm_enqueue_scan_u32(st, tf, NT + 1, scan);
-    sfm_enqueue_scan_u32(st, vf, NV + 1, scan);
+    TF.scan(st, NT + 1);
+    VF.scan(st, NV + 1);
     hipLaunchKernelGGL(mesh_filter_emit_kernel, mesh_grid(big), dim3(256), 0, st, d_xyz, d_bgr, nv, d_tri, nt, (const pu32*)vf, (const pu32*)tf, (const int32_t*)head, d_xyz_out,
                        d_bgr_out, d_tri_out, d_vertex_map, d_nv_out, d_nt_out);
     SFM_HIP_TRY(ctx, hipGetLastError());
@@ -358,22 +362,6 @@ __global__ __launch_bounds__(256) void mesh_simplify_emit_kernel(const double* _
     }
 }
 
-// the buffers of one radix sort of n records
-struct MeshSort { pu64* k[2]; pu32* v[2]; pu32 *hist, *bsum; };
-static inline void mesh_sort_carve(SfmCarve& carve, size_t n, size_t o[6])
-{
-    o[0] = carve(n * 8); o[1] = carve(n * 8); o[2] = carve(n * 4); o[3] = carve(n * 4);
-    o[4] = carve(sfm_radix_sort_hist_words(n) * 4); o[5] = carve(sfm_radix_sort_bsum_words(n) * 4);
-}
-static inline MeshSort mesh_sort_at(char* w, const size_t o[6])
-{
-    MeshSort S;
-    S.k[0] = (pu64*)(w + o[0]); S.k[1] = (pu64*)(w + o[1]); S.v[0] = (pu32*)(w + o[2]); S.v[1] = (pu32*)(w + o[3]); S.hist = (pu32*)(w + o[4]); S.bsum = (pu32*)(w + o[5]);
-    return S;
-}
-// stable sort of S.k[0] by its low `bits` bits, the values the record numbers: the index of the buffers that hold the result
-static inline int mesh_sort(hipStream_t st, const MeshSort& S, size_t n, int bits) { return sfm_enqueue_radix_sort(st, S.k[0], S.k[1], S.v[0], S.v[1], S.hist, S.bsum, n, bits, true); }
-
 static int simplify_enqueue(sfmhip_ctx* ctx, const double* d_xyz, const uint8_t* d_bgr, int nv, const int32_t* d_tri, int nt, double voxel, double* d_xyz_out,
                             uint8_t* d_bgr_out, int32_t* d_tri_out, int32_t* d_vertex_map, int32_t* d_nv_out, int32_t* d_nt_out)
 {
@@ -386,19 +374,18 @@ static int simplify_enqueue(sfmhip_ctx* ctx, const double* d_xyz, const uint8_t*
     const size_t NV = (size_t)nv, NT = (size_t)nt, big = std::max(NV, NT);
     const int bits = mesh_bits(nv), two_pass = 3 * bits > 64 ? 1 : 0;
     SfmCarve carve;
-    size_t o_sort[6];
-    const size_t o_nc = carve(sizeof(int32_t)), o_ref = carve(NV), o_mask = carve(NV * 24), o_cen = carve(NV * 24), o_cof = carve(NV * 4), o_rec = carve(NT * 12),
-                 o_tf = carve((NT + 1) * 4), o_cf = carve((NV + 1) * 4), o_scan = carve(sfm_scan_bsum_words(big + 1) * 4);
-    mesh_sort_carve(carve, big, o_sort);
+    const size_t o_nc = carve(sizeof(int32_t)), o_ref = carve(NV), o_mask = carve(NV * 24), o_cen = carve(NV * 24), o_cof = carve(NV * 4), o_rec = carve(NT * 12);
+    SfmScan TF(carve, NT + 1), CF(carve, NV + 1);
+    SfmSort S(carve, big);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    TF.bind(w); CF.bind(w); S.bind(w);
     int32_t *nc = (int32_t*)(w + o_nc), *cof = (int32_t*)(w + o_cof);
     uint8_t* ref = (uint8_t*)(w + o_ref);
     double *masked = (double*)(w + o_mask), *cen = (double*)(w + o_cen);
-    pu32 *rec = (pu32*)(w + o_rec), *tf = (pu32*)(w + o_tf), *cf = (pu32*)(w + o_cf), *scan = (pu32*)(w + o_scan);
-    const MeshSort S = mesh_sort_at(w, o_sort);
+    pu32 *rec = (pu32*)(w + o_rec), *tf = TF.data, *cf = CF.data;
     SFM_HIP_TRY(ctx, hipMemsetAsync(ref, 0, NV, st));
     hipLaunchKernelGGL(mesh_ref_kernel, mesh_grid(NT), dim3(256), 0, st, d_tri, nt, nv, ref);
     hipLaunchKernelGGL(mesh_mask_kernel, mesh_grid(NV), dim3(256), 0, st, d_xyz, (const uint8_t*)ref, nv, masked);
@@ -406,21 +393,21 @@ static int simplify_enqueue(sfmhip_ctx* ctx, const double* d_xyz, const uint8_t*
     rc = sfm_voxel_downsample_enqueue(ctx, masked, nv, voxel, cen, nullptr, cof, nc);
     if (rc != SFMHIP_OK) return rc;
     hipLaunchKernelGGL(mesh_map_tri_kernel, mesh_grid(NT), dim3(256), 0, st, d_tri, nt, nv, (const int32_t*)cof, bits, two_pass, rec, S.k[0]);
-    int cur = mesh_sort(st, S, NT, two_pass ? bits : 3 * bits);
+    int cur = S.sort(st, NT, 0, two_pass ? bits : 3 * bits, true);
     if (two_pass && nt > 0) {
         hipLaunchKernelGGL(mesh_key2_kernel, mesh_grid(NT), dim3(256), 0, st, (const pu32*)rec, (const pu32*)S.v[cur], nt, bits, S.k[cur]);
-        cur ^= sfm_enqueue_radix_sort(st, S.k[cur], S.k[cur ^ 1], S.v[cur], S.v[cur ^ 1], S.hist, S.bsum, NT, 2 * bits, false);
+        cur = S.sort(st, NT, cur, 2 * bits, false);
     }
     SFM_HIP_TRY(ctx, hipMemsetAsync(cf, 0, (NV + 1) * 4, st));
     hipLaunchKernelGGL(mesh_tri_head_kernel, mesh_grid(NT + 1), dim3(256), 0, st, (const pu32*)rec, (const pu32*)S.v[cur], nt, tf, cf);
-    sfm_enqueue_scan_u32(st, tf, NT + 1, scan);
-    sfm_enqueue_scan_u32(st, cf, NV + 1, scan);
+    TF.scan(st, NT + 1);
+    CF.scan(st, NV + 1);
     hipLaunchKernelGGL(mesh_simplify_emit_kernel, mesh_grid(big), dim3(256), 0, st, (const double*)cen, (const int32_t*)cof, nv, (const pu32*)rec, (const pu32*)S.v[cur], nt,
                        (const pu32*)cf, (const pu32*)tf, (const int32_t*)nc, d_xyz_out, d_tri_out, d_vertex_map, d_nv_out, d_nt_out);
     SFM_HIP_TRY(ctx, hipGetLastError());
     if (d_bgr) {                                                           // the triangle sort is done with: its buffers serve the vertices
         hipLaunchKernelGGL(mesh_colour_key_kernel, mesh_grid(NV), dim3(256), 0, st, (const int32_t*)cof, nv, bits, S.k[0]);
-        const int cc = mesh_sort(st, S, NV, bits);
+        const int cc = S.sort(st, NV, 0, bits, true);
         hipLaunchKernelGGL(mesh_colour_kernel, mesh_grid(NV), dim3(256), 0, st, (const pu64*)S.k[cc], (const pu32*)S.v[cc], d_bgr, nv, bits, (const pu32*)cf, d_bgr_out);
         SFM_HIP_TRY(ctx, hipGetLastError());
     }
@@ -479,18 +466,17 @@ static int normals_enqueue(sfmhip_ctx* ctx, const double* d_xyz, int nv, const i
     const size_t NV = (size_t)nv, NT = (size_t)nt, n3 = 3 * NT;
     const int bits = mesh_bits(nv);
     SfmCarve carve;
-    size_t o_sort[6];
     const size_t o_tn = carve(NT * 24), o_start = carve(NV * 4);
-    mesh_sort_carve(carve, n3, o_sort);
+    SfmSort S(carve, n3);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    S.bind(w);
     double* tn = (double*)(w + o_tn);
     pu32* start = (pu32*)(w + o_start);
-    const MeshSort S = mesh_sort_at(w, o_sort);
     hipLaunchKernelGGL(mesh_tri_normal_kernel, mesh_grid(NT), dim3(256), 0, st, d_xyz, d_tri, nt, nv, bits, tn, S.k[0]);
-    const int cur = mesh_sort(st, S, n3, bits);
+    const int cur = S.sort(st, n3, 0, bits, true);
     SFM_HIP_TRY(ctx, hipMemsetAsync(start, 0xff, NV * 4, st));
     hipLaunchKernelGGL(mesh_run_start_kernel, mesh_grid(n3), dim3(256), 0, st, (const pu64*)S.k[cur], n3, bits, start);
     hipLaunchKernelGGL(mesh_vertex_normal_kernel, mesh_grid(NV), dim3(256), 0, st, (const pu64*)S.k[cur], (const pu32*)S.v[cur], (const double*)tn, n3, nv, (const pu32*)start,
@@ -513,14 +499,6 @@ __global__ __launch_bounds__(256) void mesh_pair_key_kernel(const int32_t* __res
     k[0] = ok && a != b ? (A << bits) | B : none; k[1] = ok && a != c ? (A << bits) | C : none;
     k[2] = ok && a != b ? (B << bits) | A : none; k[3] = ok && b != c ? (B << bits) | C : none;
     k[4] = ok && a != c ? (C << bits) | A : none; k[5] = ok && b != c ? (C << bits) | B : none;
-}
-
-// flag[i] = 1 where a new pair begins in the sorted list, n + 1 entries
-__global__ __launch_bounds__(256) void mesh_pair_head_kernel(const pu64* __restrict__ key, size_t n, int bits, pu32* __restrict__ flag)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i > n) return;
-    flag[i] = i < n && key[i] != (1ull << (2 * bits)) - 1ull && (i == 0 || key[i - 1] != key[i]) ? 1u : 0u;
 }
 
 // the distinct pairs in order: pair[excl[i]] = the pair, row[v] = the place of v's first pair (row holds MESH_NONE everywhere before)
@@ -575,20 +553,20 @@ static int smooth_enqueue(sfmhip_ctx* ctx, const double* d_xyz, int nv, const in
     }
     const int bits = mesh_bits(nv);
     SfmCarve carve;
-    size_t o_sort[6];
-    const size_t o_row = carve(NV * 4), o_flag = carve((n6 + 1) * 4), o_scan = carve(sfm_scan_bsum_words(n6 + 1) * 4), o_tmp = carve(steps > 1 ? NV * 24 : 0);
-    mesh_sort_carve(carve, n6, o_sort);
+    const size_t o_row = carve(NV * 4), o_tmp = carve(steps > 1 ? NV * 24 : 0);
+    SfmScan F(carve, n6 + 1);
+    SfmSort S(carve, n6);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
-    pu32 *row = (pu32*)(w + o_row), *flag = (pu32*)(w + o_flag);
+    F.bind(w); S.bind(w);
+    pu32 *row = (pu32*)(w + o_row), *flag = F.data;
     double* tmp = (double*)(w + o_tmp);
-    const MeshSort S = mesh_sort_at(w, o_sort);
     hipLaunchKernelGGL(mesh_pair_key_kernel, mesh_grid(NT), dim3(256), 0, st, d_tri, nt, nv, bits, S.k[0]);
-    const int cur = mesh_sort(st, S, n6, 2 * bits);
-    hipLaunchKernelGGL(mesh_pair_head_kernel, mesh_grid(n6 + 1), dim3(256), 0, st, (const pu64*)S.k[cur], n6, bits, flag);
-    sfm_enqueue_scan_u32(st, flag, n6 + 1, (pu32*)(w + o_scan));
+    const int cur = S.sort(st, n6, 0, 2 * bits, true);
+    sfm_enqueue_run_heads(st, S.k[cur], n6, (1ull << (2 * bits)) - 1ull, flag);      // mesh_pair_key_kernel's "none": no pair begins there
+    F.scan(st, n6 + 1);
     SFM_HIP_TRY(ctx, hipMemsetAsync(row, 0xff, NV * 4, st));
     pu64* pair = S.k[cur ^ 1];                                             // the sort's other key buffer is free now
     hipLaunchKernelGGL(mesh_csr_kernel, mesh_grid(n6), dim3(256), 0, st, (const pu64*)S.k[cur], n6, bits, (const pu32*)flag, pair, row);

@@ -21,6 +21,7 @@
 // two hypotheses per lane, half the LDS reads per residual, was 3 % faster and was not kept).  The sampler and the winner reduction are
 // ransac.hpp's too; what is here is the plane: its active list, its three-point hypothesis, its residual, what a round writes, the refit.
 #include "common.hpp"
+#include "sortscan.hpp"
 #pragma clang fp contract(off)
 #include "eig3.hpp"
 #include "ransac.hpp"
@@ -239,19 +240,20 @@ static int planes_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double t,
                           int32_t* d_n_planes, double* d_planes, double* d_refined, int32_t* d_counts, int32_t* d_winner)
 {
     hipStream_t st = ctx->stream;
-    const size_t N = (size_t)n, scan_w = sfm_scan_bsum_words(N + 1);
+    const size_t N = (size_t)n;
     const int nb = ceil_div(n, 256), nb1 = ceil_div(n + 1, 256), hb = ceil_div(H, 256), nt = ceil_div(n, REFIT_TILE);
     const int gy = ransac_score_grid_y(n, hb);
     SfmCarve carve;
-    const size_t o_state = carve(sizeof(PlaneState)), o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4), o_act = carve(N * sizeof(double4)),
-                 o_hyp = carve((size_t)H * 4 * sizeof(double)), o_val = carve((size_t)H * 4), o_cnt = carve((size_t)H * 4),
-                 o_part = carve(d_refined ? (size_t)6 * nt * sizeof(double) : 0);
+    const size_t o_state = carve(sizeof(PlaneState)), o_act = carve(N * sizeof(double4)), o_hyp = carve((size_t)H * 4 * sizeof(double)),
+                 o_val = carve((size_t)H * 4), o_cnt = carve((size_t)H * 4), o_part = carve(d_refined ? (size_t)6 * nt * sizeof(double) : 0);
+    SfmScan F(carve, N + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    F.bind(w);
     PlaneState* state = (PlaneState*)(w + o_state);
-    pu32* flag = (pu32*)(w + o_flag);
+    pu32* flag = F.data;
     double4* act = (double4*)(w + o_act);
     double* hyp = (double*)(w + o_hyp);
     int32_t *hvalid = (int32_t*)(w + o_val), *hcnt = (int32_t*)(w + o_cnt);
@@ -260,7 +262,7 @@ static int planes_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, double t,
                        d_refined, d_counts, d_winner, state);
     for (int p = 0; p < max_planes; ++p) {
         hipLaunchKernelGGL(plane_flag_kernel, dim3(nb1), dim3(256), 0, st, d_pts, (const int32_t*)d_labels, n, (const PlaneState*)state, flag);
-        sfm_enqueue_scan_u32(st, flag, N + 1, (pu32*)(w + o_scan));
+        F.scan(st, N + 1);
         hipLaunchKernelGGL(plane_scatter_kernel, dim3(nb), dim3(256), 0, st, d_pts, n, (const pu32*)flag, state, act);
         hipLaunchKernelGGL(plane_hyp_kernel, dim3(hb), dim3(256), 0, st, (const double4*)act, (const PlaneState*)state, p, H, seed, hyp, hvalid, hcnt);
         hipLaunchKernelGGL(plane_score_kernel, dim3(hb, gy), dim3(256), 0, st, (const double4*)act, (const PlaneState*)state, (const double*)hyp, H, t, hcnt);

@@ -9,10 +9,11 @@
 //
 // SFMHIP_POINTS_BRUTE: one thread per query streams the whole cloud through LDS tiles (the sweep of normals_kernel).
 // SFMHIP_POINTS_GRID : the cloud is binned into cubic cells on the device (64-bit key, 21 bits per axis, stable radix sort of
-//   ba_setup.hpp), a query visits the cells within Chebyshev ring r = 0, 1, .. RMAX of its own and stops as soon as its K-th distance
+//   sortscan.hpp), a query visits the cells within Chebyshev ring r = 0, 1, .. RMAX of its own and stops as soon as its K-th distance
 //   is CERTIFIED final (see points_knn_grid_kernel); a query not certified by RMAX goes on a list that the brute-force sweep finishes.
 //   Nothing here needs the host: cell size, origin, list length all stay on the device.
 #include "common.hpp"
+#include "sortscan.hpp"
 #include "unionfind.hpp"
 #pragma clang fp contract(off)
 
@@ -366,23 +367,22 @@ static int points_grid_enqueue(sfmhip_ctx* ctx, SfmPoolHold& hold, const double*
         ctx->d_points_fallback = (unsigned*)q;
     }
     // one block of the cache, carved up
-    const size_t N = (size_t)n, hist_w = sfm_radix_sort_hist_words(N), bsum_w = sfm_radix_sort_bsum_words(N);
+    const size_t N = (size_t)n;
     SfmCarve carve;
-    const size_t o_par = carve(8 * sizeof(double)), o_k0 = carve(N * 8), o_k1 = carve(N * 8), o_v0 = carve(N * 4), o_v1 = carve(N * 4),
-                 o_hist = carve(hist_w * 4), o_bsum = carve(bsum_w * 4), o_spts = carve(N * 24), o_list = carve(N * 4);
+    const size_t o_par = carve(8 * sizeof(double)), o_spts = carve(N * 24), o_list = carve(N * 4);
+    SfmSort S(carve, N);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    S.bind(w);
     double* params = (double*)(w + o_par);
-    pu64* k[2] = { (pu64*)(w + o_k0), (pu64*)(w + o_k1) };
-    pu32* v[2] = { (pu32*)(w + o_v0), (pu32*)(w + o_v1) };
     double* spts = (double*)(w + o_spts);
     SFM_HIP_TRY(ctx, hipMemsetAsync(ctx->d_points_fallback, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(points_cell_stats_kernel, dim3(1), dim3(NTILE), 0, st, d_pts, n, K, rmin, params);
-    hipLaunchKernelGGL(points_cell_key_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, n, (const double*)params, k[0]);
-    const int cur = sfm_enqueue_radix_sort(st, k[0], k[1], v[0], v[1], (pu32*)(w + o_hist), (pu32*)(w + o_bsum), N, 64, true);
-    hipLaunchKernelGGL(points_gather_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, (const pu32*)v[cur], n, spts);
-    G->params = params; G->keys = k[cur]; G->order = v[cur]; G->spts = spts; G->list = (pu32*)(w + o_list);
+    hipLaunchKernelGGL(points_cell_key_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, n, (const double*)params, S.k[0]);
+    const int cur = S.sort(st, N, 0, 64, true);
+    hipLaunchKernelGGL(points_gather_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d_pts, (const pu32*)S.v[cur], n, spts);
+    G->params = params; G->keys = S.k[cur]; G->order = S.v[cur]; G->spts = spts; G->list = (pu32*)(w + o_list);
     return SFMHIP_OK;
 }
 
@@ -669,13 +669,6 @@ __global__ __launch_bounds__(256) void voxel_key_kernel(const double* __restrict
     }
     keys[i] = key;
 }
-// run heads of the sorted keys, n + 1 entries: the exclusive scan leaves the number of voxels in flag[n]
-__global__ __launch_bounds__(256) void voxel_head_kernel(const pu64* __restrict__ keys, int n, pu32* __restrict__ flag)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t > n) return;
-    flag[t] = (t < n && !(keys[t] >> 63) && (t == 0 || keys[t] != keys[t - 1])) ? 1u : 0u;
-}
 // thread t: the t-th point in key order writes its voxel number; the head of a run also sums the run
 __global__ __launch_bounds__(256) void voxel_centroid_kernel(const pu64* __restrict__ keys, const pu32* __restrict__ order, const double* __restrict__ pts, int n,
                                                              const pu32* __restrict__ excl, const pu32* __restrict__ overflow, double* __restrict__ centroids,
@@ -706,28 +699,25 @@ static int voxel_downsample_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n,
                                     int32_t* d_voxel_of, int32_t* d_n_voxels, double* d_origin)
 {
     hipStream_t st = ctx->stream;
-    const size_t N = (size_t)n, hist_w = sfm_radix_sort_hist_words(N), bsum_w = sfm_radix_sort_bsum_words(N), scan_w = sfm_scan_bsum_words(N + 1);
+    const size_t N = (size_t)n;
     const int nt = ceil_div(n, RED_TILE), nb = ceil_div(n, 256);
     SfmCarve carve;
-    const size_t o_org = carve(4 * sizeof(double)), o_ovf = carve(sizeof(pu32)), o_part = carve((size_t)3 * nt * sizeof(double)), o_k0 = carve(N * 8),
-                 o_k1 = carve(N * 8), o_v0 = carve(N * 4), o_v1 = carve(N * 4), o_hist = carve(hist_w * 4), o_bsum = carve(bsum_w * 4),
-                 o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4);
+    const size_t o_org = carve(4 * sizeof(double)), o_ovf = carve(sizeof(pu32)), o_part = carve((size_t)3 * nt * sizeof(double));
+    SfmSort S(carve, N); SfmScan F(carve, N + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    S.bind(w); F.bind(w);
     double* origin = (double*)(w + o_org);
     pu32* overflow = (pu32*)(w + o_ovf);
-    pu64* k[2] = { (pu64*)(w + o_k0), (pu64*)(w + o_k1) };
-    pu32* v[2] = { (pu32*)(w + o_v0), (pu32*)(w + o_v1) };
-    pu32* flag = (pu32*)(w + o_flag);
     hipLaunchKernelGGL(voxel_min_tile_kernel, dim3(nt), dim3(256), 0, st, d_pts, n, (double*)(w + o_part));
     hipLaunchKernelGGL(voxel_min_top_kernel, dim3(1), dim3(256), 0, st, (const double*)(w + o_part), nt, voxel, origin, overflow);
-    hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(256), 0, st, d_pts, n, voxel, (const double*)origin, k[0], overflow);
-    const int cur = sfm_enqueue_radix_sort(st, k[0], k[1], v[0], v[1], (pu32*)(w + o_hist), (pu32*)(w + o_bsum), N, 64, true);
-    hipLaunchKernelGGL(voxel_head_kernel, dim3(ceil_div(n + 1, 256)), dim3(256), 0, st, (const pu64*)k[cur], n, flag);
-    sfm_enqueue_scan_u32(st, flag, N + 1, (pu32*)(w + o_scan));
-    hipLaunchKernelGGL(voxel_centroid_kernel, dim3(nb), dim3(256), 0, st, (const pu64*)k[cur], (const pu32*)v[cur], d_pts, n, (const pu32*)flag,
+    hipLaunchKernelGGL(voxel_key_kernel, dim3(nb), dim3(256), 0, st, d_pts, n, voxel, (const double*)origin, S.k[0], overflow);
+    const int cur = S.sort(st, N, 0, 64, true);
+    sfm_enqueue_run_heads(st, S.k[cur], N, 1ull << 63, F.data);           // a point outside every voxel has the top bit set: no run of its own
+    F.scan(st, N + 1);                                                     // the number of voxels in F.data[n]
+    hipLaunchKernelGGL(voxel_centroid_kernel, dim3(nb), dim3(256), 0, st, (const pu64*)S.k[cur], (const pu32*)S.v[cur], d_pts, n, (const pu32*)F.data,
                        (const pu32*)overflow, d_centroids, d_counts, d_voxel_of, d_n_voxels);
     SFM_HIP_TRY(ctx, hipGetLastError());
     if (d_origin) SFM_HIP_TRY(ctx, hipMemcpyAsync(d_origin, origin, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -916,19 +906,20 @@ static int cluster_dbscan_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, d
 {
     method = radius_method(method, n, r, CLUSTER_AUTO_GRID_FROM);
     hipStream_t st = ctx->stream;
-    const size_t N = (size_t)n, scan_w = sfm_scan_bsum_words(N + 1);
+    const size_t N = (size_t)n;
     const int nb = ceil_div(n, NTILE), nb256 = ceil_div(n, 256);
     SfmCarve carve;
-    const size_t o_err = carve(sizeof(pu32)), o_core = carve(N), o_par = carve(N * 4), o_flag = carve((N + 1) * 4), o_scan = carve(scan_w * 4),
-                 o_cnt = carve(d_count ? 0 : N * 4);
+    const size_t o_err = carve(sizeof(pu32)), o_core = carve(N), o_par = carve(N * 4), o_cnt = carve(d_count ? 0 : N * 4);
+    SfmScan F(carve, N + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    F.bind(w);
     pu32* err = (pu32*)(w + o_err);
     uint8_t* core = (uint8_t*)(w + o_core);
     pu32* parent = (pu32*)(w + o_par);
-    pu32* flag = (pu32*)(w + o_flag);
+    pu32* flag = F.data;
     int32_t* count = d_count ? d_count : (int32_t*)(w + o_cnt);
     const RadiusGate g = radius_gate(r);
     PointsGrid G;
@@ -943,7 +934,7 @@ static int cluster_dbscan_enqueue(sfmhip_ctx* ctx, const double* d_pts, int n, d
     if (grid) hipLaunchKernelGGL(cluster_link_grid_kernel, dim3(nb), dim3(NTILE), 0, st, G.keys, G.order, G.spts, n, g, (const uint8_t*)core, parent, err);
     else hipLaunchKernelGGL(cluster_link_brute_kernel, dim3(nb), dim3(NTILE), 0, st, d_pts, n, g, (const uint8_t*)core, parent, err);
     hipLaunchKernelGGL(cluster_flatten_kernel, dim3(ceil_div(n + 1, 256)), dim3(256), 0, st, (const uint8_t*)core, n, parent, flag);
-    sfm_enqueue_scan_u32(st, flag, N + 1, (pu32*)(w + o_scan));
+    F.scan(st, N + 1);
     hipLaunchKernelGGL(cluster_label_kernel, dim3(nb256), dim3(256), 0, st, (const uint8_t*)core, (const pu32*)parent, (const pu32*)flag, (const pu32*)err, n,
                        d_labels, d_n_clusters);
     if (min_points > 1) {                                                  // min_points = 1: every finite point is core, nothing to adopt

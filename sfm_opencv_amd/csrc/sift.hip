@@ -22,7 +22,7 @@
 //   sift_orient_kernel                  a wave per refined extremum: lanes take the pixels of the window into lane-private copies of
 //                                       the 36 bins in LDS, summed lane 0..63 in order (no atomics: the histogram is a function of the
 //                                       input alone); smoothing and the peak loop; a raw key point per accepted peak
-//   sorts (sfm_enqueue_radix_sort)      three stable passes over the capacity, unused rows keyed all-ones: (octave, layer, r, c), then
+//   sorts (SfmSort, sortscan.hpp)       three stable passes over the capacity, unused rows keyed all-ones: (octave, layer, r, c), then
 //                                       (size descending, angle), then (x, y) = the host's comparator with the issue's tie rule;
 //                                       sift_unique_flag_kernel + scan + sift_compact_kernel drop repeated (x, y, size, angle);
 //                                       with a budget one more stable pass on descending response where more rows remain than wanted
@@ -38,6 +38,7 @@
 // few per thousand pixels, and a key point per 2000 (18527 on 3648 x 2736).  A list that would overflow raises a flag:
 // the host entries return SFMHIP_E_ARG with a message, the enqueue-only entry leaves -1 in *d_n_found.  Nothing is truncated silently.
 #include "common.hpp"
+#include "sortscan.hpp"
 #pragma clang fp contract(off)
 #include <cmath>
 
@@ -632,29 +633,6 @@ static void sift_enqueue_detect(sfmhip_ctx* ctx, const SiftPlan& P, const float*
     hipLaunchKernelGGL(sift_refine_kernel, dim3(nb), dim3(256), 0, st, L, pyr, (const SiftCand*)cand, P.K, cnt, ext);
 }
 
-// the sort areas of one carve
-struct SiftSort {
-    pu64* k[2]; pu32* v[2]; pu32 *hist, *bsum, *flag, *scan;
-    size_t o_k[2], o_v[2], o_hist, o_bsum, o_flag, o_scan;
-    void carve(SfmCarve& c, size_t K)
-    {
-        for (int i = 0; i < 2; ++i) { o_k[i] = c(K * 8); o_v[i] = c(K * 4); }
-        o_hist = c(sfm_radix_sort_hist_words(K) * 4); o_bsum = c(sfm_radix_sort_bsum_words(K) * 4);
-        o_flag = c((K + 1) * 4); o_scan = c(sfm_scan_bsum_words(K + 1) * 4);
-    }
-    void bind(char* w)
-    {
-        for (int i = 0; i < 2; ++i) { k[i] = (pu64*)(w + o_k[i]); v[i] = (pu32*)(w + o_v[i]); }
-        hist = (pu32*)(w + o_hist); bsum = (pu32*)(w + o_bsum); flag = (pu32*)(w + o_flag); scan = (pu32*)(w + o_scan);
-    }
-    // one stable pass: the keys are in k[cur]; afterwards keys and permutation are in k[.] / v[.] of the index returned
-    int sort(hipStream_t st, size_t K, int cur, int bits, bool identity)
-    {
-        const int side = sfm_enqueue_radix_sort(st, k[cur], k[cur ^ 1], v[cur], v[cur ^ 1], hist, bsum, K, bits, identity);
-        return side ? cur ^ 1 : cur;
-    }
-};
-
 // everything behind sfmhip_sift_extract_dev
 static int sift_enqueue(sfmhip_ctx* ctx, const uint8_t* d_img, int rows, int cols, int ch, size_t ld, int max_features, sfm_keypoint* d_kp, float* d_desc, int cap,
                         int32_t* d_n_found)
@@ -666,13 +644,12 @@ static int sift_enqueue(sfmhip_ctx* ctx, const uint8_t* d_img, int rows, int col
     SfmCarve carve;
     const size_t o_cnt = carve(sizeof(SiftCounters)), o_pyr = carve(P.pyr_floats * 4), o_tmp = carve(2 * P.base_pixels * 4),
                  o_cand = carve(K * sizeof(SiftCand)), o_ext = carve(K * sizeof(SiftExt)), o_raw = carve(Kr * sizeof(SiftRaw)), o_list = carve(Kr * 4);
-    SiftSort S;
-    S.carve(carve, Kr);
+    SfmSort S(carve, Kr); SfmScan F(carve, Kr + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
-    S.bind(w);
+    S.bind(w); F.bind(w);
     SiftCounters* cnt = (SiftCounters*)(w + o_cnt);
     float* pyr = (float*)(w + o_pyr);
     SiftCand* cand = (SiftCand*)(w + o_cand); SiftExt* ext = (SiftExt*)(w + o_ext); SiftRaw* raws = (SiftRaw*)(w + o_raw);
@@ -691,9 +668,9 @@ static int sift_enqueue(sfmhip_ctx* ctx, const uint8_t* d_img, int rows, int col
         hipLaunchKernelGGL(sift_key_kernel, dim3(kb), dim3(256), 0, st, (const SiftRaw*)raws, (const pu32*)S.v[cur], (pu32)Kr, (const SiftCounters*)cnt, pass, S.k[cur]);
         cur = S.sort(st, Kr, cur, 64, false);
     }
-    hipLaunchKernelGGL(sift_unique_flag_kernel, dim3(kb1), dim3(256), 0, st, (const SiftRaw*)raws, (const pu32*)S.v[cur], (pu32)Kr, (const SiftCounters*)cnt, S.flag);
-    sfm_enqueue_scan_u32(st, S.flag, Kr + 1, S.scan);
-    hipLaunchKernelGGL(sift_compact_kernel, dim3(kb), dim3(256), 0, st, (const pu32*)S.v[cur], (const pu32*)S.flag, (pu32)Kr, cnt, list);
+    hipLaunchKernelGGL(sift_unique_flag_kernel, dim3(kb1), dim3(256), 0, st, (const SiftRaw*)raws, (const pu32*)S.v[cur], (pu32)Kr, (const SiftCounters*)cnt, F.data);
+    F.scan(st, Kr + 1);
+    hipLaunchKernelGGL(sift_compact_kernel, dim3(kb), dim3(256), 0, st, (const pu32*)S.v[cur], (const pu32*)F.data, (pu32)Kr, cnt, list);
     const pu32* order = list;
     if (max_features > 0) {
         (void)hipMemcpyAsync(S.v[0], list, Kr * 4, hipMemcpyDeviceToDevice, st);
@@ -810,8 +787,7 @@ int sfmhip_sift_extrema(sfmhip_ctx* ctx, const uint8_t* img, int rows, int cols,
     SfmCarve carve;
     const size_t o_cnt = carve(sizeof(SiftCounters)), o_pyr = carve(P.pyr_floats * 4), o_tmp = carve(2 * P.base_pixels * 4), o_cand = carve(K * sizeof(SiftCand)),
                  o_ext = carve(K * sizeof(SiftExt)), o_xysr = carve((size_t)cap * 16), o_olrc = carve((size_t)cap * 16), o_n = carve(4);
-    SiftSort S;
-    S.carve(carve, K);
+    SfmSort S(carve, K);
     SfmPoolHold hold(ctx);
     uint8_t* d_img = nullptr; char* w = nullptr;
     int rc = sift_upload_image(ctx, hold, img, rows, cols, channels, ld, &d_img);

@@ -12,10 +12,11 @@
 //                           and the number of its triangles
 //   tsdf_edge_kernel        the voxel as the owner of its 7 edges: the mask of those that carry a vertex (a sign change, and a
 //                           processed cell among the 1, 2 or 4 around the edge), and their number
-//                           -- the exclusive scans of ba_setup.hpp then number the vertices and place the triangles
+//                           -- the exclusive scans of sortscan.hpp then number the vertices and place the triangles
 //   tsdf_vertex_kernel      the vertices of a voxel's edges: position and colour
 //   tsdf_triangle_kernel    the triangles of a cell; a vertex number is base[owner] + popcount(mask[owner] & below(bit))
 #include "common.hpp"
+#include "sortscan.hpp"
 #include <cmath>
 #pragma clang fp contract(off)
 
@@ -298,19 +299,21 @@ static int mesh_enqueue(sfmhip_ctx* ctx, const int* dims, const double* origin, 
     const TsdfGrid G = tsdf_grid(dims, origin, voxel);
     const size_t nvox = G.nvox;
     SfmCarve carve;
-    const size_t o_code = carve(nvox * 4), o_mask = carve(nvox), o_vb = carve((nvox + 1) * 4), o_tb = carve((nvox + 1) * 4), o_scan = carve(sfm_scan_bsum_words(nvox + 1) * 4);
+    const size_t o_code = carve(nvox * 4), o_mask = carve(nvox);
+    SfmScan VB(carve, nvox + 1), TB(carve, nvox + 1);
     SfmPoolHold hold(ctx);
     char* w = nullptr;
     const int rc = hold.get(carve.bytes, (void**)&w);
     if (rc != SFMHIP_OK) return rc;
+    VB.bind(w); TB.bind(w);
     uint32_t* code = (uint32_t*)(w + o_code);
     uint8_t* mask = (uint8_t*)(w + o_mask);
-    unsigned *vb = (unsigned*)(w + o_vb), *tb = (unsigned*)(w + o_tb), *scan = (unsigned*)(w + o_scan);
+    unsigned *vb = VB.data, *tb = TB.data;
     const dim3 grid = tsdf_launch_grid(ctx, nvox), block(256);
     hipLaunchKernelGGL(tsdf_cell_kernel, grid, block, 0, ctx->stream, G, d_dsum, d_wsum, min_weight, code, tb);
     hipLaunchKernelGGL(tsdf_edge_kernel, grid, block, 0, ctx->stream, G, (const uint32_t*)code, mask, vb);
-    sfm_enqueue_scan_u32(ctx->stream, vb, nvox + 1, scan);
-    sfm_enqueue_scan_u32(ctx->stream, tb, nvox + 1, scan);
+    VB.scan(ctx->stream, nvox + 1);
+    TB.scan(ctx->stream, nvox + 1);
     hipLaunchKernelGGL(tsdf_vertex_kernel, grid, block, 0, ctx->stream, G, d_dsum, d_wsum, d_csum, (const uint8_t*)mask, (const unsigned*)vb, d_xyz, d_bgr,
                        (unsigned)vertex_cap, d_nv);
     hipLaunchKernelGGL(tsdf_triangle_kernel, grid, block, 0, ctx->stream, G, (const uint32_t*)code, (const uint8_t*)mask, (const unsigned*)vb, (const unsigned*)tb, d_tri,

@@ -1,4 +1,4 @@
-"""sfmhip_ba_create builds its orderings on the device (csrc/ba_setup.hpp: radix sorts, scans, gathers).  The tables must
+"""sfmhip_ba_create builds its orderings on the device (csrc/ba_setup.hpp: gathers between the radix sorts and scans of csrc/sortscan.hip).  The tables must
 be, entry by entry, what the serial host code of rounds 1-2 produced; that construction is restated here in numpy
 (lexsort = the stable sorts it used).  Reference: bundle_adjustment() hands the observation list to ceres::Problem in
 NViewReconstuct.cpp:1187-1210; the orderings themselves are internal to this implementation."""
