@@ -1180,6 +1180,41 @@ int sfmhip_mesh_vertex_normals_dev(sfmhip_ctx*, const double* d_xyz, int nv, con
 int sfmhip_mesh_smooth    (sfmhip_ctx*, const double* xyz,   int nv, const int32_t* tri,   int nt, int iterations, double lambda, double mu, double* xyz_out);
 int sfmhip_mesh_smooth_dev(sfmhip_ctx*, const double* d_xyz, int nv, const int32_t* d_tri, int nt, int iterations, double lambda, double mu, double* d_xyz_out);
 
+/* ---- View selection for the dense stage (extension; not in the reference): which views to sweep a view against, and over which inverse
+ * depths, decided from the sparse model as Colmap and OpenMVS decide it -- by the sparse points two views share under a sufficient
+ * triangulation angle, and by the depths of the points a view sees.  The inputs are what sfmhip_ba_solve leaves: ext6 (n_views x 6,
+ * angle-axis and t, world to camera), pts (n_pt x 3 double), obs_cam / obs_pt (n_obs int32 each).  What follows is the definition;
+ * tests/select_ref.py restates it in numpy.  All arithmetic is in double, evaluated in the written order without contraction; the counts
+ * are integers; every output is the same bits for every run and launch geometry.
+ *   1. Geometry.  Rinv_i (row-major) and c_i are what sfmhip_sweep_geometry returns for view i.
+ *   2. Observations.  An observation is VALID when the three coordinates of its point are finite.  A (point, view) pair that is observed
+ *      more than once counts once; everything below speaks of the distinct valid pairs.
+ *   3. Ray and depth of point X in view i: a = X - c_i component by component; z = ((a0*Rinv_i[2] + a1*Rinv_i[5]) + a2*Rinv_i[8]).
+ *   4. Pair counts.  For every point and every two views i < j that see it, shared[i][j] and shared[j][i] grow by one, and score[i][j]
+ *      and score[j][i] grow by one when z_i > 0, z_j > 0 and, with d = (a0*b0 + a1*b1) + a2*b2, na = (a0*a0 + a1*a1) + a2*a2 and nb
+ *      likewise (a in view i, b in view j): d <= 0 || d*d <= cos2_min * (na*nb).  The diagonals are zero.  cos2_min is the squared cosine
+ *      of the smallest angle that counts; the callers convert from degrees.
+ *   5. Sources.  sources[i][0 .. n_src) starts with the views j != i of score[i][j] > 0, by score descending, then index ascending;
+ *      n_scored[i] is how many of the n_src came that way.  The rest are the views not yet listed, by squared centre distance
+ *      ((dx*dx + dy*dy) + dz*dz), dx = c_j[0] - c_i[0] ..., ascending, then index ascending.  A view always has n_src sources.
+ *   6. Depth range.  s is the ascending list of z over the pairs of view i with z > 0, m = n_depth[i] its length.  m < 2: wrange[i] =
+ *      (0, 0).  Else zlo = s[(2*(m-1)) / 100], zhi = s[(98*(m-1) + 99) / 100] (integer division: order statistics, nothing interpolated),
+ *      wlo = 1/zhi, whi = 1/zlo, span = whi - wlo, span = 0.5*wlo if !(span > 0), x = wlo - 0.25*span, y = 0.5*wlo, and
+ *      wrange[i] = (y > x ? y : x, whi + 0.25*span).
+ * shared, score: n_views x n_views int32; sources: n_views x n_src int32; n_scored, n_depth: n_views int32; wrange: n_views x 2 double.
+ * Every output may be NULL.  SFMHIP_E_ARG with the outputs left alone: ctx or ext6 NULL, pts NULL with n_pt > 0, obs_cam or obs_pt NULL
+ * with n_obs > 0, n_views outside 2 .. 4096, n_src outside 1 .. min(8, n_views - 1), cos2_min not finite or outside [0, 1], n_pt or n_obs
+ * negative, a pose or the centre it gives not finite, and, in the host form, an index of obs_cam outside [0, n_views) or of obs_pt outside
+ * [0, n_pt).  n_obs == 0 is no error: the counts are zero, the sources come from the centres and the ranges are (0, 0).  A failed
+ * allocation is SFMHIP_E_HIP, the outputs are left alone and the next call works.
+ * The _dev form takes pts, obs_cam, obs_pt and every output on the device, only enqueues on the context's stream and never synchronises;
+ * ext6 stays a host array in both forms, like the poses and intrinsics of every other _dev entry (it is read before the call returns).  It
+ * cannot look at the indices: an observation with an index out of range is IGNORED there, like one of a non-finite point. */
+int sfmhip_select_views    (sfmhip_ctx*, const double* ext6, int n_views, const double* pts,   int n_pt, const int32_t* obs_cam,   const int32_t* obs_pt,   int n_obs,
+                            double cos2_min, int n_src, int32_t* shared,   int32_t* score,   int32_t* sources,   int32_t* n_scored,   double* wrange,   int32_t* n_depth);
+int sfmhip_select_views_dev(sfmhip_ctx*, const double* ext6, int n_views, const double* d_pts, int n_pt, const int32_t* d_obs_cam, const int32_t* d_obs_pt, int n_obs,
+                            double cos2_min, int n_src, int32_t* d_shared, int32_t* d_score, int32_t* d_sources, int32_t* d_n_scored, double* d_wrange, int32_t* d_n_depth);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,7 @@ SYMBOLS = [
     "sfmhip_mesh_simplify", "sfmhip_mesh_simplify_dev", "sfmhip_mesh_vertex_normals", "sfmhip_mesh_vertex_normals_dev",
     "sfmhip_mesh_smooth", "sfmhip_mesh_smooth_dev",
     "sfmhip_debug_sort_pairs", "sfmhip_debug_scan_u32",
+    "sfmhip_select_views", "sfmhip_select_views_dev",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
@@ -244,6 +245,8 @@ def load():
         "sfmhip_mesh_smooth_dev": (i32, [vp, vp, i32, vp, i32, i32, f64, f64, vp]),
         "sfmhip_debug_sort_pairs": (i32, [vp, vp, vp, sz, i32, vp, vp]),
         "sfmhip_debug_scan_u32": (i32, [vp, vp, sz, vp, vp]),
+        "sfmhip_select_views": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_select_views_dev": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

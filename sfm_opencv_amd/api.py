@@ -5,7 +5,9 @@ get_matched_points (989), reconstruct (1117), bundle_adjustment (1162).  cv::Mat
 arrays (host entry points) or torch CUDA tensors (device entry points); outputs are returned instead of filled.
 Everything here calls libsfmhip.so; nothing falls back to the CPU.
 """
+import collections
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -1106,6 +1108,31 @@ class Context:
                                                         int(planes), float(wmin), float(wmax), int(radius), int(min_sources), float(cost_scale), int(P1), int(P2),
                                                         int(paths), int(max_cost), _dptr(d_plane), _dptr(d_win_cost), _dptr(d_depth)))
 
+    def select_views(self, ext, pts, obs_cam, obs_pt, n_src=2, min_angle_deg=1.0):
+        """SelectedViews of sfmhip_select_views (where the definition is): the covisibility counts of the views, every view's n_src sources
+        ranked by the sparse points shared under at least min_angle_deg, and every view's inverse-depth range from the points it sees.
+        ext: the bundle adjustment's (angle-axis, t) rows; pts n x 3; obs_cam, obs_pt: its observation lists"""
+        ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6); pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        oc = np.ascontiguousarray(obs_cam, np.int32).ravel(); op = np.ascontiguousarray(obs_pt, np.int32).ravel()
+        if len(oc) != len(op):
+            raise ValueError("obs_cam and obs_pt are lists of one length")
+        n, k = len(ext), int(n_src)
+        shared = np.zeros((n, n), np.int32); score = np.zeros((n, n), np.int32); sources = np.zeros((n, max(k, 0)), np.int32); n_scored = np.zeros(n, np.int32)
+        wrange = np.zeros((n, 2)); n_depth = np.zeros(n, np.int32)
+        self._check(self.lib.sfmhip_select_views(self.h, ext.ctypes.data, n, pts.ctypes.data if len(pts) else None, len(pts), oc.ctypes.data if len(oc) else None,
+                                                 op.ctypes.data if len(op) else None, len(oc), select_cos2(min_angle_deg), k, shared.ctypes.data, score.ctypes.data,
+                                                 sources.ctypes.data, n_scored.ctypes.data, wrange.ctypes.data, n_depth.ctypes.data))
+        return SelectedViews(shared, score, sources, n_scored, wrange, n_depth)
+
+    def select_views_dev(self, ext, d_pts, n_pt, d_obs_cam, d_obs_pt, n_obs, n_src, min_angle_deg, d_shared=None, d_score=None, d_sources=None, d_n_scored=None,
+                         d_wrange=None, d_n_depth=None):
+        """the same on resident arrays (torch CUDA tensors or device addresses; ext stays a host array), any output may be None: enqueues
+        on the context's stream, never synchronises.  An observation with an index out of range is ignored"""
+        ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)
+        self._check(self.lib.sfmhip_select_views_dev(self.h, ext.ctypes.data, len(ext), _dptr(d_pts), int(n_pt), _dptr(d_obs_cam), _dptr(d_obs_pt), int(n_obs),
+                                                     select_cos2(min_angle_deg), int(n_src), _dptr(d_shared), _dptr(d_score), _dptr(d_sources), _dptr(d_n_scored),
+                                                     _dptr(d_wrange), _dptr(d_n_depth)))
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
@@ -1662,11 +1689,36 @@ def dense_depth_range(sparse_pts, ext6):
     return max(wlo - 0.25 * span, 0.5 * wlo), whi + 0.25 * span
 
 
-def _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax, min_sources, min_score, min_consistent, sgm):
+SelectedViews = collections.namedtuple("SelectedViews", "shared score sources n_scored wrange n_depth")
+
+
+def select_cos2(min_angle_deg):
+    """cos^2 of the smallest triangulation angle that counts, the form sfmhip_select_views takes (0 <= angle <= 90 degrees)"""
+    a = float(min_angle_deg)
+    if not 0.0 <= a <= 90.0:
+        raise ValueError("min_angle_deg lies in [0, 90]")
+    c = math.cos(a * (math.pi / 180.0))
+    return c * c
+
+
+def select_views(ext, pts, obs_cam, obs_pt, n_src=2, min_angle_deg=1.0, ctx=None):
+    """Context.select_views on the given or a new context: SelectedViews(shared, score, sources, n_scored, wrange, n_depth)"""
+    own = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        return ctx.select_views(ext, pts, obs_cam, obs_pt, n_src, min_angle_deg)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax, min_sources, min_score, min_consistent, sgm, observations=None,
+                      min_angle_deg=1.0):
     """what dense_cloud_for_all and dense_mesh_for_all share: the images on the device, every view's sources and geometry arrays, and its
     depth map (plane sweep, or its semi-global form), all enqueued on the context's stream.  Returns (device, d_img, rows, cols, channels,
     sources, geometry, d_depth, min_consistent, scratch); the caller holds on to `scratch`, the sweeps' other outputs, until it has
-    synchronised the context: the sweeps may still be writing them."""
+    synchronised the context: the sweeps may still be writing them.  observations = (obs_cam, obs_pt) into sparse_pts: the sources and the
+    ranges come from Context.select_views instead of the camera centres and the whole cloud."""
     import torch
     ext = np.ascontiguousarray(ext, np.float64).reshape(-1, 6)
     n_img = len(images)
@@ -1682,14 +1734,29 @@ def _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, w
     if any(t.shape != d_img[0].shape or t.dtype != torch.uint8 for t in d_img) or (ch == 3 and d_img[0].shape[2] != 3):
         raise ValueError("images are uint8 arrays of one size, rows x cols or rows x cols x 3")
     torch.cuda.synchronize(dev)                      # the uploads ran on torch's stream, the stages run on the context's
-    sources = dense_sources(ext, n_src)
+    sel = None
+    if observations is not None:
+        # sources and ranges from the sparse model (sfmhip_select_views); the call drains the stream before the sweeps are enqueued
+        if sparse_pts is None:
+            raise ValueError("observations index sparse_pts: give both")
+        sel = ctx.select_views(ext, sparse_pts, observations[0], observations[1], n_src, min_angle_deg)
+        sources = [[int(j) for j in row] for row in sel.sources]
+        if (wmin is None or wmax is None) and (sel.n_depth < 2).any():
+            raise ValueError("fewer than two sparse points in front of a view: give wmin and wmax")
+    else:
+        sources = dense_sources(ext, n_src)
     geo = [sweep_geometry(K4, ext[i], ext[sources[i]]) for i in range(n_img)]
     npx = rows * cols
     d_depth = [torch.empty(npx, dtype=torch.float32, device=dev) for _ in range(n_img)]
     d_plane = torch.empty(npx, dtype=torch.int32, device=dev); d_score = torch.empty(npx, dtype=torch.float32, device=dev)
     d_cost = torch.empty(npx if sgm is not None else 0, dtype=torch.int16, device=dev)       # the winners' 16-bit costs
     for i in range(n_img):
-        lo, hi = (wmin, wmax) if wmin is not None and wmax is not None else dense_depth_range(sparse_pts, ext[i])
+        if wmin is not None and wmax is not None:
+            lo, hi = wmin, wmax
+        elif sel is None:
+            lo, hi = dense_depth_range(sparse_pts, ext[i])
+        else:
+            lo, hi = (float(x) for x in sel.wrange[i])
         if sgm is not None:
             cost_scale, P1, P2, paths, max_cost = sgm
             ctx.plane_sweep_sgm_dev(d_img[i], [d_img[j] for j in sources[i]], rows, cols, ch, cols * ch, geo[i][0], geo[i][1], planes, lo, hi, radius,
@@ -1701,7 +1768,7 @@ def _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, w
 
 
 def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, radius=2, wmin=None, wmax=None, min_sources=1, min_score=0.5, rel_tol=0.01,
-                        min_consistent=None, voxel=0.0, ctx=None, sgm=None):
+                        min_consistent=None, voxel=0.0, ctx=None, sgm=None, observations=None, min_angle_deg=1.0):
     """The dense step after the bundle adjustment: every view is swept against the n_src views with the nearest camera centres
     (sfmhip_plane_sweep_dev), its depth map is checked against theirs (sfmhip_depth_consistency_dev), the kept pixels become coloured
     world points (sfmhip_depth_to_points_dev), and the views' points are concatenated in view order.  images: uint8 arrays (or torch
@@ -1710,13 +1777,17 @@ def dense_cloud_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, ra
     given.  voxel > 0: the cloud is replaced by one centroid per voxel (voxel_downsample; a voxel's colour is the rounded mean of its
     points' per channel).  sgm = (cost_scale, P1, P2, paths, max_cost): the sweep's costs are aggregated along 4 or 8 directions before
     the winner is taken (sfmhip_plane_sweep_sgm_dev; at most 256 planes, min_score is not used); None: the winner per pixel.  The
-    images, depth maps and masks stay on the device between the stages.  Returns (xyz n x 3 float64, bgr n x 3 uint8)."""
+    images, depth maps and masks stay on the device between the stages.  observations = (obs_cam, obs_pt), the bundle adjustment's lists
+    into sparse_pts: every view is swept against the n_src views it shares the most sparse points with under at least min_angle_deg of
+    triangulation angle, over the depths of the points it sees (sfmhip_select_views); wmin and wmax, where given, still set the range.
+    Returns (xyz n x 3 float64, bgr n x 3 uint8)."""
     import torch
     own = ctx is None
     ctx = ctx or Context(0)
     try:
         dev, d_img, rows, cols, ch, sources, geo, d_depth, min_consistent, scratch = _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax,
-                                                                                                         min_sources, min_score, min_consistent, sgm)
+                                                                                                         min_sources, min_score, min_consistent, sgm, observations,
+                                                                                                         min_angle_deg)
         n_img, npx = len(d_img), rows * cols
         d_keep = torch.empty(npx, dtype=torch.uint8, device=dev)
         d_xyz = torch.empty((npx, 3), dtype=torch.float64, device=dev); d_bgr = torch.empty((npx, 3), dtype=torch.uint8, device=dev)
@@ -1778,7 +1849,7 @@ def tsdf_bounds(sparse_pts, voxels=128, margin=0.1):
 
 def dense_mesh_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, radius=2, wmin=None, wmax=None, min_sources=1, min_score=0.5, rel_tol=0.01,
                        min_consistent=None, ctx=None, voxels=128, trunc_voxels=4, min_weight=2, sgm=None, volume=None, min_component=None, keep_largest=False,
-                       simplify_voxels=None, smooth=None, normals=False):
+                       simplify_voxels=None, smooth=None, normals=False, observations=None, min_angle_deg=1.0):
     """The dense surface after the bundle adjustment: the depth maps and keep masks of dense_cloud_for_all's chain (same arguments, same
     meaning) stay on the device, all views are fused into one truncated signed distance volume 8 per call (sfmhip_tsdf_integrate_dev) and
     the volume is meshed by marching tetrahedra (sfmhip_tsdf_mesh_dev, once for the counts and once into arrays of that size).  The
@@ -1793,7 +1864,8 @@ def dense_mesh_for_all(images, K4, ext, sparse_pts=None, n_src=2, planes=64, rad
     ctx = ctx or Context(0)
     try:
         dev, d_img, rows, cols, ch, sources, geo, d_depth, min_consistent, scratch = _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax,
-                                                                                                         min_sources, min_score, min_consistent, sgm)
+                                                                                                         min_sources, min_score, min_consistent, sgm, observations,
+                                                                                                         min_angle_deg)
         n_img, npx = len(d_img), rows * cols
         dims, origin, voxel = volume if volume is not None else tsdf_bounds(sparse_pts, voxels)
         nvox = int(dims[0]) * int(dims[1]) * int(dims[2])

@@ -821,6 +821,10 @@ struct DenseOptions {
     int mesh_smooth_iterations = 0;
     double mesh_smooth_lambda = 0.5, mesh_smooth_mu = -0.53;
     bool mesh_normals = false;
+    // the bundle adjustment's observation lists into sparse_pts (empty: the sources are the nearest camera centres and the range comes from
+    // the whole cloud, as before): the sources and every view's range come from select_views, pairs counted from min_angle_deg on
+    std::vector<int32_t> obs_cam, obs_pt;
+    double min_angle_deg = 1.0;
 };
 // numpy.percentile(z, q) with its default linear interpolation, z sorted ascending
 inline double dense_percentile(const std::vector<double>& z, const double q)
@@ -851,9 +855,36 @@ inline bool dense_depth_range(const std::vector<Point3d>& sparse_pts, const doub
     wmax = whi + 0.25 * span;
     return true;
 }
+// ---- view selection (extension; sfmhip_select_views, where the definition is), the mirror of api.select_views: the covisibility counts of
+// the views (shared, score: n_views x n_views), every view's n_src sources ranked by the sparse points shared under at least min_angle_deg
+// (sources: n_views x n_src; n_scored of them by score, the rest by centre distance), and every view's inverse-depth range from the n_depth
+// points it sees in front of it (wrange: n_views x 2, zeros where n_depth < 2).  false on error.
+struct SelectedViews {
+    int n_views = 0, n_src = 0;
+    std::vector<int32_t> shared, score, sources, n_scored, n_depth;
+    std::vector<double> wrange;
+};
+inline bool select_views(const std::vector<Mat>& extrinsics, const std::vector<Point3d>& pts, const std::vector<int32_t>& obs_cam, const std::vector<int32_t>& obs_pt,
+                         const int n_src, const double min_angle_deg, SelectedViews& out)
+{
+    sfmhip_ctx* ctx = context();
+    const int n = (int)extrinsics.size();
+    if (!ctx || n < 2 || n_src < 1 || obs_cam.size() != obs_pt.size() || !(min_angle_deg >= 0.0 && min_angle_deg <= 90.0)) return false;
+    std::vector<double> ext((size_t)n * 6);
+    for (int i = 0; i < n; ++i) std::memcpy(&ext[6 * (size_t)i], extrinsics[i].ptr<double>(), 6 * sizeof(double));
+    const double c = std::cos(min_angle_deg * (M_PI / 180.0));
+    out.n_views = n; out.n_src = n_src;
+    out.shared.assign((size_t)n * n, 0); out.score.assign((size_t)n * n, 0); out.sources.assign((size_t)n * n_src, 0);
+    out.n_scored.assign(n, 0); out.n_depth.assign(n, 0); out.wrange.assign((size_t)n * 2, 0.0);
+    const int rc = sfmhip_select_views(ctx, ext.data(), n, pts.empty() ? nullptr : &pts[0].x, (int)pts.size(), obs_cam.empty() ? nullptr : obs_cam.data(),
+                                       obs_pt.empty() ? nullptr : obs_pt.data(), (int)obs_cam.size(), c * c, n_src, out.shared.data(), out.score.data(),
+                                       out.sources.data(), out.n_scored.data(), out.wrange.data(), out.n_depth.data());
+    if (rc != SFMHIP_OK) printf("[Err]: select_views: %s\n", sfmhip_last_error(ctx));
+    return rc == SFMHIP_OK;
+}
 struct DenseGeo { float A[72], b[24]; double Rrel[72], trel[24], Rinv[9], c[3]; };
-// what dense_cloud_for_all and dense_mesh_for_all share: the sources of every view (the nearest camera centres), its geometry arrays and
-// its depth map (the plane sweep, or its semi-global form); false on error, with the message printed under the caller's name
+// what dense_cloud_for_all and dense_mesh_for_all share: the sources of every view (the nearest camera centres, or select_views' where
+// opt.obs_cam is given), its geometry arrays and its depth map (the plane sweep, or its semi-global form); false on error, with the message printed under the caller's name
 inline bool dense_depth_maps(sfmhip_ctx* ctx, const char* who, const std::vector<const uint8_t*>& images, const int rows, const int cols, const int channels,
                              const Mat& intrinsic, const std::vector<Mat>& extrinsics, const std::vector<Point3d>& sparse_pts, const DenseOptions& opt, int& n_src,
                              std::vector<std::vector<int>>& sources, std::vector<DenseGeo>& geo, std::vector<std::vector<float>>& depth)
@@ -870,7 +901,14 @@ inline bool dense_depth_maps(sfmhip_ctx* ctx, const char* who, const std::vector
     for (int i = 0; i < n_img; ++i)
         if (sfmhip_sweep_geometry(K1, extrinsics[i].ptr<double>(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &cen[3 * (size_t)i]) != SFMHIP_OK) return false;
     sources.assign(n_img, std::vector<int>());
+    SelectedViews sel;
+    const bool by_model = !opt.obs_cam.empty();
+    if (by_model && !select_views(extrinsics, sparse_pts, opt.obs_cam, opt.obs_pt, n_src, opt.min_angle_deg, sel)) return false;
     for (int i = 0; i < n_img; ++i) {
+        if (by_model) {
+            sources[i].assign(sel.sources.begin() + (size_t)i * n_src, sel.sources.begin() + (size_t)(i + 1) * n_src);
+            continue;
+        }
         std::vector<std::pair<double, int>> d;
         for (int j = 0; j < n_img; ++j) {
             if (j == i) continue;
@@ -892,7 +930,9 @@ inline bool dense_depth_maps(sfmhip_ctx* ctx, const char* who, const std::vector
         DenseGeo& g = geo[i];
         if (sfmhip_sweep_geometry(K4, extrinsics[i].ptr<double>(), e, n_src, g.A, g.b, g.Rrel, g.trel, g.Rinv, g.c) != SFMHIP_OK) return false;
         double wmin = opt.wmin, wmax = opt.wmax;
-        if (!(wmin < wmax) && !dense_depth_range(sparse_pts, extrinsics[i].ptr<double>(), wmin, wmax)) {
+        bool have = wmin < wmax;
+        if (!have && by_model && sel.n_depth[i] >= 2) { wmin = sel.wrange[2 * (size_t)i]; wmax = sel.wrange[2 * (size_t)i + 1]; have = true; }
+        if (!have && (by_model || !dense_depth_range(sparse_pts, extrinsics[i].ptr<double>(), wmin, wmax))) {
             printf("[Err]: %s: no depth range for view %d\n", who, i);
             return false;
         }
