@@ -168,7 +168,7 @@ __global__ void fill_kernel(double* __restrict__ p, size_t n, double v)
 // host-side problem
 // ------------------------------------------------------------------------------------------------
 enum { SEAM_LIN_IN_BACK = 4, SEAM_INTR_FRONT = 8, SEAM_CAMSTEP_ROLES = 16, SEAM_TREE_BACKWARD = 32, SEAM_BACK_REDUCE = 64, SEAM_PIVOT_FOLD = 128,
-       SEAM_ALL = 4 | 8 | 16 | 32 | 64 | 128 };
+       SEAM_SPEC_BUILD = 256, SEAM_ALL = 4 | 8 | 16 | 32 | 64 | 128 | 256 };
 struct sfmhip_ba {
     sfmhip_ctx* ctx = nullptr;
     sfm_ba_options o;
@@ -258,6 +258,10 @@ struct sfmhip_ba {
     // loads in flight; 32: one backward launch for the tree below the top (chol_tree_backward_kernel); 64: ba_back_reduce_kernel with
     // its loads in flight.  Bit 7 (128): a node's first pivot block factored under its assembly (ba_solver.hpp, SolverPlan::overlap): nodes with
     // an assembly step (chol_node_forward_kernel's separators, chol_top_kernel) fold that block first and the rest beside wave 0's factorisation.
+    // Bit 8 (256, needs bits 2 and 3): the LM step is judged under the next Schur build, not in front of it.  ba_loop queues the next
+    // ba_camschur_kernel at the candidate right behind ba_back_kernel_lin, and the first workgroup of its front group does ba_back_reduce_kernel's
+    // job (the sums and the publication to the host), so that launch disappears; an accepted step with the guessed radius adopts the partials
+    // (ba_fold_kernel follows), any other outcome leaves them unfolded and builds again (enqueue_spec_build).
     // 0 = every piece a launch / a loop / a phase of its own.
     int seam = SEAM_ALL;
     int* d_tree_path = nullptr; size_t tree_path_cap = 0; bool tree_ok = false;      // per-leaf ancestor lists of the solver plan (bit 5)
@@ -266,6 +270,7 @@ struct sfmhip_ba {
     int err_cur = 0;               // which of the two flags belongs to the current set
     bool pt_ready = false;         // the current set holds the point pass at the current parameters and radius (adopted, not yet consumed)
     bool pt_fold_err = false;      // ... and its flag has yet to reach the host: the next ba_back_reduce_kernel folds it in
+    long long spec_launched = 0, spec_adopted = 0;      // SFMHIP_EXPERIMENTS builds only: ba_camschur_kernel launches queued ahead of the decision (bit 8), and those folded
     bool built = false; int build_parity = 0;    // d_msg holds the undamped linearisation at the CURRENT parameters (set by a speculative build)
     double phase_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; int phase_cnt = 0;
 };
@@ -404,7 +409,7 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
         // the intrinsic block + scalars need only the point pass: a front group of this launch reduces them (SFMHIP_BA_SEAM bit 3)
         intr_in_front = (h->seam & SEAM_INTR_FRONT) != 0;
         hipLaunchKernelGGL(ba_camschur_kernel, dim3(n_cam_blocks + n_schur_blocks + (intr_in_front ? 8 : 0)), dim3(256), 0, st, P, n_cam_blocks, h->d_chunk_desc, h->nchunk,
-                           h->d_items, h->d_part_schur, intr_in_front ? h->n_pt_blocks : 0);
+                           h->d_items, h->d_part_schur, intr_in_front ? h->n_pt_blocks : 0, BackPub{});
         if (tv) { (void)hipEventRecord(tv[2], st); (void)hipEventRecord(tv[4], st); }
     }
     if (!folded)
@@ -414,6 +419,50 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
         hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3(ceil_div(h->nblk * 36, 256)), dim3(256), 0, st, P, h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, 1);
     SFM_HIP_TRY(ctx, hipGetLastError());
     return enqueue_build_exchange(h, carry);
+}
+
+// SFMHIP_BA_SEAM bit 8, single rank, one-launch form only.  The next build's ba_camschur_kernel at the candidate, queued right behind
+// ba_back_kernel_lin and before the host has judged the step: it reads the point pass that kernel left in the second point-side set
+// (damped with spec_radius), and the first workgroup of its front group reduces and publishes the step scalars first (R: what
+// ba_back_reduce_kernel would have been given).  Besides that publication the launch stores only part_cam and part_schur (partials nothing
+// reads before ba_fold_kernel), and from ba_finalize_intr_role the intrinsic block of S, its rhs / diagU / graw entries, the padding zeros
+// of the tail and scal[SCAL_COST] / this rank's gradient-maximum slot: plain stores, none of them an accumulation, and every one is
+// stored again by the ba_camschur_kernel of a build at the current point (same role, same addresses) before anything reads it.  So a
+// step that is rejected, invalid or ends at another radius simply leaves the launch unfolded and builds again; S stays as K_back
+// zero-filled it (h->cleared) but for that block.
+static bool spec_build_applies(const sfmhip_ba* h)
+{
+    const int n_cam_blocks = round_up(h->nc * h->cam_split * (h->fixK ? 1 : 2), 8);
+    const int n_schur_blocks = h->nblk > 0 ? round_up(ceil_div(h->nchunk, 4), 8) : 0;
+    return (h->seam & SEAM_SPEC_BUILD) && (h->seam & SEAM_INTR_FRONT) && !h->ar_fn && h->d_Vinv2 &&
+           !(n_schur_blocks > 0 && n_cam_blocks + n_schur_blocks > h->fuse_max_blocks);
+}
+static int enqueue_spec_build(sfmhip_ba* h, double spec_radius, const BackPub& R)
+{
+    BADev P = make_dev(h, spec_radius, true);
+    P.Vinv = h->d_Vinv2; P.bp = h->d_bp2; P.WK = h->d_WK2; P.colsq_p = h->d_colsq_p2; P.part_pt = h->d_part_pt2;
+    const int n_cam_blocks = round_up(h->nc * h->cam_split * (h->fixK ? 1 : 2), 8);
+    const int n_schur_blocks = h->nblk > 0 ? round_up(ceil_div(h->nchunk, 4), 8) : 0;
+    hipLaunchKernelGGL(ba_camschur_kernel, dim3(n_cam_blocks + n_schur_blocks + 8), dim3(256), 0, h->ctx->stream, P, n_cam_blocks, h->d_chunk_desc, h->nchunk,
+                       h->d_items, h->d_part_schur, h->n_pt_blocks, R);
+    SFM_HIP_TRY(h->ctx, hipGetLastError());
+    return SFMHIP_OK;
+}
+// ... adopted: the step was accepted with spec_radius and ba_loop has swapped the parameter and point-side sets, so those partials belong to
+// the current point.  The rest of the build, as enqueue_build queues it behind its ba_camschur_kernel.
+static int enqueue_spec_adopt(sfmhip_ba* h)
+{
+    hipStream_t st = h->ctx->stream;
+    BADev P = make_dev(h, h->radius);
+    h->build_timed = false; h->cleared = false;
+    h->pt_ready = false; h->pt_fold_err = true;          // the adopted point pass is consumed; its flag reaches the host with the next reduction
+    hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + (h->nblk > 0 ? ceil_div(h->nblk * 36, 256) : 0)), dim3(256), 0, st, P, h->n_pt_blocks,
+                       h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, 0);
+    if (h->n_diag_blk > 0)
+        hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3(ceil_div(h->nblk * 36, 256)), dim3(256), 0, st, P, h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, 1);
+    SFM_HIP_TRY(h->ctx, hipGetLastError());
+    h->built = true;
+    return SFMHIP_OK;
 }
 
 // multi-rank: the packed sum of the reduced-system message over the ranks
@@ -546,7 +595,8 @@ static int enqueue_solve(sfmhip_ba* h)
 }
 
 // lin_radius > 0: ba_back_kernel_lin, the point pass of the next linearisation damped with lin_radius into the second set
-static int enqueue_back(sfmhip_ba* h, double radius, double lin_radius = 0.0)
+// pub_later (single rank, publishing): ba_back_reduce_kernel is not launched, its arguments are handed back instead
+static int enqueue_back(sfmhip_ba* h, double radius, double lin_radius = 0.0, BackPub* pub_later = nullptr)
 {
     sfmhip_ctx* ctx = h->ctx;
     hipStream_t st = ctx->stream;
@@ -581,9 +631,10 @@ static int enqueue_back(sfmhip_ba* h, double radius, double lin_radius = 0.0)
         hipLaunchKernelGGL(ba_back_const_kernel, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1);
     else
         hipLaunchKernelGGL(ba_back_kernel, back_grid, dim3(256), 0, st, P, h->n_pt_blocks, h->d_msg, n0, h->d_topbuf, n1);
-    hipLaunchKernelGGL(ba_back_reduce_kernel, dim3(1), dim3(256), 0, st, h->d_part_back, h->n_pt_blocks, h->d_back4,
-                       d_scal, h->d_cam2, h->d_err, fuse_publish ? h->h_scal : (double*)nullptr, fuse_publish ? ++h->pub_seq : 0ull, err_fold,
-                       (h->seam & SEAM_BACK_REDUCE) ? 1 : 0);
+    const BackPub R = { h->d_part_back, h->n_pt_blocks, h->d_back4, d_scal, h->d_cam2, h->d_err, fuse_publish ? h->h_scal : (double*)nullptr,
+                        fuse_publish ? ++h->pub_seq : 0ull, err_fold, (h->seam & SEAM_BACK_REDUCE) ? 1 : 0 };
+    if (pub_later) *pub_later = R;          // the caller's next launch reduces and publishes (enqueue_spec_build)
+    else hipLaunchKernelGGL(ba_back_reduce_kernel, dim3(1), dim3(256), 0, st, R.part, R.nblocks, R.out4, R.scal2, R.cam2, R.err, R.host_out, R.seq, R.err_fold, R.staged);
     if (err_fold) h->pt_fold_err = false;
     h->published = fuse_publish;
     SFM_HIP_TRY(ctx, hipGetLastError());
@@ -1042,21 +1093,18 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
     const int it_end = h->iter + max_it;
     const size_t np2 = (size_t)h->npad * h->npad;
     const double* d_scal = h->d_msg + np2 + 3 * (size_t)h->npad;
-    // Per iteration the host needs four scalars back before it can accept or reject the step.  SFMHIP_SPECULATE=1 enqueues
-    // the NEXT linearisation at the candidate parameters right behind the scalar copies (guessing the radius growth of a
-    // good step), so that an accepted step finds its build already running.  Measured at C4: 11 of 12 guesses hit, results
-    // bit-identical, but no gain (0.695 vs 0.686 ms per step): the round trip is ~10 us of a 0.67 ms iteration and the extra
-    // enqueue work costs as much.  Off by default.
-    // On several ranks the speculation is how the LM iteration gets by with ONE collective: the step's five scalars ride in the
-    // message of the speculative linearisation at the candidate (accepted with the guessed radius: the next iteration starts
-    // from it; rejected or another radius: it is discarded and the next iteration linearises again -- one more collective).
-#ifdef SFMHIP_EXPERIMENTS
-    static const bool speculate_env = getenv("SFMHIP_SPECULATE") != nullptr;
-#else
-    constexpr bool speculate_env = false;
-#endif
+    // Per iteration the host needs the step's scalars back before it can accept or reject the step, and the device has nothing to do
+    // while they travel.  Two paths queue work for the NEXT iteration at the candidate parameters ahead of that decision, guessing the
+    // radius growth of a good step (the point blocks are damped while they are built):
+    // On several ranks a whole speculative linearisation is how the LM iteration gets by with ONE collective: the step's five scalars
+    // ride in its message (accepted with the guessed radius: the next iteration starts from it; rejected or another radius: it is
+    // discarded and the next iteration linearises again -- one more collective).
+    // On one rank (SFMHIP_BA_SEAM bit 8) only the next ba_camschur_kernel is queued ahead, and it carries the reduction and publication
+    // of the scalars in its front group (enqueue_spec_build): ba_back_reduce_kernel's launch and the round trip to the host leave the
+    // critical path.  A wrong guess costs that launch once: the path is taken again only after a step that was accepted with its
+    // guessed radius (or at the start of a call), never in a call's last iteration, under kernel timing or above the one-launch size.
     const bool folded = h->ar_fn != nullptr;
-    const bool speculate = speculate_env || folded;
+    bool spec_ok = spec_build_applies(h);        // the last decided step kept to the guess (a call starts eligible)
     for (;;) {
         if (h->iter >= it_end) { h->termination = SFMHIP_BA_NO_CONVERGENCE; break; }
         if (!forced && h->radius < o.min_trust_region_radius) { h->termination = SFMHIP_BA_CONVERGENCE; break; }
@@ -1076,11 +1124,19 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
         // rho >= 0.937 (the normal case while LM is making progress) grows it by exactly 1 / (1/3)
         const double spec_radius = std::min(o.max_trust_region_radius, h->radius / (1.0 / 3.0));
         // single rank: the back-substitution carries the next point pass (SFMHIP_BA_SEAM bit 2)
-        const bool lin_in_back = (h->seam & SEAM_LIN_IN_BACK) && !h->ar_fn && !speculate && h->d_Vinv2;
+        const bool lin_in_back = (h->seam & SEAM_LIN_IN_BACK) && !h->ar_fn && h->d_Vinv2;
+        const bool spec_build = lin_in_back && spec_ok && !ctx->timing && h->iter + 1 < it_end && spec_build_applies(h);
+        BackPub pub;
         h->publish_in_back = true; h->fold_step_scalars = folded;
-        rc = enqueue_back(h, h->radius, lin_in_back ? spec_radius : 0.0); h->publish_in_back = false; h->fold_step_scalars = false; if (rc) return rc;
+        rc = enqueue_back(h, h->radius, lin_in_back ? spec_radius : 0.0, spec_build ? &pub : nullptr); h->publish_in_back = false; h->fold_step_scalars = false; if (rc) return rc;
         if (timing) SFM_HIP_TRY(ctx, hipEventRecord(ti[2], st));
         bool speculated = false;
+        if (spec_build) {
+            rc = enqueue_spec_build(h, spec_radius, pub); if (rc) return rc;
+#ifdef SFMHIP_EXPERIMENTS
+            ++h->spec_launched;
+#endif
+        }
         // folded: ba_back_reduce_kernel has parked this linearisation's cost and gradient maximum in d_back4[5..6] (the build below
         // overwrites the message tail they live in), and the exchange of the build sums d_back4[0..4] over the ranks
         if (folded) {
@@ -1095,7 +1151,6 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
             hipLaunchKernelGGL(ba_publish_kernel, dim3(1), dim3(64), 0, st, folded ? (const double*)(h->d_back4 + 5) : d_scal, h->d_back4, h->d_cam2, h->d_err, h->h_scal, seq,
                                folded ? 2 : (h->ar_fn ? 0 : 1));
         }
-        if (!folded && speculate && h->iter + 1 < it_end) { rc = enqueue_build(h, spec_radius, true, true); if (rc) return rc; speculated = true; }
         read_pending_timing(h);                     // the PREVIOUS iteration's events, while the GPU works on this one
         if (timing) { h->pending_build = par; h->pending_iter = h->iter_parity; }
         {   // spin on the sequence number; if the stream drains without publishing (a failed launch) the query ends the wait.
@@ -1154,6 +1209,15 @@ static int ba_loop(sfmhip_ba* h, int max_it, bool forced)
         }
         // a point pass that was not adopted may have left its flag up: re-arm it before the next back-substitution writes the set again
         if (lin_in_back && !h->pt_ready) SFM_HIP_TRY(ctx, hipMemsetAsync(h->d_err_pt + (h->err_cur ^ 1), 0, sizeof(int), st));
+        // the launch queued ahead was built at what is now the current point, with the radius it guessed: fold it (else: left unfolded)
+        const bool guess_held = accepted && h->radius == spec_radius;
+        if (spec_build && guess_held) {
+            rc = enqueue_spec_adopt(h); if (rc) return rc;
+#ifdef SFMHIP_EXPERIMENTS
+            ++h->spec_adopted;
+#endif
+        }
+        spec_ok = guess_held && spec_build_applies(h);
 #ifdef SFMHIP_EXPERIMENTS
         if (o.verbose) fprintf(stderr, "[sfmhip_ba dbg] err %d mcc %.6e cand %.12e dn %.3e\n", err, mcc, cand_raw, dn);
 #endif
@@ -1556,13 +1620,14 @@ static int ba_create_impl(sfmhip_ctx* ctx, const double* K4, const double* ext6,
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { sfmhip_ba_destroy(h); ctx->last_error = "upload failed"; return SFMHIP_E_HIP; }
     h->setup_ms[3] = ms_since(t0);
     if (h->o.verbose)
-        printf("[sfmhip_ba] seam %d: the next point pass %s; intrinsic block + scalars %s; gradient maximum %s; backward sweep below the top %s; ba_back_reduce_kernel's loads %s; an assembling node's first pivot block %s\n", h->seam,
+        printf("[sfmhip_ba] seam %d: the next point pass %s; intrinsic block + scalars %s; gradient maximum %s; backward sweep below the top %s; ba_back_reduce_kernel's loads %s; an assembling node's first pivot block %s; the next ba_camschur_kernel %s\n", h->seam,
                h->d_Vinv2 ? "rides in the back-substitution (ba_back_kernel_lin)" : "is a launch of its own (ba_point_kernel)",
                (h->seam & SEAM_INTR_FRONT) ? "in ba_camschur_kernel's front group (where camera items and pair chunks share that launch)" : "in ba_fold_kernel",
                (h->seam & SEAM_CAMSTEP_ROLES) ? "in a workgroup of its own" : "behind the step in block 0",
                (h->seam & SEAM_TREE_BACKWARD) ? "in one launch (if the plan has parallel separator levels)" : "a launch per level",
                (h->seam & SEAM_BACK_REDUCE) ? "in flight together" : "trip by trip",
-               (h->seam & SEAM_PIVOT_FOLD) ? "factored under the rest of the assembly" : "factored after the assembly");
+               (h->seam & SEAM_PIVOT_FOLD) ? "factored under the rest of the assembly" : "factored after the assembly",
+               spec_build_applies(h) ? "queued ahead of the step decision, publishing the step scalars" : "queued after the step decision");
     if (h->o.verbose)
         printf("[sfmhip_ba] create %.2f ms (inputs + observation sort %.2f, orderings %.2f, pair lists %.2f)\n", h->setup_ms[3], h->setup_ms[0],
                h->setup_ms[1] - h->setup_ms[0], h->setup_ms[2] - h->setup_ms[1]);
@@ -1743,6 +1808,15 @@ int sfmhip_ba_debug_table(sfmhip_ba* h, const char* name, void* out, size_t cap_
         if (out && cap_bytes >= sz) memcpy(out, h->h_scal, sz);
         return SFMHIP_OK;
     }
+#ifdef SFMHIP_EXPERIMENTS
+    else if (nm == "speculation") {
+        // SFMHIP_BA_SEAM bit 8: [ba_camschur_kernel launches queued ahead of the host's decision, those adopted] since sfmhip_ba_create
+        const int v[2] = { (int)h->spec_launched, (int)h->spec_adopted };
+        if (n_bytes) *n_bytes = sizeof v;
+        if (out && cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
+        return SFMHIP_OK;
+    }
+#endif
     else if (nm == "setup_ms") { if (n_bytes) *n_bytes = sizeof h->setup_ms; if (out && cap_bytes >= sizeof h->setup_ms) memcpy(out, h->setup_ms, sizeof h->setup_ms); return SFMHIP_OK; }
     else { ctx->last_error = "sfmhip_ba_debug_table: unknown table"; return SFMHIP_E_ARG; }
     if (n_bytes) *n_bytes = bytes;

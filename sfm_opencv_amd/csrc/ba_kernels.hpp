@@ -849,13 +849,76 @@ __device__ __forceinline__ void ba_schur_reduce_role(const BADev& P, const int* 
     }
 }
 
+// The arguments of ba_back_reduce_kernel (K_back's closing reduction, below), as a block: ba_camschur_kernel's front group takes them
+// too when it does that kernel's job (SFMHIP_BA_SEAM bit 8).  host_out == nullptr there: the launch carries no such role.
+struct BackPub {
+    const double* part; int nblocks; double* out4; const double *scal2, *cam2; int* err; double* host_out; unsigned long long seq; int* err_fold; int staged;
+};
+
+// out4 = sum over blocks of part_back (K_back's per-block records) by one workgroup of 256.
+// With host_out != nullptr (single rank: nothing is all-reduced in between) the block also publishes the decision scalars,
+// i.e. does ba_publish_kernel's job in the same launch.  red: 16 doubles of LDS.  (No __restrict__ here: the kernel's arguments carry it, and
+// with it repeated on these parameters ba_back_reduce_kernel compiled to another instruction order than it had as a kernel body.)
+__device__ __forceinline__ void ba_back_reduce_body(double (*red)[4], const double* part, int nblocks, double* out4, const double* scal2, const double* cam2, int* err,
+                                                    double* host_out, unsigned long long seq, int* err_fold, int staged)
+{
+    double acc[4] = { 0, 0, 0, 0 };
+    if (staged) {
+        // the records of up to eight trips requested (two 16-byte loads each) before the first add; the adds in the same order
+        for (int b0 = threadIdx.x; b0 < nblocks; b0 += 256 * 8) {
+            double2 v[8][2];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int b = b0 + 256 * u;
+                if (b < nblocks) { v[u][0] = *(const double2*)(part + 4 * (size_t)b); v[u][1] = *(const double2*)(part + 4 * (size_t)b + 2); }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (b0 + 256 * u < nblocks) { acc[0] += v[u][0].x; acc[1] += v[u][0].y; acc[2] += v[u][1].x; acc[3] += v[u][1].y; }
+        }
+    } else
+    for (int b = threadIdx.x; b < nblocks; b += 256)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] += part[4 * (size_t)b + i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = wave_sum(acc[i]);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[threadIdx.x >> 6][i] = acc[i];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const double v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        out4[threadIdx.x] = v;
+        if (host_out) host_out[2 + threadIdx.x] = v;
+    }
+    // multi-rank: the error flag travels with the step scalars (summed by the all-reduce: > 0 on every rank if any rank set it);
+    // out4[5..6] keep this linearisation's cost and gradient maximum (scal2[0..1]) for the publish kernel: with the step scalars
+    // folded into the next message, the next build has overwritten the message tail by the time the host is told
+    if (!host_out && threadIdx.x == 4) out4[4] = *err != 0 ? 1.0 : 0.0;
+    if (!host_out && (threadIdx.x == 5 || threadIdx.x == 6)) out4[threadIdx.x] = scal2[threadIdx.x - 5];
+    if (host_out) {
+        const int l = threadIdx.x;
+        if (l >= 64 && l < 66) host_out[l - 64] = scal2[l - 64];
+        else if (l >= 66 && l < 68) host_out[6 + l - 66] = cam2[l - 66];
+        else if (l == 68) {
+            // err_fold: this iteration's point pass came out of the previous ba_back_kernel_lin, its non-SPD flag with it
+            int e = *err;
+            if (err_fold) { if (*err_fold != 0) e = 1; *err_fold = 0; }
+            host_out[8] = (double)e; *err = 0;
+        }
+        __threadfence_system();
+        __syncthreads();
+        if (l == 0) __hip_atomic_store((unsigned long long*)(host_out + 15), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // The launches of the build after K_pt.  K_cam and K_schur depend only on K_pt and both leave issue slots idle, so their
 // workgroups share ONE launch (first n_cam_blocks: camera items, the rest: pair chunks; both counts multiples of 8, so a
 // workgroup's XCD is its role-local index mod 8) -- as two launches on two streams the fork / join events cost 5-7 us of stream
 // gap each.  Likewise the two folds: K_finalize's workgroups and the off-diagonal pass of K_schur_reduce write disjoint parts
 // of the message; the rare (a, a) blocks add onto what K_finalize wrote and keep their own launch (diag_pass = 1).
 __global__ __launch_bounds__(256, 3) void ba_camschur_kernel(BADev P, int n_cam_blocks, const int4* __restrict__ chunk_desc, int n_chunk,
-                                                          const int4* __restrict__ items, double* __restrict__ part, int front)      // front: 0, or the number of point blocks
+                                                          const int4* __restrict__ items, double* __restrict__ part, int front, BackPub R)      // front: 0, or the number of point blocks
 {
     __shared__ double red[4][CAMACC];
     // front > 0: one more group of 8 in front of the grid, whose first workgroup reduces the point pass's records into the intrinsic
@@ -868,7 +931,15 @@ __global__ __launch_bounds__(256, 3) void ba_camschur_kernel(BADev P, int n_cam_
     const int before = (int)(((long long)g * Gc) / G), upto = (int)(((long long)(g + 1) * Gc) / G);      // camera groups in [0, g) and [0, g]
     // (the front group as the first branch of this chain, not as an early return in front of it: that form cost the camera role its
     // register allocation -- 109 spilled registers instead of 10)
-    if (bx < 0) { if (blockIdx.x == 0) ba_finalize_intr_role<40>(P, front); }
+    // R.host_out != nullptr: this launch was queued right behind K_back, at the candidate, before the host has judged the step (ba_loop,
+    // SFMHIP_BA_SEAM bit 8), and the front group's first workgroup does ba_back_reduce_kernel's job first: it must read scal[SCAL_COST]
+    // and the gradient maximum of the linearisation the step came from before ba_finalize_intr_role stores the candidate's over them.
+    if (bx < 0) {
+        if (blockIdx.x == 0) {
+            if (R.host_out) ba_back_reduce_body((double (*)[4])&red[0][0], R.part, R.nblocks, R.out4, R.scal2, R.cam2, R.err, R.host_out, R.seq, R.err_fold, R.staged);
+            ba_finalize_intr_role<40>(P, front);
+        }
+    }
     else if (upto > before) ba_camera_role(P, red, before * 8 + (bx & 7), n_cam_blocks);
     else ba_schur_role(P, chunk_desc, n_chunk, items, part, (g - before) * 8 + (bx & 7), nbx - n_cam_blocks);
 }
@@ -1269,62 +1340,13 @@ __global__ __launch_bounds__(256, 3) void ba_back_lin_const_kernel(BADev P, int 
     ba_back_body<true, true>(P, n_pt_blocks, z0, n0, z1, n1, O, next_radius, err_n);
 }
 
-// out4 = sum over blocks of part_back
-// With host_out != nullptr (single rank: nothing is all-reduced in between) the block also publishes the decision scalars,
-// i.e. does ba_publish_kernel's job in the same launch.
+// K_back's closing reduction as a launch of its own (ba_back_reduce_body, in front of ba_camschur_kernel)
 __global__ __launch_bounds__(256) void ba_back_reduce_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ out4,
                                                              const double* __restrict__ scal2, const double* __restrict__ cam2, int* __restrict__ err,
                                                              double* __restrict__ host_out, unsigned long long seq, int* __restrict__ err_fold, int staged)
 {
     __shared__ double red[4][4];
-    double acc[4] = { 0, 0, 0, 0 };
-    if (staged) {
-        // the records of up to eight trips requested (two 16-byte loads each) before the first add; the adds in the same order
-        for (int b0 = threadIdx.x; b0 < nblocks; b0 += 256 * 8) {
-            double2 v[8][2];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int b = b0 + 256 * u;
-                if (b < nblocks) { v[u][0] = *(const double2*)(part + 4 * (size_t)b); v[u][1] = *(const double2*)(part + 4 * (size_t)b + 2); }
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (b0 + 256 * u < nblocks) { acc[0] += v[u][0].x; acc[1] += v[u][0].y; acc[2] += v[u][1].x; acc[3] += v[u][1].y; }
-        }
-    } else
-    for (int b = threadIdx.x; b < nblocks; b += 256)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] += part[4 * (size_t)b + i];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = wave_sum(acc[i]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[threadIdx.x >> 6][i] = acc[i];
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const double v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        out4[threadIdx.x] = v;
-        if (host_out) host_out[2 + threadIdx.x] = v;
-    }
-    // multi-rank: the error flag travels with the step scalars (summed by the all-reduce: > 0 on every rank if any rank set it);
-    // out4[5..6] keep this linearisation's cost and gradient maximum (scal2[0..1]) for the publish kernel: with the step scalars
-    // folded into the next message, the next build has overwritten the message tail by the time the host is told
-    if (!host_out && threadIdx.x == 4) out4[4] = *err != 0 ? 1.0 : 0.0;
-    if (!host_out && (threadIdx.x == 5 || threadIdx.x == 6)) out4[threadIdx.x] = scal2[threadIdx.x - 5];
-    if (host_out) {
-        const int l = threadIdx.x;
-        if (l >= 64 && l < 66) host_out[l - 64] = scal2[l - 64];
-        else if (l >= 66 && l < 68) host_out[6 + l - 66] = cam2[l - 66];
-        else if (l == 68) {
-            // err_fold: this iteration's point pass came out of the previous ba_back_kernel_lin, its non-SPD flag with it
-            int e = *err;
-            if (err_fold) { if (*err_fold != 0) e = 1; *err_fold = 0; }
-            host_out[8] = (double)e; *err = 0;
-        }
-        __threadfence_system();
-        __syncthreads();
-        if (l == 0) __hip_atomic_store((unsigned long long*)(host_out + 15), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    ba_back_reduce_body(red, part, nblocks, out4, scal2, cam2, err, host_out, seq, err_fold, staged);
 }
 
 // cost only at the current parameters (used for |x| bookkeeping at start-up): not needed separately --
