@@ -1215,6 +1215,58 @@ int sfmhip_select_views    (sfmhip_ctx*, const double* ext6, int n_views, const 
 int sfmhip_select_views_dev(sfmhip_ctx*, const double* ext6, int n_views, const double* d_pts, int n_pt, const int32_t* d_obs_cam, const int32_t* d_obs_pt, int n_obs,
                             double cos2_min, int n_src, int32_t* d_shared, int32_t* d_score, int32_t* d_sources, int32_t* d_n_scored, double* d_wrange, int32_t* d_n_depth);
 
+/* ---- Tracks from pairwise matches (extension; the reference links consecutive pairs only, NViewReconstuct.cpp:959-983, 1246-1301): the
+ * connected components of the match graph over ANY pair list, as Colmap, OpenMVG (TracksBuilder) and OpenCV's sfm module build them, and
+ * from them the observation lists that sfmhip_triangulate_tracks, the bundle adjustment and sfmhip_select_views take.  What follows is the
+ * definition; tests/tracks_ref.py restates it in numpy.  Integer work only.
+ *   Inputs.  n_img images (1 .. 65536) with n_kp[i] >= 0 key points; off[i] is the exclusive prefix sum of n_kp, feature (i, k) has the
+ *      global id g = off[i] + k, n_feat = off[n_img] < 2^31.  pairs[2q] is the query image of pair q and pairs[2q+1] its train image;
+ *      matches (n_pairs x max_per_pair sfm_dmatch) and counts (n_pairs int32) are laid out as sfmhip_match_pairs_dev,
+ *      sfmhip_verify_matches_dev and sfmhip_two_view_geometry_matches_dev leave them.
+ *   1. Valid elements.  Pair q = (a, b) contributes its first c = min(max(counts[q], 0), max_per_pair) elements.  One of them is VALID iff
+ *      0 <= a, b < n_img, a != b, 0 <= queryIdx < n_kp[a] and 0 <= trainIdx < n_kp[b]; every other one among those c is ignored and
+ *      counted.  imgIdx and distance are not read.
+ *   2. Components.  The connected components of the graph on the n_feat features whose edges are the valid elements; a component's root
+ *      is its smallest global id.
+ *   3. Conflicts.  List a component's features in ascending g -- ascending (image, key point).  A feature is FIRST OF ITS IMAGE if it is
+ *      the component's first feature or its image differs from that of the feature before it.  A component with a feature that is not
+ *      first of its image is CONFLICTING.  flags = SFMHIP_TRACKS_DROP_CONFLICTS (0, OpenMVG's rule) drops it whole;
+ *      SFMHIP_TRACKS_KEEP_FIRST keeps it with its first-of-image features only.
+ *   4. Length.  A component's length is its number of first-of-image features.  A component of at least two features that survived step
+ *      3 is a TRACK iff its length is >= min_len (min_len >= 2); otherwise it is SHORT.
+ *   5. Numbering.  Tracks are numbered 0, 1, ... by ascending root; the observations are the kept features in ascending (track, g) order,
+ *      which is (track, image).
+ * The same bytes therefore come out for any order of the pairs, any order of the elements inside a pair, any duplication of an edge, every
+ * run and every launch geometry.
+ * Outputs, each may be NULL:
+ *   track_of    n_feat int32: the track of a kept feature, else -1.  Image by image this is the correspond_struct_idx of the reference.
+ *   obs_cam, obs_pt, obs_kp   int32, capacity n_feat, the first n_obs entries written: image, track and key-point index in the image.
+ *   obs_uv      capacity n_feat pairs of double, ((double)kp.x, (double)kp.y).  It needs kp: n_img pointers to sfm_keypoint arrays (in the
+ *               _dev form a host array of device pointers, as in sfmhip_verify_matches_dev); an entry may be NULL only where n_kp[i] == 0.
+ *   track_len   int32, capacity n_feat / 2, the first n_tracks entries written.
+ *   matches_out, counts_out   in the layout of the input: in order, the elements of every pair that are valid and whose two features are
+ *               both kept observations (of one track, then); counts_out[q] is their number, and nothing behind them is written.  For the
+ *               sequential drivers and sfmhip_triangulate2_matches_dev: OpenMVG's match filtering by track consistency.
+ *   stats       int32[8]: n_tracks, n_obs, components of at least two features, conflicting components (dropped or repaired), short
+ *               components, ignored elements, the longest track, 1 if a union gave up after its retry cap (as in sfmhip_cluster_dbscan).
+ * SFMHIP_E_ARG with every output untouched: ctx, n_kp, pairs (with n_pairs > 0), or matches or counts (with n_pairs > 0 and
+ * max_per_pair > 0) NULL; n_pairs, max_per_pair or an n_kp[i] negative; n_img outside 1 .. 65536; n_feat >= 2^31; min_len < 2; a bit of
+ * flags other than SFMHIP_TRACKS_KEEP_FIRST; obs_uv without kp or with a NULL entry of an image that has key points; outputs that overlap
+ * one another, matches or counts.  n_pairs == 0 or n_feat == 0 is no error: track_of is all -1, counts_out and stats are zero.  A failed
+ * allocation is SFMHIP_E_HIP with no output touched, and the next call works.  If a union gave up (stats[7]), the host form returns
+ * SFMHIP_E_NUMERIC with the outputs left alone; the _dev form reports n_tracks = -1 and the other outputs are unspecified.
+ * The _dev form takes matches, counts, the key points and every output on the device, only enqueues on the context's stream and never
+ * synchronises; n_kp, pairs and the pointer table stay host arrays, read before the call returns.  The host form copies back only the
+ * written prefixes. */
+#define SFMHIP_TRACKS_DROP_CONFLICTS 0
+#define SFMHIP_TRACKS_KEEP_FIRST     1
+int sfmhip_build_tracks    (sfmhip_ctx*, int n_img, const int32_t* n_kp, const int32_t* pairs, int n_pairs, const sfm_dmatch* matches,   int max_per_pair,
+                            const int32_t* counts,   const sfm_keypoint* const* kp,   int min_len, int flags, int32_t* track_of,   int32_t* obs_cam,   int32_t* obs_pt,
+                            int32_t* obs_kp,   double* obs_uv,   int32_t* track_len,   sfm_dmatch* matches_out,   int32_t* counts_out,   int32_t* stats);
+int sfmhip_build_tracks_dev(sfmhip_ctx*, int n_img, const int32_t* n_kp, const int32_t* pairs, int n_pairs, const sfm_dmatch* d_matches, int max_per_pair,
+                            const int32_t* d_counts, const sfm_keypoint* const* d_kp, int min_len, int flags, int32_t* d_track_of, int32_t* d_obs_cam, int32_t* d_obs_pt,
+                            int32_t* d_obs_kp, double* d_obs_uv, int32_t* d_track_len, sfm_dmatch* d_matches_out, int32_t* d_counts_out, int32_t* d_stats);
+
 #ifdef __cplusplus
 }
 #endif

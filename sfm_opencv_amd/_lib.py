@@ -85,9 +85,11 @@ SYMBOLS = [
     "sfmhip_mesh_smooth", "sfmhip_mesh_smooth_dev",
     "sfmhip_debug_sort_pairs", "sfmhip_debug_scan_u32",
     "sfmhip_select_views", "sfmhip_select_views_dev",
+    "sfmhip_build_tracks", "sfmhip_build_tracks_dev",
 ]
 
 MATCH_MUTUAL = 1          # SFMHIP_MATCH_MUTUAL
+TRACKS_CONFLICTS = {"drop": 0, "keep-first": 1}      # SFMHIP_TRACKS_DROP_CONFLICTS, SFMHIP_TRACKS_KEEP_FIRST
 POINTS_METHODS = {"auto": 0, "brute": 1, "grid": 2}      # SFMHIP_POINTS_*
 
 _lib = None
@@ -247,6 +249,8 @@ def load():
         "sfmhip_debug_scan_u32": (i32, [vp, vp, sz, vp, vp]),
         "sfmhip_select_views": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
         "sfmhip_select_views_dev": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_build_tracks": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sfmhip_build_tracks_dev": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

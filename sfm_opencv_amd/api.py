@@ -1133,6 +1133,58 @@ class Context:
                                                      select_cos2(min_angle_deg), int(n_src), _dptr(d_shared), _dptr(d_score), _dptr(d_sources), _dptr(d_n_scored),
                                                      _dptr(d_wrange), _dptr(d_n_depth)))
 
+    # ---------------------------------------------------------------- tracks from pairwise matches
+    def build_tracks(self, n_kp, pairs, matches, counts, kp=None, min_len=2, conflicts="drop", filter_matches=True):
+        """Tracks of sfmhip_build_tracks (where the definition is) from match lists of any pair list.  n_kp: key points per image; pairs
+        (n_pairs, 2); matches (n_pairs, max_per_pair) DMATCH and counts (n_pairs,), the layout match_pairs_dev leaves; kp: one KEYPOINT
+        array per image, for obs_uv.  Returns (track_of, obs_cam, obs_pt, obs_kp, obs_uv or None, track_len, stats, matches_out,
+        counts_out), trimmed to the written prefixes (matches_out: full rows, counts_out[q] of them written; both None without
+        filter_matches)"""
+        n_kp = np.ascontiguousarray(n_kp, np.int32).ravel(); pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        matches = np.ascontiguousarray(matches, DMATCH); counts = np.ascontiguousarray(counts, np.int32).ravel()
+        flags = _tracks_flags(min_len, conflicts)
+        P = len(pairs)
+        if matches.ndim != 2 or matches.shape[0] != P or len(counts) != P:
+            raise ValueError("matches is n_pairs x max_per_pair, counts n_pairs")
+        if (n_kp < 0).any() or int(n_kp.astype(np.int64).sum()) >= 2 ** 31:
+            raise ValueError("n_kp: non-negative counts with a sum below 2^31")
+        n = int(n_kp.sum()); S = matches.shape[1]
+        arr = None
+        if kp is not None:
+            if len(kp) != len(n_kp):
+                raise ValueError("one key-point array per image")
+            kp = [np.ascontiguousarray(k, KEYPOINT) for k in kp]
+            if any(len(k) < c for k, c in zip(kp, n_kp)):
+                raise ValueError("a key-point array is shorter than n_kp says")
+            arr = (C.c_void_p * len(kp))(*[k.ctypes.data if len(k) else None for k in kp])
+        track_of = np.empty(n, np.int32); oc = np.empty(n, np.int32); op = np.empty(n, np.int32); ok = np.empty(n, np.int32)
+        uv = np.empty((n, 2)) if kp is not None else None
+        tl = np.empty(n // 2, np.int32); stats = np.zeros(8, np.int32)
+        mo = np.zeros((P, S), DMATCH) if filter_matches else None
+        co = np.zeros(P, np.int32) if filter_matches else None
+        self._check(self.lib.sfmhip_build_tracks(self.h, len(n_kp), n_kp.ctypes.data, pairs.ctypes.data if P else None, P, matches.ctypes.data if P * S else None, S,
+                                                 counts.ctypes.data if P else None, arr, int(min_len), flags, _ptr(track_of), _ptr(oc), _ptr(op), _ptr(ok), _ptr(uv),
+                                                 _ptr(tl), _ptr(mo), _ptr(co), _ptr(stats)))
+        nt, no = int(stats[0]), int(stats[1])
+        return track_of, oc[:no], op[:no], ok[:no], (uv[:no] if uv is not None else None), tl[:nt], stats, mo, co
+
+    def build_tracks_dev(self, n_kp, pairs, d_matches, max_per_pair, d_counts, d_kp=None, min_len=2, conflicts="drop", d_track_of=None, d_obs_cam=None,
+                         d_obs_pt=None, d_obs_kp=None, d_obs_uv=None, d_track_len=None, d_matches_out=None, d_counts_out=None, d_stats=None):
+        """the same on resident arrays (torch CUDA tensors or device addresses; n_kp and pairs stay host arrays, d_kp is a list of
+        device KEYPOINT arrays), any output may be None: enqueues on the context's stream, never synchronises.  d_stats[0] = -1: a
+        union gave up"""
+        n_kp = np.ascontiguousarray(n_kp, np.int32).ravel(); pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        flags = _tracks_flags(min_len, conflicts)
+        arr = None
+        if d_kp is not None:
+            if len(d_kp) != len(n_kp):
+                raise ValueError("one key-point array per image")
+            arr = (C.c_void_p * len(d_kp))(*[_dptr(k) for k in d_kp])
+        self._check(self.lib.sfmhip_build_tracks_dev(self.h, len(n_kp), n_kp.ctypes.data, pairs.ctypes.data if len(pairs) else None, len(pairs), _dptr(d_matches),
+                                                     int(max_per_pair), _dptr(d_counts), arr, int(min_len), flags, _dptr(d_track_of), _dptr(d_obs_cam),
+                                                     _dptr(d_obs_pt), _dptr(d_obs_kp), _dptr(d_obs_uv), _dptr(d_track_len), _dptr(d_matches_out),
+                                                     _dptr(d_counts_out), _dptr(d_stats)))
+
     def points_fallback_count(self):
         """queries the last grid search of this context handed to its brute-force pass (synchronises)"""
         c = C.c_int(0)
@@ -1710,6 +1762,79 @@ def select_views(ext, pts, obs_cam, obs_pt, n_src=2, min_angle_deg=1.0, ctx=None
     finally:
         if own:
             ctx.close()
+
+
+Tracks = collections.namedtuple("Tracks", "correspond_struct_idx obs_cam obs_pt obs_kp obs_uv track_len stats matches_for_all")
+
+
+def _tracks_flags(min_len, conflicts):
+    """the flags of sfmhip_build_tracks for conflicts = "drop" (OpenMVG's rule) or "keep-first"; min_len is at least 2"""
+    if conflicts not in _lib.TRACKS_CONFLICTS:
+        raise ValueError('conflicts is "drop" or "keep-first"')
+    if int(min_len) != min_len or int(min_len) < 2:
+        raise ValueError("min_len is an integer, at least 2")
+    return _lib.TRACKS_CONFLICTS[conflicts]
+
+
+def _tracks_inputs(key_points_for_all, pairs, matches_for_all):
+    """(n_kp, pairs (n_pairs, 2), matches (n_pairs, max_per_pair) padded with -1, counts) of a list of DMATCH arrays; pairs=None: the chain"""
+    n_img = len(key_points_for_all)
+    if n_img < 1:
+        raise ValueError("at least one image")
+    n_kp = np.array([len(k) for k in key_points_for_all], np.int32)
+    if pairs is None:
+        pairs = np.stack([np.arange(n_img - 1), np.arange(1, n_img)], axis=1)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    if len(matches_for_all) != len(pairs):
+        raise ValueError("one match list per pair (pairs=None: the chain (i, i + 1))")
+    if len(pairs) and (pairs.min() < 0 or pairs.max() >= n_img or (pairs[:, 0] == pairs[:, 1]).any()):
+        raise ValueError("a pair names two different images of key_points_for_all")
+    lists = [np.ascontiguousarray(m, DMATCH).ravel() for m in matches_for_all]
+    S = max([len(m) for m in lists], default=0)
+    matches = np.zeros((len(pairs), S), DMATCH)
+    matches["queryIdx"] = -1; matches["trainIdx"] = -1; matches["imgIdx"] = -1
+    for q, m in enumerate(lists):
+        matches[q, :len(m)] = m
+    return n_kp, pairs, matches, np.array([len(m) for m in lists], np.int32)
+
+
+def tracks_for_all(key_points_for_all, pairs, matches_for_all, min_len=2, conflicts="drop", ctx=None):
+    """Tracks from the match lists of ANY pair list (sfmhip_build_tracks, where the definition is): the connected components of the match
+    graph, conflicting components dropped (conflicts="drop", OpenMVG's rule) or cut down to one key point per image ("keep-first"), tracks
+    shorter than min_len left out.  matches_for_all[q] is the DMATCH array of pairs[q] = (query image, train image) as
+    match_features_for_all returns them; pairs=None is the chain (i, i + 1).  key_points_for_all[img]: KEYPOINT array or (n, 2) array.
+    Returns Tracks(correspond_struct_idx, obs_cam, obs_pt, obs_kp, obs_uv, track_len, stats, matches_for_all): one int32 array per image
+    with the track of every key point or -1 (what bundle_adjustment takes), the observation lists in (track, image) order, the length of
+    every track, the eight counters of the C call, and the match lists reduced to the elements between two observations of a track."""
+    flags_ok = _tracks_flags(min_len, conflicts); del flags_ok
+    n_kp, pairs, matches, counts = _tracks_inputs(key_points_for_all, pairs, matches_for_all)
+    structured = all(getattr(k, "dtype", None) is not None and k.dtype.names for k in key_points_for_all)
+    ctx = ctx or default_context()
+    track_of, oc, op, ok, uv, tl, stats, mo, co = ctx.build_tracks(n_kp, pairs, matches, counts, kp=list(key_points_for_all) if structured else None,
+                                                                  min_len=min_len, conflicts=conflicts)
+    if uv is None:                                    # plain coordinate arrays: the same gather on the host, nothing narrowed to float
+        uv = np.zeros((len(oc), 2))
+        for img in np.unique(oc):
+            sel = oc == img
+            uv[sel] = np.asarray(key_points_for_all[img], np.float64).reshape(-1, 2)[ok[sel]]
+    off = np.concatenate([[0], np.cumsum(n_kp.astype(np.int64))])
+    idx = [track_of[off[i]:off[i + 1]].copy() for i in range(len(n_kp))]
+    return Tracks(idx, oc, op, ok, uv, tl, stats, [mo[q, :co[q]].copy() for q in range(len(pairs))])
+
+
+def structure_from_tracks(K, extrinsics, key_points_for_all, pairs, matches_for_all, min_len=2, conflicts="drop", ctx=None):
+    """tracks_for_all, then the N-view DLT of every track under the given poses (Context.triangulate_tracks).  K: 3 x 3 or (fx, fy, cx,
+    cy); extrinsics (n_img, 6) angle-axis and t.  Returns (structure (n_tracks, 3), correspond_struct_idx, tracks), ready for
+    bundle_adjustment"""
+    K = np.asarray(K, np.float64)
+    K4 = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]]) if K.shape == (3, 3) else K.reshape(4)
+    ext = np.ascontiguousarray(extrinsics, np.float64).reshape(-1, 6)
+    if len(ext) != len(key_points_for_all):
+        raise ValueError("one pose per image")
+    ctx = ctx or default_context()
+    tr = tracks_for_all(key_points_for_all, pairs, matches_for_all, min_len, conflicts, ctx)
+    structure, _ = ctx.triangulate_tracks(K4, ext, tr.obs_cam, tr.obs_pt, tr.obs_uv, len(tr.track_len))
+    return structure, tr.correspond_struct_idx, tr
 
 
 def _dense_depth_maps(ctx, images, K4, ext, sparse_pts, n_src, planes, radius, wmin, wmax, min_sources, min_score, min_consistent, sgm, observations=None,

@@ -882,6 +882,53 @@ inline bool select_views(const std::vector<Mat>& extrinsics, const std::vector<P
     if (rc != SFMHIP_OK) printf("[Err]: select_views: %s\n", sfmhip_last_error(ctx));
     return rc == SFMHIP_OK;
 }
+// ---- tracks from pairwise matches (extension; sfmhip_build_tracks, where the definition is), the mirror of api.tracks_for_all: the
+// connected components of the match graph over any pair list.  pairs: (query image, train image) of every list of matches_for_all, empty:
+// the chain (i, i + 1).  correspond_struct_idx[img][kp] = track or -1, as bundle_adjustment takes it; the observation lists are in (track,
+// image) order; matches_for_all comes back reduced to the elements between two observations of a track.  false on error.
+struct Tracks {
+    std::vector<std::vector<int>> correspond_struct_idx;
+    std::vector<int32_t> obs_cam, obs_pt, obs_kp, track_len;
+    std::vector<double> obs_uv;
+    int32_t stats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    std::vector<std::vector<DMatch>> matches_for_all;
+};
+inline bool build_tracks_for_all(const std::vector<std::vector<KeyPoint>>& key_points_for_all, const std::vector<std::pair<int, int>>& pairs,
+                                 const std::vector<std::vector<DMatch>>& matches_for_all, const int min_len, const bool keep_first, Tracks& out)
+{
+    static_assert(sizeof(KeyPoint) == sizeof(sfm_keypoint) && sizeof(DMatch) == sizeof(sfm_dmatch), "layouts of include/sfmhip.h");
+    sfmhip_ctx* ctx = context();
+    const int n_img = (int)key_points_for_all.size();
+    std::vector<int32_t> pr;
+    if (pairs.empty()) for (int i = 0; i + 1 < n_img; ++i) { pr.push_back(i); pr.push_back(i + 1); }
+    else for (const auto& p : pairs) { pr.push_back(p.first); pr.push_back(p.second); }
+    const size_t P = pr.size() / 2;
+    if (!ctx || n_img < 1 || matches_for_all.size() != P) return false;
+    std::vector<int32_t> n_kp(n_img), counts(P);
+    std::vector<const sfm_keypoint*> kp(n_img);
+    size_t n = 0, S = 0;
+    for (int i = 0; i < n_img; ++i) {
+        n_kp[i] = (int32_t)key_points_for_all[i].size(); n += key_points_for_all[i].size();
+        kp[i] = key_points_for_all[i].empty() ? nullptr : (const sfm_keypoint*)key_points_for_all[i].data();
+    }
+    for (size_t q = 0; q < P; ++q) { counts[q] = (int32_t)matches_for_all[q].size(); S = std::max(S, matches_for_all[q].size()); }
+    std::vector<DMatch> m(P * S), mo(P * S);
+    for (size_t q = 0; q < P; ++q) std::copy(matches_for_all[q].begin(), matches_for_all[q].end(), m.begin() + q * S);
+    std::vector<int32_t> track_of(n), counts_out(P, 0);
+    out.obs_cam.assign(n, 0); out.obs_pt.assign(n, 0); out.obs_kp.assign(n, 0); out.track_len.assign(n / 2, 0); out.obs_uv.assign(2 * n, 0.0);
+    const int rc = sfmhip_build_tracks(ctx, n_img, n_kp.data(), pr.data(), (int)P, (const sfm_dmatch*)m.data(), (int)S, counts.data(), kp.data(), min_len,
+                                       keep_first ? SFMHIP_TRACKS_KEEP_FIRST : SFMHIP_TRACKS_DROP_CONFLICTS, track_of.data(), out.obs_cam.data(), out.obs_pt.data(),
+                                       out.obs_kp.data(), out.obs_uv.data(), out.track_len.data(), (sfm_dmatch*)mo.data(), counts_out.data(), out.stats);
+    if (rc != SFMHIP_OK) { printf("[Err]: build_tracks_for_all: %s\n", sfmhip_last_error(ctx)); return false; }
+    const size_t n_tracks = (size_t)out.stats[0], n_obs = (size_t)out.stats[1];
+    out.obs_cam.resize(n_obs); out.obs_pt.resize(n_obs); out.obs_kp.resize(n_obs); out.obs_uv.resize(2 * n_obs); out.track_len.resize(n_tracks);
+    out.correspond_struct_idx.assign(n_img, std::vector<int>());
+    size_t at = 0;
+    for (int i = 0; i < n_img; ++i) { out.correspond_struct_idx[i].assign(track_of.begin() + at, track_of.begin() + at + n_kp[i]); at += (size_t)n_kp[i]; }
+    out.matches_for_all.assign(P, std::vector<DMatch>());
+    for (size_t q = 0; q < P; ++q) out.matches_for_all[q].assign(mo.begin() + q * S, mo.begin() + q * S + counts_out[q]);
+    return true;
+}
 struct DenseGeo { float A[72], b[24]; double Rrel[72], trel[24], Rinv[9], c[3]; };
 // what dense_cloud_for_all and dense_mesh_for_all share: the sources of every view (the nearest camera centres, or select_views' where
 // opt.obs_cam is given), its geometry arrays and its depth map (the plane sweep, or its semi-global form); false on error, with the message printed under the caller's name
