@@ -378,6 +378,23 @@ int  sfmhip_debug_fail_allocations(sfmhip_ctx*, int n);
  * Both: n < 2^31, no output may overlap an input or the other output (SFMHIP_E_ARG), one block of the cache, the stream drained on return. */
 int  sfmhip_debug_sort_pairs(sfmhip_ctx*, const uint64_t* keys, const uint32_t* vals_or_null, size_t n, int bits, uint64_t* keys_out, uint32_t* vals_out);
 int  sfmhip_debug_scan_u32(sfmhip_ctx*, const uint32_t* in, size_t n, uint32_t* out, uint64_t* total64_out);
+/* test hook: the pinned staging ring under every large host array (csrc/common.hpp: sfm_upload, sfm_upload_produced), on host arrays.
+ * The n sources (bytes[i] bytes each) go to n areas of one block of the cache, back to back on the context's stream with no host wait
+ * between them: granule[i] = 0 through sfm_upload, else through sfm_upload_produced with that granule and a fill that copies whole
+ * granules by the share rule of the descriptor batches (thread t of nt takes the granules [c * t / nt, c * (t + 1) / nt) of a piece's c,
+ * the last thread also the bytes behind the piece's last whole granule).  Then the stream is drained once and out[i] receives area i
+ * by a plain hipMemcpy.  stats4 (may be NULL), over the sources with a granule: [0] pieces filled, [1] bytes the fills copied, [2] the
+ * promises a fill saw broken (SFMHIP_UPLOAD_*; such a fill copies nothing), [3] the largest nt a fill saw (1: every piece was filled
+ * by the caller alone; 0: no fill ran).  A granule above 16 MiB is SFMHIP_E_ARG, as are a null array, a null source or output of
+ * bytes[i] > 0 and an output (or stats4) that overlaps a source or another output; n = 0 is SFMHIP_OK.  On every error the outputs and
+ * stats4 are untouched and the stream is drained. */
+#define SFMHIP_UPLOAD_BAD_OFF    1   /* a piece's offset is no multiple of the granule */
+#define SFMHIP_UPLOAD_BAD_PIECE  2   /* a piece that is not the last is no multiple of the granule */
+#define SFMHIP_UPLOAD_BAD_SIZE   4   /* a piece of more than 16 MiB */
+#define SFMHIP_UPLOAD_BAD_THREAD 8   /* t outside [0, nt) */
+#define SFMHIP_UPLOAD_TWICE      16  /* the same (offset, t) twice in one transfer */
+#define SFMHIP_UPLOAD_BAD_RANGE  32  /* a piece that ends behind the transfer */
+int  sfmhip_debug_upload_many(sfmhip_ctx*, const void* const* src, const size_t* bytes, const size_t* granule, int n, void* const* out, uint64_t* stats4);
 /* run the LM loop to termination */
 int  sfmhip_ba_run(sfmhip_ba*, sfm_ba_summary* summary);
 /* run exactly n_iter LM iterations (tolerance checks disabled); state carries over between calls */

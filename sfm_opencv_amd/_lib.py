@@ -83,7 +83,7 @@ SYMBOLS = [
     "sfmhip_mesh_components", "sfmhip_mesh_components_dev", "sfmhip_mesh_filter_components", "sfmhip_mesh_filter_components_dev",
     "sfmhip_mesh_simplify", "sfmhip_mesh_simplify_dev", "sfmhip_mesh_vertex_normals", "sfmhip_mesh_vertex_normals_dev",
     "sfmhip_mesh_smooth", "sfmhip_mesh_smooth_dev",
-    "sfmhip_debug_sort_pairs", "sfmhip_debug_scan_u32",
+    "sfmhip_debug_sort_pairs", "sfmhip_debug_scan_u32", "sfmhip_debug_upload_many",
     "sfmhip_select_views", "sfmhip_select_views_dev",
     "sfmhip_build_tracks", "sfmhip_build_tracks_dev",
 ]
@@ -247,6 +247,7 @@ def load():
         "sfmhip_mesh_smooth_dev": (i32, [vp, vp, i32, vp, i32, i32, f64, f64, vp]),
         "sfmhip_debug_sort_pairs": (i32, [vp, vp, vp, sz, i32, vp, vp]),
         "sfmhip_debug_scan_u32": (i32, [vp, vp, sz, vp, vp]),
+        "sfmhip_debug_upload_many": (i32, [vp, vp, vp, vp, i32, vp, vp]),
         "sfmhip_select_views": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
         "sfmhip_select_views_dev": (i32, [vp, vp, i32, vp, i32, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
         "sfmhip_build_tracks": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

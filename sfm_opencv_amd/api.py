@@ -137,6 +137,20 @@ class Context:
         self._check(self.lib.sfmhip_debug_scan_u32(self.h, a.ctypes.data, a.size, out.ctypes.data, C.byref(total)))
         return out, total.value
 
+    def debug_upload_many(self, sources, granules):
+        """The uint8 arrays `sources` through the pinned staging ring, back to back with no host wait between them, granule 0 by
+        sfm_upload and any other by sfm_upload_produced; returns (what arrived on the device, one uint8 array per source, and
+        dict(pieces, bytes, violations, nt) of the produced transfers) (sfmhip_debug_upload_many, test helper)"""
+        src = [np.ascontiguousarray(s, np.uint8).reshape(-1) for s in sources]
+        n = len(src)
+        outs = [np.full(s.size, 0xEE, np.uint8) for s in src]
+        ptrs = (C.c_void_p * n)(*[s.ctypes.data for s in src]); optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        nb = (C.c_size_t * n)(*[s.size for s in src]); gr = (C.c_size_t * n)(*[int(g) for g in granules])
+        assert len(granules) == n
+        stats = (C.c_uint64 * 4)()
+        self._check(self.lib.sfmhip_debug_upload_many(self.h, ptrs, nb, gr, n, optrs, stats))
+        return outs, dict(pieces=stats[0], bytes=stats[1], violations=stats[2], nt=stats[3])
+
     def set_kernel_timing(self, enable=True):
         """bracket every kNN launch sequence with HIP events (sfmhip_set_kernel_timing)"""
         self._check(self.lib.sfmhip_set_kernel_timing(self.h, 1 if enable else 0))
@@ -192,7 +206,8 @@ class Context:
         n = len(arrs)
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
         rows = np.array([a.shape[0] for a in arrs], np.int32)
-        ld = (C.c_size_t * n)(*[a.strides[0] // a.itemsize for a in arrs])
+        # (numpy gives an array without rows the strides (0, 0): its row stride says nothing, and the library wants ld >= dim)
+        ld = (C.c_size_t * n)(*[a.strides[0] // a.itemsize if a.shape[0] else dim for a in arrs])
         out = (C.c_void_p * n)()
         fn = self.lib.sfmhip_descsets_create_hamming2_host if ham else self.lib.sfmhip_descsets_create_l2_host
         self._check(fn(self.h, ptrs, rows.ctypes.data, dim, ld, n, out))

@@ -25,7 +25,7 @@ struct sfmhip_ctx {
     hipEvent_t stage_ev[2] = { nullptr, nullptr };
     bool   stage_busy[2] = { false, false };
     int    stage_next = 0;
-    struct CopyPool* copy_pool = nullptr;      // three helper threads that fill the staging buffers beside the caller (context.hip)
+    struct CopyPool* copy_pool = nullptr;      // 4 to 16 threads, the caller among them, that fill the staging buffers (copy_pool.hpp)
     // Cache of device blocks (sfm_pool_get / sfm_pool_put), the one source of device memory of this library: the arrays of
     // descriptor sets and bundle-adjustment problems, and every temporary of every call (through an SfmPoolHold, below).
     //  * Who may take blocks: code that works on ctx->stream, and only on it (a BA problem also runs on a second stream:
@@ -133,8 +133,19 @@ static inline int sfm_pinned(sfmhip_ctx* ctx, size_t bytes, void** out)
 // threads instead (43 GB/s, experiments/h2d_bench.hip).  The source has been consumed when the call returns.
 int sfm_upload(sfmhip_ctx* ctx, void* dst, const void* src, size_t bytes);
 // the same, but every pinned piece is PRODUCED on the copy threads on its way into the staging ring (a conversion, a gather of strided
-// rows): fill(piece, off, n, t, nt) writes thread t's share of the bytes [off, off + n) of the transfer to piece[0 .. n); pieces are
-// multiples of `granule` bytes except the last.  Everything fill reads has been consumed when the call returns.
+// rows).  The contract of the ring, in one place (the arithmetic is in copy_pool.hpp):
+//  * Pieces.  The transfer is cut, in order, into pieces [off, off + n) of stage_piece_bytes(STAGE_BYTES, granule) bytes, the last one
+//    shorter: every off is a multiple of `granule`, every n but the last is, no n exceeds STAGE_BYTES.  granule 0 promises nothing
+//    (pieces of STAGE_BYTES); a granule above STAGE_BYTES is refused with SFMHIP_E_ARG before anything is enqueued, whatever `bytes`.
+//  * fill(piece, off, n, t, nt) writes thread t's share of the transfer's bytes [off, off + n) to piece[0 .. n).  A piece of at least
+//    STAGE_PARALLEL_BYTES is filled by one call for every t of [0, nt) at once, on nt = 4 .. 16 threads (the machine decides), a
+//    shorter one by the single call (t, nt) = (0, 1) on the caller's thread; the shares of a piece must cover it for every nt.  fill
+//    runs only inside this call, a piece's calls have all returned before the next piece's begin, and no (off, t) comes twice.
+//  * The source.  Everything fill reads has been consumed when the call returns; the copies to `dst` are then queued on ctx->stream,
+//    not finished.
+//  * Reuse.  The two buffers alternate, across calls too.  A buffer is refilled only after hipEventSynchronize on the event recorded
+//    behind its last copy, so never before that copy has run; when the context moves to another stream, sfmhip_set_stream has drained
+//    the old one first, and the events of the old stream are complete.
 int sfm_upload_produced(sfmhip_ctx* ctx, void* dst, size_t bytes, size_t granule, const std::function<void(char*, size_t, size_t, int, int)>& fill);
 // f(t, nt) on every copy thread of the context, the caller included
 void sfm_parallel(sfmhip_ctx* ctx, const std::function<void(int, int)>& f);
@@ -203,6 +214,12 @@ static inline int sfm_finish(sfmhip_ctx* ctx, hipError_t e)
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline int ceil_div(int x, int m) { return (x + m - 1) / m; }
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// do the host ranges [a, a + na) and [b, b + nb) share a byte (a null pointer shares none): the test hooks refuse such arguments
+static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+}
 
 // one pool block carved into areas that start at multiples of 256 bytes: carve(n) is the offset of the next area of n bytes, and
 // carve.bytes the size of the block that holds the areas handed out so far

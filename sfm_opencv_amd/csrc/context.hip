@@ -1,11 +1,11 @@
 // context.hip -- context lifetime + the host-only ratio tail of libsfmhip.so.
 #include "common.hpp"
+#include "copy_pool.hpp"
+#include <atomic>
 #include <cfloat>
 #include <dlfcn.h>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <sched.h>
+#include <set>
+#include <utility>
 
 SfmRoctx::SfmRoctx()
 {
@@ -18,56 +18,6 @@ SfmRoctx::SfmRoctx()
         push = nullptr; pop = nullptr;
     }
 }
-
-// Helper threads of sfm_upload / sfm_upload_produced: they sleep on a condition variable and each runs its share of the current job.
-// As many as the cores this process may use, between 4 and 16 (the caller is one of them): a memcpy into the staging ring reaches
-// 43 GB/s with four, and a float -> byte conversion on the way in is bound by the DRAM read rate of as many as there are.
-struct CopyPool {
-    int NT;
-    std::vector<std::thread> th;
-    std::mutex mu; std::condition_variable cv_go, cv_done;
-    unsigned long long gen = 0; int pending = 0; bool quit = false;
-    const std::function<void(int, int)>* job = nullptr;
-    static int pick_threads()
-    {
-        int cores = (int)std::thread::hardware_concurrency();
-        cpu_set_t set;
-        if (sched_getaffinity(0, sizeof set, &set) == 0) cores = CPU_COUNT(&set);
-        return std::min(16, std::max(4, cores));
-    }
-    CopyPool() : NT(pick_threads())
-    {
-        for (int t = 1; t < NT; ++t)
-            th.emplace_back([this, t] {
-                unsigned long long seen = 0;
-                for (;;) {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv_go.wait(lk, [&] { return quit || gen != seen; });
-                    if (quit) return;
-                    seen = gen;
-                    const std::function<void(int, int)>* f = job;
-                    lk.unlock();
-                    (*f)(t, NT);
-                    lk.lock();
-                    if (--pending == 0) cv_done.notify_one();
-                }
-            });
-    }
-    ~CopyPool()
-    {
-        { std::lock_guard<std::mutex> lk(mu); quit = true; }
-        cv_go.notify_all();
-        for (auto& t : th) t.join();
-    }
-    void run(const std::function<void(int, int)>& f)
-    {
-        { std::lock_guard<std::mutex> lk(mu); job = &f; pending = NT - 1; ++gen; }
-        cv_go.notify_all();
-        f(0, NT);
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return pending == 0; });
-    }
-};
 
 void sfm_parallel(sfmhip_ctx* ctx, const std::function<void(int, int)>& f)
 {
@@ -87,21 +37,20 @@ static int stage_ring(sfmhip_ctx* ctx)
 
 int sfm_upload_produced(sfmhip_ctx* ctx, void* dst, size_t bytes, size_t granule, const std::function<void(char*, size_t, size_t, int, int)>& fill)
 {
+    SFM_ARG_CHECK(ctx, granule <= sfmhip_ctx::STAGE_BYTES);          // no piece could be a multiple of it
     if (bytes == 0) return SFMHIP_OK;
     { const int rc = stage_ring(ctx); if (rc) return rc; }
-    const size_t CH = granule > 0 && granule <= sfmhip_ctx::STAGE_BYTES ? sfmhip_ctx::STAGE_BYTES / granule * granule : sfmhip_ctx::STAGE_BYTES;
-    for (size_t off = 0; off < bytes; off += CH) {
-        const size_t n = std::min(CH, bytes - off);
+    return stage_for_each_piece(bytes, sfmhip_ctx::STAGE_BYTES, granule, [&](size_t off, size_t n) -> int {
         const int b = ctx->stage_next;
         if (ctx->stage_busy[b]) SFM_HIP_TRY(ctx, hipEventSynchronize(ctx->stage_ev[b]));
         char* d = (char*)ctx->stage[b];
-        if (n >= ((size_t)256 << 10)) sfm_parallel(ctx, [&](int t, int nt) { fill(d, off, n, t, nt); });
+        if (n >= STAGE_PARALLEL_BYTES) sfm_parallel(ctx, [&](int t, int nt) { fill(d, off, n, t, nt); });
         else fill(d, off, n, 0, 1);
         SFM_HIP_TRY(ctx, hipMemcpyAsync((char*)dst + off, d, n, hipMemcpyHostToDevice, ctx->stream));
         SFM_HIP_TRY(ctx, hipEventRecord(ctx->stage_ev[b], ctx->stream));
         ctx->stage_busy[b] = true; ctx->stage_next = b ^ 1;
-    }
-    return SFMHIP_OK;
+        return SFMHIP_OK;
+    });
 }
 
 int sfm_upload(sfmhip_ctx* ctx, void* dst, const void* src, size_t bytes)
@@ -211,6 +160,63 @@ int sfmhip_debug_fail_allocations(sfmhip_ctx* ctx, int n)
 {
     if (!ctx || n < 0) return SFMHIP_E_ARG;
     ctx->inject_alloc_failures = n;
+    return SFMHIP_OK;
+}
+
+// test hook: the staging ring by itself (the contract is stated at sfm_upload_produced in common.hpp and in sfmhip.h)
+int sfmhip_debug_upload_many(sfmhip_ctx* ctx, const void* const* src, const size_t* bytes, const size_t* granule, int n, void* const* out, uint64_t* stats4)
+{
+    SFM_DEVICE_GUARD(ctx);
+    SFM_RANGE("sfmhip_debug_upload_many");
+    SFM_ARG_CHECK(ctx, ctx && n >= 0 && (n == 0 || (src && bytes && granule && out)));
+    for (int i = 0; i < n; ++i) {
+        SFM_ARG_CHECK(ctx, bytes[i] == 0 || (src[i] && out[i]));
+        SFM_ARG_CHECK(ctx, !ranges_overlap(stats4, 32, src[i], bytes[i]) && !ranges_overlap(stats4, 32, out[i], bytes[i]));
+        for (int j = 0; j < n; ++j)
+            SFM_ARG_CHECK(ctx, !ranges_overlap(out[i], bytes[i], src[j], bytes[j]) && (j <= i || !ranges_overlap(out[i], bytes[i], out[j], bytes[j])));
+    }
+    SfmCarve carve;
+    std::vector<size_t> at((size_t)n);
+    for (int i = 0; i < n; ++i) at[i] = carve(bytes[i]);
+    SfmPoolHold hold(ctx);
+    char* d = nullptr;
+    int rc = hold.get(carve.bytes, (void**)&d);
+    if (rc != SFMHIP_OK) return rc;
+    std::atomic<uint64_t> pieces{0}, produced{0}, bad{0}, max_nt{0};
+    std::mutex mu;
+    for (int i = 0; i < n && rc == SFMHIP_OK; ++i) {
+        if (granule[i] == 0) { rc = sfm_upload(ctx, d + at[i], src[i], bytes[i]); continue; }
+        const size_t G = granule[i], B = bytes[i];
+        const char* s = (const char*)src[i];
+        const std::vector<long long> first = { 0, (long long)(B / G) };          // one image of whole granules; the rest goes with the last share
+        std::set<std::pair<size_t, int>> seen;
+        rc = sfm_upload_produced(ctx, d + at[i], B, G, [&](char* piece, size_t off, size_t nb, int t, int nt) {
+            uint64_t v = 0;
+            if (off % G) v |= SFMHIP_UPLOAD_BAD_OFF;
+            if (off + nb < B && nb % G) v |= SFMHIP_UPLOAD_BAD_PIECE;
+            if (nb > sfmhip_ctx::STAGE_BYTES) v |= SFMHIP_UPLOAD_BAD_SIZE;
+            if (t < 0 || t >= nt) v |= SFMHIP_UPLOAD_BAD_THREAD;
+            if (off + nb > B || off + nb < off) v |= SFMHIP_UPLOAD_BAD_RANGE;
+            { std::lock_guard<std::mutex> lk(mu); if (!seen.insert({ off, t }).second) v |= SFMHIP_UPLOAD_TWICE; }
+            if (v) { bad.fetch_or(v); return; }          // (nothing is copied on a broken promise: the bytes then differ as well)
+            if (t == 0) pieces.fetch_add(1);
+            uint64_t m = max_nt.load();
+            while ((uint64_t)nt > m && !max_nt.compare_exchange_weak(m, (uint64_t)nt)) {}
+            size_t done = 0;
+            stage_share_runs(first, G, off, nb, t, nt, [&](int, long long row, long long run, size_t to) {
+                memcpy(piece + to, s + (size_t)row * G, (size_t)run * G); done += (size_t)run * G;
+            });
+            const size_t whole = nb / G * G;
+            if (t == nt - 1 && whole < nb) { memcpy(piece + whole, s + off + whole, nb - whole); done += nb - whole; }
+            produced.fetch_add(done);
+        });
+    }
+    if (rc != SFMHIP_OK) return sfm_drain(ctx, rc);
+    rc = sfm_finish(ctx, hipSuccess);
+    if (rc != SFMHIP_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (bytes[i]) SFM_HIP_TRY(ctx, hipMemcpy(out[i], d + at[i], bytes[i], hipMemcpyDeviceToHost));
+    if (stats4) { stats4[0] = pieces.load(); stats4[1] = produced.load(); stats4[2] = bad.load(); stats4[3] = max_nt.load(); }
     return SFMHIP_OK;
 }
 

@@ -11,6 +11,7 @@
 //   * Hamming2 (AKAZE, the live reference configuration): VALU popcount of non-zero 2-bit cells.
 // Tie-breaking everywhere: smaller distance, then smaller train index (cv::batchDistance's stable insertion).
 #include "common.hpp"
+#include "copy_pool.hpp"
 // float32 results must be bit-exact with the CPU restatement: no FMA contraction, correctly rounded sqrt
 // (HIP's __fsqrt_rn/__fmul_rn are NOT the rounded forms on this toolchain: native sqrt / contractible mul).
 #pragma clang fp contract(off)
@@ -1644,17 +1645,10 @@ static int stage_host_images(sfmhip_ctx* ctx, SfmPoolHold& hold, const T* const*
     const long long total = first[n];
     const int rc = hold.get((size_t)std::max<long long>(total, 1) * w, (void**)d_rows); if (rc) return rc;
     return sfm_upload_produced(ctx, *d_rows, (size_t)total * w, (size_t)w, [&](char* piece, size_t off, size_t nb, int t, int nt) {
-        const long long g0 = (long long)(off / w), cnt = (long long)(nb / w);
-        long long r = g0 + cnt * t / nt;
-        const long long re = g0 + cnt * (t + 1) / nt;
-        int img = (int)(std::upper_bound(first.begin(), first.end(), r) - first.begin()) - 1;
-        while (r < re) {
-            while (r >= first[img + 1]) ++img;
-            const long long run = std::min(re, first[img + 1]) - r;          // rows of this image in the share
+        stage_share_runs(first, (size_t)w, off, nb, t, nt, [&](int img, long long row, long long run, size_t at) {
             const size_t l = ld ? ld[img] : (size_t)w;
-            visit(img, desc[img] + (size_t)(r - first[img]) * l, l, run, (uint8_t*)piece + (size_t)(r - g0) * w);
-            r += run;
-        }
+            visit(img, desc[img] + (size_t)row * l, l, run, (uint8_t*)piece + at);
+        });
     });
 }
 

@@ -193,11 +193,6 @@ void sfm_enqueue_run_heads(hipStream_t st, const su64* keys, size_t n, su64 limi
 // ------------------------------------------------------------------------------------------------
 // the two primitives on host arrays, for the tests of the contract of sortscan.hpp
 // ------------------------------------------------------------------------------------------------
-static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    return a && b && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
-}
-
 extern "C" {
 
 int sfmhip_debug_sort_pairs(sfmhip_ctx* ctx, const uint64_t* keys, const uint32_t* vals, size_t n, int bits, uint64_t* keys_out, uint32_t* vals_out)

@@ -273,6 +273,36 @@ def test_c5_bundle_adjustment_full_size(ctx, c5_scene):
     pb.close()
 
 
+def test_c5_observations_arrive_in_every_row(ctx, c5_scene):
+    """The 128 MB of obs_uv cross the pinned staging ring in eight pieces (sfm_upload in sfmhip_ba_create; the ring's own test is
+    tests/test_upload_gpu.py).  Both device copies, "ouv" (by point slot, then camera) and "cam_uv" (by camera), are put back into
+    the caller's order through the tables that say where each observation went -- its camera and its point's slot -- and compared
+    with the input byte for byte.  A (camera, point) pair occurs once in this scene, so the way back is unique."""
+    sc = c5_scene
+    n_obs, n_pt, n_cam = sc["n_obs"], sc["n_pt"], sc["n_cam"]
+    uv = np.ascontiguousarray(sc["obs_uv"], np.float64).reshape(-1, 2)
+    assert uv.nbytes > 32 << 20
+    pb = ctx.ba_create(sc["K0"], sc["ext0"], sc["pts0"], sc["obs_cam"], sc["obs_pt"], sc["obs_uv"])
+    slot, ocam, opt, ouv, cam_start, cam_pt, cam_uv = (pb.debug_table(t) for t in ("pt_slot", "ocam", "opt", "ouv", "cam_start", "cam_pt", "cam_uv"))
+    pb.close()
+    assert ouv.dtype == np.float64 and cam_uv.dtype == np.float64 and ouv.size == cam_uv.size == 2 * n_obs
+    assert np.array_equal(np.sort(slot), np.arange(n_pt))
+    want_key = np.asarray(sc["obs_cam"], np.int64) * n_pt + slot[sc["obs_pt"]]
+    by_key = np.argsort(want_key)
+    assert (np.diff(want_key[by_key]) > 0).all()                                   # every (camera, point) once
+    want = uv[by_key].view(np.uint64)
+    got_key = ocam.astype(np.int64) * n_pt + opt
+    o = np.argsort(got_key)
+    assert np.array_equal(got_key[o], want_key[by_key])
+    assert np.array_equal(ouv.reshape(-1, 2)[o].view(np.uint64), want)
+    assert cam_start[0] == 0 and cam_start[-1] == n_obs and cam_start.size == n_cam + 1
+    cam_of = np.repeat(np.arange(n_cam, dtype=np.int64), np.diff(cam_start))
+    got_key = cam_of * n_pt + cam_pt
+    o = np.argsort(got_key)
+    assert np.array_equal(got_key[o], want_key[by_key])
+    assert np.array_equal(cam_uv.reshape(-1, 2)[o].view(np.uint64), want)
+
+
 def test_c5_point_shards_add_up(ctx, c5_scene):
     """the multi-GPU contract at C5's size: the partial reduced systems of four point shards sum to the full one"""
     sc = c5_scene
