@@ -168,7 +168,7 @@ __global__ void fill_kernel(double* __restrict__ p, size_t n, double v)
 // host-side problem
 // ------------------------------------------------------------------------------------------------
 enum { SEAM_LIN_IN_BACK = 4, SEAM_INTR_FRONT = 8, SEAM_CAMSTEP_ROLES = 16, SEAM_TREE_BACKWARD = 32, SEAM_BACK_REDUCE = 64, SEAM_PIVOT_FOLD = 128,
-       SEAM_SPEC_BUILD = 256, SEAM_ALL = 4 | 8 | 16 | 32 | 64 | 128 | 256 };
+       SEAM_SPEC_BUILD = 256, SEAM_FOLD_IN_BUILD = 512, SEAM_ALL = 4 | 8 | 16 | 32 | 64 | 128 | 256 | 512 };
 struct sfmhip_ba {
     sfmhip_ctx* ctx = nullptr;
     sfm_ba_options o;
@@ -195,6 +195,7 @@ struct sfmhip_ba {
     double *d_campre = nullptr, *d_campre_c = nullptr;     // per-camera rotation blocks (CAMPRE doubles), current / candidate
     // structure
     int *d_pt_start = nullptr, *d_ocam = nullptr, *d_opt = nullptr, *d_cam_start = nullptr, *d_cam_pt = nullptr, *d_blk_crange = nullptr;
+    int *d_chunk_blk = nullptr, *d_fold_tickets = nullptr; size_t fold_ticket_count = 0; FoldTab* d_fold_tab = nullptr;      // chunk -> camera-pair block; arrival counters (FoldTab, ba_kernels.hpp), a block of their own
     int *d_blk_cam = nullptr, *d_blk_chunk = nullptr; int4 *d_items = nullptr, *d_chunk_desc = nullptr; int nchunk = 0; double* d_part_schur = nullptr;
     int *d_prow_start = nullptr, *d_prow = nullptr; bool use_sparse = false; int max_panel_rows = 0;
     std::vector<int> host_blk_cam;
@@ -262,6 +263,9 @@ struct sfmhip_ba {
     // ba_camschur_kernel at the candidate right behind ba_back_kernel_lin, and the first workgroup of its front group does ba_back_reduce_kernel's
     // job (the sums and the publication to the host), so that launch disappears; an accepted step with the guessed radius adopts the partials
     // (ba_fold_kernel follows), any other outcome leaves them unfolded and builds again (enqueue_spec_build).
+    // Bit 9 (512): the one-launch form of the build folds its own partials.  ba_camschur_kernel_fold's producers store them write-through and draw a
+    // ticket per camera / camera-pair block; whoever draws the last one does ba_fold_kernel's sums for that camera or block, so that launch
+    // disappears (the (a, a) blocks keep their diagonal pass; without bit 3 the intrinsic block keeps a launch, ba_intr_kernel).
     // 0 = every piece a launch / a loop / a phase of its own.
     int seam = SEAM_ALL;
     int* d_tree_path = nullptr; size_t tree_path_cap = 0; bool tree_ok = false;      // per-leaf ancestor lists of the solver plan (bit 5)
@@ -358,6 +362,16 @@ static int drop_point_pass(sfmhip_ba* h)
     return SFMHIP_OK;
 }
 
+// The one-launch form of the camera items and pair chunks; SFMHIP_BA_SEAM bit 9: with the camera and pair-block folds behind their last tickets.
+static void launch_camschur(sfmhip_ba* h, const BADev& P, int n_cam_blocks, int n_schur_blocks, int front, const BackPub& R)
+{
+    const dim3 grid(n_cam_blocks + n_schur_blocks + (front ? 8 : 0));
+    if (h->seam & SEAM_FOLD_IN_BUILD)
+        hipLaunchKernelGGL(ba_camschur_kernel_fold, grid, dim3(256), 0, h->ctx->stream, P, n_cam_blocks, h->d_chunk_desc, h->nchunk, h->d_items, (const FoldTab*)h->d_fold_tab, front, R);
+    else
+        hipLaunchKernelGGL(ba_camschur_kernel, grid, dim3(256), 0, h->ctx->stream, P, n_cam_blocks, h->d_chunk_desc, h->nchunk, h->d_items, h->d_part_schur, front, R);
+}
+
 // linearise: message = [S | rhs | diagU | graw | scal] (undamped), summed over ranks.  at_candidate: at the candidate
 // parameters the last back-substitution produced (speculative build of the next iteration, see ba_loop).
 static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool timed, double* carry = nullptr)
@@ -383,7 +397,8 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
     if (h->pt_ready && !at_candidate) { h->pt_ready = false; h->pt_fold_err = true; }
     else if (h->d_ptfix) hipLaunchKernelGGL(ba_point_kernel<true>, dim3(h->n_pt_blocks), dim3(256), 0, st, P, h->d_err);
     else hipLaunchKernelGGL(ba_point_kernel<false>, dim3(h->n_pt_blocks), dim3(256), 0, st, P, h->d_err);
-    // camera items and pair chunks in one launch, then their folds in one launch (ba_kernels.hpp: ba_camschur_kernel)
+    // camera items and pair chunks in one launch (ba_kernels.hpp: ba_camschur_kernel); their folds in a launch behind it (ba_fold_kernel), or,
+    // SFMHIP_BA_SEAM bit 9, inside that same launch (ba_camschur_kernel_fold)
     const int n_cam_blocks = round_up(h->nc * h->cam_split * (h->fixK ? 1 : 2), 8);
     const int n_schur_blocks = h->nblk > 0 ? round_up(ceil_div(h->nchunk, 4), 8) : 0;
     // Up to a few thousand workgroups one launch is ahead (C3: 0.190 -> 0.169 ms per iteration, C4: 0.314 -> 0.306: the fork /
@@ -408,9 +423,12 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
         if (tv) { (void)hipEventRecord(tv[1], st); (void)hipEventRecord(tv[3], st); h->build_fused[h->build_parity] = true; }
         // the intrinsic block + scalars need only the point pass: a front group of this launch reduces them (SFMHIP_BA_SEAM bit 3)
         intr_in_front = (h->seam & SEAM_INTR_FRONT) != 0;
-        hipLaunchKernelGGL(ba_camschur_kernel, dim3(n_cam_blocks + n_schur_blocks + (intr_in_front ? 8 : 0)), dim3(256), 0, st, P, n_cam_blocks, h->d_chunk_desc, h->nchunk,
-                           h->d_items, h->d_part_schur, intr_in_front ? h->n_pt_blocks : 0, BackPub{});
+        launch_camschur(h, P, n_cam_blocks, n_schur_blocks, intr_in_front ? h->n_pt_blocks : 0, BackPub{});
         if (tv) { (void)hipEventRecord(tv[2], st); (void)hipEventRecord(tv[4], st); }
+        if (h->seam & SEAM_FOLD_IN_BUILD) {          // the launch has folded its cameras and pair blocks itself
+            if (!intr_in_front) hipLaunchKernelGGL(ba_intr_kernel, dim3(1), dim3(256), 0, st, P, h->n_pt_blocks);
+            folded = true;
+        }
     }
     if (!folded)
         hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + (intr_in_front ? 0 : 1) + (h->nblk > 0 ? ceil_div(h->nblk * 36, 256) : 0)), dim3(256), 0, st, P, h->n_pt_blocks,
@@ -424,12 +442,20 @@ static int enqueue_build(sfmhip_ba* h, double radius, bool at_candidate, bool ti
 // SFMHIP_BA_SEAM bit 8, single rank, one-launch form only.  The next build's ba_camschur_kernel at the candidate, queued right behind
 // ba_back_kernel_lin and before the host has judged the step: it reads the point pass that kernel left in the second point-side set
 // (damped with spec_radius), and the first workgroup of its front group reduces and publishes the step scalars first (R: what
-// ba_back_reduce_kernel would have been given).  Besides that publication the launch stores only part_cam and part_schur (partials nothing
-// reads before ba_fold_kernel), and from ba_finalize_intr_role the intrinsic block of S, its rhs / diagU / graw entries, the padding zeros
-// of the tail and scal[SCAL_COST] / this rank's gradient-maximum slot: plain stores, none of them an accumulation, and every one is
-// stored again by the ba_camschur_kernel of a build at the current point (same role, same addresses) before anything reads it.  So a
-// step that is rejected, invalid or ends at another radius simply leaves the launch unfolded and builds again; S stays as K_back
-// zero-filled it (h->cleared) but for that block.
+// ba_back_reduce_kernel would have been given).  What the launch stores besides that publication, output by output:
+//  - part_cam and part_schur: partials, read by nothing but the folds of the launch that stored them (bit 9: inside it; else ba_fold_kernel,
+//    queued only when the launch is adopted) and, the (a, a) chunks, by the diagonal pass, which is queued behind an adopted launch or a rebuild only;
+//  - from ba_finalize_intr_role: the intrinsic block of S, its rhs / diagU / graw entries, the padding zeros of the tail and
+//    scal[SCAL_COST] / this rank's gradient-maximum slot;
+//  - with bit 9 (ba_finalize_cam_role<true> and ba_fold_tail, behind the last ticket of each camera / block): every free camera's 6 x 6
+//    block of S, its 6 x 4 block against the intrinsics in both triangles, its six entries of rhs, diagU and graw, and every (a, b) pair
+//    block of S, a != b, in both triangles; and the ticket counters, which every launch leaves at 0 because it runs to its end.
+// All of these are plain stores, none an accumulation, into S as K_back zero-filled it in front of the launch, and the structure of the
+// problem fixes their addresses: the ba_camschur_kernel[_fold] (+ ba_fold_kernel) of a build at the current point stores every one of
+// them again before anything reads it.  The one accumulation of a build, the diagonal pass ('-=' onto a camera's 6 x 6 block), is never
+// queued behind a launch that is not adopted: after a miss it follows the rebuild's plain store of that block, not the one stored ahead.
+// So a step that is rejected, invalid or ends at another radius leaves the launch where it is and builds again (h->cleared stays true:
+// outside those blocks S is still zero); a call that ends with such a launch behind it starts its next build from h->built == false.
 static bool spec_build_applies(const sfmhip_ba* h)
 {
     const int n_cam_blocks = round_up(h->nc * h->cam_split * (h->fixK ? 1 : 2), 8);
@@ -443,8 +469,7 @@ static int enqueue_spec_build(sfmhip_ba* h, double spec_radius, const BackPub& R
     P.Vinv = h->d_Vinv2; P.bp = h->d_bp2; P.WK = h->d_WK2; P.colsq_p = h->d_colsq_p2; P.part_pt = h->d_part_pt2;
     const int n_cam_blocks = round_up(h->nc * h->cam_split * (h->fixK ? 1 : 2), 8);
     const int n_schur_blocks = h->nblk > 0 ? round_up(ceil_div(h->nchunk, 4), 8) : 0;
-    hipLaunchKernelGGL(ba_camschur_kernel, dim3(n_cam_blocks + n_schur_blocks + 8), dim3(256), 0, h->ctx->stream, P, n_cam_blocks, h->d_chunk_desc, h->nchunk,
-                       h->d_items, h->d_part_schur, h->n_pt_blocks, R);
+    launch_camschur(h, P, n_cam_blocks, n_schur_blocks, h->n_pt_blocks, R);
     SFM_HIP_TRY(h->ctx, hipGetLastError());
     return SFMHIP_OK;
 }
@@ -456,8 +481,9 @@ static int enqueue_spec_adopt(sfmhip_ba* h)
     BADev P = make_dev(h, h->radius);
     h->build_timed = false; h->cleared = false;
     h->pt_ready = false; h->pt_fold_err = true;          // the adopted point pass is consumed; its flag reaches the host with the next reduction
-    hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + (h->nblk > 0 ? ceil_div(h->nblk * 36, 256) : 0)), dim3(256), 0, st, P, h->n_pt_blocks,
-                       h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, 0);
+    if (!(h->seam & SEAM_FOLD_IN_BUILD))         // (bit 9: the launch queued ahead has folded its cameras and pair blocks itself)
+        hipLaunchKernelGGL(ba_fold_kernel, dim3(h->nc + (h->nblk > 0 ? ceil_div(h->nblk * 36, 256) : 0)), dim3(256), 0, st, P, h->n_pt_blocks,
+                           h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, 0);
     if (h->n_diag_blk > 0)
         hipLaunchKernelGGL(ba_schur_reduce_kernel, dim3(ceil_div(h->nblk * 36, 256)), dim3(256), 0, st, P, h->d_blk_cam, h->d_blk_chunk, h->nblk, h->d_part_schur, 1);
     SFM_HIP_TRY(h->ctx, hipGetLastError());
@@ -1364,7 +1390,7 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
 #ifdef SFMHIP_EXPERIMENTS
     if (const char* e = getenv("SFMHIP_SCHUR_CHUNK")) schur_chunk = std::max(64, atoi(e));
 #endif
-    std::vector<int> blk_cam, blk_chunk;
+    std::vector<int> blk_cam, blk_chunk, chunk_blk;
     std::vector<int4> chunk_desc;
     if (npairs) {
         su64 *pK[2], *blk_key = nullptr; su32 *pV[2], *flag = nullptr, *hist2 = nullptr, *bsum2 = nullptr, *blk_first = nullptr; int2* raw = nullptr;
@@ -1400,7 +1426,7 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
             blk_chunk.push_back((int)chunk_desc.size());
             const size_t t = hfirst[bI], u = hfirst[bI + 1];
             const size_t cnt = u - t, nch = (cnt + schur_chunk - 1) / schur_chunk, per = round_up((int)((cnt + nch - 1) / nch), 64);
-            for (size_t a = t; a < u; a += per) chunk_desc.push_back(make_int4(ca, cb2, (int)a, (int)std::min(u, a + per)));
+            for (size_t a = t; a < u; a += per) { chunk_desc.push_back(make_int4(ca, cb2, (int)a, (int)std::min(u, a + per))); chunk_blk.push_back((int)bI); }
         }
     } else {
         TRY_RC(dalloc(h, &h->d_items, (size_t)0));
@@ -1412,8 +1438,16 @@ static int ba_build_orderings(sfmhip_ba* h, const double* pts, const int32_t* ob
     h->n_diag_blk = 0;
     for (size_t b = 0; b + 1 < blk_cam.size(); b += 2) if (blk_cam[b] == blk_cam[b + 1]) ++h->n_diag_blk;
     TRY_RC(dupload(h, &h->d_blk_cam, blk_cam.data(), blk_cam.size())); TRY_RC(dupload(h, &h->d_blk_chunk, blk_chunk.data(), blk_chunk.size()));
-    TRY_RC(dupload(h, &h->d_chunk_desc, chunk_desc.data(), chunk_desc.size()));
+    TRY_RC(dupload(h, &h->d_chunk_desc, chunk_desc.data(), chunk_desc.size())); TRY_RC(dupload(h, &h->d_chunk_blk, chunk_blk.data(), chunk_blk.size()));
+    // the arrival counters of the in-launch folds: zero here and in sfmhip_ba_reset, and every launch that counts runs to its end and leaves them at zero
+    h->fold_ticket_count = (size_t)round_up(nc + h->nblk, 4);
+    TRY_RC(dalloc(h, &h->d_fold_tickets, h->fold_ticket_count));
+    SFM_HIP_TRY(ctx, hipMemsetAsync(h->d_fold_tickets, 0, h->fold_ticket_count * sizeof(int), st));
     TRY_RC(dalloc(h, &h->d_part_schur, 36 * (size_t)h->nchunk));
+    {
+        const FoldTab tab = { h->d_part_schur, h->d_fold_tickets, h->d_chunk_blk, h->d_blk_chunk };
+        TRY_RC(dupload(h, &h->d_fold_tab, &tab, 1));
+    }
     stamp("pair lists");
     h->setup_ms[2] = ms_since(t0);
 
@@ -1673,6 +1707,7 @@ int sfmhip_ba_reset(sfmhip_ba* h)
     SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_ext, h->d_ext0, 6 * (size_t)h->nc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     if (h->np) SFM_HIP_TRY(ctx, hipMemcpyAsync(h->d_pts, h->d_pts0, 3 * (size_t)h->np * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     { int rc = drop_point_pass(h); if (rc) return rc; }
+    SFM_HIP_TRY(ctx, hipMemsetAsync(h->d_fold_tickets, 0, h->fold_ticket_count * sizeof(int), ctx->stream));
     h->started = false; h->built = false; h->cleared = false; h->campre_valid = false; h->top_cleared = false;
     for (double& v : h->phase_acc) v = 0; h->phase_cnt = 0;
     return SFMHIP_OK;
@@ -1798,6 +1833,23 @@ int sfmhip_ba_debug_table(sfmhip_ba* h, const char* name, void* out, size_t cap_
         const int v[4] = { tree ? h->nseg : 1, tree ? nlev - 1 : 0, tree ? h->nbk - h->top_blk : 0, tree && nlev > 1 && h->tree_ok && (h->seam & SEAM_TREE_BACKWARD) ? 1 : 0 };
         if (n_bytes) *n_bytes = sizeof v;
         if (out && cap_bytes >= sizeof v) memcpy(out, v, sizeof v);
+        return SFMHIP_OK;
+    }
+    else if (nm == "fold_tickets") {
+        // SFMHIP_BA_SEAM bit 9, the arrival counters of the in-launch folds, a camera each, then a camera-pair block each:
+        // [targets (cam_split x parts per camera, the chunk count per block) | current values (0 between launches)].
+        // An (a, a) block reports target 0: its chunks draw no ticket, the diagonal pass behind the build folds it.
+        const size_t n = nc + (size_t)h->nblk;
+        std::vector<int> v(2 * n), bc((size_t)h->nblk + 1), cam(2 * (size_t)h->nblk);
+        SFM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        SFM_HIP_TRY(ctx, hipMemcpy(bc.data(), h->d_blk_chunk, bc.size() * sizeof(int), hipMemcpyDeviceToHost));
+        if (n) SFM_HIP_TRY(ctx, hipMemcpy(v.data() + n, h->d_fold_tickets, n * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < nc; ++c) v[c] = h->cam_split * (h->fixK ? 1 : 2);
+        if (h->nblk) SFM_HIP_TRY(ctx, hipMemcpy(cam.data(), h->d_blk_cam, cam.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < (size_t)h->nblk; ++b) v[nc + b] = cam[2 * b] == cam[2 * b + 1] ? 0 : bc[b + 1] - bc[b];
+        if (n_bytes) *n_bytes = v.size() * sizeof(int);
+        if (out && cap_bytes < v.size() * sizeof(int)) { ctx->last_error = "sfmhip_ba_debug_table: buffer too small"; return SFMHIP_E_ARG; }
+        if (out) memcpy(out, v.data(), v.size() * sizeof(int));
         return SFMHIP_OK;
     }
     else if (nm == "step_scalars") {

@@ -564,7 +564,53 @@ __device__ __forceinline__ int xcd_item_of(int L, int n_blocks, int n_items, int
 }
 __device__ __forceinline__ int xcd_item(int n_items, int plain) { return xcd_item_of(blockIdx.x, gridDim.x, n_items, plain); }
 
-template <int PART>
+// ------------------------------------------------------------------------------------------------
+// SFMHIP_BA_SEAM bit 9: ba_fold_kernel's camera and pair-block sums run inside ba_camschur_kernel_fold, by whoever stores a camera's or
+// a block's last partial.  Every producer stores its partials write-through (relaxed agent-scope atomic stores: 8 bytes per lane, out
+// of the XCD's L2 as they are issued), drains them (s_waitcnt vmcnt(0)) and then draws a ticket from the counter of its camera or
+// block; the one that draws the last ticket sums the partials -- behind an agent-scope acquire of its own and with agent-scope loads,
+// in the order and from the 0.0 that ba_finalize_cam_role / ba_schur_reduce_role use -- and sets the counter back to 0.  Nobody waits
+// for anybody: there is no poll, so nothing can hang, and which XCD a workgroup runs on decides nothing.
+// tickets: [0, nc) a camera each (target: cam_split x parts arrivals), [nc, nc + blocks) a camera-pair block each (target: its chunks);
+// zero between launches.  chunk_blk: chunk -> block.  part: the pair partials (part_schur).
+// The table lives in device memory and the kernel takes its address where ba_camschur_kernel takes `part`: the same kernel arguments byte for byte.
+// WHERE this code stands decides the register allocation of the roles.  The compiler lays the two roles out one behind the other (pair chunks,
+// then camera items), and a uniform load (a camera's rotation block, K, the scales) goes through the scalar unit only if no store that may
+// alias stands in front of it on that layout; an atomic, or inline assembly, counts against every load.  With the hand-off inside the roles
+// the camera role's constants came through vector loads and it spilled 28 registers, some inside its loops, instead of 10.  So a role only
+// returns what it would have stored (FoldOut), and ba_fold_tail, behind both roles, stores, draws the ticket and folds.
+// ------------------------------------------------------------------------------------------------
+struct FoldTab { double* part; int* tickets; const int* chunk_blk; const int* blk_chunk; };
+// kind: 0 nothing; 1 a camera item (idx: the item; the same in the whole workgroup), its sums in LDS (ba_camera_body); 2 a pair chunk
+// (idx: the chunk; the same in the wave), val: this lane's sum
+struct FoldOut { int kind, idx; double val; };
+
+// every access of a hand-off is a global_ instruction with agent scope (sc1), never a flat_ one: the pointers out of the table are cast
+typedef __attribute__((address_space(1))) double gdouble;
+typedef __attribute__((address_space(1))) int gint;
+__device__ __forceinline__ void handoff_store(double* p, double v) { __hip_atomic_store((gdouble*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double handoff_load(const double* p) { return __hip_atomic_load((const gdouble*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int ticket_draw(int* t) { return __hip_atomic_fetch_add((gint*)t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void ticket_rearm(int* t) { __hip_atomic_store((gint*)t, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// a wave-uniform value the compiler must take as new (so that it does not move ba_fold_tail's branches back behind the roles they come from)
+__device__ __forceinline__ int fold_again(int v) { asm volatile("" : "+s"(v)); return v; }
+// this wave's stores have left (every storing wave runs it before anyone signals for it)
+__device__ __forceinline__ void handoff_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// sum of n handed-off values at p, p + stride, ...: up to eight loads in flight, the additions in index order starting from 0.0
+__device__ __forceinline__ double handoff_sum(const double* p, size_t stride, int n)
+{
+    double sum = 0.0;
+    for (int k0 = 0; k0 < n; k0 += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = k0 + u < n ? handoff_load(p + (size_t)(k0 + u) * stride) : 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) if (k0 + u < n) sum += v[u];
+    }
+    return sum;
+}
+
+template <int PART, bool FOLD>
 __device__ __forceinline__ void ba_camera_body(const BADev& P, double (*red)[CAMACC], int c, int sp_i)
 {
     const int co = cam_off(P, c);
@@ -653,25 +699,19 @@ __device__ __forceinline__ void ba_camera_body(const BADev& P, double (*red)[CAM
     if (threadIdx.x < 77) {
         const int i = threadIdx.x;
         const bool mine = (PART == 0) ? (i < 21 || (i >= 45 && i < 51) || i >= 65) : (i >= 21 && i < 45);
-        if (mine) P.part_cam[((size_t)c * P.cam_split + sp_i) * CAMACC + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+        // FOLD: the sum stays in LDS, in the slot of the thread that formed it: ba_fold_tail stores it (an output parameter for it
+        // changed the instruction order of the plain instances)
+        if (FOLD) { if (mine) red[0][i] = red[0][i] + red[1][i] + red[2][i] + red[3][i]; }
+        else if (mine) P.part_cam[((size_t)c * P.cam_split + sp_i) * CAMACC + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
     }
-}
-
-// workgroup L of n_blocks: one (camera, slice, part) item
-__device__ __forceinline__ void ba_camera_role(const BADev& P, double (*red)[CAMACC], int L, int n_blocks)
-{
-    // item = (camera * cam_split + slice) * parts + part: the two parts of a slice sit next to each other
-    const int parts = P.fixK ? 1 : 2;
-    const int v = xcd_item_of(L, n_blocks, P.nc * P.cam_split * parts, P.xcd_plain);
-    if (v < 0) return;
-    const int part = v % parts, cs = v / parts, c = cs / P.cam_split, sp_i = cs % P.cam_split;
-    if (part == 0) ba_camera_body<0>(P, red, c, sp_i); else ba_camera_body<1>(P, red, c, sp_i);
 }
 
 // ------------------------------------------------------------------------------------------------
 // K_finalize: block c < nc sums camera c's split partials and writes its S blocks / rhs / diagU / graw;
 // block nc reduces the intrinsic terms: S_KK = sum_c UKK - sum_blocks SKK, rhs_K, cost, local gmax.
 // ------------------------------------------------------------------------------------------------
+// HANDOFF: the partials were stored in this launch by other workgroups (ba_camera_role<true>, which calls this behind the last ticket).
+template <bool HANDOFF>
 __device__ __forceinline__ void ba_finalize_cam_role(const BADev& P, int blk)
 {
     __shared__ double sh[CAMACC];
@@ -679,7 +719,12 @@ __device__ __forceinline__ void ba_finalize_cam_role(const BADev& P, int blk)
     const int ld = P.npad;
     const int c = blk, co = cam_off(P, c);
     if (co < 0) return;
-    if (tid < CAMACC) {
+    if (HANDOFF) {
+        if (tid < 128) {          // the two waves that load: each behind an acquire of its own, so none waits for another's
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            if (tid < CAMACC) sh[tid] = handoff_sum(P.part_cam + (size_t)c * P.cam_split * CAMACC + tid, CAMACC, P.cam_split);
+        }
+    } else if (tid < CAMACC) {
         double v = 0.0;
         for (int s = 0; s < P.cam_split; ++s) v += P.part_cam[((size_t)c * P.cam_split + s) * CAMACC + tid];
         sh[tid] = v;
@@ -701,6 +746,21 @@ __device__ __forceinline__ void ba_finalize_cam_role(const BADev& P, int blk)
         P.graw[co + i] = sh[71 + i];
     }
 }
+// workgroup L of n_blocks: one (camera, slice, part) item
+template <bool FOLD>
+__device__ __forceinline__ FoldOut ba_camera_role(const BADev& P, double (*red)[CAMACC], int L, int n_blocks)
+{
+    FoldOut fo = { 0, 0, 0.0 };
+    // item = (camera * cam_split + slice) * parts + part: the two parts of a slice sit next to each other
+    const int parts = P.fixK ? 1 : 2;
+    const int v = xcd_item_of(L, n_blocks, P.nc * P.cam_split * parts, P.xcd_plain);
+    if (v < 0) return fo;
+    const int part = v % parts, cs = v / parts, c = cs / P.cam_split, sp_i = cs % P.cam_split;
+    if (part == 0) ba_camera_body<0, FOLD>(P, red, c, sp_i); else ba_camera_body<1, FOLD>(P, red, c, sp_i);
+    fo.kind = 1; fo.idx = v;
+    return fo;
+}
+
 // The intrinsic block + scalars.  Everything here comes out of part_pt, the point pass's per-block records: it needs no camera
 // partial, so it may run anywhere between the point pass and the solve (ba_camschur_kernel's front group, or block nc of ba_fold_kernel).
 // Thread (value i = tid & 31, slice = tid >> 5) sums value i over the point blocks of its slice -- a wave reads whole 256-byte
@@ -762,14 +822,17 @@ __device__ __forceinline__ void ba_finalize_intr_role(const BADev& P, int n_pt_b
 // S_ab = S_ba' = -sum; a == b (one point seen twice by one camera) adds the symmetrised term onto the diagonal
 // block written by K_finalize.  chunk_desc: [ca, cb, first item, end item]; items: [obs i, obs j, point, -].
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ba_schur_role(const BADev& P, const int4* __restrict__ chunk_desc, int n_chunk,
-                                              const int4* __restrict__ items, double* __restrict__ part, int L, int n_blocks)
+// FOLD: the wave's 36 sums are returned, not stored (part is unused)
+template <bool FOLD>
+__device__ __forceinline__ FoldOut ba_schur_role(const BADev& P, const int4* __restrict__ chunk_desc, int n_chunk,
+                                                 const int4* __restrict__ items, double* __restrict__ part, int L, int n_blocks)
 {
+    FoldOut fo = { 0, 0, 0.0 };
     const int lane = threadIdx.x & 63;
     const int item = xcd_item_of(L, n_blocks, (n_chunk + 3) >> 2, P.xcd_plain);  // four consecutive chunks per workgroup
-    if (item < 0) return;
+    if (item < 0) return fo;
     const int chunk = item * 4 + (threadIdx.x >> 6);
-    if (chunk >= n_chunk) return;
+    if (chunk >= n_chunk) return fo;
     const int4 cd = chunk_desc[chunk];
     const int ca = __builtin_amdgcn_readfirstlane(cd.x), cb = __builtin_amdgcn_readfirstlane(cd.y);
     const int s0 = __builtin_amdgcn_readfirstlane(cd.z), s1 = __builtin_amdgcn_readfirstlane(cd.w);
@@ -822,7 +885,60 @@ __device__ __forceinline__ void ba_schur_role(const BADev& P, const int4* __rest
     }
     const double tot = wave_reduce_scatter(acc, lane);
     const int e = wave_scatter_index(lane);
-    if (e < 36) part[36 * (size_t)chunk + e] = tot;
+    if (FOLD) { fo.kind = 2; fo.idx = chunk; fo.val = tot; }
+    else if (e < 36) part[36 * (size_t)chunk + e] = tot;
+    return fo;
+}
+
+// Behind both roles of ba_camschur_kernel_fold: what they returned is stored write-through and drained, the ticket drawn, and the camera or
+// camera-pair block folded by whoever drew its last ticket.  red: the roles' LDS, free by now.
+__device__ __forceinline__ void ba_fold_tail(const BADev& P, double (*red)[CAMACC], const int4* __restrict__ chunk_desc, const FoldTab* F, const FoldOut& fo)
+{
+    const int kind = fold_again(__builtin_amdgcn_readfirstlane(fo.kind));
+    if (kind == 1) {
+        // a camera item.  Every wave drains its stores, one lane draws the camera's ticket for the workgroup (target: cam_split x parts
+        // arrivals), and the value comes back through LDS.
+        const int item = __builtin_amdgcn_readfirstlane(fo.idx), parts = P.fixK ? 1 : 2;
+        const int part = item % parts, cs = item / parts, c = cs / P.cam_split, sp_i = cs % P.cam_split;
+        if (threadIdx.x < 77) {
+            const int i = threadIdx.x;
+            const bool mine = (part == 0) ? (i < 21 || (i >= 45 && i < 51) || i >= 65) : (i >= 21 && i < 45);
+            if (mine) handoff_store(P.part_cam + ((size_t)c * P.cam_split + sp_i) * CAMACC + i, red[0][i]);
+        }
+        handoff_drain();
+        __syncthreads();
+        int* ticket = (int*)&red[0][0];
+        if (threadIdx.x == 0) *ticket = ticket_draw(F->tickets + c);
+        __syncthreads();
+        if (*ticket != P.cam_split * parts - 1) return;          // the same in the whole workgroup
+        if (threadIdx.x == 0) ticket_rearm(F->tickets + c);      // a constant camera counts and re-arms too
+        ba_finalize_cam_role<true>(P, c);
+    } else if (kind == 2) {
+        // a pair chunk: the wave signals for its own stores only
+        const int lane = threadIdx.x & 63, chunk = __builtin_amdgcn_readfirstlane(fo.idx);
+        double* part = F->part;
+        if (wave_scatter_index(lane) < 36) handoff_store(part + 36 * (size_t)chunk + wave_scatter_index(lane), fo.val);
+        const int4 cd = chunk_desc[chunk];
+        const int ca = __builtin_amdgcn_readfirstlane(cd.x), cb = __builtin_amdgcn_readfirstlane(cd.y);
+        if (ca == cb) return;          // (a, a) blocks add onto what the camera's fold stores: they keep ba_schur_reduce_kernel's diagonal pass behind the build
+        handoff_drain();
+        const __attribute__((address_space(1))) int* blk_chunk = (const __attribute__((address_space(1))) int*)F->blk_chunk;
+        const int blk = __builtin_amdgcn_readfirstlane(((const __attribute__((address_space(1))) int*)F->chunk_blk)[chunk]);
+        const int c0 = __builtin_amdgcn_readfirstlane(blk_chunk[blk]), c1 = __builtin_amdgcn_readfirstlane(blk_chunk[blk + 1]);
+        int* ticket = F->tickets + P.nc + blk;
+        int drawn = 0;
+        if (lane == 0) drawn = ticket_draw(ticket);
+        if (__builtin_amdgcn_readfirstlane(drawn) != c1 - c0 - 1) return;
+        // last of the block's chunks to arrive: S_ab = S_ba' = -sum, as ba_schur_reduce_role's diag_pass = 0 stores them
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        if (lane < 36) {
+            const double sum = handoff_sum(part + 36 * (size_t)c0 + lane, 36, c1 - c0);
+            const int i = lane / 6, j = lane % 6, ld = P.npad, oa = cam_off(P, ca), ob = cam_off(P, cb);
+            P.S[(size_t)(oa + i) * ld + ob + j] = -sum;
+            P.S[(size_t)(ob + j) * ld + oa + i] = -sum;
+        }
+        if (lane == 0) ticket_rearm(ticket);
+    }
 }
 
 // diag_pass = 0: the off-diagonal blocks (the only writer of those: runs on the pair kernel's stream, beside K_cam and
@@ -940,8 +1056,28 @@ __global__ __launch_bounds__(256, 3) void ba_camschur_kernel(BADev P, int n_cam_
             ba_finalize_intr_role<40>(P, front);
         }
     }
-    else if (upto > before) ba_camera_role(P, red, before * 8 + (bx & 7), n_cam_blocks);
-    else ba_schur_role(P, chunk_desc, n_chunk, items, part, (g - before) * 8 + (bx & 7), nbx - n_cam_blocks);
+    else if (upto > before) ba_camera_role<false>(P, red, before * 8 + (bx & 7), n_cam_blocks);
+    else ba_schur_role<false>(P, chunk_desc, n_chunk, items, part, (g - before) * 8 + (bx & 7), nbx - n_cam_blocks);
+}
+// ... with the camera and pair-block sums of ba_fold_kernel behind the last ticket of each camera and block (SFMHIP_BA_SEAM bit 9, FoldTab above):
+// the same grid and the same choice of role per workgroup; the roles hand what they would have stored to ba_fold_tail
+__global__ __launch_bounds__(256, 3) void ba_camschur_kernel_fold(BADev P, int n_cam_blocks, const int4* __restrict__ chunk_desc, int n_chunk,
+                                                               const int4* __restrict__ items, const FoldTab* __restrict__ F, int front, BackPub R)
+{
+    __shared__ double red[4][CAMACC];
+    const int bx = (int)blockIdx.x - (front ? 8 : 0), nbx = (int)gridDim.x - (front ? 8 : 0);
+    const int G = nbx >> 3, Gc = n_cam_blocks >> 3, g = bx >> 3;
+    const int before = (int)(((long long)g * Gc) / G), upto = (int)(((long long)(g + 1) * Gc) / G);
+    FoldOut fo = { 0, 0, 0.0 };
+    if (bx < 0) {
+        if (blockIdx.x == 0) {
+            if (R.host_out) ba_back_reduce_body((double (*)[4])&red[0][0], R.part, R.nblocks, R.out4, R.scal2, R.cam2, R.err, R.host_out, R.seq, R.err_fold, R.staged);
+            ba_finalize_intr_role<40>(P, front);
+        }
+    }
+    else if (upto > before) fo = ba_camera_role<true>(P, red, before * 8 + (bx & 7), n_cam_blocks);
+    else fo = ba_schur_role<true>(P, chunk_desc, n_chunk, items, nullptr, (g - before) * 8 + (bx & 7), nbx - n_cam_blocks);
+    ba_fold_tail(P, red, chunk_desc, F, fo);
 }
 // the two roles as launches of their own: large problems run them on two streams (see enqueue_build).  Compiled for TWO waves per SIMD
 // (256 registers, nothing spilled), unlike the one-launch form above: at C5, where the gathers miss the L2s, the linearisation phase
@@ -950,20 +1086,25 @@ __global__ __launch_bounds__(256, 3) void ba_camschur_kernel(BADev P, int n_cam_
 __global__ __launch_bounds__(256, 2) void ba_camera_kernel(BADev P)
 {
     __shared__ double red[4][CAMACC];
-    ba_camera_role(P, red, blockIdx.x, gridDim.x);
+    ba_camera_role<false>(P, red, blockIdx.x, gridDim.x);
 }
 __global__ __launch_bounds__(256, 2) void ba_schur_kernel(BADev P, const int4* __restrict__ chunk_desc, int n_chunk,
                                                        const int4* __restrict__ items, double* __restrict__ part)
 {
-    ba_schur_role(P, chunk_desc, n_chunk, items, part, blockIdx.x, gridDim.x);
+    ba_schur_role<false>(P, chunk_desc, n_chunk, items, part, blockIdx.x, gridDim.x);
 }
 __global__ __launch_bounds__(256) void ba_fold_kernel(BADev P, int n_pt_blocks, const int* __restrict__ blk_cam, const int* __restrict__ blk_chunk,
                                                       int n_blk, const double* __restrict__ part, int intr)
 {
     // blocks [0, nc): a camera each; intr = 1: block nc is the intrinsic block + scalars (0: an earlier launch has done it); then the pair-block sums
-    if ((int)blockIdx.x < P.nc) ba_finalize_cam_role(P, blockIdx.x);
+    if ((int)blockIdx.x < P.nc) ba_finalize_cam_role<false>(P, blockIdx.x);
     else if (intr && (int)blockIdx.x == P.nc) ba_finalize_intr_role<40>(P, n_pt_blocks);
     else ba_schur_reduce_role(P, blk_cam, blk_chunk, n_blk, part, 0, blockIdx.x - (P.nc + intr));
+}
+// the intrinsic block + scalars alone: SFMHIP_BA_SEAM bit 9 without bit 3 (ba_camschur_kernel_fold has done the rest of ba_fold_kernel's work)
+__global__ __launch_bounds__(256) void ba_intr_kernel(BADev P, int n_pt_blocks)
+{
+    ba_finalize_intr_role<40>(P, n_pt_blocks);
 }
 __global__ __launch_bounds__(256) void ba_schur_reduce_kernel(BADev P, const int* __restrict__ blk_cam, const int* __restrict__ blk_chunk,
                                                               int n_blk, const double* __restrict__ part, int diag_pass)
